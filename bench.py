@@ -11,10 +11,17 @@ configuration the throughput metric is quoted on; per rank the batch is fixed (w
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (largest share of the step),
-`kernels` lists both; `cpu_baseline` times the CPU oracle on a bounded sample of the same pairs through a C driver
-(oracle/cpu_baseline.c: -O3 -march=native, taskset-pinned, warm-up + median of 5 passes, no Python in the timed loop;
-plus the labelled OpenMP all-cores figure) and `parity` compares the GPU poses of that sample with the oracle's.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline figures
+(`value`, `ms_per_step`, the configuration).  `--dump-outputs DIR` also writes what the last timed step computed -- the
+poses and the per-registration result fields the caller receives -- as DIR/<name>.npy (float64); the inputs are the same
+from run to run, so two builds can be compared output for output.
+
+`--full` adds everything else, outside the timed region: `roofline` for the dominant kernel (largest share of the step),
+`kernels` lists both (isolated kernel durations from serial steps of their own, HBM fractions, the committed PMC
+traffic); `steady_state` repeats the step over 100 steps; `cpu_baseline` times the CPU oracle on a bounded sample of the
+same pairs through a C driver (oracle/cpu_baseline.c: -O3 -march=native, taskset-pinned, warm-up + median of 5 passes,
+no Python in the timed loop; plus the labelled OpenMP all-cores figure) and `parity` compares the GPU poses of that
+sample with the oracle's; then the PCIe-inclusive rate, the single-pair latencies, the dense-scene and fuser legs.
 
   python bench.py --config 4 [--nodes N] [--gated]     configs[3]: replay harness -- N node maps, all-pairs (or gated)
                                                        candidate edges sharded over the ranks, nodes/s, edges/s and the
@@ -86,6 +93,23 @@ def cpu_baseline_c(fixed_h, moving_h, T0, res, size_m, rng_lim, delta, nn, itr_m
             pass
     one["pinned_core"] = pin
     return one, omp, poses
+
+
+# the fields of ndtgpu_match_result a caller reads; cycles_eval / cycles_solver are clock readings, not results
+DUMP_RESULT_FIELDS = ("converged", "iterations", "fevals", "exit_code", "score", "n_source", "n_target", "pair_terms_g",
+                      "pair_terms_h")
+
+
+def dump_outputs(out_dir, T16, results):
+    """--dump-outputs: the poses (row-major [B, 4, 4]) and the result fields ([B]) of one step, float64 .npy files."""
+    from ndt_feature_graph_amd import binding
+    os.makedirs(out_dir, exist_ok=True)
+    n = T16.shape[0]
+    T = T16.cpu().numpy().reshape(n, 4, 4).transpose(0, 2, 1)
+    np.save(os.path.join(out_dir, "poses.npy"), np.ascontiguousarray(T, dtype=np.float64))
+    r = results.cpu().numpy().view(binding.RESULT_DTYPE).reshape(n)
+    for f in DUMP_RESULT_FIELDS:
+        np.save(os.path.join(out_dir, "result_%s.npy" % f), r[f].astype(np.float64))
 
 
 def config4(args, torch, dist, N, binding, synth, rank, world, dev, size_m, rng_lim):
@@ -212,9 +236,9 @@ def config4(args, torch, dist, N, binding, synth, rank, world, dev, size_m, rng_
         return ev, (Tg_, Rg_)
 
     E = Edges(edges)
-    steps = args.steps if args.steps != 100 else 3
+    steps, warmup = args.steps, max(1, args.warmup)
     barrier()
-    for _ in range(1 if args.warmup == 5 else max(1, args.warmup)):
+    for _ in range(warmup):
         one_pass(E)
     barrier()
     t0 = time.perf_counter()
@@ -291,7 +315,7 @@ def config4(args, torch, dist, N, binding, synth, rank, world, dev, size_m, rng_
     out = {"metric": "NDT graph-edge registrations/sec on fused node maps (%d scans x %d pts per node, %.2f m cells), %s candidate edges"
                      % (S, NPn, res, what),
            "value": n_edges * steps / elapsed,
-           "unit": "registrations/s", "n_gpus": world, "steps": steps, "warmup": 1, "ms_per_step": 1e3 * elapsed / steps,
+           "unit": "registrations/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps,
            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
            "config": {"workload": "configs[3]: graph replay, %d nodes 2 m apart through %d rooms, every node a fused map of %d scans x %d pts "
                                   "(%.2f m cells); one step = A. build the node maps k %% world == rank (%d add_cloud calls), B. pack + ONE "
@@ -689,12 +713,17 @@ def config_fuse(args, torch, N, binding, synth, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 100; --config 4: 3; --config 5 and fuse time fixed repetitions)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default: 5; --config 4: 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: isolated kernel figures, roofline, steady state, CPU baseline + parity, "
+                         "PCIe-inclusive rate, single-pair latencies, dense-scene and fuser legs (config 3)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write the poses and result fields of the last timed step as DIR/<name>.npy (config 3)")
     ap.add_argument("--pairs", type=int, default=1024, help="scan pairs per GPU per step")
     ap.add_argument("--points", type=int, default=100000)
     ap.add_argument("--res", type=float, default=0.5)
-    ap.add_argument("--cpu-sample", type=int, default=128, help="pairs timed on the CPU oracle (0 = skip): 6 passes of ~2 s")
+    ap.add_argument("--cpu-sample", type=int, default=128, help="--full: pairs timed on the CPU oracle (0 = skip): 6 passes of ~2 s")
     ap.add_argument("--config", type=str, default="3", choices=["3", "4", "5", "fuse"],
                     help="3: BASELINE configs[2], the batch the metric is quoted on (default); 4: configs[3], the graph replay harness; "
                          "5: configs[4], 3D mode; fuse: the node-map path (add_cloud, link covariance and overlap)")
@@ -705,9 +734,9 @@ def main():
     ap.add_argument("--gate-dist", type=float, default=6.0, help="--config 4: candidate gate on the odometry distance of two nodes [m]")
     ap.add_argument("--scans-per-node", type=int, default=10, help="--config 4: scans fused into every node map")
     ap.add_argument("--node-points", type=int, default=20000, help="--config 4: points per scan")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--dense-pairs", type=int, default=384, help="pairs of the dense-scene leg (0 = skip it)")
-    ap.add_argument("--dense-cpu-sample", type=int, default=16, help="pairs of the dense-scene leg timed on the CPU")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU legs")
+    ap.add_argument("--dense-pairs", type=int, default=384, help="--full: pairs of the dense-scene leg (0 = skip it)")
+    ap.add_argument("--dense-cpu-sample", type=int, default=16, help="--full: pairs of the dense-scene leg timed on the CPU")
     ap.add_argument("--buffers", type=int, default=8, help="pipeline depth (the registrar's internal map sets; at most 8)")
     ap.add_argument("--cu-split", type=int, default=0, help="CUs given to the build streams (hipExtStreamCreateWithCUMask), the "
                     "matcher streams get the rest; 0: every stream sees the whole chip")
@@ -721,6 +750,14 @@ def main():
                     help="one stream, one mapset pair: every step waits for the previous one (default: --buffers mapset pairs, the "
                          "grid builds of step k+1 run on the CUs the matcher of step k has already left)")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 3 if args.config == "4" else 100
+    if args.warmup is None:
+        args.warmup = 1 if args.config == "4" else 5
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.config != "3":
+        ap.error("--dump-outputs writes the outputs of the headline configuration (--config 3)")
 
     import torch
     import torch.distributed as dist
@@ -873,24 +910,25 @@ def main():
         torch.cuda.synchronize()
 
     barrier()
-    # isolated kernel durations (a serial step on a plain map set: build launch, then matcher launch, alone on the chip;
-    # events inside the library), outside the timed region
-    # (a map set of its own: the registrar's sets keep their matcher launches on part of the chip)
-    iso = bufs[0].maps if legacy else N.MapSet(res, [0, 0, 0], size_m, n_maps=2 * B, max_cells=4096)
-    iso.profiling(True)
-    iso_T16 = T_init_cm.clone()
-    iso_b, iso_m = [], []
-    for _ in range(6):
-        iso.build(both, range_limit=rng_lim, stream=main_stream)
-        iso_T16.copy_(T_init_cm)
-        binding.match_batch_device(iso, idx, iso, idx_src, iso_T16, bufs[0].results, B, stream=main_stream)
-        barrier()
-        iso_b.append(iso.last_kernel_ms(0)); iso_m.append(iso.last_kernel_ms(1))
-    iso_build_ms = float(np.median(iso_b[1:]))     # one launch: 2B scans (median of five warm serial steps)
-    iso_match_ms = float(np.median(iso_m[1:]))
-    iso.profiling(False)
-    if not legacy:
-        iso.close()
+    if args.full:
+        # isolated kernel durations (a serial step on a plain map set: build launch, then matcher launch, alone on the chip;
+        # events inside the library), outside the timed region
+        # (a map set of its own: the registrar's sets keep their matcher launches on part of the chip)
+        iso = bufs[0].maps if legacy else N.MapSet(res, [0, 0, 0], size_m, n_maps=2 * B, max_cells=4096)
+        iso.profiling(True)
+        iso_T16 = T_init_cm.clone()
+        iso_b, iso_m = [], []
+        for _ in range(6):
+            iso.build(both, range_limit=rng_lim, stream=main_stream)
+            iso_T16.copy_(T_init_cm)
+            binding.match_batch_device(iso, idx, iso, idx_src, iso_T16, bufs[0].results, B, stream=main_stream)
+            barrier()
+            iso_b.append(iso.last_kernel_ms(0)); iso_m.append(iso.last_kernel_ms(1))
+        iso_build_ms = float(np.median(iso_b[1:]))     # one launch: 2B scans (median of five warm serial steps)
+        iso_match_ms = float(np.median(iso_m[1:]))
+        iso.profiling(False)
+        if not legacy:
+            iso.close()
     for _ in range(n_buf):     # one serial step per buffer: code objects loaded, every buffer's pages touched
         step()
         if reg is not None:
@@ -928,10 +966,20 @@ def main():
     else:
         k_build = [m[0].elapsed_time(m[1]) for m in marks]
         k_match = [m[4].elapsed_time(m[3]) for m in marks]
+    # ---- what the last timed step handed back to its caller (host copies, before any later step reuses its buffers) -----
+    last = bufs[(state["k"] - 1) % n_buf]
+    res_np = last.results.cpu().numpy().view(binding.RESULT_DTYPE).reshape(B)
+    T_out = last.T16.cpu().numpy().reshape(B, 4, 4).transpose(0, 2, 1)
+    # this rank's rows of the last step's gathered poses / results are the rows it computed
+    gathered_rows_equal_local = (bool(torch.equal(last.gathered[0][rank * B:(rank + 1) * B], last.T16) and
+                                      torch.equal(last.gathered[1][rank * B:(rank + 1) * B], last.results)) if use_dist else None)
+    if args.dump_outputs and rank == 0:
+        # with a process group the caller receives every rank's rows: the gathered arrays
+        dump_outputs(args.dump_outputs, *((last.gathered[0], last.gathered[1]) if use_dist else (last.T16, last.results)))
     # ---- labelled extra, outside the timed region: the same steps over a region long enough for the ring's fill and drain not to
     # matter (a burst pays one pipeline latency, ~3.6 ms, whatever its length: a tenth of 20 steps, a fortieth of 100)
     steady = None
-    if reg is not None and args.steps < 100 and not args.no_pipeline:
+    if args.full and reg is not None and args.steps < 100 and not args.no_pipeline:
         barrier()
         ts0 = time.perf_counter()
         for _ in range(100):
@@ -945,8 +993,6 @@ def main():
             steady_s = float(tm2.item())
         steady = {"value": world * B * 100 / steady_s, "unit": "registrations/s", "steps": 100, "ms_per_step": 1e3 * steady_s / 100,
                   "note": "the same call, 100 steps between the same barriers, after the timed region: not the headline value"}
-    last = bufs[(state["k"] - 1) % n_buf]
-    T16, results = last.T16, last.results
     if use_dist:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -955,92 +1001,91 @@ def main():
     value = world * B * args.steps / elapsed
 
     # ---- bookkeeping outside the timed region -------------------------------------------------
-    res_np = results.cpu().numpy().view(binding.RESULT_DTYPE).reshape(B)
-    T_out = T16.cpu().numpy().reshape(B, 4, 4).transpose(0, 2, 1)
     m_t, m_s = res_np["n_target"].astype(np.int64), res_np["n_source"].astype(np.int64)
-    build_ms = float(np.mean(k_build))                                 # per launch (2B scans)
-    match_ms = float(np.mean(k_match))
-    # algorithmic bytes: build 12*N + 80*M per scan; match 80*(M_src+M_tgt) per pair
-    build_bytes = 2 * B * 12.0 * NP + 80.0 * float(m_t.sum() + m_s.sum())           # per launch
-    match_bytes = 80.0 * float(m_t.sum() + m_s.sum())
-    kern = {
-        "ndt_build_kernel": {"ms_per_launch": build_ms, "ms_isolated": iso_build_ms, "launches_per_step": 1,
-                             "scans_per_launch": 2 * B,
-                             "algorithmic_bytes": build_bytes, "GBps": build_bytes / build_ms / 1e6,
-                             "GBps_isolated": build_bytes / iso_build_ms / 1e6},
-        "ndt_match_kernel": {"ms_per_launch": match_ms, "ms_isolated": iso_match_ms, "launches_per_step": 1,
-                             "algorithmic_bytes": match_bytes,
-                             "GBps": match_bytes / match_ms / 1e6,
-                             # k-bar, E and the matcher's fp64 work (SURVEY.md 8d asks for them as measured outputs)
-                             "pair_terms_per_launch": int(res_np["pair_terms_g"].sum() + res_np["pair_terms_h"].sum()),
-                             "mean_neighbours_kbar": float((res_np["pair_terms_g"].sum() + res_np["pair_terms_h"].sum())
-                                                           / max(1, int((res_np["fevals"].astype(np.int64) * m_s).sum()))),
-                             "fp64_gflop_per_launch": (130.0 * float(res_np["pair_terms_g"].sum())
-                                                       + 610.0 * float(res_np["pair_terms_h"].sum())) / 1e9,
-                             "mean_iterations": float(res_np["iterations"].mean()),
-                             "mean_fevals": float(res_np["fevals"].mean()),
-                             "converged_frac": float(res_np["converged"].mean())},
-    }
-    mk = kern["ndt_match_kernel"]
-    mk["fp64_tflops"] = mk["fp64_gflop_per_launch"] / match_ms          # GFLOP / ms = TFLOP/s
-    mk["fp64_note"] = ("pair-term flops: 130 per gradient term, 610 per Hessian term -- the per-term figures of the formulation in "
-                       "csrc/ndt_match.hip, the unit of every round's line (DESIGN.md 4.2); the shipped loops EXECUTE 145 / 394 fp64 "
-                       "flops per term (ISA count, fma = 2: since library 0.5.8 the Hessian term no longer issues its 42 "
-                       "multiplications by the structural zeros of e_k x v, since 0.5.9 its rotational blocks are d_i^T B d_k with "
-                       "d_k = j_k - r_k), i.e. %.2f GFLOP per launch; "
-                       "MI355X fp64 vector peak 78.6 TFLOP/s (AMD datasheet) -> frac %.4f"
-                       % ((145.0 * float(res_np["pair_terms_g"].sum()) + 394.0 * float(res_np["pair_terms_h"].sum())) / 1e9,
-                          mk["fp64_tflops"] / 78.6))
-    mk["fp64_gflop_executed_per_launch"] = (145.0 * float(res_np["pair_terms_g"].sum()) + 394.0 * float(res_np["pair_terms_h"].sum())) / 1e9
-    # What the REFERENCE's loop needs: per registration one evaluation with the Hessian per Newton iteration
-    # (fusion.h:856) and gradient-only evaluations for everything else it runs -- every line-search trial, the re-evaluation of
-    # the Newton pose that opens a line search (fusion.h:444; the kernel reuses the Newton sums and neither runs nor counts it),
-    # the score at the returned pose (fusion.h:1085): `fevals` + `iterations` evaluations, `iterations` of them with the Hessian.
-    # Terms per evaluation of a registration: its own mean.  Hessians the kernel evaluates on speculation (trials from the second
-    # on, the first trial while first trials are accepted) are NOT in this figure.
-    ev_terms = (res_np["pair_terms_g"] + res_np["pair_terms_h"]).astype(np.float64) / np.maximum(1, res_np["fevals"]).astype(np.float64)
-    mk["fp64_gflop_needed_per_launch"] = float((ev_terms * (610.0 * res_np["iterations"] + 130.0 * res_np["fevals"])).sum()) / 1e9
-    dominant = "ndt_build_kernel" if iso_build_ms >= iso_match_ms else "ndt_match_kernel"   # by time alone on the chip
-    dk = kern[dominant]
-    # HBM traffic per launch from the committed rocprofv3 PMC passes of this same command
-    # (tools/collect_profiles.sh -> profiles/rNN_pmc_traffic.json; FETCH_SIZE x2 on gfx950 + WRITE_SIZE)
-    traffic = None
-    traffic_note = "no PMC summary for this library version under profiles/ (tools/collect_profiles.sh): traffic = null"
-    lib_version = binding.lib().ndtgpu_version().decode()
-    try:
-        if B == 1024 and NP == 100000:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_FILE)))
-            # a summary taken with another binary says nothing about this one: refuse it
-            if pmc.get("lib_version") == lib_version:
-                for k in kern:
-                    kern[k]["pmc_hbm_bytes_per_launch"] = pmc["kernels"][k]["hbm_bytes_per_launch"]
-                traffic = pmc["kernels"][dominant]["hbm_bytes_per_launch"]
-                traffic_note = ("traffic = HBM bytes per launch from the rocprofv3 PMC passes of this library version committed as "
-                                "profiles/%s" % PMC_FILE)
-    except Exception:
+    if args.full:
+        build_ms = float(np.mean(k_build))                                 # per launch (2B scans)
+        match_ms = float(np.mean(k_match))
+        # algorithmic bytes: build 12*N + 80*M per scan; match 80*(M_src+M_tgt) per pair
+        build_bytes = 2 * B * 12.0 * NP + 80.0 * float(m_t.sum() + m_s.sum())           # per launch
+        match_bytes = 80.0 * float(m_t.sum() + m_s.sum())
+        kern = {
+            "ndt_build_kernel": {"ms_per_launch": build_ms, "ms_isolated": iso_build_ms, "launches_per_step": 1,
+                                 "scans_per_launch": 2 * B,
+                                 "algorithmic_bytes": build_bytes, "GBps": build_bytes / build_ms / 1e6,
+                                 "GBps_isolated": build_bytes / iso_build_ms / 1e6},
+            "ndt_match_kernel": {"ms_per_launch": match_ms, "ms_isolated": iso_match_ms, "launches_per_step": 1,
+                                 "algorithmic_bytes": match_bytes,
+                                 "GBps": match_bytes / match_ms / 1e6,
+                                 # k-bar, E and the matcher's fp64 work (SURVEY.md 8d asks for them as measured outputs)
+                                 "pair_terms_per_launch": int(res_np["pair_terms_g"].sum() + res_np["pair_terms_h"].sum()),
+                                 "mean_neighbours_kbar": float((res_np["pair_terms_g"].sum() + res_np["pair_terms_h"].sum())
+                                                               / max(1, int((res_np["fevals"].astype(np.int64) * m_s).sum()))),
+                                 "fp64_gflop_per_launch": (130.0 * float(res_np["pair_terms_g"].sum())
+                                                           + 610.0 * float(res_np["pair_terms_h"].sum())) / 1e9,
+                                 "mean_iterations": float(res_np["iterations"].mean()),
+                                 "mean_fevals": float(res_np["fevals"].mean()),
+                                 "converged_frac": float(res_np["converged"].mean())},
+        }
+        mk = kern["ndt_match_kernel"]
+        mk["fp64_tflops"] = mk["fp64_gflop_per_launch"] / match_ms          # GFLOP / ms = TFLOP/s
+        mk["fp64_note"] = ("pair-term flops: 130 per gradient term, 610 per Hessian term -- the per-term figures of the formulation in "
+                           "csrc/ndt_match.hip, the unit of every round's line (DESIGN.md 4.2); the shipped loops EXECUTE 145 / 394 fp64 "
+                           "flops per term (ISA count, fma = 2: since library 0.5.8 the Hessian term no longer issues its 42 "
+                           "multiplications by the structural zeros of e_k x v, since 0.5.9 its rotational blocks are d_i^T B d_k with "
+                           "d_k = j_k - r_k), i.e. %.2f GFLOP per launch; "
+                           "MI355X fp64 vector peak 78.6 TFLOP/s (AMD datasheet) -> frac %.4f"
+                           % ((145.0 * float(res_np["pair_terms_g"].sum()) + 394.0 * float(res_np["pair_terms_h"].sum())) / 1e9,
+                              mk["fp64_tflops"] / 78.6))
+        mk["fp64_gflop_executed_per_launch"] = (145.0 * float(res_np["pair_terms_g"].sum()) + 394.0 * float(res_np["pair_terms_h"].sum())) / 1e9
+        # What the REFERENCE's loop needs: per registration one evaluation with the Hessian per Newton iteration
+        # (fusion.h:856) and gradient-only evaluations for everything else it runs -- every line-search trial, the re-evaluation of
+        # the Newton pose that opens a line search (fusion.h:444; the kernel reuses the Newton sums and neither runs nor counts it),
+        # the score at the returned pose (fusion.h:1085): `fevals` + `iterations` evaluations, `iterations` of them with the Hessian.
+        # Terms per evaluation of a registration: its own mean.  Hessians the kernel evaluates on speculation (trials from the second
+        # on, the first trial while first trials are accepted) are NOT in this figure.
+        ev_terms = (res_np["pair_terms_g"] + res_np["pair_terms_h"]).astype(np.float64) / np.maximum(1, res_np["fevals"]).astype(np.float64)
+        mk["fp64_gflop_needed_per_launch"] = float((ev_terms * (610.0 * res_np["iterations"] + 130.0 * res_np["fevals"])).sum()) / 1e9
+        dominant = "ndt_build_kernel" if iso_build_ms >= iso_match_ms else "ndt_match_kernel"   # by time alone on the chip
+        dk = kern[dominant]
+        # HBM traffic per launch from the committed rocprofv3 PMC passes of this same command
+        # (tools/collect_profiles.sh -> profiles/rNN_pmc_traffic.json; FETCH_SIZE x2 on gfx950 + WRITE_SIZE)
         traffic = None
-    note = ("achieved / frac = algorithmic work per launch / HIP-event duration of the launch ALONE on the chip (events on the "
-            "launch stream, the median of five warm serial steps of this run before the timed region; agrees with profiles/%s_bench_kernel_stats_serial.csv); "
-            "*_timed_region = the same work / the HIP-event duration of the launch inside the timed region, where it shares the chip "
-            "with the neighbouring steps' kernels (events on the registrar's internal streams); " % ROUND_TAG + traffic_note)
-    if dominant == "ndt_build_kernel":       # streaming pass over the points: HBM roof
-        roofline = {"kernel": dominant, "bound": "hbm", "achieved": dk["algorithmic_bytes"] / dk["ms_isolated"] / 1e6, "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": dk["algorithmic_bytes"] / dk["ms_isolated"] / 1e6 / HBM_PEAK_GBS, "traffic": traffic,
-                    "achieved_timed_region": dk["GBps"], "frac_timed_region": dk["GBps"] / HBM_PEAK_GBS, "note": note}
-    else:
-        # the matcher re-reads two cell maps that live in L2 ~1000 times: its roof is fp64 arithmetic,
-        # 78.6 TFLOP/s on MI355X for matrix and vector fp64 alike.  Flops = the kernel's own pair-term counters x
-        # 130 (gradient term) / 610 (Hessian term), DESIGN.md 4.2.  kernels.ndt_match_kernel.GBps is the HBM view.
-        roofline = {"kernel": dominant, "bound": "fp64_valu", "achieved": mk["fp64_gflop_per_launch"] / mk["ms_isolated"], "peak": 78.6,
-                    "unit": "TFLOP/s", "frac": mk["fp64_gflop_per_launch"] / mk["ms_isolated"] / 78.6, "traffic": traffic,
-                    "achieved_timed_region": mk["fp64_tflops"], "frac_timed_region": mk["fp64_tflops"] / 78.6,
-                    "frac_step": mk["fp64_gflop_per_launch"] / ms_per_step / 78.6,
-                    # the same launch priced by the fp64 flops its loops EXECUTE (ISA count; see kernels.ndt_match_kernel.fp64_note)
-                    "frac_executed_flops": mk["fp64_gflop_executed_per_launch"] / mk["ms_isolated"] / 78.6,
-                    # ... and by the evaluations the reference's loop needs (speculated Hessians are no credit)
-                    "frac_needed": mk["fp64_gflop_needed_per_launch"] / mk["ms_isolated"] / 78.6,
-                    "note": note + "; frac_step = the same flops / ms_per_step (what the pipelined step sustains); fp64 vector work (no "
-                                   "MFMA instruction is issued: every pair term has its own 3x3 inverse), counted against the fp64 peak"}
+        traffic_note = "no PMC summary for this library version under profiles/ (tools/collect_profiles.sh): traffic = null"
+        lib_version = binding.lib().ndtgpu_version().decode()
+        try:
+            if B == 1024 and NP == 100000:
+                pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_FILE)))
+                # a summary taken with another binary says nothing about this one: refuse it
+                if pmc.get("lib_version") == lib_version:
+                    for k in kern:
+                        kern[k]["pmc_hbm_bytes_per_launch"] = pmc["kernels"][k]["hbm_bytes_per_launch"]
+                    traffic = pmc["kernels"][dominant]["hbm_bytes_per_launch"]
+                    traffic_note = ("traffic = HBM bytes per launch from the rocprofv3 PMC passes of this library version committed as "
+                                    "profiles/%s" % PMC_FILE)
+        except Exception:
+            traffic = None
+        note = ("achieved / frac = algorithmic work per launch / HIP-event duration of the launch ALONE on the chip (events on the "
+                "launch stream, the median of five warm serial steps of this run before the timed region; agrees with profiles/%s_bench_kernel_stats_serial.csv); "
+                "*_timed_region = the same work / the HIP-event duration of the launch inside the timed region, where it shares the chip "
+                "with the neighbouring steps' kernels (events on the registrar's internal streams); " % ROUND_TAG + traffic_note)
+        if dominant == "ndt_build_kernel":       # streaming pass over the points: HBM roof
+            roofline = {"kernel": dominant, "bound": "hbm", "achieved": dk["algorithmic_bytes"] / dk["ms_isolated"] / 1e6, "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": dk["algorithmic_bytes"] / dk["ms_isolated"] / 1e6 / HBM_PEAK_GBS, "traffic": traffic,
+                        "achieved_timed_region": dk["GBps"], "frac_timed_region": dk["GBps"] / HBM_PEAK_GBS, "note": note}
+        else:
+            # the matcher re-reads two cell maps that live in L2 ~1000 times: its roof is fp64 arithmetic,
+            # 78.6 TFLOP/s on MI355X for matrix and vector fp64 alike.  Flops = the kernel's own pair-term counters x
+            # 130 (gradient term) / 610 (Hessian term), DESIGN.md 4.2.  kernels.ndt_match_kernel.GBps is the HBM view.
+            roofline = {"kernel": dominant, "bound": "fp64_valu", "achieved": mk["fp64_gflop_per_launch"] / mk["ms_isolated"], "peak": 78.6,
+                        "unit": "TFLOP/s", "frac": mk["fp64_gflop_per_launch"] / mk["ms_isolated"] / 78.6, "traffic": traffic,
+                        "achieved_timed_region": mk["fp64_tflops"], "frac_timed_region": mk["fp64_tflops"] / 78.6,
+                        "frac_step": mk["fp64_gflop_per_launch"] / ms_per_step / 78.6,
+                        # the same launch priced by the fp64 flops its loops EXECUTE (ISA count; see kernels.ndt_match_kernel.fp64_note)
+                        "frac_executed_flops": mk["fp64_gflop_executed_per_launch"] / mk["ms_isolated"] / 78.6,
+                        # ... and by the evaluations the reference's loop needs (speculated Hessians are no credit)
+                        "frac_needed": mk["fp64_gflop_needed_per_launch"] / mk["ms_isolated"] / 78.6,
+                        "note": note + "; frac_step = the same flops / ms_per_step (what the pipelined step sustains); fp64 vector work (no "
+                                       "MFMA instruction is issued: every pair term has its own 3x3 inverse), counted against the fp64 peak"}
 
     out = {
         "metric": "NDT scan-pair registrations/sec (100k pts, 0.5 m cells)",
@@ -1061,24 +1106,25 @@ def main():
                    "mean_cells_per_map": float((m_t.mean() + m_s.mean()) / 2),
                    "registrar": (reg.info() if reg is not None else None),
                    "batch_latency_ms": (batch_latency_ms if reg is not None else None)},
-        "roofline": roofline, "kernels": kern,
-        # SURVEY.md 8d (config 4): node maps and edges are separate units when node maps are reused across edges
-        # north_star: scans/s and achieved HBM-bandwidth fraction (algorithmic bytes / time / 8 TB/s), per kernel
-        "scans_per_s": 2 * value,
-        "steady_state": steady,
-        "hbm_fraction": {k: {"timed_region": kern[k]["GBps"] / HBM_PEAK_GBS,
-                             "kernel_alone": kern[k]["algorithmic_bytes"] / kern[k]["ms_isolated"] / 1e6 / HBM_PEAK_GBS}
-                         for k in kern},
-        "collectives": {"process_group": "nccl (RCCL)" if use_dist else None, "world": world,
-                        "forced_on_one_rank": bool(use_dist and world == 1),
-                        "all_gather_into_tensor_calls": 2 * (args.steps + args.warmup + n_buf) if use_dist else 0,
-                        # this rank's rows of the last step's gathered poses / results are the rows it computed
-                        "gathered_rows_equal_local": (bool(torch.equal(last.gathered[0][rank * B:(rank + 1) * B], last.T16) and
-                                                           torch.equal(last.gathered[1][rank * B:(rank + 1) * B], last.results))
-                                                      if use_dist else None)},
-        "nodes_per_s_build_only": world * 2 * B / (iso_build_ms * 1e-3),
-        "edges_per_s_match_only_prebuilt_maps": world * B / (iso_match_ms * 1e-3),
     }
+    if args.full:
+        out.update({"roofline": roofline, "kernels": kern})
+    # SURVEY.md 8d (config 4): node maps and edges are separate units when node maps are reused across edges
+    # north_star: scans/s and achieved HBM-bandwidth fraction (algorithmic bytes / time / 8 TB/s), per kernel
+    out["scans_per_s"] = 2 * value
+    if args.full:
+        out.update({
+            "steady_state": steady,
+            "hbm_fraction": {k: {"timed_region": kern[k]["GBps"] / HBM_PEAK_GBS,
+                                 "kernel_alone": kern[k]["algorithmic_bytes"] / kern[k]["ms_isolated"] / 1e6 / HBM_PEAK_GBS}
+                             for k in kern}})
+    out["collectives"] = {"process_group": "nccl (RCCL)" if use_dist else None, "world": world,
+                          "forced_on_one_rank": bool(use_dist and world == 1),
+                          "all_gather_into_tensor_calls": 2 * (args.steps + args.warmup + n_buf) if use_dist else 0,
+                          "gathered_rows_equal_local": gathered_rows_equal_local}
+    if args.full:
+        out.update({"nodes_per_s_build_only": world * 2 * B / (iso_build_ms * 1e-3),
+                    "edges_per_s_match_only_prebuilt_maps": world * B / (iso_match_ms * 1e-3)})
 
     # ---- CPU baseline + parity on a bounded sample (rank 0, N=1 only) ---------------------------
     # ---- single-pair latency of the other single-GPU configs, GPU side: the reference's call shape (build x2 + match, one
@@ -1098,14 +1144,14 @@ def main():
         return {"gpu_ms": 1e3 * best, "gpu_ms_min_max": [1e3 * times[0], 1e3 * times[-1]], "T": T, "r": r}
 
     lat_gpu = []
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         a2 = (fixed[0], moving[0], pr["T_init"][0].cpu().numpy(), res, size_m, rng_lim, 4096)
         lat_gpu.append(("configs[1] single 2D pair, %d pts, %.2f m cells (build x2 + match, host-synchronous call)" % (NP, res),
                         a2, one_pair_gpu(*a2)))
         p3 = synth.pair_3d(torch.tensor([1], device=dev), device=dev)
         a3 = (p3["fixed"][0], p3["moving"][0], p3["T_init"][0].cpu().numpy(), 0.25, [100.0, 100.0, 10.0], 70.0, 120000)
         lat_gpu.append(("configs[4] single 3D pair, 200000 pts, 0.25 m voxels, 100x100x10 m, 6-DoF", a3, one_pair_gpu(*a3)))
-    if rank == 0 and world == 1 and not args.no_cpu and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and args.cpu_sample > 0:
         S = min(args.cpu_sample, B)
         f_h, m_h = fixed[:S].cpu().numpy(), moving[:S].cpu().numpy()
         Ti = pr["T_init"][:S].cpu().numpy()
@@ -1186,7 +1232,7 @@ def main():
         del hs2
         del hs
     # ---- single-pair latency of the other single-GPU configs (outside the timed region; rank 0, N=1): oracle side ---
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         import oracle as O
         lat = {}
         for name, (fx, mv, T0, res_, size_, rng_, cap), g in lat_gpu:
@@ -1207,7 +1253,7 @@ def main():
             lat[name] = g
         out["single_pair_latency"] = lat
     # ---- the same configuration on a scene with ~2 k cells per map (SURVEY.md 8a/8d's size of a 2D map), labelled extra ----
-    if rank == 0 and world == 1 and args.dense_pairs > 0 and B == 1024 and NP == 100000:
+    if args.full and rank == 0 and world == 1 and args.dense_pairs > 0 and B == 1024 and NP == 100000:
         for b in bufs:
             b.maps.close()
         if reg is not None:

@@ -31,7 +31,8 @@ def bench_line(out):
 
 
 def test_bench_headline_path_through_rccl_on_one_rank():
-    out = run(["bench.py", "--steps", "4", "--warmup", "1", "--pairs", "96", "--points", "20000", "--no-cpu", "--dense-pairs", "0"], 29611)
+    out = run(["bench.py", "--full", "--steps", "4", "--warmup", "1", "--pairs", "96", "--points", "20000", "--no-cpu", "--dense-pairs", "0"],
+              29611)
     line = bench_line(out)
     c = line["collectives"]
     assert c["process_group"] == "nccl (RCCL)" and c["forced_on_one_rank"] and c["all_gather_into_tensor_calls"] >= 8

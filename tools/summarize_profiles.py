@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""Turns gpurun_out/prof_* (rocprofv3 CSV) into the committed profiles/rNN_* summaries.
-usage: python tools/summarize_profiles.py r02"""
+"""Turns the prof_* directories (rocprofv3 CSV) of tools/collect_profiles.sh into the committed profiles/rNN_* summaries.
+usage: python tools/summarize_profiles.py TAG [OUT_DIR [RAW_DIR]]   (defaults: profiles/, profile_runs/)"""
 import collections, csv, json, os, sys
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-go = os.path.join(root, "gpurun_out")
-# (on the GPU box the summaries go under gpurun_out/ -- the only directory that travels back -- and are copied to profiles/ here)
+go = sys.argv[3] if len(sys.argv) > 3 else os.path.join(root, "profile_runs")
+# (collect_profiles.sh writes the summaries next to the raw tables; they are copied to profiles/ by hand)
 pr = sys.argv[2] if len(sys.argv) > 2 else os.path.join(root, "profiles")
 os.makedirs(pr, exist_ok=True)
 # kernel stats
