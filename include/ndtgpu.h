@@ -448,6 +448,42 @@ ndtgpu_status ndtgpu_register_batch_host(ndtgpu_registrar *reg, const void *targ
                                          size_t n_points, size_t stride_bytes, size_t map_stride_bytes, double range_limit,
                                          const ndtgpu_cell_params *cell, double *T16, size_t n_pairs,
                                          const ndtgpu_match_params *prm, ndtgpu_match_result *results);
+/* ndtgpu_register_batch_device + NDTMatcherD2D::covariance(target, source, T, cov) of every pair at its registered pose
+ * (ndt_feature_graph.cpp:283-310; ndt_feature_fuser_hmt.cpp:399-413): what the reference's link update produces per link besides
+ * the pose (the link covariance cov_3d).  Poses and the deterministic result fields (converged, iterations, fevals, exit_code,
+ * score, n_source, n_target, pair_terms_g / _h) are the bits ndtgpu_register_batch_device gives for the same call: the
+ * covariance's evaluation is not counted.  covariance_mode: `mode` of ndtgpu_covariance_batch (0 or 1; else NDTGPU_ERR_INVALID),
+ * with prm->n_neighbours, lfd1, lfd2.  cov36_dev: DEVICE, n_pairs x 36 doubles, row-major 6x6 over (x, y, z, roll, pitch, yaw) --
+ * always the full 6x6, whatever prm->dof_mask is; cov_flags_dev: DEVICE, one NDTGPU_COV_* bit set per pair.  Tickets,
+ * ndtgpu_registrar_wait_stream and ndtgpu_registrar_sync cover these outputs as they cover poses and results.
+ * How: a registration that is done does not release its slot -- it asks for one more evaluation with the Hessian at the final
+ * pose, through the same shares, sums J^T J over its source cells (one target lookup each) and solves
+ * H^-1 (0.03^2 J^T J) H^-1 on the solver lane, then writes cov, flags, pose and result together.  Sub-batches that go to the
+ * grid-barrier / pool matcher (at most half as many pairs as CUs on 3D sets, max_cells >= 16384) get their covariance from a
+ * follow-on ndtgpu_covariance_batch launch on the same stream instead.  Stream-fed form: a running matcher instance is compiled
+ * with or without the covariance tail, so a call that switches between this entry and ndtgpu_register_batch_device drains the
+ * pipeline first, as a change of n_neighbours does: the host waits for everything submitted, and the next sub-batch's build no
+ * longer overlaps the previous sub-batch's registrations -- about one sub-batch of pipeline overlap lost per switch.  Measured
+ * (tools/registrar_covariance_cost.py, the bench's workload, 100 steps): 663 k registrations/s with the covariance against
+ * 722 k without, +8.9 % per step. */
+enum {
+    NDTGPU_COV_SINGULAR = 1,       /* the Hessian is singular: cov is all zeros (ndtgpu_covariance_batch's `singular`) */
+    NDTGPU_COV_POSE_UNCHANGED = 2, /* the registered pose equals the initial guess bit for bit -- the reference's "NOTHING HAPPENED"
+                                    * test (graph.cpp:283-291), after which the graph uses 0.02 I; cov is still the matcher's */
+    NDTGPU_COV_NOT_COMPUTED = 4    /* exit_code -2, -3 or -4: the registration did not run; cov is all zeros */
+};
+ndtgpu_status ndtgpu_register_batch_cov_device(ndtgpu_registrar *reg, const void *targets_dev, const void *sources_dev,
+                                               size_t n_points, size_t stride_bytes, size_t map_stride_bytes, double range_limit,
+                                               const ndtgpu_cell_params *cell, double *T16_dev, size_t n_pairs,
+                                               const ndtgpu_match_params *prm, ndtgpu_match_result *results_dev,
+                                               int covariance_mode, double *cov36_dev, int32_t *cov_flags_dev,
+                                               ndtgpu_stream stream, uint64_t *ticket);
+/* the same in HOST memory, synchronous like ndtgpu_register_batch_host: cov36 (n_pairs x 36) and cov_flags come back with the poses */
+ndtgpu_status ndtgpu_register_batch_cov_host(ndtgpu_registrar *reg, const void *targets_host, const void *sources_host,
+                                             size_t n_points, size_t stride_bytes, size_t map_stride_bytes, double range_limit,
+                                             const ndtgpu_cell_params *cell, double *T16, size_t n_pairs,
+                                             const ndtgpu_match_params *prm, ndtgpu_match_result *results,
+                                             int covariance_mode, double *cov36, int32_t *cov_flags);
 /* `stream` waits (on the device, the host does not) for the call `ticket` names and every call before it; ticket 0: for
  * every call submitted so far.  Stream-fed form: the wait is a device-side kernel that ends when the running matcher instance
  * has completed the batch, so `stream` must not share the matcher stream's hardware queue -- a stream created with the HIGHEST

@@ -130,7 +130,8 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_default_registrar_params", "ndtgpu_registrar_create_ex", "ndtgpu_registrar_get_info",
            "ndtgpu_default_fuser_params", "ndtgpu_fuser_prepare", "ndtgpu_fuser_bank_create", "ndtgpu_fuser_bank_destroy",
            "ndtgpu_fuser_bank_mapsets", "ndtgpu_fuser_initialize_batch", "ndtgpu_fuser_update_batch", "ndtgpu_fuser_poses",
-           "ndtgpu_fuser_initialize_batch_host", "ndtgpu_fuser_update_batch_host", "ndtgpu_registrar_inject_abort"]
+           "ndtgpu_fuser_initialize_batch_host", "ndtgpu_fuser_update_batch_host", "ndtgpu_registrar_inject_abort",
+           "ndtgpu_register_batch_cov_device", "ndtgpu_register_batch_cov_host"]
 
 _lib = None
 
@@ -223,6 +224,10 @@ def lib():
                                                vp, C.c_size_t, C.POINTER(MatchParams), vp, vp, C.POINTER(C.c_uint64)]
     L.ndtgpu_register_batch_host.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(CellParams),
                                              dp, C.c_size_t, C.POINTER(MatchParams), vp]
+    L.ndtgpu_register_batch_cov_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(CellParams),
+                                                   vp, C.c_size_t, C.POINTER(MatchParams), vp, C.c_int, vp, vp, vp, C.POINTER(C.c_uint64)]
+    L.ndtgpu_register_batch_cov_host.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(CellParams),
+                                                 dp, C.c_size_t, C.POINTER(MatchParams), vp, C.c_int, dp, i32p]
     L.ndtgpu_registrar_wait_stream.argtypes = [vp, C.c_uint64, vp]
     L.ndtgpu_registrar_sync.argtypes = [vp]
     L.ndtgpu_registrar_profiling.argtypes = [vp, C.c_int]
@@ -579,6 +584,8 @@ class RegistrarInfo(C.Structure):
 
 
 MATCHER_AUTO, MATCHER_PER_BATCH, MATCHER_STREAM_FED = 0, 1, 2
+# the registrar's covariance flags (include/ndtgpu.h NDTGPU_COV_*)
+COV_SINGULAR, COV_POSE_UNCHANGED, COV_NOT_COMPUTED = 1, 2, 4
 
 
 class Registrar:
@@ -623,24 +630,35 @@ class Registrar:
         except Exception:
             pass
 
-    def submit(self, targets, sources, T16_dev, results_dev, range_limit=-1.0, n_min=3, eval_factor=1000.0, stream=None, **params):
+    def submit(self, targets, sources, T16_dev, results_dev, range_limit=-1.0, n_min=3, eval_factor=1000.0, stream=None,
+               covariance_mode=None, cov36_dev=None, cov_flags_dev=None, **params):
         """targets / sources: torch CUDA float32 tensors [n, N, 3 or 4] (contiguous in the last two dims); T16_dev float64
         [n, 16] column-major (in: initial guess, out: pose); results_dev uint8 [n, 64].  Asynchronous; returns the call's
-        ticket (wait_stream / sync)."""
+        ticket (wait_stream / sync).  covariance_mode 0 / 1 (ndtgpu_register_batch_cov_device): also the covariance of every
+        pair at its registered pose into cov36_dev (float64 [n, 36], row-major 6x6) and cov_flags_dev (int32 [n], COV_*)."""
         n, npts = int(targets.shape[0]), int(targets.shape[1])
         assert tuple(sources.shape) == tuple(targets.shape) and targets.stride(1) == targets.shape[2] and targets.stride(2) == 1
         assert sources.stride(0) == targets.stride(0) and sources.stride(1) == targets.stride(1) and sources.stride(2) == 1
         cp = CellParams(int(n_min), float(eval_factor))
         p = match_params(**params)
         t = C.c_uint64()
-        _check(lib().ndtgpu_register_batch_device(self.h, C.c_void_p(targets.data_ptr()), C.c_void_p(sources.data_ptr()), npts,
-                                                  4 * int(targets.shape[2]), 4 * int(targets.stride(0)), float(range_limit),
-                                                  C.byref(cp), C.c_void_p(T16_dev.data_ptr()), n, C.byref(p),
-                                                  C.c_void_p(results_dev.data_ptr()), _stream_ptr(stream), C.byref(t)))
+        args = (self.h, C.c_void_p(targets.data_ptr()), C.c_void_p(sources.data_ptr()), npts, 4 * int(targets.shape[2]),
+                4 * int(targets.stride(0)), float(range_limit), C.byref(cp), C.c_void_p(T16_dev.data_ptr()), n, C.byref(p),
+                C.c_void_p(results_dev.data_ptr()))
+        if covariance_mode is None:
+            _check(lib().ndtgpu_register_batch_device(*args, _stream_ptr(stream), C.byref(t)))
+        else:
+            for a, what in ((cov36_dev, "cov36_dev"), (cov_flags_dev, "cov_flags_dev")):
+                if a is None:
+                    raise ValueError("Registrar.submit: covariance_mode needs %s" % what)
+            assert cov36_dev.numel() >= 36 * n and cov_flags_dev.numel() >= n
+            _check(lib().ndtgpu_register_batch_cov_device(*args, int(covariance_mode), C.c_void_p(cov36_dev.data_ptr()),
+                                                          C.c_void_p(cov_flags_dev.data_ptr()), _stream_ptr(stream), C.byref(t)))
         return int(t.value)
 
-    def register_host(self, targets, sources, T, range_limit=-1.0, n_min=3, eval_factor=1000.0, **params):
-        """Host form: targets / sources NumPy float32 [n, N, 3 or 4], T [n, 4, 4] initial guesses -> (T [n, 4, 4], results)."""
+    def register_host(self, targets, sources, T, range_limit=-1.0, n_min=3, eval_factor=1000.0, covariance_mode=None, **params):
+        """Host form: targets / sources NumPy float32 [n, N, 3 or 4], T [n, 4, 4] initial guesses -> (T [n, 4, 4], results);
+        with covariance_mode 0 / 1 (ndtgpu_register_batch_cov_host) -> (T, results, cov [n, 6, 6], flags [n] int32 COV_*)."""
         tg = np.ascontiguousarray(targets, dtype=np.float32)
         sc = np.ascontiguousarray(sources, dtype=np.float32)
         n, npts, w = tg.shape
@@ -649,9 +667,15 @@ class Registrar:
         res = np.zeros(n, dtype=RESULT_DTYPE)
         cp = CellParams(int(n_min), float(eval_factor))
         p = match_params(**params)
-        _check(lib().ndtgpu_register_batch_host(self.h, C.c_void_p(tg.ctypes.data), C.c_void_p(sc.ctypes.data), npts, 4 * w, 4 * w * npts,
-                                                float(range_limit), C.byref(cp), _dp(Tc), n, C.byref(p), C.c_void_p(res.ctypes.data)))
-        return np.transpose(Tc.reshape(n, 4, 4), (0, 2, 1)).copy(), res
+        args = (self.h, C.c_void_p(tg.ctypes.data), C.c_void_p(sc.ctypes.data), npts, 4 * w, 4 * w * npts, float(range_limit),
+                C.byref(cp), _dp(Tc), n, C.byref(p), C.c_void_p(res.ctypes.data))
+        if covariance_mode is None:
+            _check(lib().ndtgpu_register_batch_host(*args))
+            return np.transpose(Tc.reshape(n, 4, 4), (0, 2, 1)).copy(), res
+        cov = np.zeros((n, 36), dtype=np.float64)
+        flags = np.zeros(n, dtype=np.int32)
+        _check(lib().ndtgpu_register_batch_cov_host(*args, int(covariance_mode), _dp(cov), flags.ctypes.data_as(C.POINTER(C.c_int32))))
+        return np.transpose(Tc.reshape(n, 4, 4), (0, 2, 1)).copy(), res, cov.reshape(n, 6, 6), flags
 
     def wait_stream(self, stream=None, ticket=0):
         """`stream` waits for the call `ticket` names (0: for everything submitted so far); the host does not wait."""

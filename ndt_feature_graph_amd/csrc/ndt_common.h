@@ -202,7 +202,8 @@ hipError_t ndt_launch_match(const NdtSetView &tset, const uint32_t *tidx_dev, co
                             const uint32_t *sidx_dev, double *T16_dev, size_t n_pairs, const NdtMatchParamsDev &prm,
                             NdtMatchResultDev *res_dev, const double *Q36_dev, const unsigned *feat_off_dev,
                             const double *feat_cells_dev, unsigned n_groups, int park_iters, int slots,
-                            unsigned double_thresh, void *work_dev, hipStream_t stream);
+                            unsigned double_thresh, void *work_dev, hipStream_t stream, int cov_mode = -1,
+                            double *cov36_dev = nullptr, int *cov_flags_dev = nullptr);   // cov_mode >= 0: the covariance tail (registrar)
 hipError_t ndt_launch_covariance(const NdtSetView &tset, const uint32_t *tidx_dev, const NdtSetView &sset,
                                  const uint32_t *sidx_dev, const double *T16_dev, size_t n_links, int n_neighbours,
                                  double lfd1, double lfd2, int mode, double *cov36_dev, int *status_dev, hipStream_t stream);
@@ -212,11 +213,16 @@ size_t ndt_stream_abort_offset();
 size_t ndt_stream_live_offset();
 unsigned ndt_stream_ring();
 hipError_t ndt_stream_publish(void *queue_dev, const NdtSetView &set, double *T16_dev, NdtMatchResultDev *res_dev,
-                              const NdtMatchParamsDev &prm, unsigned n_pairs, unsigned seq, hipStream_t stream);
+                              const NdtMatchParamsDev &prm, unsigned n_pairs, unsigned seq, hipStream_t stream, int cov_mode = -1,
+                              double *cov36_dev = nullptr, int *cov_flags_dev = nullptr);
 size_t ndt_stream_ring_offset();
 hipError_t ndt_stream_wait(void *queue_dev, unsigned ring, unsigned seq, hipStream_t stream);   // `stream` waits until batch `seq` is complete
 hipError_t ndt_stream_skip(void *queue_dev, unsigned seq, hipStream_t stream);
-hipError_t ndt_launch_match_stream(void *queue_dev, int n_neighbours, int slots, unsigned n_groups, hipStream_t stream);
+hipError_t ndt_launch_match_stream(void *queue_dev, int n_neighbours, int slots, unsigned n_groups, hipStream_t stream, int with_cov = 0);
+// the registrar's covariance flags where the covariance came from ndt_covariance_kernel (grid-barrier / pool batches): SINGULAR from
+// its status, POSE_UNCHANGED against the initial guesses saved before the match, NOT_COMPUTED (zeros) for registrations that did not run
+hipError_t ndt_launch_cov_flags(const double *T16_in_dev, const double *T16_dev, const NdtMatchResultDev *res_dev, double *cov36_dev,
+                                int *cov_flags_dev, size_t n_pairs, hipStream_t stream);
 unsigned ndt_stream_stamps();
 hipError_t ndt_stream_final(void *queue_dev, unsigned published, hipStream_t stream);     // instances stop lingering once `published` batches are complete
 hipError_t ndt_stream_reset(void *queue_dev, unsigned submitted, unsigned ring);                 // after an abort, streams idle

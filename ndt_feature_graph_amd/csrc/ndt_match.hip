@@ -942,6 +942,15 @@ NDT_D void eval_chunks(const MapView &tg, gcell_ptr src, int msrc, const rigid &
 // A list slot is reserved BEFORE the fresh ticket is drawn, so whoever sees the tickets exhausted and then
 // head == reserve knows that no registration can be parked any more; a workgroup whose slots have all seen that exits,
 // and its CU is free for the next launch (bench.py's pipeline).
+// Where the registrar's covariance goes: per registration 36 doubles (row-major 6x6) and one flag word (include/ndtgpu.h
+// NDTGPU_COV_*).  mode < 0: none.
+struct CovOut {
+    double *cov36;
+    int *flags;
+    int mode, pad_;
+};
+enum { COV_SINGULAR = 1, COV_POSE_UNCHANGED = 2, COV_NOT_COMPUTED = 4 };
+
 struct NdtMatchWork {
     unsigned fresh, reserve, head;
     unsigned abort;        // a wave that found nothing to do for about a second raises it and everybody leaves (guard against
@@ -1169,19 +1178,114 @@ NDT_D void slot_step(MatchSlot<QL> &S, const NdtMatchParamsDev &prm)
     }
 }
 
+// One row of J of NDTMatcherD2D::covariance (perception_oru) for source cell `sc` at pose T, from the
+// target cell that holds its transformed mean (one lookup, no neighbourhood), added to the 21 sums of J^T J (upper triangle,
+// row-major; jj[21..N) stay 0).  mode 0: the cell's own pose Jacobians, mode 1: the matcher's constructor values j = [I 0],
+// Z = 0.  ndt_covariance_kernel and the registrar's covariance tail (slot_covariance).
+template <int N>
+NDT_D void cov_jtj_row(const rigid &T, gcell_ptr sc, const MapView &tg, const uint2 *trank, double lfd1, double lfd2, int mode,
+                       double (&jj)[N])
+{
+    const double sigmaS = 0.03 * 0.03;
+    const d3 m = apply(T, d3{sc->mean[0], sc->mean[1], sc->mean[2]});
+    const sym3 C = rotate_cov(T.r, sym3{sc->cov[0], sc->cov[1], sc->cov[2], sc->cov[3], sc->cov[4], sc->cov[5]});
+    const int ix = lazygrid_index(m.x, tg.cx, tg.res, tg.sx), iy = lazygrid_index(m.y, tg.cy, tg.res, tg.sy),
+              iz = lazygrid_index(m.z, tg.cz, tg.res, tg.sz);
+    if ((unsigned)ix >= (unsigned)tg.sx || (unsigned)iy >= (unsigned)tg.sy || (unsigned)iz >= (unsigned)tg.sz) return;
+    const int r = ndt_rank_of(trank, (unsigned)((ix * tg.sy + iy) * tg.sz + iz));
+    if (r < 0) return;
+    gcell_ptr tc = tg.cells + r;
+    const d3 x = m - d3{tc->mean[0], tc->mean[1], tc->mean[2]};
+    sym3 B;
+    if (!inverse_check(C + sym3{tc->cov[0], tc->cov[1], tc->cov[2], tc->cov[3], tc->cov[4], tc->cov[5]}, B)) return;
+    const d3 Bx = mul(B, x);
+    double factor = -dot(x, Bx) / 2;
+    if (factor < -120) return;
+    factor = exp(lfd2 * factor) / 2;
+    if (factor > 1 || factor < 0 || factor * 0 != 0) return;
+    // Q = -sigma_S B B (symmetric): Q x = -sigma_S B (B x)
+    const d3 Qx = (-sigmaS) * mul(B, Bx);
+    const double f1 = dot(x, Qx);
+    double G[6] = {Qx.x, Qx.y, Qx.z, 0.0, 0.0, 0.0};     // x^T Q j_a, translations
+    if (mode == 0) {
+        // rotations: j_a = e_a x m;  Z_a = [e_a]x C + C [e_a]x^T  =>  Z_a v = e_a x (C v) - C (e_a x v)
+        const d3 CBx = mul(C, Bx), CQx = mul(C, Qx);
+        const d3 ja[3] = {ex_cross(m), ey_cross(m), ez_cross(m)};
+        const d3 zb[3] = {ex_cross(CBx) - mul(C, ex_cross(Bx)), ey_cross(CBx) - mul(C, ey_cross(Bx)), ez_cross(CBx) - mul(C, ez_cross(Bx))};
+        const d3 zq[3] = {ex_cross(CQx) - mul(C, ex_cross(Qx)), ey_cross(CQx) - mul(C, ey_cross(Qx)), ez_cross(CQx) - mul(C, ez_cross(Qx))};
+#pragma unroll
+        for (int a = 0; a < 3; a++) G[3 + a] = dot(Qx, ja[a]) - dot(Qx, zb[a]) - dot(Bx, zq[a]);
+    }
+    const double sc2 = factor * lfd1 * lfd2 / 2;
+#pragma unroll
+    for (int a = 0; a < 6; a++) G[a] = (G[a] + (-lfd2 / 2) * f1) * sc2;
+    int o = 0;
+#pragma unroll
+    for (int a = 0; a < 6; a++)
+#pragma unroll
+        for (int b = a; b < 6; b++) jj[o++] += G[a] * G[b];
+}
+
+// The J^T J pass of the covariance tail over the source cells of slot S at the final pose, on this wave's lanes: the 21 sums to
+// S.part[0..20] (the shares' rows, consumed).  Not inlined: as a call it works in the caller-saved registers like the solver
+// stages, and the COV instances keep the matcher's register budget (inlined, the row formula's temporaries took the NN = 3
+// instances past 256 VGPRs).  All lanes.
+template <int QL>
+__attribute__((noinline)) NDT_D void slot_cov_jtj(MatchSlot<QL> &S, double lfd1, double lfd2, int mode)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    const rigid T = S.st.Teval;
+    const int msrc = S.sv.n_cells;
+    const MapView tg = S.tg;
+    const gcell_ptr cells = S.sv.cells;
+    const uint2 *trank = (const uint2 *)(const void *)tg.rankmap;
+    // (21 sums, reduced one after the other: no padded butterfly)
+    double jj[21];
+#pragma unroll
+    for (int k = 0; k < 21; k++) jj[k] = 0.0;
+    for (int i = (int)lane; i < msrc; i += 64) cov_jtj_row(T, cells + i, tg, trank, lfd1, lfd2, mode, jj);
+#pragma unroll
+    for (int k = 0; k < 21; k++) {
+        const double t = wave_sum_d(jj[k]);
+        if (lane == 0) S.part[k] = t;
+    }
+}
+
+// The covariance tail of a registration (phase PH_COV), run by the wave that delivered the last share of the evaluation with
+// the Hessian at the final pose (S.sums): the J^T J pass, then on lane 0 the Gauss-Jordan of cov_from_sums, the flags --
+// POSE_UNCHANGED compares with the initial guess still at T16 -- and the registration is done again (the caller writes pose and
+// result and releases the slot).  All lanes.
+template <int QL>
+NDT_D void slot_covariance(MatchSlot<QL> &S, double lfd1, double lfd2, const CovOut &co, const double *T16)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    slot_cov_jtj(S, lfd1, lfd2, co.mode);
+    ndt_wave_sync();
+    if (lane == 0) {
+        const unsigned pair = S.pair;
+        const int singular = cov_from_sums(S.sums + 7, S.part, S.part + 32, S.part + 104, co.cov36 + (size_t)pair * 36);
+        const int unchanged = match_state_pose_unchanged(S.st, T16 + (size_t)pair * 16);
+        co.flags[pair] = (singular ? COV_SINGULAR : 0) | (unchanged ? COV_POSE_UNCHANGED : 0);
+        S.st.done = 1;
+    }
+    ndt_wave_sync();
+}
+
 NDT_D unsigned lds_load(const unsigned *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 NDT_D void lds_store(unsigned *p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 NDT_D unsigned clock_lo() { return (unsigned)__builtin_readcyclecounter(); }
 }  // namespace
 
-template <int NN, int R>
+// COV = 1: the registrar's covariance entries -- every registration ends with its covariance tail (PH_COV, slot_covariance)
+// written to `co` (co.mode >= 0) before its pose and result; COV = 0 instances are the plain matcher, `co` unused.
+template <int NN, int R, int COV>
 __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void ndt_match_kernel(
     NdtSetView tset, const uint32_t *__restrict__ tidx, NdtSetView sset, const uint32_t *__restrict__ sidx,
     double *__restrict__ T16, NdtMatchParamsDev prm, NdtMatchResultDev *__restrict__ res,
     const double *__restrict__ Q36 /* per pair Tcov^-1 (matchFusion) or NULL */,
     const unsigned *__restrict__ feat_off /* [n_pairs + 1] first correspondence of every pair, or NULL */,
     const double *__restrict__ feat_cells /* 18 doubles per correspondence */,
-    unsigned n_pairs, int park_iters, unsigned double_thresh, char *__restrict__ work_mem)
+    unsigned n_pairs, int park_iters, unsigned double_thresh, char *__restrict__ work_mem, CovOut co)
 {
     constexpr int QL = R >= 3 ? 640 : 1024;     // (three slots: 5/8 of the hit list per share -- what fits; longer lists take two passes)
     typedef MatchSlot<QL> Slot;
@@ -1367,7 +1471,9 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
             const long long c0 = __builtin_readcyclecounter();
             const int with_h = S.with_h;
             // (NDTMatcherD2D_2D without the Tikhonov term: the planar pair term, see pair_term)
-            const bool planar = (s_prm.dof_mask & 0x3f) == 0x23 && !(s_prm.fusion_flags & 2);
+            // (and not for the covariance: it reads the full 6x6 Hessian)
+            bool planar = (s_prm.dof_mask & 0x3f) == 0x23 && !(s_prm.fusion_flags & 2);
+            if constexpr (COV != 0) planar = planar && S.st.phase != PH_COV;
             if (planar) {
                 if (with_h) run_share<NN, true, QL, true>(S, v, wsrc, wwin, s_prm.lfd1, s_prm.lfd2);
                 else run_share<NN, false, QL, true>(S, v, wsrc, wwin, s_prm.lfd1, s_prm.lfd2);
@@ -1392,15 +1498,20 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
         }
         ndt_wave_sync();
         const long long c1 = __builtin_readcyclecounter();
-        slot_step(S, s_prm);
+        bool cov_eval = false;
+        if constexpr (COV != 0) cov_eval = S.st.phase == PH_COV;
+        if (cov_eval) slot_covariance(S, s_prm.lfd1, s_prm.lfd2, co, T16);
+        else slot_step(S, s_prm);
         ndt_wave_sync();
         if (lane == 0) {
 #ifdef NDT_MATCH_TL
             S.wall += (unsigned long long)(c1 - S.t_pub);
 #endif
-            S.cnt[S.with_h ? 3 : 2] += (unsigned long long)S.sums[28];
+            if (!cov_eval) S.cnt[S.with_h ? 3 : 2] += (unsigned long long)S.sums[28];   // (the covariance's evaluation is not the matcher's)
             S.cnt[1] += (unsigned long long)((long long)__builtin_readcyclecounter() - c1);
             bool release = false;
+            if constexpr (COV != 0)
+                if (S.st.done && !cov_eval && co.mode >= 0) match_state_cov_request(S.st);    // one more evaluation, with the Hessian
             if (S.st.done) {
                 slot_result(S, T16, res);
                 NDT_TL(S.pair, 3)
@@ -1474,6 +1585,10 @@ struct NdtStreamBatch {
     // batch (zeroing `fresh` in two steps could hand a ticket out twice).
     unsigned long long fresh;
     unsigned done, pad_;             // registrations finished
+    // the registrar's covariance entries: per registration 36 doubles and a flag word (include/ndtgpu.h); cov_mode < 0: none
+    double *cov36;
+    int *cov_flags;
+    int cov_mode, pad2_;
 };
 struct NdtStreamQueue {
     unsigned published;              // batches published so far (their descriptors are complete)
@@ -1542,11 +1657,17 @@ __global__ void ndt_stream_publish_kernel(NdtStreamQueue *q, NdtStreamBatch desc
         o->score = 0.0; o->n_source = 0; o->n_target = 0;
         o->cycles_eval = 0; o->cycles_solver = 0; o->pair_terms_g = 0; o->pair_terms_h = 0;
     }
+    if (desc.cov_mode >= 0)              // ... and so does every covariance: zeros, NOT_COMPUTED
+        for (unsigned i = threadIdx.x; i < desc.n_pairs; i += blockDim.x) {
+            for (int k = 0; k < 36; k++) desc.cov36[(size_t)i * 36 + k] = 0.0;
+            desc.cov_flags[i] = COV_NOT_COMPUTED;
+        }
     __threadfence_system();
     __syncthreads();
     if (threadIdx.x != 0) return;
     NdtStreamBatch *b = &q->b[desc.seq % q->ring];
     b->set = desc.set; b->T16 = desc.T16; b->res = desc.res; b->prm = desc.prm;
+    b->cov36 = desc.cov36; b->cov_flags = desc.cov_flags; b->cov_mode = desc.cov_mode;
     b->n_pairs = desc.n_pairs; b->seq = desc.seq;
     b->done = 0u;
     q->stamp[desc.seq % NDT_STREAM_STAMPS][0] = wall_clock64();
@@ -1586,7 +1707,10 @@ __global__ void ndt_stream_wait_kernel(NdtStreamQueue *q, unsigned entry, unsign
 // in one-lane solver steps that a third registration covers (round 6, bench: 666 -> 722-738 k registrations/s; the cluttered scene,
 // 1 085 hits per share in two passes: 88-92 against 99 k -- the registrar picks by the cells per map it measured; four with lists
 // of 384: 660 k).  Same shares, same sums: the same bits.
-template <int NN, int R>
+// COV = 1: instances for batches published with a covariance (NdtStreamBatch::cov_mode >= 0): every registration ends with its
+// covariance tail (PH_COV, slot_covariance) before it is counted in done_ctr.  The registrar keeps one kind of instance running at a
+// time (ndtgpu_register_batch_device drains the pipeline when a call switches).
+template <int NN, int R, int COV>
 __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void ndt_match_stream_kernel(NdtStreamQueue *q)
 {
 #ifndef NDT_STREAM_RETRY
@@ -1602,6 +1726,7 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
     typedef MatchSlot<QL> Slot;
     __shared__ Slot slots[R];
     __shared__ StreamSlotExt ext[R];
+    __shared__ CovOut cext[R];           // (COV instances only: referenced nowhere else, the plain instances do not have it)
     __shared__ double w_src[NDT_MATCH_WAVES * 9 * 64];
     __shared__ uint2 w_win[NDT_MATCH_WAVES * 7 * 64];
     __shared__ unsigned s_session, s_closed, s_seen, s_left;
@@ -1730,6 +1855,8 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
                     const double d_ds = Bv->prm.delta_score, d_l1 = Bv->prm.lfd1, d_l2 = Bv->prm.lfd2;
                     double *const d_T16 = Bv->T16;
                     NdtMatchResultDev *const d_res = Bv->res;
+                    CovOut d_co{nullptr, nullptr, -1, 0};
+                    if constexpr (COV != 0) { d_co.cov36 = Bv->cov36; d_co.flags = Bv->cov_flags; d_co.mode = Bv->cov_mode; }
                     // a ticket of another generation than the descriptor's: the entry is being re-published (this slot was held up
                     // for longer than a whole batch takes).  The draw is void -- the publisher's store erases it -- : look again
                     if ((unsigned)(ticket >> 32) != bseq + 1u) continue;
@@ -1752,6 +1879,7 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
                     E.prm.fusion_flags = d_ff; E.prm.delta_score = d_ds;
                     E.prm.lfd1 = d_l1; E.prm.lfd2 = d_l2;
                     E.T16 = d_T16; E.res = d_res; E.done_ctr = &B->done; E.n_pairs = n; E.seq = c;
+                    if constexpr (COV != 0) cext[s] = d_co;
                     const unsigned pair = f, ti = f, si = n + f;
                     bool finished = false;
                     if (B->set.counters[ti].overflow != 0u || B->set.counters[si].overflow != 0u) {
@@ -1807,7 +1935,8 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             const long long c0 = __builtin_readcyclecounter();
             const int with_h = S.with_h;
-            const bool planar = (E.prm.dof_mask & 0x3f) == 0x23 && !(E.prm.fusion_flags & 2);
+            bool planar = (E.prm.dof_mask & 0x3f) == 0x23 && !(E.prm.fusion_flags & 2);
+            if constexpr (COV != 0) planar = planar && S.st.phase != PH_COV;     // (the covariance reads the full Hessian)
             if (planar) {
                 if (with_h) run_share<NN, true, QL, true>(S, v, wsrc, wwin, E.prm.lfd1, E.prm.lfd2);
                 else run_share<NN, false, QL, true>(S, v, wsrc, wwin, E.prm.lfd1, E.prm.lfd2);
@@ -1831,12 +1960,21 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
         }
         ndt_wave_sync();
         const long long c1 = __builtin_readcyclecounter();
-        slot_step(S, E.prm);
+        bool cov_eval = false;
+        if constexpr (COV != 0) cov_eval = S.st.phase == PH_COV;
+        if constexpr (COV != 0) {
+            if (cov_eval) slot_covariance(S, E.prm.lfd1, E.prm.lfd2, cext[task >> 4], E.T16);
+            else slot_step(S, E.prm);
+        } else {
+            slot_step(S, E.prm);
+        }
         ndt_wave_sync();
         if (lane == 0) {
-            S.cnt[S.with_h ? 3 : 2] += (unsigned long long)S.sums[28];
+            if (!cov_eval) S.cnt[S.with_h ? 3 : 2] += (unsigned long long)S.sums[28];   // (the covariance's evaluation is not the matcher's)
             S.cnt[1] += (unsigned long long)((long long)__builtin_readcyclecounter() - c1);
             lds_store(&S.done, 0u);
+            if constexpr (COV != 0)
+                if (S.st.done && !cov_eval && cext[task >> 4].mode >= 0) match_state_cov_request(S.st);   // one more evaluation, with the Hessian
             if (S.st.done) {
                 slot_result(S, E.T16, E.res);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");              // (system scope: pose and result reach memory)
@@ -1883,10 +2021,12 @@ hipError_t ndt_stream_skip(void *queue_dev, unsigned seq, hipStream_t stream)
 }
 
 hipError_t ndt_stream_publish(void *queue_dev, const NdtSetView &set, double *T16_dev, NdtMatchResultDev *res_dev,
-                              const NdtMatchParamsDev &prm, unsigned n_pairs, unsigned seq, hipStream_t stream)
+                              const NdtMatchParamsDev &prm, unsigned n_pairs, unsigned seq, hipStream_t stream, int cov_mode,
+                              double *cov36_dev, int *cov_flags_dev)
 {
     NdtStreamBatch d;
     d.set = set; d.T16 = T16_dev; d.res = res_dev; d.prm = prm; d.n_pairs = n_pairs; d.seq = seq; d.fresh = 0ull; d.done = 0u; d.pad_ = 0u;
+    d.cov36 = cov36_dev; d.cov_flags = cov_flags_dev; d.cov_mode = cov_mode; d.pad2_ = 0;
     hipLaunchKernelGGL(ndt_stream_publish_kernel, dim3(1), dim3(256), 0, stream, (NdtStreamQueue *)queue_dev, d);
     return hipGetLastError();
 }
@@ -1897,13 +2037,16 @@ hipError_t ndt_stream_wait(void *queue_dev, unsigned ring, unsigned seq, hipStre
     return hipGetLastError();
 }
 
-hipError_t ndt_launch_match_stream(void *queue_dev, int n_neighbours, int slots, unsigned n_groups, hipStream_t stream)
+hipError_t ndt_launch_match_stream(void *queue_dev, int n_neighbours, int slots, unsigned n_groups, hipStream_t stream, int with_cov)
 {
     NdtStreamQueue *q = (NdtStreamQueue *)queue_dev;
 #define NDT_LAUNCH_STREAM(NN_)                                                                                                   \
     do {                                                                                                                         \
-        if (slots >= 3) hipLaunchKernelGGL((ndt_match_stream_kernel<NN_, NDT_STREAM_RX>), dim3(n_groups), dim3(NDT_MATCH_THREADS), 0, stream, q); \
-        else hipLaunchKernelGGL((ndt_match_stream_kernel<NN_, 2>), dim3(n_groups), dim3(NDT_MATCH_THREADS), 0, stream, q);         \
+        if (with_cov) {                                                                                                          \
+            if (slots >= 3) hipLaunchKernelGGL((ndt_match_stream_kernel<NN_, NDT_STREAM_RX, 1>), dim3(n_groups), dim3(NDT_MATCH_THREADS), 0, stream, q); \
+            else hipLaunchKernelGGL((ndt_match_stream_kernel<NN_, 2, 1>), dim3(n_groups), dim3(NDT_MATCH_THREADS), 0, stream, q);     \
+        } else if (slots >= 3) hipLaunchKernelGGL((ndt_match_stream_kernel<NN_, NDT_STREAM_RX, 0>), dim3(n_groups), dim3(NDT_MATCH_THREADS), 0, stream, q); \
+        else hipLaunchKernelGGL((ndt_match_stream_kernel<NN_, 2, 0>), dim3(n_groups), dim3(NDT_MATCH_THREADS), 0, stream, q);      \
     } while (0)
     switch (n_neighbours) {
     case 0: NDT_LAUNCH_STREAM(0); break;
@@ -1966,46 +2109,7 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) void ndt_covariance_kernel(
 #pragma unroll
     for (int k = 0; k < 32; k++) jj[k] = 0.0;
     const rigid T = s_T;
-    for (int i = (int)tid; i < sv.n_cells; i += NDT_MATCH_THREADS) {
-        gcell_ptr sc = sv.cells + i;
-        const d3 m = apply(T, d3{sc->mean[0], sc->mean[1], sc->mean[2]});
-        const sym3 C = rotate_cov(T.r, sym3{sc->cov[0], sc->cov[1], sc->cov[2], sc->cov[3], sc->cov[4], sc->cov[5]});
-        const int ix = lazygrid_index(m.x, tg.cx, tg.res, tg.sx), iy = lazygrid_index(m.y, tg.cy, tg.res, tg.sy),
-                  iz = lazygrid_index(m.z, tg.cz, tg.res, tg.sz);
-        if ((unsigned)ix >= (unsigned)tg.sx || (unsigned)iy >= (unsigned)tg.sy || (unsigned)iz >= (unsigned)tg.sz) continue;
-        const int r = ndt_rank_of(trank, (unsigned)((ix * tg.sy + iy) * tg.sz + iz));
-        if (r < 0) continue;
-        gcell_ptr tc = tg.cells + r;
-        const d3 x = m - d3{tc->mean[0], tc->mean[1], tc->mean[2]};
-        sym3 B;
-        if (!inverse_check(C + sym3{tc->cov[0], tc->cov[1], tc->cov[2], tc->cov[3], tc->cov[4], tc->cov[5]}, B)) continue;
-        const d3 Bx = mul(B, x);
-        double factor = -dot(x, Bx) / 2;
-        if (factor < -120) continue;
-        factor = exp(lfd2 * factor) / 2;
-        if (factor > 1 || factor < 0 || factor * 0 != 0) continue;
-        // Q = -sigma_S B B (symmetric): Q x = -sigma_S B (B x)
-        const d3 Qx = (-sigmaS) * mul(B, Bx);
-        const double f1 = dot(x, Qx);
-        double G[6] = {Qx.x, Qx.y, Qx.z, 0.0, 0.0, 0.0};     // x^T Q j_a, translations
-        if (mode == 0) {
-            // rotations: j_a = e_a x m;  Z_a = [e_a]x C + C [e_a]x^T  =>  Z_a v = e_a x (C v) - C (e_a x v)
-            const d3 CBx = mul(C, Bx), CQx = mul(C, Qx);
-            const d3 ja[3] = {ex_cross(m), ey_cross(m), ez_cross(m)};
-            const d3 zb[3] = {ex_cross(CBx) - mul(C, ex_cross(Bx)), ey_cross(CBx) - mul(C, ey_cross(Bx)), ez_cross(CBx) - mul(C, ez_cross(Bx))};
-            const d3 zq[3] = {ex_cross(CQx) - mul(C, ex_cross(Qx)), ey_cross(CQx) - mul(C, ey_cross(Qx)), ez_cross(CQx) - mul(C, ez_cross(Qx))};
-#pragma unroll
-            for (int a = 0; a < 3; a++) G[3 + a] = dot(Qx, ja[a]) - dot(Qx, zb[a]) - dot(Bx, zq[a]);
-        }
-        const double sc2 = factor * lfd1 * lfd2 / 2;
-#pragma unroll
-        for (int a = 0; a < 6; a++) G[a] = (G[a] + (-lfd2 / 2) * f1) * sc2;
-        int o = 0;
-#pragma unroll
-        for (int a = 0; a < 6; a++)
-#pragma unroll
-            for (int b = a; b < 6; b++) jj[o++] += G[a] * G[b];
-    }
+    for (int i = (int)tid; i < sv.n_cells; i += NDT_MATCH_THREADS) cov_jtj_row(T, sv.cells + i, tg, trank, lfd1, lfd2, mode, jj);
     {
         const double tot = wave_sum_all<32>(jj);
         if ((lane & 1u) == 0u && (lane >> 1) < 21u) sh.part[wave * 32 + (lane >> 1)] = tot;
@@ -2775,24 +2879,34 @@ hipError_t ndt_launch_match(const NdtSetView &tset, const uint32_t *tidx_dev, co
                             const uint32_t *sidx_dev, double *T16_dev, size_t n_pairs, const NdtMatchParamsDev &prm,
                             NdtMatchResultDev *res_dev, const double *Q36_dev, const unsigned *feat_off_dev,
                             const double *feat_cells_dev, unsigned n_groups, int park_iters,
-                            int slots, unsigned double_thresh, void *work_dev, hipStream_t stream)
+                            int slots, unsigned double_thresh, void *work_dev, hipStream_t stream, int cov_mode, double *cov36_dev,
+                            int *cov_flags_dev)
 {
     if (n_pairs == 0) return hipSuccess;
     if (slots < 1 || slots > 3) return hipErrorInvalidValue;
+    if (cov_mode >= 0 && (!cov36_dev || !cov_flags_dev || Q36_dev || feat_off_dev)) return hipErrorInvalidValue;
     // ticket counters and the parked list start at zero
     hipError_t e = hipMemsetAsync(work_dev, 0, sizeof(NdtMatchWork) + (n_pairs + (size_t)n_groups * slots + 1) * sizeof(unsigned), stream);
     if (e != hipSuccess) return e;
+    const CovOut co{cov36_dev, cov_flags_dev, cov_mode, 0};
+    if (cov_mode >= 0) {
+        // a registration that does not run (map index out of range, overflowed map, a launch that gave up) keeps these
+        if ((e = hipMemsetAsync(cov36_dev, 0, n_pairs * 36 * sizeof(double), stream)) != hipSuccess) return e;
+        if ((e = hipMemsetD32Async((hipDeviceptr_t)cov_flags_dev, COV_NOT_COMPUTED, n_pairs, stream)) != hipSuccess) return e;
+    }
+#define NDT_LAUNCH_MATCH_R(NN, R, CV)                                                                                \
+    hipLaunchKernelGGL((ndt_match_kernel<NN, R, CV>), dim3(n_groups), dim3(NDT_MATCH_THREADS), 0, stream, tset, tidx_dev, sset, \
+                       sidx_dev, T16_dev, prm, res_dev, Q36_dev, feat_off_dev, feat_cells_dev, (unsigned)n_pairs, park_iters, double_thresh, \
+                       (char *)work_dev, co)
 #define NDT_LAUNCH_MATCH(NN)                                                                                         \
     do {                                                                                                             \
-        if (slots == 3)                                                                                              \
-            hipLaunchKernelGGL((ndt_match_kernel<NN, 3>), dim3(n_groups), dim3(NDT_MATCH_THREADS), 0, stream, tset, tidx_dev, sset, \
-                               sidx_dev, T16_dev, prm, res_dev, Q36_dev, feat_off_dev, feat_cells_dev, (unsigned)n_pairs, park_iters, double_thresh, (char *)work_dev); \
-        else if (slots == 2)                                                                                         \
-            hipLaunchKernelGGL((ndt_match_kernel<NN, 2>), dim3(n_groups), dim3(NDT_MATCH_THREADS), 0, stream, tset, tidx_dev, sset, \
-                               sidx_dev, T16_dev, prm, res_dev, Q36_dev, feat_off_dev, feat_cells_dev, (unsigned)n_pairs, park_iters, double_thresh, (char *)work_dev); \
-        else                                                                                                         \
-            hipLaunchKernelGGL((ndt_match_kernel<NN, 1>), dim3(n_groups), dim3(NDT_MATCH_THREADS), 0, stream, tset, tidx_dev, sset, \
-                               sidx_dev, T16_dev, prm, res_dev, Q36_dev, feat_off_dev, feat_cells_dev, (unsigned)n_pairs, park_iters, double_thresh, (char *)work_dev); \
+        if (cov_mode >= 0) {                                                                                         \
+            if (slots == 3) NDT_LAUNCH_MATCH_R(NN, 3, 1);                                                            \
+            else if (slots == 2) NDT_LAUNCH_MATCH_R(NN, 2, 1);                                                       \
+            else NDT_LAUNCH_MATCH_R(NN, 1, 1);                                                                       \
+        } else if (slots == 3) NDT_LAUNCH_MATCH_R(NN, 3, 0);                                                         \
+        else if (slots == 2) NDT_LAUNCH_MATCH_R(NN, 2, 0);                                                           \
+        else NDT_LAUNCH_MATCH_R(NN, 1, 0);                                                                           \
     } while (0)
     switch (prm.n_neighbours) {
     case 0: NDT_LAUNCH_MATCH(0); break;
@@ -2802,6 +2916,7 @@ hipError_t ndt_launch_match(const NdtSetView &tset, const uint32_t *tidx_dev, co
     default: return hipErrorInvalidValue;
     }
 #undef NDT_LAUNCH_MATCH
+#undef NDT_LAUNCH_MATCH_R
     return hipGetLastError();
 }
 
@@ -2908,6 +3023,34 @@ extern "C" int ndtgpu_debug_prof(long long out[16], int reset)
     return 0;
 }
 #endif
+
+// The registrar's covariance flags where ndt_covariance_kernel computed the covariance (grid-barrier / pool batches): `flags` holds
+// that kernel's status (1 = singular Hessian) on entry; T16_in: the initial guesses, saved before the match overwrote them.
+__global__ void ndt_cov_flags_kernel(const double *__restrict__ T16_in, const double *__restrict__ T16,
+                                     const NdtMatchResultDev *__restrict__ res, double *__restrict__ cov36, int *__restrict__ flags,
+                                     unsigned n)
+{
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int ec = res[i].exit_code;
+    if (ec == -2 || ec == -3 || ec == -4) {              // did not run: what the fused tail leaves for such a registration
+        for (int k = 0; k < 36; k++) cov36[(size_t)i * 36 + k] = 0.0;
+        flags[i] = COV_NOT_COMPUTED;
+        return;
+    }
+    int same = 1;
+    for (int k = 0; k < 16; k++)
+        if (__double_as_longlong(T16_in[(size_t)i * 16 + k]) != __double_as_longlong(T16[(size_t)i * 16 + k])) same = 0;
+    flags[i] = (flags[i] ? COV_SINGULAR : 0) | (same ? COV_POSE_UNCHANGED : 0);
+}
+hipError_t ndt_launch_cov_flags(const double *T16_in_dev, const double *T16_dev, const NdtMatchResultDev *res_dev, double *cov36_dev,
+                                int *cov_flags_dev, size_t n_pairs, hipStream_t stream)
+{
+    if (n_pairs == 0) return hipSuccess;
+    hipLaunchKernelGGL(ndt_cov_flags_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream, T16_in_dev, T16_dev, res_dev,
+                       cov36_dev, cov_flags_dev, (unsigned)n_pairs);
+    return hipGetLastError();
+}
 
 hipError_t ndt_launch_covariance(const NdtSetView &tset, const uint32_t *tidx_dev, const NdtSetView &sset,
                                  const uint32_t *sidx_dev, const double *T16_dev, size_t n_links, int n_neighbours,

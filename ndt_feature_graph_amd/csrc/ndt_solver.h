@@ -19,7 +19,9 @@
 #define NDT_HDN static __host__ __device__ __attribute__((noinline)) NDT_SOLVER_VGPRS
 #endif
 
-enum { PH_NEWTON = 0, PH_LS_TRIAL = 1, PH_FINAL = 2 };
+// PH_COV: the registration is over (pose and result final) and its covariance is wanted -- the registrar's covariance entries:
+// one more evaluation with the Hessian at the returned pose, then cov_from_sums (match_state_cov_request)
+enum { PH_NEWTON = 0, PH_LS_TRIAL = 1, PH_FINAL = 2, PH_COV = 3 };
 // what a stage of the solver asks its caller to run next (stages never call each other: a value that lives across a call
 // sits in a callee-saved register, and saving those is the only thing that would give the kernels a stack)
 enum { NEXT_NONE = 0, NEXT_APPLY_STEP = 1, NEXT_REQUEST_TRIAL = 2 };
@@ -758,6 +760,88 @@ NDT_HD void match_state_step(MatchState &st, const double *sums, const NdtMatchP
     }
     if (st.phase == PH_NEWTON) newton_step(st, sums, prm, ws);
     else if (st.phase == PH_FINAL) match_state_final(st, sums);
+}
+
+// ---- NDTMatcherD2D::covariance(target, source, T, cov) at the registered pose as the TAIL of a registration
+// (ndt_feature_graph.cpp:283-310; ndt_feature_fuser_hmt.cpp:399-413): the solver is done, the slot asks for one more
+// evaluation WITH the Hessian at st.T.  It is not counted in fevals / pair terms: the result is that of the plain matcher.
+NDT_HD void match_state_cov_request(MatchState &st)
+{
+    st.phase = PH_COV;
+    st.Teval = st.T;
+    st.with_h = 1;
+    st.done = 0;
+}
+
+// the pose match_state_result writes equals the 16 doubles at T16 bit for bit (the reference's "NOTHING HAPPENED" test,
+// graph.cpp:283-291, on the caller's initial guess before it is overwritten)
+NDT_HD int match_state_pose_unchanged(const MatchState &st, const double *T16)
+{
+    double o[16];
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) o[c * 4 + r] = st.T.r[r * 3 + c];
+        o[12 + r] = st.T.t[r];
+        o[r * 4 + 3] = 0.0;
+    }
+    o[15] = 1.0;
+    int same = 1;
+    for (int k = 0; k < 16; k++)
+        if (__builtin_bit_cast(unsigned long long, o[k]) != __builtin_bit_cast(unsigned long long, T16[k])) same = 0;
+    return same;
+}
+
+// cov = H^-1 (sigma_S J^T J) H^-1, sigma_S = 0.03^2, by Gauss-Jordan with partial pivoting (Eigen: cov.inverse()) -- the
+// arithmetic of ndt_covariance_kernel.  h21 / jj21: upper triangles (row-major, a <= b) of the Hessian and of J^T J.  w: 72
+// doubles of scratch ([H | I], rows of 12), t: 36; both indexed dynamically by the pivot search, so they live in memory (LDS
+// on the device), not in registers.  Returns 1 (out all zero) when H is singular, else 0.
+NDT_HDN int cov_from_sums(const double *h21, const double *jj21, double *w, double *t, double *out36)
+{
+    const double sigmaS = 0.03 * 0.03;
+    double *jk = t;                        // sigma_S J^T J first, H^-1 (sigma_S J^T J) over it row by row below
+    int o = 0;
+    for (int a = 0; a < 6; a++)
+        for (int b = a; b < 6; b++) {
+            jk[a * 6 + b] = jk[b * 6 + a] = sigmaS * jj21[o];
+            w[a * 12 + b] = w[b * 12 + a] = h21[o];
+            o++;
+        }
+    bool ok = true;
+    for (int a = 0; a < 6; a++)
+        for (int b = 0; b < 6; b++) w[a * 12 + 6 + b] = (a == b) ? 1.0 : 0.0;
+    for (int c = 0; c < 6 && ok; c++) {
+        int piv = c;
+        for (int r = c + 1; r < 6; r++)
+            if (fabs(w[r * 12 + c]) > fabs(w[piv * 12 + c])) piv = r;
+        if (w[piv * 12 + c] == 0.0) { ok = false; break; }
+        if (piv != c)
+            for (int j = 0; j < 12; j++) { const double x = w[c * 12 + j]; w[c * 12 + j] = w[piv * 12 + j]; w[piv * 12 + j] = x; }
+        const double d = w[c * 12 + c];
+        for (int j = 0; j < 12; j++) w[c * 12 + j] /= d;
+        for (int r = 0; r < 6; r++) {
+            if (r == c) continue;
+            const double f = w[r * 12 + c];
+            if (f != 0.0)
+                for (int j = 0; j < 12; j++) w[r * 12 + j] -= f * w[c * 12 + j];
+        }
+    }
+    if (!ok) {
+        for (int k = 0; k < 36; k++) out36[k] = 0.0;
+        return 1;
+    }
+    // (a row of H^-1 JK depends only on row a of H^-1 and on all of JK: computed into a row buffer, written over w's left half)
+    for (int a = 0; a < 6; a++)
+        for (int b = 0; b < 6; b++) {
+            double s2 = 0;
+            for (int k = 0; k < 6; k++) s2 += w[a * 12 + 6 + k] * jk[k * 6 + b];
+            w[a * 12 + b] = s2;
+        }
+    for (int a = 0; a < 6; a++)
+        for (int b = 0; b < 6; b++) {
+            double s2 = 0;
+            for (int k = 0; k < 6; k++) s2 += w[a * 12 + k] * w[k * 12 + 6 + b];
+            out36[a * 6 + b] = s2;
+        }
+    return 0;
 }
 
 NDT_HD void match_state_result(const MatchState &st, double *T16, NdtMatchResultDev &o)

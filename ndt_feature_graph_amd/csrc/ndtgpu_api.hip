@@ -1081,7 +1081,8 @@ static ndtgpu_status coop_enqueue(ndtgpu_mapset *ts, ndtgpu_mapset *ss, const ui
 static ndtgpu_status match_device_core(ndtgpu_mapset *ts, const uint32_t *tidx_dev, ndtgpu_mapset *ss, const uint32_t *sidx_dev,
                                        double *T16_dev, size_t n_pairs, const NdtMatchParamsDev &p,
                                        ndtgpu_match_result *results_dev, const double *Q36_dev, hipStream_t st,
-                                       const unsigned *feat_off_dev = nullptr, const double *feat_cells_dev = nullptr)
+                                       const unsigned *feat_off_dev = nullptr, const double *feat_cells_dev = nullptr,
+                                       int cov_mode = -1, double *cov36_dev = nullptr, int32_t *cov_flags_dev = nullptr)
 {
     if (n_pairs == 0) return NDTGPU_OK;
     // persistent workgroups, one per CU (8 waves x 256 VGPRs), each with `slots` registrations in flight whose evaluation
@@ -1115,7 +1116,7 @@ static ndtgpu_status match_device_core(ndtgpu_mapset *ts, const uint32_t *tidx_d
     if (ts->profiling) HIP_TRY(hipEventRecord(ts->ev[2], st));
     hipError_t e = ndt_launch_match(ts->v, tidx_dev, ss->v, sidx_dev, T16_dev, n_pairs, p,
                                     reinterpret_cast<NdtMatchResultDev *>(results_dev), Q36_dev, feat_off_dev, feat_cells_dev,
-                                    n_groups, park_iters, slots, double_thresh, ts->work, st);
+                                    n_groups, park_iters, slots, double_thresh, ts->work, st, cov_mode, cov36_dev, cov_flags_dev);
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "match: launch", e);
     if (ts->profiling) { HIP_TRY(hipEventRecord(ts->ev[3], st)); ts->ev_valid[1] = true; }
     if (!ts->work_ev) HIP_TRY(hipEventCreateWithFlags(&ts->work_ev, hipEventDisableTiming));
@@ -1132,10 +1133,14 @@ static ndtgpu_status match_coop(ndtgpu_mapset *ts, const uint32_t *tidx, ndtgpu_
                                 double *T16, size_t n_pairs, const NdtMatchParamsDev &p, const double *Q36,
                                 ndtgpu_match_result *results, hipStream_t st, bool *done);
 
-ndtgpu_status ndtgpu_match_batch_device(ndtgpu_mapset *ts, const uint32_t *tidx_dev, ndtgpu_mapset *ss,
-                                        const uint32_t *sidx_dev, double *T16_dev, size_t n_pairs,
-                                        const ndtgpu_match_params *prm, ndtgpu_match_result *results_dev,
-                                        ndtgpu_stream stream)
+// ndtgpu_match_batch_device, and with cov_mode >= 0 the registrar's covariance of every pair at its registered pose: the tail of
+// the persistent kernel (ndt_match_kernel<.., COV = 1>), or -- grid-barrier / pool batches -- a launch of ndt_covariance_kernel
+// behind the match on the same stream and ndt_cov_flags_kernel (T16_save: n_pairs x 16 doubles of device scratch for the initial
+// guesses, which the match overwrites).
+static ndtgpu_status match_batch_device_ex(ndtgpu_mapset *ts, const uint32_t *tidx_dev, ndtgpu_mapset *ss, const uint32_t *sidx_dev,
+                                           double *T16_dev, size_t n_pairs, const ndtgpu_match_params *prm,
+                                           ndtgpu_match_result *results_dev, ndtgpu_stream stream, int cov_mode, double *cov36_dev,
+                                           int32_t *cov_flags_dev, double *T16_save_dev)
 {
     if (!ts || !ss || (n_pairs && (!tidx_dev || !sidx_dev || !T16_dev || !results_dev)))
         return fail(NDTGPU_ERR_INVALID, "match_batch_device: bad argument");
@@ -1157,18 +1162,40 @@ ndtgpu_status ndtgpu_match_batch_device(ndtgpu_mapset *ts, const uint32_t *tidx_
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         CoopPlan pl;
         if (n_pairs > 0 && n_pairs <= (size_t)n_cu / 2 && ss->v.grid.max_cells >= NDTGPU_COOP_MIN_SET_CELLS && !(dc_env && atoi(dc_env) == 0) &&
-            hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone && coop_plan(ss, n_pairs, p, pl)) {
+            hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone && coop_plan(ss, n_pairs, p, pl) &&
+            (cov_mode < 0 || T16_save_dev)) {
             std::lock_guard<std::mutex> coop_lock(g_coop_mutex);
             ndtgpu_status rc = ts->ensure_coop(n_pairs * pl.stride + (pl.pool ? ndt_match_pool_ctrl_bytes() : 0));
             if (rc != NDTGPU_OK) return rc;
             ts->coop_clean_stride = pl.stride;
             ts->coop_clean_upto = 0;                            // (nobody will look how this launch ended: the next call clears)
             ts->ev_valid[1] = false;
-            return coop_enqueue(ts, ss, tidx_dev, sidx_dev, T16_dev, reinterpret_cast<NdtMatchResultDev *>(results_dev), nullptr,
-                                n_pairs, p, pl, true, true, st);
+            if (cov_mode >= 0) HIP_TRY(hipMemcpyAsync(T16_save_dev, T16_dev, n_pairs * 16 * sizeof(double), hipMemcpyDeviceToDevice, st));
+            rc = coop_enqueue(ts, ss, tidx_dev, sidx_dev, T16_dev, reinterpret_cast<NdtMatchResultDev *>(results_dev), nullptr,
+                              n_pairs, p, pl, true, true, st);
+            if (rc != NDTGPU_OK || cov_mode < 0) return rc;
+            // (these registrations run on many workgroups each: the covariance is a follow-on launch, as in the fuser bank)
+            hipError_t e = ndt_launch_covariance(ts->v, tidx_dev, ss->v, sidx_dev, T16_dev, n_pairs, p.n_neighbours, p.lfd1, p.lfd2,
+                                                 cov_mode, cov36_dev, cov_flags_dev, st);
+            if (e == hipSuccess)
+                e = ndt_launch_cov_flags(T16_save_dev, T16_dev, reinterpret_cast<const NdtMatchResultDev *>(results_dev), cov36_dev,
+                                         cov_flags_dev, n_pairs, st);
+            if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "match: covariance launch", e);
+            { ndtgpu_status trc = ts->touch(st); if (trc != NDTGPU_OK) return trc; }
+            if (ss != ts) { ndtgpu_status trc = ss->touch(st); if (trc != NDTGPU_OK) return trc; }
+            return NDTGPU_OK;
         }
     }
-    return match_device_core(ts, tidx_dev, ss, sidx_dev, T16_dev, n_pairs, p, results_dev, nullptr, (hipStream_t)stream);
+    return match_device_core(ts, tidx_dev, ss, sidx_dev, T16_dev, n_pairs, p, results_dev, nullptr, (hipStream_t)stream, nullptr,
+                             nullptr, cov_mode, cov36_dev, cov_flags_dev);
+}
+
+ndtgpu_status ndtgpu_match_batch_device(ndtgpu_mapset *ts, const uint32_t *tidx_dev, ndtgpu_mapset *ss,
+                                        const uint32_t *sidx_dev, double *T16_dev, size_t n_pairs,
+                                        const ndtgpu_match_params *prm, ndtgpu_match_result *results_dev,
+                                        ndtgpu_stream stream)
+{
+    return match_batch_device_ex(ts, tidx_dev, ss, sidx_dev, T16_dev, n_pairs, prm, results_dev, stream, -1, nullptr, nullptr, nullptr);
 }
 
 // ---- the registrar: scans in, poses out (include/ndtgpu.h) ---------------------------------------------------------------
@@ -1236,6 +1263,9 @@ struct ndtgpu_registrar {
         return NDTGPU_OK;
     }
     int stream_nn = -1;
+    int stream_cov = 0;                // the running instances' kind: 1 = with the covariance tail (an instance is compiled for one)
+    double *cov_save = nullptr;        // per-batch form, grid-barrier / pool sub-batches with a covariance: the initial guesses of
+    size_t cov_save_pairs = 0;         // slot k at [k * per * 16] (the match overwrites them; ndt_cov_flags_kernel compares)
     int n_cu = 256;
     // the split of the chip is measured on a sub-batch and re-measured when the maps change: per slot the map counters of
     // the last build travel to pinned host memory on a side stream; a later call looks at what has arrived (no waiting)
@@ -1302,6 +1332,7 @@ ndtgpu_status ndtgpu_registrar_destroy(ndtgpu_registrar *r)
     for (hipStream_t st : r->streams)
         if (st) (void)hipStreamDestroy(st);
     if (r->iota) (void)hipFree(r->iota);
+    if (r->cov_save) (void)hipFree(r->cov_save);
     delete r;
     return NDTGPU_OK;
 }
@@ -1531,16 +1562,20 @@ ndtgpu_status ndtgpu_registrar_kernel_ms(ndtgpu_registrar *r, float mean_ms[2], 
     return NDTGPU_OK;
 }
 
-ndtgpu_status ndtgpu_register_batch_device(ndtgpu_registrar *r, const void *targets_dev, const void *sources_dev, size_t n_points,
-                                           size_t stride_bytes, size_t map_stride_bytes, double range_limit,
-                                           const ndtgpu_cell_params *cell, double *T16_dev, size_t n_pairs,
-                                           const ndtgpu_match_params *prm, ndtgpu_match_result *results_dev, ndtgpu_stream stream,
-                                           uint64_t *ticket)
+// ndtgpu_register_batch_device (cov_mode < 0) and ndtgpu_register_batch_cov_device (cov_mode 0 / 1): one code path
+static ndtgpu_status register_batch_core(ndtgpu_registrar *r, const void *targets_dev, const void *sources_dev, size_t n_points,
+                                         size_t stride_bytes, size_t map_stride_bytes, double range_limit,
+                                         const ndtgpu_cell_params *cell, double *T16_dev, size_t n_pairs,
+                                         const ndtgpu_match_params *prm, ndtgpu_match_result *results_dev, ndtgpu_stream stream,
+                                         uint64_t *ticket, int cov_mode, double *cov36_dev, int32_t *cov_flags_dev)
 {
     if (ticket) *ticket = r ? (uint64_t)r->submitted : 0;
     if (!r || (n_pairs && (!T16_dev || !results_dev || (n_points && (!targets_dev || !sources_dev)))) || stride_bytes < 12 ||
         (stride_bytes & 3) || n_points > 0xFFFFFFFFull)
         return fail(NDTGPU_ERR_INVALID, "register_batch_device: bad argument");
+    const bool with_cov = cov_mode >= 0;
+    if (with_cov && n_pairs && (!cov36_dev || !cov_flags_dev))
+        return fail(NDTGPU_ERR_INVALID, "register_batch_cov_device: bad argument (cov36_dev / cov_flags_dev)");
     if (n_pairs == 0) return NDTGPU_OK;
     NdtMatchParamsDev pdev = to_dev(prm);
     pdev.fusion_flags = 0;
@@ -1575,9 +1610,11 @@ ndtgpu_status ndtgpu_register_batch_device(ndtgpu_registrar *r, const void *targ
             if (r->hst) HIP_TRY(hipStreamSynchronize(r->hst));
             return NDTGPU_OK;
         };
-        if (r->stream_nn != pdev.n_neighbours) {                 // (an instance is compiled for one neighbourhood size)
+        // (an instance is compiled for one neighbourhood size, and with or without the covariance tail)
+        if (r->stream_nn != pdev.n_neighbours || r->stream_cov != (with_cov ? 1 : 0)) {
             if (r->stream_nn >= 0) { ndtgpu_status drc = drain(); if (drc != NDTGPU_OK) return drc; }
             r->stream_nn = pdev.n_neighbours;
+            r->stream_cov = with_cov ? 1 : 0;
         }
         for (size_t off = 0; off < n_pairs; off += r->per) {
             const size_t p = std::min(r->per, n_pairs - off);
@@ -1631,7 +1668,8 @@ ndtgpu_status ndtgpu_register_batch_device(ndtgpu_registrar *r, const void *targ
                 if (mk0) { HIP_TRY(hipEventRecord(mk0->e[1], st)); HIP_TRY(hipEventRecord(mk0->e[2], st)); }
                 const unsigned saved_groups = set->match_groups;
                 set->match_groups = 0;                            // (the whole chip)
-                rc0 = ndtgpu_match_batch_device(set, r->iota, set, r->iota + p, T16_dev + off * 16, p, prm, results_dev + off, st);
+                rc0 = match_batch_device_ex(set, r->iota, set, r->iota + p, T16_dev + off * 16, p, prm, results_dev + off, st, cov_mode,
+                                            with_cov ? cov36_dev + off * 36 : nullptr, with_cov ? cov_flags_dev + off : nullptr, nullptr);
                 set->match_groups = saved_groups;
                 if (rc0 != NDTGPU_OK) return rc0;
                 if (mk0) HIP_TRY(hipEventRecord(mk0->e[3], st));
@@ -1816,18 +1854,25 @@ ndtgpu_status ndtgpu_register_batch_device(ndtgpu_registrar *r, const void *targ
             HIP_TRY(hipEventRecord(r->built[slot], st));
             HIP_TRY(hipStreamWaitEvent(r->pst, r->built[slot], 0));
             hipError_t pe = ndt_stream_publish(r->queue, set->v, T16_dev + off * 16, reinterpret_cast<NdtMatchResultDev *>(results_dev + off),
-                                               pdev, (unsigned)p, (unsigned)j, r->pst);
+                                               pdev, (unsigned)p, (unsigned)j, r->pst, with_cov ? cov_mode : -1,
+                                               with_cov ? cov36_dev + off * 36 : nullptr, with_cov ? cov_flags_dev + off : nullptr);
             if (pe != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: publish", pe);
             HIP_TRY(hipEventRecord(r->pub_ev[slot], r->pst));
             // every published batch is followed by an instance launch: it starts when the running instance has ended (and
             // then serves this batch and whatever is published while it runs), or finds the batch taken and leaves
             HIP_TRY(hipStreamWaitEvent(r->mst, r->pub_ev[slot], 0));
-            pe = ndt_launch_match_stream(r->queue, pdev.n_neighbours, r->stream_slots, r->stream_groups, r->mst);
+            pe = ndt_launch_match_stream(r->queue, pdev.n_neighbours, r->stream_slots, r->stream_groups, r->mst, r->stream_cov);
             if (pe != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: matcher launch", pe);
             r->submitted++;
             if (ticket) *ticket = (uint64_t)r->submitted;
         }
         return NDTGPU_OK;
+    }
+    if (with_cov && !r->cov_save) {
+        // (only grid-barrier / pool sub-batches read it -- sets of large maps, at most half as many pairs as CUs)
+        const size_t n = std::min(r->per, (size_t)r->n_cu);
+        HIP_TRY(hipMalloc((void **)&r->cov_save, (size_t)r->depth * n * 16 * sizeof(double)));
+        r->cov_save_pairs = n;
     }
     for (size_t off = 0; off < n_pairs; off += r->per) {
         const size_t p = std::min(r->per, n_pairs - off);
@@ -1852,7 +1897,9 @@ ndtgpu_status ndtgpu_register_batch_device(ndtgpu_registrar *r, const void *targ
             const int n_gap = env_int("NDTGPU_REG_GAP", 2);
             for (int g = 0; g < n_gap; g++) HIP_TRY(hipMemsetAsync(r->iota + 2 * r->per, 0, 4, st));
         }
-        rc = ndtgpu_match_batch_device(set, r->iota, set, r->iota + p, T16_dev + off * 16, p, prm, results_dev + off, st);
+        rc = match_batch_device_ex(set, r->iota, set, r->iota + p, T16_dev + off * 16, p, prm, results_dev + off, st, cov_mode,
+                                   with_cov ? cov36_dev + off * 36 : nullptr, with_cov ? cov_flags_dev + off : nullptr,
+                                   with_cov && p <= r->cov_save_pairs ? r->cov_save + (size_t)slot * r->cov_save_pairs * 16 : nullptr);
         if (rc != NDTGPU_OK) return rc;
         if (mk) HIP_TRY(hipEventRecord(mk->e[3], st));
         HIP_TRY(hipEventRecord(r->done[r->submitted % r->done.size()], st));
@@ -1860,6 +1907,30 @@ ndtgpu_status ndtgpu_register_batch_device(ndtgpu_registrar *r, const void *targ
         if (ticket) *ticket = (uint64_t)r->submitted;      // "every sub-batch before this count"
     }
     return NDTGPU_OK;
+}
+
+ndtgpu_status ndtgpu_register_batch_device(ndtgpu_registrar *r, const void *targets_dev, const void *sources_dev, size_t n_points,
+                                           size_t stride_bytes, size_t map_stride_bytes, double range_limit,
+                                           const ndtgpu_cell_params *cell, double *T16_dev, size_t n_pairs,
+                                           const ndtgpu_match_params *prm, ndtgpu_match_result *results_dev, ndtgpu_stream stream,
+                                           uint64_t *ticket)
+{
+    return register_batch_core(r, targets_dev, sources_dev, n_points, stride_bytes, map_stride_bytes, range_limit, cell, T16_dev, n_pairs,
+                               prm, results_dev, stream, ticket, -1, nullptr, nullptr);
+}
+
+ndtgpu_status ndtgpu_register_batch_cov_device(ndtgpu_registrar *r, const void *targets_dev, const void *sources_dev, size_t n_points,
+                                               size_t stride_bytes, size_t map_stride_bytes, double range_limit,
+                                               const ndtgpu_cell_params *cell, double *T16_dev, size_t n_pairs,
+                                               const ndtgpu_match_params *prm, ndtgpu_match_result *results_dev, int covariance_mode,
+                                               double *cov36_dev, int32_t *cov_flags_dev, ndtgpu_stream stream, uint64_t *ticket)
+{
+    if (covariance_mode != 0 && covariance_mode != 1) {
+        if (ticket) *ticket = r ? (uint64_t)r->submitted : 0;
+        return fail(NDTGPU_ERR_INVALID, "register_batch_cov_device: covariance_mode must be 0 or 1");
+    }
+    return register_batch_core(r, targets_dev, sources_dev, n_points, stride_bytes, map_stride_bytes, range_limit, cell, T16_dev, n_pairs,
+                               prm, results_dev, stream, ticket, covariance_mode, cov36_dev, cov_flags_dev);
 }
 
 ndtgpu_status ndtgpu_registrar_wait_stream(ndtgpu_registrar *r, uint64_t ticket, ndtgpu_stream stream)
@@ -1905,7 +1976,8 @@ ndtgpu_status ndtgpu_registrar_sync(ndtgpu_registrar *r)
             if ((unsigned)n_cu > r->stream_groups + 8u) {
                 if (!r->hst) HIP_TRY(hipStreamCreateWithFlags(&r->hst, hipStreamNonBlocking));
                 HIP_TRY(hipStreamWaitEvent(r->hst, r->pub_ev[(r->submitted - 1) % (size_t)r->depth], 0));
-                hipError_t he = ndt_launch_match_stream(r->queue, r->stream_nn, r->stream_slots, (unsigned)n_cu - r->stream_groups, r->hst);
+                hipError_t he = ndt_launch_match_stream(r->queue, r->stream_nn, r->stream_slots, (unsigned)n_cu - r->stream_groups, r->hst,
+                                                        r->stream_cov);
                 if (he != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: helper launch", he);
             }
             r->helped = r->submitted;
@@ -1962,27 +2034,34 @@ ndtgpu_status ndtgpu_registrar_sync(ndtgpu_registrar *r)
 // sub-batch the scans travel to a device staging area of the slot they will be built in (one copy stream; the copies of
 // sub-batch j + 1 run under the builds and registrations of sub-batch j), then the device entry takes over; poses and results
 // come back with one copy each when everything is done.  Synchronous.
-ndtgpu_status ndtgpu_register_batch_host(ndtgpu_registrar *r, const void *targets_host, const void *sources_host, size_t n_points,
-                                         size_t stride_bytes, size_t map_stride_bytes, double range_limit,
-                                         const ndtgpu_cell_params *cell, double *T16, size_t n_pairs, const ndtgpu_match_params *prm,
-                                         ndtgpu_match_result *results)
+static ndtgpu_status register_batch_host_core(ndtgpu_registrar *r, const void *targets_host, const void *sources_host, size_t n_points,
+                                              size_t stride_bytes, size_t map_stride_bytes, double range_limit,
+                                              const ndtgpu_cell_params *cell, double *T16, size_t n_pairs, const ndtgpu_match_params *prm,
+                                              ndtgpu_match_result *results, int cov_mode, double *cov36, int32_t *cov_flags)
 {
     if (!r || (n_pairs && (!T16 || !results || (n_points && (!targets_host || !sources_host)))) || stride_bytes < 12 ||
         (stride_bytes & 3) || n_points > 0xFFFFFFFFull || (n_pairs > 1 && map_stride_bytes < n_points * stride_bytes))
         return fail(NDTGPU_ERR_INVALID, "register_batch_host: bad argument (clouds must not overlap: map_stride_bytes >= n_points * stride_bytes)");
+    const bool with_cov = cov_mode >= 0;
+    if (with_cov && n_pairs && (!cov36 || !cov_flags)) return fail(NDTGPU_ERR_INVALID, "register_batch_cov_host: bad argument (cov36 / cov_flags)");
     if (n_pairs == 0) return NDTGPU_OK;
     if (!r->hcopy) HIP_TRY(hipStreamCreateWithFlags(&r->hcopy, hipStreamNonBlocking));
     if (r->hstage.empty()) { r->hstage.assign(r->depth, nullptr); r->hstage_bytes.assign(r->depth, 0); }
     const size_t bT = n_pairs * 16 * sizeof(double), bR = n_pairs * sizeof(ndtgpu_match_result), offR = (bT + 255) & ~(size_t)255;
-    if (r->hio_bytes < offR + bR) {
+    // (with the covariance: 36 doubles and a flag word per pair behind the results)
+    const size_t bC = with_cov ? n_pairs * 36 * sizeof(double) : 0, offC = (offR + bR + 255) & ~(size_t)255;
+    const size_t bF = with_cov ? n_pairs * sizeof(int32_t) : 0, offF = offC + bC, need_io = with_cov ? offF + bF : offR + bR;
+    if (r->hio_bytes < need_io) {
         HIP_TRY(hipStreamSynchronize(r->hcopy));
         if (r->hio) (void)hipFree(r->hio);
         r->hio = nullptr; r->hio_bytes = 0;
-        HIP_TRY(hipMalloc(&r->hio, offR + bR));
-        r->hio_bytes = offR + bR;
+        HIP_TRY(hipMalloc(&r->hio, need_io));
+        r->hio_bytes = need_io;
     }
     double *T_dev = (double *)r->hio;
     ndtgpu_match_result *R_dev = (ndtgpu_match_result *)((char *)r->hio + offR);
+    double *C_dev = with_cov ? (double *)((char *)r->hio + offC) : nullptr;
+    int32_t *F_dev = with_cov ? (int32_t *)((char *)r->hio + offF) : nullptr;
     HIP_TRY(hipMemcpyAsync(T_dev, T16, bT, hipMemcpyHostToDevice, r->hcopy));
     const size_t cloud_bytes = n_points * stride_bytes;
     for (size_t off = 0; off < n_pairs; off += r->per) {
@@ -2004,15 +2083,40 @@ ndtgpu_status ndtgpu_register_batch_host(ndtgpu_registrar *r, const void *target
             HIP_TRY(hipMemcpyAsync(sc, (const char *)sources_host + off * map_stride_bytes, half, hipMemcpyHostToDevice, r->hcopy));
         }
         // (p <= pairs_per_batch: ONE sub-batch, in this slot, behind these copies)
-        ndtgpu_status rc = ndtgpu_register_batch_device(r, tg, sc, n_points, stride_bytes, map_stride_bytes, range_limit, cell,
-                                                        T_dev + off * 16, p, prm, R_dev + off, (ndtgpu_stream)r->hcopy, nullptr);
+        ndtgpu_status rc = register_batch_core(r, tg, sc, n_points, stride_bytes, map_stride_bytes, range_limit, cell, T_dev + off * 16, p,
+                                               prm, R_dev + off, (ndtgpu_stream)r->hcopy, nullptr, cov_mode,
+                                               with_cov ? C_dev + off * 36 : nullptr, with_cov ? F_dev + off : nullptr);
         if (rc != NDTGPU_OK) return rc;
     }
     ndtgpu_status rc = ndtgpu_registrar_sync(r);
     if (rc != NDTGPU_OK) return rc;
     HIP_TRY(hipMemcpy(T16, T_dev, bT, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(results, R_dev, bR, hipMemcpyDeviceToHost));
+    if (with_cov) {
+        HIP_TRY(hipMemcpy(cov36, C_dev, bC, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cov_flags, F_dev, bF, hipMemcpyDeviceToHost));
+    }
     return NDTGPU_OK;
+}
+
+ndtgpu_status ndtgpu_register_batch_host(ndtgpu_registrar *r, const void *targets_host, const void *sources_host, size_t n_points,
+                                         size_t stride_bytes, size_t map_stride_bytes, double range_limit,
+                                         const ndtgpu_cell_params *cell, double *T16, size_t n_pairs, const ndtgpu_match_params *prm,
+                                         ndtgpu_match_result *results)
+{
+    return register_batch_host_core(r, targets_host, sources_host, n_points, stride_bytes, map_stride_bytes, range_limit, cell, T16,
+                                    n_pairs, prm, results, -1, nullptr, nullptr);
+}
+
+ndtgpu_status ndtgpu_register_batch_cov_host(ndtgpu_registrar *r, const void *targets_host, const void *sources_host, size_t n_points,
+                                             size_t stride_bytes, size_t map_stride_bytes, double range_limit,
+                                             const ndtgpu_cell_params *cell, double *T16, size_t n_pairs, const ndtgpu_match_params *prm,
+                                             ndtgpu_match_result *results, int covariance_mode, double *cov36, int32_t *cov_flags)
+{
+    if (covariance_mode != 0 && covariance_mode != 1)
+        return fail(NDTGPU_ERR_INVALID, "register_batch_cov_host: covariance_mode must be 0 or 1");
+    return register_batch_host_core(r, targets_host, sources_host, n_points, stride_bytes, map_stride_bytes, range_limit, cell, T16,
+                                    n_pairs, prm, results, covariance_mode, cov36, cov_flags);
 }
 
 // host arrays -> staging -> persistent matcher -> host arrays; synchronous

@@ -656,6 +656,27 @@ public:
                             double range_limit = -1., bool useInitialGuess = true, std::vector<ndtgpu_match_result> *results = nullptr,
                             int dof_mask = 0x3f)
     {
+        return run(matcher, fixed, moving, T, range_limit, useInitialGuess, results, dof_mask, nullptr, nullptr);
+    }
+
+    // ... and NDTMatcherD2D::covariance(fixed, moving, T, cov) of every pair at its registered pose, as the link update computes it
+    // after each match (ndt_feature_graph.cpp:283-310; matcher.covariance_mode selects the row formula): cov[k] the full 6x6
+    // whatever dof_mask is, cov_flags[k] the NDTGPU_COV_* bits (NDTGPU_COV_POSE_UNCHANGED: the pose is the initial guess bit for bit
+    // -- where the graph substitutes 0.02 I, graph.cpp:283-291)
+    std::vector<bool> match(const lslgeneric::NDTMatcherD2D &matcher, const std::vector<pcl::PointCloud<pcl::PointXYZ>> &fixed,
+                            const std::vector<pcl::PointCloud<pcl::PointXYZ>> &moving, std::vector<Eigen::Affine3d> &T,
+                            std::vector<Eigen::MatrixXd> &cov, std::vector<int32_t> &cov_flags, double range_limit = -1.,
+                            bool useInitialGuess = true, std::vector<ndtgpu_match_result> *results = nullptr, int dof_mask = 0x3f)
+    {
+        return run(matcher, fixed, moving, T, range_limit, useInitialGuess, results, dof_mask, &cov, &cov_flags);
+    }
+
+private:
+    std::vector<bool> run(const lslgeneric::NDTMatcherD2D &matcher, const std::vector<pcl::PointCloud<pcl::PointXYZ>> &fixed,
+                          const std::vector<pcl::PointCloud<pcl::PointXYZ>> &moving, std::vector<Eigen::Affine3d> &T, double range_limit,
+                          bool useInitialGuess, std::vector<ndtgpu_match_result> *results, int dof_mask, std::vector<Eigen::MatrixXd> *cov,
+                          std::vector<int32_t> *cov_flags)
+    {
         const size_t n = fixed.size();
         if (moving.size() != n || T.size() != n) throw Error(NDTGPU_ERR_INVALID, "ScanRegistrar::match: one moving cloud and one pose per fixed cloud");
         size_t np = 0;
@@ -680,8 +701,20 @@ public:
             for (int e = 0; e < 16; e++) T16[16 * k + e] = T[k].data()[e];
         std::vector<ndtgpu_match_result> res(n);
         ndtgpu_match_params p = matcher.params(dof_mask, useInitialGuess);
-        check(ndtgpu_register_batch_host(reg_, pts_.data(), pts_.data() + n * np * 4, np, 16, np * 16, range_limit, nullptr, T16.data(), n, &p,
-                                         res.data()), "ndtgpu_register_batch_host");
+        if (cov) {
+            std::vector<double> c36(36 * n);
+            cov_flags->assign(n, 0);
+            check(ndtgpu_register_batch_cov_host(reg_, pts_.data(), pts_.data() + n * np * 4, np, 16, np * 16, range_limit, nullptr, T16.data(),
+                                                 n, &p, res.data(), matcher.covariance_mode, c36.data(), cov_flags->data()),
+                  "ndtgpu_register_batch_cov_host");
+            cov->assign(n, Eigen::MatrixXd(6, 6));
+            for (size_t k = 0; k < n; k++)
+                for (int a = 0; a < 6; a++)
+                    for (int b = 0; b < 6; b++) (*cov)[k](a, b) = c36[36 * k + a * 6 + b];
+        } else {
+            check(ndtgpu_register_batch_host(reg_, pts_.data(), pts_.data() + n * np * 4, np, 16, np * 16, range_limit, nullptr, T16.data(), n,
+                                             &p, res.data()), "ndtgpu_register_batch_host");
+        }
         std::vector<bool> ok(n);
         for (size_t k = 0; k < n; k++) {
             for (int e = 0; e < 16; e++) T[k].data()[e] = T16[16 * k + e];
@@ -691,7 +724,6 @@ public:
         return ok;
     }
 
-private:
     ndtgpu_registrar *reg_ = nullptr;
     std::vector<float> pts_;
 };
