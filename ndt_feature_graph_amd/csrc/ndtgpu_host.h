@@ -1,0 +1,277 @@
+// ndtgpu_host.h -- what the C-ABI sources share (ndtgpu_api.hip: map sets; ndtgpu_matcher.hip; ndtgpu_registrar.hip;
+// ndtgpu_fuser_bank.hip): error reporting, the map set handle and the helpers one of them defines for the others.  Host
+// side only and internal: not installed, and nothing declared here is exported from libndtgpu.so.
+#pragma once
+#include "../../include/ndtgpu.h"
+#include "ndt_math.h"
+#include "ndt_solver.h"
+#include "ndt_pose.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+
+extern thread_local std::string g_err;      // (ndtgpu_api.hip: what ndtgpu_last_error returns)
+
+inline ndtgpu_status fail(ndtgpu_status s, const char *what, hipError_t e = hipSuccess)
+{
+    char buf[512];
+    if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
+    else snprintf(buf, sizeof buf, "%s", what);
+    g_err = buf;
+    return s;
+}
+
+#define HIP_TRY(expr)                                                       \
+    do {                                                                    \
+        hipError_t _e = (expr);                                             \
+        if (_e != hipSuccess) return fail(NDTGPU_ERR_HIP, #expr, _e);       \
+    } while (0)
+
+inline bool have_device()
+{
+    int n = 0;
+    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
+}
+
+inline int device_cus()
+{
+    int dev = 0, n_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
+        n_cu = 256;
+    return n_cu;
+}
+
+// An experiment's environment variable overrides a field the caller LEFT AT ITS DEFAULT (0 / auto); what a caller sets wins.
+inline int env_int(const char *name, int fallback)
+{
+    const char *e = getenv(name);
+    return e ? atoi(e) : fallback;
+}
+
+struct CoopOrder;     // (ndtgpu_matcher.hip: the last grid-barrier launch of a device)
+
+struct ndtgpu_mapset {
+    NdtSetView v{};
+    size_t n_maps = 0;
+    std::vector<double> centres_host;
+    std::vector<unsigned char> nice_host;   // per map: fp32 cell offsets are exact (ndt_grid_is_nice)
+    int nice_range(size_t first, size_t count) const
+    {
+        for (size_t m = first; m < first + count; m++)
+            if (!nice_host[m]) return 0;
+        return 1;
+    }
+    // Streams that may still hold work on this set (writers: builds, unpack, add_cloud; readers: matcher launches): one event
+    // per recently used stream, recorded AFTER the launch.  The host-synchronous entries wait for these events -- not for
+    // stream handles, which the caller may have destroyed since, and not only for the last writer (a matcher that still reads
+    // the maps on another stream is waited for as well).
+    struct StreamMark { hipStream_t st; hipEvent_t ev; };
+    std::vector<StreamMark> marks;
+    bool null_stream_used = false;       // the null stream needs no event: its handle is always valid (and an event record
+                                         // costs the reference's one-pair-at-a-time call shape ~10 us of its 0.37 ms)
+    ndtgpu_status touch(hipStream_t st)
+    {
+        if (st == nullptr) { null_stream_used = true; return NDTGPU_OK; }
+        for (StreamMark &m : marks)
+            if (m.st == st) { HIP_TRY(hipEventRecord(m.ev, st)); return NDTGPU_OK; }
+        if (marks.size() >= 8) {                 // many streams over time: retire the oldest entry once its work is done
+            HIP_TRY(hipEventSynchronize(marks.front().ev));
+            (void)hipEventDestroy(marks.front().ev);
+            marks.erase(marks.begin());
+        }
+        StreamMark m{st, nullptr};
+        HIP_TRY(hipEventCreateWithFlags(&m.ev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(m.ev, st));
+        marks.push_back(m);
+        return NDTGPU_OK;
+    }
+    // ... for work that is about to be enqueued on `st`: what was recorded on `st` itself is ordered by the stream
+    ndtgpu_status wait_all_on(hipStream_t st)
+    {
+        if (null_stream_used && st != nullptr) { HIP_TRY(hipStreamSynchronize(nullptr)); null_stream_used = false; }
+        for (StreamMark &m : marks)
+            if (m.st != st) HIP_TRY(hipEventSynchronize(m.ev));
+        return NDTGPU_OK;
+    }
+    ndtgpu_status wait_all()
+    {
+        if (null_stream_used) { HIP_TRY(hipStreamSynchronize(nullptr)); null_stream_used = false; }
+        for (StreamMark &m : marks) HIP_TRY(hipEventSynchronize(m.ev));
+        return NDTGPU_OK;
+    }
+    // staging buffers reused across calls
+    void *stage = nullptr;
+    size_t stage_bytes = 0;
+    double *origins_dev = nullptr;
+    size_t origins_cap = 0;
+    hipEvent_t origins_ev = nullptr;   // recorded after the last launch that reads origins_dev (it may be on another stream)
+    bool origins_ev_valid = false;
+    // room for `n` doubles in origins_dev, ordered behind its last reader: `st` waits for that launch before the buffer is
+    // overwritten (or the host does, before it is replaced)
+    ndtgpu_status origins_reserve(size_t n, hipStream_t st)
+    {
+        if (origins_cap < n) {
+            if (origins_ev_valid) HIP_TRY(hipEventSynchronize(origins_ev));
+            if (origins_dev) (void)hipFree(origins_dev);
+            origins_dev = nullptr;
+            origins_cap = 0;
+            HIP_TRY(hipMalloc((void **)&origins_dev, n * sizeof(double)));
+            origins_cap = n;
+        } else if (origins_ev_valid) {
+            HIP_TRY(hipStreamWaitEvent(st, origins_ev, 0));
+        }
+        return NDTGPU_OK;
+    }
+    ndtgpu_status origins_used(hipStream_t st)
+    {
+        if (!origins_ev) HIP_TRY(hipEventCreateWithFlags(&origins_ev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(origins_ev, st));
+        origins_ev_valid = true;
+        return NDTGPU_OK;
+    }
+    // workgroups the persistent matcher launches with this set as target get at most (0: one per CU).  The registrar keeps its
+    // matcher launches on part of the chip: the rest stays free for the next sub-batch's builds while a launch runs
+    unsigned match_groups = 0;
+    // matcher work area: ticket counters, parked list, parked solver states
+    void *work = nullptr;
+    size_t work_bytes = 0;
+    hipEvent_t work_ev = nullptr;      // recorded after the last launch that uses `work`
+    bool work_ev_valid = false;
+    hipStream_t work_stream = nullptr;
+    // profiling hooks: [0,1] bracket the build kernel, [2,3] the match kernel
+    bool profiling = false;
+    bool profile_span = false;         // a chunked host build is ONE bracket: the chunks' launches do not re-record the events
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool ev_valid[2] = {false, false};
+
+    ndtgpu_status ensure_work(size_t bytes)
+    {
+        if (bytes <= work_bytes) return NDTGPU_OK;
+        if (work) (void)hipFree(work);
+        work = nullptr;
+        work_bytes = 0;
+        HIP_TRY(hipMalloc(&work, bytes));
+        work_bytes = bytes;
+        return NDTGPU_OK;
+    }
+    // work area of the grid-barrier matcher (a control block + partial sums per registration); its kernels leave the
+    // control blocks zeroed, so a call only clears what it cannot know to be clean
+    void *coop_work = nullptr;
+    size_t coop_bytes = 0, coop_clean_stride = 0, coop_clean_upto = 0;
+    // (both defined in ndtgpu_matcher.hip: a block that grows is freed once the device's last grid-barrier launch, which may
+    //  still use it, has ended)
+    ndtgpu_status ensure_coop(size_t bytes, const CoopOrder &last);
+    // pinned host mirror of small staging blocks (poses, indices, results of a host-pointer matcher call): copies from /
+    // to pinned memory are truly asynchronous and skip the runtime's own bounce buffer
+    void *pin = nullptr;
+    size_t pin_bytes = 0;
+    ndtgpu_status ensure_pin(size_t bytes, const CoopOrder &last);
+    // Host clouds (the reference's call sites hand over pcl::PointCloud on the host): a ring of pinned slots that host
+    // threads fill from the caller's pageable memory while earlier slots travel to the device and earlier chunks of
+    // maps are being built (stage_host_clouds below).  The copies run on a stream of their own.
+    static constexpr int HOST_SLOTS = 6;
+    static constexpr size_t HOST_SLOT_BYTES = 16u << 20;
+    void *host_ring[HOST_SLOTS] = {};
+    hipEvent_t host_ev[HOST_SLOTS] = {};
+    bool host_ev_used[HOST_SLOTS] = {};
+    hipStream_t host_copy_stream = nullptr;
+    hipStream_t host_build_stream = nullptr;  // the synchronous host-cloud entries build on a stream of their own (no device-wide wait)
+    ndtgpu_status ensure_host_build_stream()
+    {
+        if (!host_build_stream) HIP_TRY(hipStreamCreateWithFlags(&host_build_stream, hipStreamNonBlocking));
+        return NDTGPU_OK;
+    }
+    hipEvent_t stage_free_ev = nullptr;      // recorded after the last kernel that reads the staged clouds
+    bool stage_free_valid = false;
+    ndtgpu_status ensure_host_ring()
+    {
+        if (host_copy_stream) return NDTGPU_OK;
+        for (int k = 0; k < HOST_SLOTS; k++) {
+            HIP_TRY(hipHostMalloc(&host_ring[k], HOST_SLOT_BYTES, hipHostMallocDefault));
+            HIP_TRY(hipEventCreateWithFlags(&host_ev[k], hipEventDisableTiming));
+        }
+        HIP_TRY(hipEventCreateWithFlags(&stage_free_ev, hipEventDisableTiming));
+        HIP_TRY(hipStreamCreateWithFlags(&host_copy_stream, hipStreamNonBlocking));
+        return NDTGPU_OK;
+    }
+    ndtgpu_status ensure_stage(size_t bytes)
+    {
+        if (bytes <= stage_bytes) return NDTGPU_OK;
+        if (stage_free_valid) { HIP_TRY(hipEventSynchronize(stage_free_ev)); stage_free_valid = false; }
+        if (stage) (void)hipFree(stage);
+        stage = nullptr;
+        stage_bytes = 0;
+        HIP_TRY(hipMalloc(&stage, bytes));
+        stage_bytes = bytes;
+        return NDTGPU_OK;
+    }
+};
+
+// Consecutive regions of one staging block, each on a 256-byte boundary: take(bytes) returns where the region starts; `at` is
+// where the next one would.
+struct StageLayout {
+    size_t at = 0;
+    size_t take(size_t bytes)
+    {
+        const size_t o = at;
+        at = (at + bytes + 255) & ~(size_t)255;
+        return o;
+    }
+};
+
+inline NdtMatchParamsDev to_dev(const ndtgpu_match_params *p)
+{
+    ndtgpu_match_params d;
+    ndtgpu_default_match_params(&d);
+    if (p) d = *p;
+    NdtMatchParamsDev o;
+    o.n_neighbours = d.n_neighbours;
+    o.itr_max = d.itr_max;
+    o.step_control = d.step_control;
+    o.dof_mask = d.dof_mask;
+    o.use_initial_guess = d.use_initial_guess;
+    o.delta_score = d.delta_score;
+    o.lfd1 = d.lfd1;
+    o.lfd2 = d.lfd2;
+    o.fusion_flags = 1;
+    return o;
+}
+
+// ndtgpu_api.hip
+// the build proper; `orig_dev`: per-map range origins already in device memory (or NULL: the grid centres)
+ndtgpu_status mapset_build_core(ndtgpu_mapset *s, size_t first, size_t count, const void *xyz_dev, size_t n_points,
+                                size_t stride_bytes, size_t map_stride_bytes, double range_limit, const double *orig_dev,
+                                const ndtgpu_cell_params *cell, hipStream_t st);
+// host-side packing of caller-provided Gaussians into NdtCell records keyed by LazyGrid slot
+ndtgpu_status pack_cells(const NdtGrid &g, const double *centre, const double *mean3, const double *cov9, size_t n, bool need_slot,
+                         std::vector<NdtCell> &out);
+
+// ndtgpu_matcher.hip
+struct MatchKnobs;    // (the matcher's environment switches, read once per call)
+// The persistent matcher on device-resident arguments: asynchronous on `stream`.
+ndtgpu_status match_device_core(ndtgpu_mapset *ts, const uint32_t *tidx_dev, ndtgpu_mapset *ss, const uint32_t *sidx_dev,
+                                double *T16_dev, size_t n_pairs, const NdtMatchParamsDev &p, ndtgpu_match_result *results_dev,
+                                const double *Q36_dev, hipStream_t st, const unsigned *feat_off_dev = nullptr,
+                                const double *feat_cells_dev = nullptr, int cov_mode = -1, double *cov36_dev = nullptr,
+                                int32_t *cov_flags_dev = nullptr, const MatchKnobs *knobs = nullptr);
+// ndtgpu_match_batch_device, and with cov_mode >= 0 the registrar's covariance of every pair at its registered pose: the tail of
+// the persistent kernel (ndt_match_kernel<.., COV = 1>), or -- grid-barrier / pool batches -- a launch of ndt_covariance_kernel
+// behind the match on the same stream and ndt_cov_flags_kernel (T16_save: n_pairs x 16 doubles of device scratch for the initial
+// guesses, which the match overwrites).
+ndtgpu_status match_batch_device_ex(ndtgpu_mapset *ts, const uint32_t *tidx_dev, ndtgpu_mapset *ss, const uint32_t *sidx_dev,
+                                    double *T16_dev, size_t n_pairs, const ndtgpu_match_params *prm,
+                                    ndtgpu_match_result *results_dev, ndtgpu_stream stream, int cov_mode, double *cov36_dev,
+                                    int32_t *cov_flags_dev, double *T16_save_dev);
+// 6x6 inverse by Gauss-Jordan with partial pivoting (Eigen: Tcov.inverse(), fusion.h:845)
+bool invert6(const double *A, double *inv);
+// the device form of a call's match parameters, checked (every matcher entry, the registrar)
+ndtgpu_status match_params_dev(const ndtgpu_match_params *prm, int fusion_flags, NdtMatchParamsDev &p);
+
+#pragma GCC visibility pop
