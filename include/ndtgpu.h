@@ -592,6 +592,73 @@ ndtgpu_status ndtgpu_fuser_update_batch_host(ndtgpu_fuser_bank *bank, size_t fir
  * slots it covered, zeroes for the others */
 ndtgpu_status ndtgpu_fuser_poses(ndtgpu_fuser_bank *bank, size_t first, size_t count, double *Tnow16, ndtgpu_fuser_result *results);
 
+/* ---- coarse to fine: multi-resolution D2D registration of raw scan pairs ----------------------------------------------------
+ * NDTMatcherD2D(isIrregularGrid, useDefaultGridResolutions, resolutions).match(target_pc, source_pc, T, useInitialGuess), the
+ * raw-cloud overload (ndt_feature/src/ndt_odom_debug.cpp:159-165: matcher.match(static_pc, moving_pc, T_p2p, true);
+ * ndt_feature/src/ndt_feature_pcl_eval.cpp:620-642: matcher.match(moving_pc, static_pc, T_p2p)).
+ * PROVENANCE: the body lives in perception_oru (ndt_registration/src/ndt_matcher_d2d.cpp), which the reference does not vendor;
+ * restated from memory:
+ *   - useDefaultGridResolutions: the list is {0.2, 0.5, 1, 2} (ndtgpu_default_resolutions); else the caller's.  isIrregularGrid
+ *     (OctTree maps) has no counterpart here.
+ *   - useInitialGuess: the source cloud is moved by T (transformPointCloudInPlace: a double-precision product, stored back as
+ *     float) and Tinit = T; else Tinit = I.  Then T = I.
+ *   - for r = n_levels - 1 down to 0 -- in LIST order, the list is not sorted: build the target map and the source map (from the
+ *     moved cloud) on a fresh LazyGrid(resolutions[r]); Temp = I; ret = match(targetNDT, sourceNDT, Temp) (the map overload,
+ *     from the identity); move the source cloud by Temp, again rounded to float; T = Temp * T.
+ *   - finally T = T * Tinit; the call returns the last level's ret.
+ *   - n_neighbours, ITR_MAX, DELTA_SCORE, lfd1 / lfd2 and step_control are the same at every level (DELTA_SCORE is not rescaled).
+ * DEVIATION: upstream's un-sized LazyGrid centres each map on the centroid of its cloud (guess_size_).  Here every map of a level
+ * sits on the caller's grid -- ndtgpu_grid_params' centre and size, with res replaced by the level's cell size -- as the
+ * registrar places its maps.  grid->res is ignored.
+ * range_limit <= 0: no range filter (upstream's overload).  A positive value filters each RAW scan around its own origin
+ * (NDTMap::loadPointCloud's test), the source before it is moved.
+ * Outputs: T16 the final T; results[k * n_levels + j] the result of pair k at list position j.  A level that does not run stops
+ * its pair -- a map over max_cells (exit_code -3), or a grid barrier that gave up (-4): every level after it is not run either
+ * and reports the same exit_code, T16 gets the levels that did complete times Tinit.
+ * Work per sub-batch of pairs_per_batch pairs, in turn, asynchronous on `stream`; a call's work waits (on the device) for the
+ * previous call on the same handle, whatever stream that one named -- the handle's map sets and buffers are reused.  The target maps of
+ * a level are built with the library's build kernels; the source build moves each cloud on load (an instance of the flat-grid
+ * kernel, ndt_build_flat_kernel<SD, true>, with a per-map rigid transform that is uniform per workgroup, which also writes the
+ * moved cloud for the next level; levels whose build ndtgpu_mapset_build would not give to the flat kernel -- max_cells <= 4096,
+ * even cell counts, fp32 cell centres, and >= 256 maps per sub-batch unless NDTGPU_FLAT=2 -- ndt_cloud_transform_kernel, then
+ * ndtgpu_mapset_build's own choice of kernel: the maps are those ndtgpu_mapset_build makes of the moved clouds, bit for bit,
+ * either way); the matcher runs in the per-batch
+ * form of ndtgpu_match_batch_device; a small kernel composes the poses between levels.  Each level has its own pair of
+ * internal map sets (2 x pairs_per_batch maps).  Environment NDTGPU_MR_FUSED=0 (read per call): never the fused source build
+ * (A/B measurements, tools/multires_cost.py).  Measured there on MI355X (1024 pairs x 100 k points, the bench's 2D scenes,
+ * max_cells 4096): 84 k registrations/s with the default list (the 0.2 m match is 10.7 of 12.2 ms), 108 k with {0.5, 1, 2, 4};
+ * fused source builds 12.2 / 9.45 ms per call against 12.4 / 9.67 ms for a separate move plus build.  (Holding the transform
+ * costs the fused instances register room: 13 VGPR and 111-113 SGPR spills, 56 bytes of scratch, against 11, 52-60 and 48 for the
+ * plain build.)  ndtgpu_multires_get_info counts the source builds of each kind. */
+typedef struct ndtgpu_multires ndtgpu_multires;
+#define NDTGPU_MAX_LEVELS 8
+void ndtgpu_default_resolutions(double res[4], int *n_levels);    /* {0.2, 0.5, 1, 2}, 4 */
+/* n_levels in 1 .. NDTGPU_MAX_LEVELS and every resolution > 0, else NDTGPU_ERR_INVALID */
+ndtgpu_status ndtgpu_multires_create(const ndtgpu_grid_params *grid, const double *resolutions, int n_levels,
+                                     size_t pairs_per_batch, ndtgpu_multires **out);
+ndtgpu_status ndtgpu_multires_destroy(ndtgpu_multires *mr);
+/* targets_dev / sources_dev: DEVICE clouds as ndtgpu_register_batch_device takes them; T16_dev: DEVICE n_pairs x 16 (in: the
+ * initial guess when use_initial_guess, out: the registered pose); results_dev: DEVICE n_pairs x n_levels.  prm's
+ * use_initial_guess is not read (the argument decides; every level matches from the identity).  Asynchronous on `stream`. */
+ndtgpu_status ndtgpu_register_multires_device(ndtgpu_multires *mr, const void *targets_dev, const void *sources_dev,
+                                              size_t n_points, size_t stride_bytes, size_t map_stride_bytes, double range_limit,
+                                              const ndtgpu_cell_params *cell, double *T16_dev, size_t n_pairs,
+                                              const ndtgpu_match_params *prm, int use_initial_guess,
+                                              ndtgpu_match_result *results_dev, ndtgpu_stream stream);
+typedef struct {
+    int32_t n_levels;
+    size_t pairs_per_batch;
+    uint64_t levels_fused;     /* source builds so far that moved the clouds on load (one per sub-batch and level) */
+    uint64_t levels_unfused;   /* ... and that moved them first (ndt_cloud_transform_kernel), then built */
+} ndtgpu_multires_info;
+ndtgpu_status ndtgpu_multires_get_info(const ndtgpu_multires *mr, ndtgpu_multires_info *info);
+/* the same with clouds, poses and results in HOST memory; synchronous */
+ndtgpu_status ndtgpu_register_multires_host(ndtgpu_multires *mr, const void *targets_host, const void *sources_host,
+                                            size_t n_points, size_t stride_bytes, size_t map_stride_bytes, double range_limit,
+                                            const ndtgpu_cell_params *cell, double *T16, size_t n_pairs,
+                                            const ndtgpu_match_params *prm, int use_initial_guess,
+                                            ndtgpu_match_result *results);
+
 /* single pair convenience == graph.cpp:273 */
 ndtgpu_status ndtgpu_match_d2d(ndtgpu_mapset *target_set, size_t target_map, ndtgpu_mapset *source_set,
                                size_t source_map, double T16[16], const ndtgpu_match_params *prm,

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _SO = os.path.join(_HERE, "libndtgpu.so")
 _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hip", "ndt_pack.hip", "ndt_fuser.hip", "ndtgpu_api.hip",
-            "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip"]
+            "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip"]
 
 STATUS = {0: "OK", -1: "ERR_INVALID", -2: "ERR_HIP", -3: "ERR_NO_DEVICE", -4: "ERR_CAPACITY", -5: "ERR_ALLOC"}
 
@@ -132,7 +132,9 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_default_fuser_params", "ndtgpu_fuser_prepare", "ndtgpu_fuser_bank_create", "ndtgpu_fuser_bank_destroy",
            "ndtgpu_fuser_bank_mapsets", "ndtgpu_fuser_initialize_batch", "ndtgpu_fuser_update_batch", "ndtgpu_fuser_poses",
            "ndtgpu_fuser_initialize_batch_host", "ndtgpu_fuser_update_batch_host", "ndtgpu_registrar_inject_abort",
-           "ndtgpu_register_batch_cov_device", "ndtgpu_register_batch_cov_host"]
+           "ndtgpu_register_batch_cov_device", "ndtgpu_register_batch_cov_host", "ndtgpu_default_resolutions",
+           "ndtgpu_multires_create", "ndtgpu_multires_destroy", "ndtgpu_register_multires_device", "ndtgpu_register_multires_host",
+           "ndtgpu_multires_get_info"]
 
 _lib = None
 
@@ -234,6 +236,15 @@ def lib():
     L.ndtgpu_registrar_profiling.argtypes = [vp, C.c_int]
     L.ndtgpu_registrar_kernel_ms.argtypes = [vp, C.POINTER(C.c_float), i32p]
     L.ndtgpu_registrar_mapset.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.ndtgpu_default_resolutions.restype = None
+    L.ndtgpu_default_resolutions.argtypes = [dp, i32p]
+    L.ndtgpu_multires_create.argtypes = [C.POINTER(GridParams), dp, C.c_int, C.c_size_t, C.POINTER(vp)]
+    L.ndtgpu_multires_destroy.argtypes = [vp]
+    L.ndtgpu_multires_get_info.argtypes = [vp, C.POINTER(MultiResInfo)]
+    L.ndtgpu_register_multires_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(CellParams),
+                                                  vp, C.c_size_t, C.POINTER(MatchParams), C.c_int, vp, vp]
+    L.ndtgpu_register_multires_host.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(CellParams),
+                                                dp, C.c_size_t, C.POINTER(MatchParams), C.c_int, vp]
     _lib = L
     return L
 
@@ -699,6 +710,95 @@ class Registrar:
         h = C.c_void_p()
         _check(lib().ndtgpu_registrar_mapset(self.h, int(slot), C.byref(h)))
         return _BorrowedMapSet(h, 2 * self.per, self.res)
+
+
+MAX_LEVELS = 8      # NDTGPU_MAX_LEVELS
+
+
+class MultiResInfo(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("pairs_per_batch", C.c_size_t), ("levels_fused", C.c_uint64), ("levels_unfused", C.c_uint64)]
+
+
+def default_resolutions():
+    """NDTMatcherD2D's default list (ndtgpu_default_resolutions): (0.2, 0.5, 1.0, 2.0)"""
+    r = (C.c_double * 4)()
+    n = C.c_int32()
+    lib().ndtgpu_default_resolutions(r, C.byref(n))
+    return tuple(r[:n.value])
+
+
+class MultiRes:
+    """ndtgpu_multires: NDTMatcherD2D(irregular, useDefaultGridResolutions, resolutions).match(target_pc, source_pc, T,
+    useInitialGuess) -- coarse-to-fine D2D registration of raw scan pairs, sub-batch after sub-batch of pairs_per_batch
+    (include/ndtgpu.h).  Every level's maps sit on the grid (centre, size_m) at the level's cell size; resolutions=None: the
+    default list.  The levels run from the last entry of the list to the first."""
+
+    def __init__(self, centre, size_m, resolutions=None, pairs_per_batch=1024, max_cells=0):
+        gp = GridParams()
+        gp.res = 0.0                                   # (ignored: each level has its own)
+        gp.centre[:] = [float(x) for x in centre]
+        gp.size[:] = [float(x) for x in size_m]
+        gp.max_cells = int(max_cells)
+        res = default_resolutions() if resolutions is None else tuple(float(r) for r in resolutions)
+        arr = (C.c_double * max(1, len(res)))(*res)
+        h = C.c_void_p()
+        _check(lib().ndtgpu_multires_create(C.byref(gp), arr, len(res), int(pairs_per_batch), C.byref(h)))
+        self.h, self.resolutions, self.per = h, res, int(pairs_per_batch)
+
+    @property
+    def n_levels(self):
+        return len(self.resolutions)
+
+    def info(self):
+        """ndtgpu_multires_get_info: n_levels, pairs_per_batch, and the source builds so far that moved the clouds on load
+        (levels_fused) or before a separate build (levels_unfused)"""
+        i = MultiResInfo()
+        _check(lib().ndtgpu_multires_get_info(self.h, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in MultiResInfo._fields_}
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ndtgpu_multires_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def register_device(self, targets, sources, T16_dev, results_dev, use_initial_guess=True, range_limit=-1.0, n_min=3,
+                        eval_factor=1000.0, stream=None, **params):
+        """targets / sources: torch CUDA float32 [n, N, 3 or 4] (contiguous in the last two dims); T16_dev float64 [n, 16]
+        column-major (in: initial guess, out: pose); results_dev uint8 [n, n_levels * 64] (result of pair k at list position j:
+        record k * n_levels + j).  Asynchronous on `stream`."""
+        n, npts = int(targets.shape[0]), int(targets.shape[1])
+        assert tuple(sources.shape) == tuple(targets.shape) and targets.stride(1) == targets.shape[2] and targets.stride(2) == 1
+        assert sources.stride(0) == targets.stride(0) and sources.stride(1) == targets.stride(1) and sources.stride(2) == 1
+        assert T16_dev.numel() >= 16 * n and results_dev.numel() >= 64 * n * self.n_levels
+        cp = CellParams(int(n_min), float(eval_factor))
+        p = match_params(**params)
+        _check(lib().ndtgpu_register_multires_device(self.h, C.c_void_p(targets.data_ptr()), C.c_void_p(sources.data_ptr()), npts,
+                                                     4 * int(targets.shape[2]), 4 * int(targets.stride(0)), float(range_limit),
+                                                     C.byref(cp), C.c_void_p(T16_dev.data_ptr()), n, C.byref(p),
+                                                     1 if use_initial_guess else 0, C.c_void_p(results_dev.data_ptr()),
+                                                     _stream_ptr(stream)))
+
+    def register_host(self, targets, sources, T, use_initial_guess=True, range_limit=-1.0, n_min=3, eval_factor=1000.0, **params):
+        """Host form: targets / sources NumPy float32 [n, N, 3 or 4], T [n, 4, 4] initial guesses -> (T [n, 4, 4],
+        results [n, n_levels] RESULT_DTYPE, in list order)."""
+        tg = np.ascontiguousarray(targets, dtype=np.float32)
+        sc = np.ascontiguousarray(sources, dtype=np.float32)
+        n, npts, w = tg.shape
+        assert sc.shape == tg.shape and w in (3, 4)
+        Tc = np.ascontiguousarray(np.transpose(np.asarray(T, dtype=np.float64).reshape(n, 4, 4), (0, 2, 1))).copy()
+        res = np.zeros(n * self.n_levels, dtype=RESULT_DTYPE)
+        cp = CellParams(int(n_min), float(eval_factor))
+        p = match_params(**params)
+        _check(lib().ndtgpu_register_multires_host(self.h, C.c_void_p(tg.ctypes.data), C.c_void_p(sc.ctypes.data), npts, 4 * w,
+                                                   4 * w * npts, float(range_limit), C.byref(cp), _dp(Tc), n, C.byref(p),
+                                                   1 if use_initial_guess else 0, C.c_void_p(res.ctypes.data)))
+        return np.transpose(Tc.reshape(n, 4, 4), (0, 2, 1)).copy(), res.reshape(n, self.n_levels)
 
 
 class FuserParams(C.Structure):

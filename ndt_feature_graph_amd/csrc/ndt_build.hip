@@ -1124,25 +1124,22 @@ bool ndt_grid_is_nice(const NdtGrid &g, const double centre[3])
     return true;
 }
 
-hipError_t ndt_launch_build(const NdtSetView &set, size_t first, size_t count, const void *xyz_dev, size_t n_points,
-                            size_t stride_bytes, size_t map_stride_bytes, double range_limit,
-                            const double *range_origins_dev, int n_min, double eval_factor, int nice, hipStream_t stream)
+void ndt_build_shifts(const NdtGrid &g, size_t n_points, int *s1_shift, int *s2_shift)
 {
-    if (count == 0) return hipSuccess;
     // scales that keep every 64-bit accumulator below 2^62.  Even grid sizes: |u| <= 1/2 (+ rounding), so
     // N/2 * 2^s1 and N/4 * 2^s2 must stay below 2^62.  An odd size lets the reference's double->int truncation put
     // offsets of up to 1.5 cells into index 0: bound |u| < 2 there.
     int lg = 1;
     while ((1ull << lg) < (unsigned long long)(n_points ? n_points : 1)) lg++;
-    const bool odd = (set.grid.size[0] | set.grid.size[1] | set.grid.size[2]) & 1;
-    int s1_shift = (odd ? 60 : 62) - lg;
-    int s2_shift = (odd ? 58 : 62) - lg;
-    if (s1_shift > 45) s1_shift = 45;
-    if (s2_shift > 45) s2_shift = 45;
-    const int dbg = 0;   // reserved kernel argument
-    const bool aligned4 = (((uintptr_t)xyz_dev | map_stride_bytes) & 3u) == 0;
-    const int sdw = (stride_bytes == 12 && aligned4) ? 3 : (stride_bytes == 16 && aligned4) ? 4 : 0;
-    // Few maps: spread each scan over several workgroups (accumulate) and finalise in a second launch.
+    const bool odd = (g.size[0] | g.size[1] | g.size[2]) & 1;
+    *s1_shift = std::min((odd ? 60 : 62) - lg, 45);
+    *s2_shift = std::min((odd ? 58 : 62) - lg, 45);
+}
+
+// Few maps: spread each scan over several workgroups (accumulate) and finalise in a second launch -- `parts` workgroups per map
+// (1: one workgroup per map, the whole build in one launch).
+static unsigned build_parts(size_t count, size_t n_points)
+{
     const unsigned n_tiles = (unsigned)((n_points + NDT_TILE - 1) / NDT_TILE);
     unsigned parts = 1;
     if (count < 256 && n_tiles > 8) {
@@ -1156,15 +1153,48 @@ hipError_t ndt_launch_build(const NdtSetView &set, size_t first, size_t count, c
         if (parts > n_tiles / 4) parts = n_tiles / 4;
         if (parts < 1) parts = 1;
     }
-    // batches of planar scans on a grid whose cell centres are fp32 numbers: the wave-uniform kernel of
-    // csrc/ndt_build_flat.hip (NDTGPU_FLAT=0: never, 2: also for the few-maps case, one workgroup per map)
-    {
-        const char *fe = getenv("NDTGPU_FLAT");
-        const int flat_mode = fe ? atoi(fe) : 1;
-        if (flat_mode && (parts == 1 || flat_mode == 2) && ndt_build_flat_ok(set.grid, nice, sdw))
-            return ndt_launch_build_flat(set, first, count, xyz_dev, n_points, sdw, map_stride_bytes, range_limit,
-                                         range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, stream);
-    }
+    return parts;
+}
+
+// batches of planar scans on a grid whose cell centres are fp32 numbers: the wave-uniform kernel of
+// csrc/ndt_build_flat.hip (NDTGPU_FLAT=0: never, 2: also for the few-maps case, one workgroup per map)
+static bool build_takes_flat(const NdtGrid &g, int nice, int sdw, unsigned parts)
+{
+    const char *fe = getenv("NDTGPU_FLAT");
+    const int flat_mode = fe ? atoi(fe) : 1;
+    return flat_mode && (parts == 1 || flat_mode == 2) && ndt_build_flat_ok(g, nice, sdw);
+}
+
+hipError_t ndt_launch_build_flat_xf(const NdtSetView &set, size_t first, size_t count, const void *xyz_dev, size_t n_points,
+                                    size_t stride_bytes, size_t map_stride_bytes, int n_min, double eval_factor, int nice,
+                                    const double *xf16_dev, float *xf_out_dev, hipStream_t stream)
+{
+    const bool aligned4 = (((uintptr_t)xyz_dev | map_stride_bytes) & 3u) == 0;
+    const int sdw = (stride_bytes == 12 && aligned4) ? 3 : (stride_bytes == 16 && aligned4) ? 4 : 0;
+    // only where ndt_launch_build would take the flat kernel for the moved clouds itself: the flat kernel and the general one
+    // agree to rounding, not bit for bit (the flat one sums a run's moments over a wave before the fixed-point conversion)
+    if (!xf16_dev || !build_takes_flat(set.grid, nice, sdw, build_parts(count, n_points))) return hipErrorNotSupported;
+    if (count == 0) return hipSuccess;
+    int s1_shift, s2_shift;
+    ndt_build_shifts(set.grid, n_points, &s1_shift, &s2_shift);
+    return ndt_launch_build_flat(set, first, count, xyz_dev, n_points, sdw, map_stride_bytes, 0.0, nullptr, n_min, eval_factor,
+                                 s1_shift, s2_shift, stream, xf16_dev, xf_out_dev);
+}
+
+hipError_t ndt_launch_build(const NdtSetView &set, size_t first, size_t count, const void *xyz_dev, size_t n_points,
+                            size_t stride_bytes, size_t map_stride_bytes, double range_limit,
+                            const double *range_origins_dev, int n_min, double eval_factor, int nice, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    int s1_shift, s2_shift;
+    ndt_build_shifts(set.grid, n_points, &s1_shift, &s2_shift);
+    const int dbg = 0;   // reserved kernel argument
+    const bool aligned4 = (((uintptr_t)xyz_dev | map_stride_bytes) & 3u) == 0;
+    const int sdw = (stride_bytes == 12 && aligned4) ? 3 : (stride_bytes == 16 && aligned4) ? 4 : 0;
+    const unsigned parts = build_parts(count, n_points);
+    if (build_takes_flat(set.grid, nice, sdw, parts))
+        return ndt_launch_build_flat(set, first, count, xyz_dev, n_points, sdw, map_stride_bytes, range_limit,
+                                     range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, stream);
     // thick grids hold 3D sweeps, whose consecutive points change cell every few points: replaced runs go to the wide
     // flush list (SCAT).  Flat grids hold planar scans, whose points stay in a cell for hundreds of points.
     const bool scat = set.grid.size[2] > 4;

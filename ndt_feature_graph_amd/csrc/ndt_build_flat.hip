@@ -109,14 +109,28 @@ NDT_D int flat_id_of(unsigned *hash, unsigned hash_mask, unsigned hash_shift, un
     return -1;
 }
 
+// (float)(X * (double)p) of one point, X's top three rows column by column (x[c * 3 + r] = X(r, c)): the arithmetic of
+// ndt_cloud_transform_kernel (csrc/ndt_fuser.hip), without fused multiply-adds
+NDT_D void flat_move_point(const double (&x)[12], float &px, float &py, float &pz)
+{
+#pragma clang fp contract(off)
+    const double a = (double)px, b = (double)py, c = (double)pz;
+    px = (float)(x[0] * a + x[3] * b + x[6] * c + x[9]);
+    py = (float)(x[1] * a + x[4] * b + x[7] * c + x[10]);
+    pz = (float)(x[2] * a + x[5] * b + x[8] * c + x[11]);
+}
+
 }  // namespace
 
-// SD: dwords per point record (3 = packed xyz, 4 = pcl::PointXYZ)
-template <int SD>
+// SD: dwords per point record (3 = packed xyz, 4 = pcl::PointXYZ).  XF (the multi-resolution registrar's source maps,
+// csrc/ndtgpu_multires.hip): every point is moved by its map's rigid transform (xf16: 16 doubles per map of the launch,
+// column-major) as it is loaded, before it is binned, and -- with xf_out -- the moved cloud is written out as packed xyz
+// (n_points records per map of the launch) for the next level.  The transform is uniform per workgroup: scalar registers.
+template <int SD, bool XF>
 __global__ __launch_bounds__(NDT_FLAT_THREADS) __attribute__((amdgpu_waves_per_eu(NDT_FLAT_WPE, NDT_FLAT_WPE))) void ndt_build_flat_kernel(
     NdtSetView set, unsigned first, const char *__restrict__ xyz, unsigned n_points, size_t map_stride_bytes,
     double range_limit, const double *__restrict__ range_origins, int n_min, double eval_factor, int s1_shift, int s2_shift,
-    unsigned hash_log2)
+    unsigned hash_log2, const double *__restrict__ xf16, float *__restrict__ xf_out)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned s_dyn[];
     __shared__ long long s_lval[NDT_FLAT_WAVES * NDT_FLAT_LIST * 10];
@@ -155,6 +169,14 @@ __global__ __launch_bounds__(NDT_FLAT_THREADS) __attribute__((amdgpu_waves_per_e
     double ox = 0, oy = 0, oz = 0;
     if (range_origins) { ox = range_origins[map_local * 3]; oy = range_origins[map_local * 3 + 1]; oz = range_origins[map_local * 3 + 2]; }
     const char *pts = xyz + (size_t)map_local * map_stride_bytes;
+    [[maybe_unused]] double xm[12];
+    if constexpr (XF) {
+        const double *X = xf16 + (size_t)map_local * 16;
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+#pragma unroll
+            for (int r = 0; r < 3; r++) xm[c * 3 + r] = X[c * 4 + r];
+    }
 
     for (unsigned i = tid; i < hash_entries; i += NDT_FLAT_THREADS) s_hash[i] = 0u;
     if (tid == 0) { s_nalloc = 0u; s_binned = 0u; s_ovf = 0u; }
@@ -417,13 +439,19 @@ __global__ __launch_bounds__(NDT_FLAT_THREADS) __attribute__((amdgpu_waves_per_e
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 if ((unsigned)u < nr) {
-                    float px = qx[u];
+                    float px = qx[u], &py = qy[u], &pz = qz[u];
+                    if constexpr (XF) {
+                        flat_move_point(xm, px, py, pz);
+                        const unsigned r = r0 + (unsigned)u;
+                        if (xf_out && (r != last_round || lane < tail))
+                            reinterpret_cast<P3 *>(xf_out)[(size_t)map_local * n_points + (size_t)r * 64u + lane] = P3{px, py, pz};
+                    }
                     if (r0 + (unsigned)u == last_round) px = lane < tail ? px : __builtin_nanf("");   // past the end: NaN points
-                    bool todo = fast_round(px, qy[u], qz[u], 0ull);
+                    bool todo = fast_round(px, py, pz, 0ull);
 #if NDT_FLAT_GONE
                     if (todo && seen_gone) {           // (a scan that has not dropped a point so far does not pay for the test)
-                        const unsigned long long m_gone = gone_mask(px, qy[u], qz[u]);
-                        if (m_gone) todo = fast_round(px, qy[u], qz[u], m_gone);
+                        const unsigned long long m_gone = gone_mask(px, py, pz);
+                        if (m_gone) todo = fast_round(px, py, pz, m_gone);
                     }
 #endif
                     if (todo) {
@@ -431,7 +459,7 @@ __global__ __launch_bounds__(NDT_FLAT_THREADS) __attribute__((amdgpu_waves_per_e
 #ifdef NDT_FLAT_STATS
                         const long long ts = __builtin_readcyclecounter();
 #endif
-                        slow_round(px, qy[u], qz[u]);
+                        slow_round(px, py, pz);
 #ifdef NDT_FLAT_STATS
                         if (lane == 0) atomicAdd(&s_stat[0], (unsigned)(__builtin_readcyclecounter() - ts) >> 2);   // mean over the 4 waves
 #endif
@@ -600,7 +628,8 @@ bool ndt_build_flat_ok(const NdtGrid &g, int nice, int sdw)
 
 hipError_t ndt_launch_build_flat(const NdtSetView &set, size_t first, size_t count, const void *xyz_dev, size_t n_points,
                                  int sdw, size_t map_stride_bytes, double range_limit, const double *range_origins_dev,
-                                 int n_min, double eval_factor, int s1_shift, int s2_shift, hipStream_t stream)
+                                 int n_min, double eval_factor, int s1_shift, int s2_shift, hipStream_t stream,
+                                 const double *xf16_dev, float *xf_out_dev)
 {
     const NdtGrid &g = set.grid;
     const unsigned bm_words = (unsigned)((g.slots + 31) / 32);
@@ -612,23 +641,36 @@ hipError_t ndt_launch_build_flat(const NdtSetView &set, size_t first, size_t cou
     const size_t region0 = NDT_FLAT_LDSRED ? std::max<size_t>(bm_words, (size_t)NDT_FLAT_WAVES * NDT_FLAT_RED_DOUBLES * 2) : bm_words;
     const size_t dyn = (region0 + ((size_t)1 << hash_log2)) * sizeof(unsigned);
     // (static + dynamic LDS of the largest configuration exceed the 64 KB a workgroup gets by default)
-    static bool attr_set[2][16] = {};
+    static bool attr_set[4][16] = {};
     int dev = 0;
     (void)hipGetDevice(&dev);
-    const void *fn = sdw == 3 ? reinterpret_cast<const void *>(&ndt_build_flat_kernel<3>)
-                              : reinterpret_cast<const void *>(&ndt_build_flat_kernel<4>);
-    if (dev < 0 || dev >= 16 || !attr_set[sdw == 3 ? 0 : 1][dev]) {
+    const bool xf = xf16_dev != nullptr;
+    const int which = (sdw == 3 ? 0 : 1) + (xf ? 2 : 0);
+    const void *fn = which == 0 ? reinterpret_cast<const void *>(&ndt_build_flat_kernel<3, false>)
+                   : which == 1 ? reinterpret_cast<const void *>(&ndt_build_flat_kernel<4, false>)
+                   : which == 2 ? reinterpret_cast<const void *>(&ndt_build_flat_kernel<3, true>)
+                                : reinterpret_cast<const void *>(&ndt_build_flat_kernel<4, true>);
+    if (dev < 0 || dev >= 16 || !attr_set[which][dev]) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
         if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 16) attr_set[sdw == 3 ? 0 : 1][dev] = true;
+        if (dev >= 0 && dev < 16) attr_set[which][dev] = true;
     }
-    if (sdw == 3)
-        hipLaunchKernelGGL((ndt_build_flat_kernel<3>), dim3((unsigned)count), dim3(NDT_FLAT_THREADS), dyn, stream, set,
+    if (xf) {
+        if (sdw == 3)
+            hipLaunchKernelGGL((ndt_build_flat_kernel<3, true>), dim3((unsigned)count), dim3(NDT_FLAT_THREADS), dyn, stream, set,
+                               (unsigned)first, (const char *)xyz_dev, (unsigned)n_points, map_stride_bytes, range_limit,
+                               range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, hash_log2, xf16_dev, xf_out_dev);
+        else
+            hipLaunchKernelGGL((ndt_build_flat_kernel<4, true>), dim3((unsigned)count), dim3(NDT_FLAT_THREADS), dyn, stream, set,
+                               (unsigned)first, (const char *)xyz_dev, (unsigned)n_points, map_stride_bytes, range_limit,
+                               range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, hash_log2, xf16_dev, xf_out_dev);
+    } else if (sdw == 3)
+        hipLaunchKernelGGL((ndt_build_flat_kernel<3, false>), dim3((unsigned)count), dim3(NDT_FLAT_THREADS), dyn, stream, set,
                            (unsigned)first, (const char *)xyz_dev, (unsigned)n_points, map_stride_bytes, range_limit,
-                           range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, hash_log2);
+                           range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, hash_log2, nullptr, nullptr);
     else
-        hipLaunchKernelGGL((ndt_build_flat_kernel<4>), dim3((unsigned)count), dim3(NDT_FLAT_THREADS), dyn, stream, set,
+        hipLaunchKernelGGL((ndt_build_flat_kernel<4, false>), dim3((unsigned)count), dim3(NDT_FLAT_THREADS), dyn, stream, set,
                            (unsigned)first, (const char *)xyz_dev, (unsigned)n_points, map_stride_bytes, range_limit,
-                           range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, hash_log2);
+                           range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, hash_log2, nullptr, nullptr);
     return hipGetLastError();
 }

@@ -149,9 +149,25 @@ hipError_t ndt_launch_build(const NdtSetView &set, size_t first, size_t count, c
                             const double *range_origins_dev, int n_min, double eval_factor, int nice, hipStream_t stream);
 // the batch kernel for flat grids (csrc/ndt_build_flat.hip); ndt_launch_build hands over when ndt_build_flat_ok
 bool ndt_build_flat_ok(const NdtGrid &g, int nice, int sdw);
+// (xf16_dev: the transform variant -- points moved by their map's 16-double pose on load, and written out to xf_out_dev when
+//  that is not NULL; csrc/ndt_build_flat.hip)
 hipError_t ndt_launch_build_flat(const NdtSetView &set, size_t first, size_t count, const void *xyz_dev, size_t n_points,
                                  int sdw, size_t map_stride_bytes, double range_limit, const double *range_origins_dev,
-                                 int n_min, double eval_factor, int s1_shift, int s2_shift, hipStream_t stream);
+                                 int n_min, double eval_factor, int s1_shift, int s2_shift, hipStream_t stream,
+                                 const double *xf16_dev = nullptr, float *xf_out_dev = nullptr);
+// the multi-resolution registrar's small kernels (csrc/ndt_multires.hip)
+hipError_t ndt_launch_multires_range(const void *xyz_dev, size_t count, size_t n_points, size_t stride_bytes, size_t map_stride_bytes,
+                                     double range_limit, float *out_dev, hipStream_t stream);
+hipError_t ndt_launch_multires_step(size_t count, int step, int level, int n_levels, int last, int use_initial_guess, double *T16_dev,
+                                    double *Temp16_dev, double *X16_dev, double *state_dev, int *stopped_dev, uint32_t *sidx_dev,
+                                    const NdtMatchResultDev *res_lvl_dev, NdtMatchResultDev *results_dev, hipStream_t stream);
+// the fixed-point scales of the moment accumulators that ndt_launch_build uses for a batch of n_points-point clouds
+void ndt_build_shifts(const NdtGrid &g, size_t n_points, int *s1_shift, int *s2_shift);
+// ndt_launch_build_flat with the transform on load, for a batch that ndt_launch_build would hand to the flat kernel (else
+// hipErrorNotSupported and nothing is launched): the same maps as ndt_launch_build on the moved clouds
+hipError_t ndt_launch_build_flat_xf(const NdtSetView &set, size_t first, size_t count, const void *xyz_dev, size_t n_points,
+                                    size_t stride_bytes, size_t map_stride_bytes, int n_min, double eval_factor, int nice,
+                                    const double *xf16_dev, float *xf_out_dev, hipStream_t stream);
 // accumulate only (phase A of the build: points -> per-cell moment accumulators), z_max: points above it are dropped
 hipError_t ndt_launch_accumulate(const NdtSetView &set, size_t first, size_t count, const void *xyz_dev, size_t n_points,
                                  size_t stride_bytes, size_t map_stride_bytes, double range_limit,

@@ -16,6 +16,7 @@
 #include "../../include/ndtgpu.h"
 #include "ndt_gpu_types.h"
 
+#include <algorithm>
 #include <array>
 #include <memory>
 #include <stdexcept>
@@ -399,8 +400,76 @@ public:
     int covariance_mode = 0;     // ndtgpu_covariance_batch `mode`
     ndtgpu_match_result last_result{};
 
+    NDTMatcherD2D() = default;
+    // NDTMatcherD2D(isIrregularGrid, useDefaultGridResolutions, resolutions) (ndt_odom_debug.cpp:159-165,
+    // ndt_feature_pcl_eval.cpp:620-642): the level list of the raw-cloud match below -- {0.2, 0.5, 1, 2} with
+    // useDefaultGridResolutions (ndtgpu_default_resolutions), else the caller's, in the caller's order.  An irregular (OctTree) grid
+    // has no counterpart in the library: std::invalid_argument.
+    NDTMatcherD2D(bool isIrregularGrid, bool useDefaultGridResolutions, std::vector<double> _resolutions)
+    {
+        if (isIrregularGrid) throw std::invalid_argument("NDTMatcherD2D: irregular (OctTree) grids are not supported");
+        if (useDefaultGridResolutions) {
+            double r[4];
+            int n = 0;
+            ndtgpu_default_resolutions(r, &n);
+            resolutions.assign(r, r + n);
+        } else {
+            resolutions = std::move(_resolutions);
+        }
+    }
+    std::vector<double> resolutions;   // the levels of the raw-cloud match, run from the last entry to the first (empty: the default list)
+    // DEVIATION (include/ndtgpu.h): upstream's raw-cloud match centres every level's LazyGrid on the centroid of its cloud; here
+    // every map of every level sits on this grid -- centre and extent [m], the level's cell size -- like the registrar's maps.
+    // Points outside it are not binned.  max_cells: ndtgpu_grid_params.max_cells (0: the library's choice).
+    struct MultiresGrid {
+        double centre[3] = {0.0, 0.0, 0.0};
+        double size[3] = {100.0, 100.0, 4.0};
+        uint32_t max_cells = 0;
+    } multires_grid;
+    std::vector<ndtgpu_match_result> multires_results;   // the last raw-cloud match: one result per level, in list order
+
     // bool match(NDTMap& target, NDTMap& source, Affine3d& T, bool useInitialGuess)  (graph.cpp:273)
     bool match(NDTMap &target, NDTMap &source, Eigen::Affine3d &T, bool useInitialGuess = false) { return match_dof(target, source, T, useInitialGuess, 0x3f); }
+
+    // bool match(PointCloud& target, PointCloud& source, Affine3d& T, bool useInitialGuess) -- the raw-cloud overload, coarse to fine
+    // over `resolutions` (ndt_odom_debug.cpp:165, ndt_feature_pcl_eval.cpp:642): ONE ndtgpu_register_multires_host call.  T: in the
+    // initial guess (with useInitialGuess), out the registered pose; last_result: the result of the last level run (list position
+    // 0, the finest of an ascending list), whose `converged` is the return value.  No range filter, like upstream's overload.
+    bool match(pcl::PointCloud<pcl::PointXYZ> &target, pcl::PointCloud<pcl::PointXYZ> &source, Eigen::Affine3d &T,
+               bool useInitialGuess = false)
+    {
+        std::vector<double> lv = resolutions;
+        if (lv.empty()) {
+            double r[4];
+            int n = 0;
+            ndtgpu_default_resolutions(r, &n);
+            lv.assign(r, r + n);
+        }
+        const size_t np = std::max(target.size(), source.size());
+        static_assert(sizeof(pcl::PointXYZ) == 16, "pcl::PointXYZ is four floats");
+        std::vector<float> pts(2 * np * 4, std::nanf(""));    // (the shorter cloud is padded with NaN points, which builds drop)
+        for (size_t i = 0; i < target.size(); i++) {
+            pts[4 * i] = target.points[i].x; pts[4 * i + 1] = target.points[i].y; pts[4 * i + 2] = target.points[i].z;
+        }
+        for (size_t i = 0; i < source.size(); i++) {
+            float *o = &pts[4 * (np + i)];
+            o[0] = source.points[i].x; o[1] = source.points[i].y; o[2] = source.points[i].z;
+        }
+        ndtgpu_grid_params g;
+        g.res = lv[0];
+        for (int a = 0; a < 3; a++) { g.centre[a] = multires_grid.centre[a]; g.size[a] = multires_grid.size[a]; }
+        g.max_cells = multires_grid.max_cells;
+        ndtgpu_multires *mr = nullptr;
+        ndtgpu_host::check(ndtgpu_multires_create(&g, lv.data(), (int)lv.size(), 1, &mr), "ndtgpu_multires_create");
+        struct Destroy { ndtgpu_multires *h; ~Destroy() { ndtgpu_multires_destroy(h); } } guard{mr};
+        ndtgpu_match_params p = params(0x3f, useInitialGuess);
+        multires_results.assign(lv.size(), ndtgpu_match_result{});
+        ndtgpu_host::check(ndtgpu_register_multires_host(mr, pts.data(), pts.data() + np * 4, np, 16, np * 16, -1.0, nullptr, T.data(), 1,
+                                                         &p, useInitialGuess ? 1 : 0, multires_results.data()),
+                           "ndtgpu_register_multires_host");
+        last_result = multires_results[0];
+        return last_result.converged != 0;
+    }
 
     // double derivativesNDT(sourceCells, targetNDT, score_gradient (6x1), Hessian (6x6), computeHessian)  (fusion.h:856, 1085;
     // the line searches :80, 238, 444, 617): ONE device evaluation per call
