@@ -659,6 +659,104 @@ ndtgpu_status ndtgpu_register_multires_host(ndtgpu_multires *mr, const void *tar
                                             const ndtgpu_match_params *prm, int use_initial_guess,
                                             ndtgpu_match_result *results);
 
+/* ---- NDT Monte Carlo localisation in a built map: a bank of NDTMCL3D particle filters ----------------------------------------
+ * ndt_feature/src/ndt_feature_mcl_node.cpp localises a robot in a saved NDT map with perception_oru's NDTMCL3D (:48 includes
+ * ndt_mcl/3d_ndt_mcl.h; :174 `new NDTMCL3D(resolution, ndmap, -5)`; :175-184 its public parameters; :335 initializeFilter(x, y,
+ * z, r, p, t, 0.5, 0.5, 0.1, 2 deg, 2 deg, 2 deg, numParticles); :361 updateAndPredictEff(Tm, cloud, subsample_level) per
+ * odometry step; :377-396 reads pf.pcloud[i], pf.size() and pf.getMean()).  A bank holds n_filters independent filters of
+ * n_particles particles each (robots, bags, hypotheses); filter k localises in map map_idx[k] of a BORROWED map set.
+ * PROVENANCE: NDTMCL3D and mcl::ParticleFilter3D live in perception_oru's ndt_mcl, which the reference does not vendor;
+ * restated from memory:
+ *   - constructor: the map at map_resolution, zfilt_min = zfilter, resolution_sensor = map_resolution, sinceSIR = 0.
+ *   - initializeFilter: N particles T = Translation(x + sx n1, y + sy n2, z + sz n3) * AngleAxis(r + sr n4, X) *
+ *     AngleAxis(p + sp n5, Y) * AngleAxis(t + st n6, Z) (n standard normal), every weight p = 1/N.
+ *   - updateAndPredictEff(Tmotion, cloud, subsample_level):
+ *     1. subsample_level outside [0, 1] becomes 1.
+ *     2. the local map: NDTMap(new LazyGrid(resolution_sensor)), guessSize(0,0,0, 100,100,8), loadPointCloud(cloud),
+ *        computeNDTCells(SAMPLE_VARIANCE) -- the cloud in the base frame (the node applies sensorPoseT first, :357).
+ *     3. tr = Tmotion.translation(), rot = Tmotion.rotation().eulerAngles(0,1,2) (Eigen: first angle in [0, pi]),
+ *        sigma = motion_model * (|tr|, |rot|) + motion_model_offset.
+ *     4. predict: T <- T * (Translation(tr + sigma[0..2] n) * AngleAxis(rot0 + sigma3 n, X) * AngleAxis(rot1 + sigma4 n, Y) *
+ *        AngleAxis(rot2 + sigma5 n, Z)).
+ *     5. the local map's Gaussian cells; when subsample_level < 1 each is kept with probability subsample_level (the same cells
+ *        for every particle of the filter).
+ *     6. per particle lik = sum over kept cells c of 0.1 + 0.9 exp(-0.05 l / 2), l = (mu - m)^T (C + R c.cov R^T)^-1 (mu - m),
+ *        m = T c.mean, (mu, C) the map cell at pcl::PointXYZ(m) (float coordinates); a cell is skipped when m.z < zfilt_min,
+ *        when m falls outside the grid or in a cell without a Gaussian, when computeInverseAndDetWithCheck fails
+ *        (|det| <= 1e-12), or when l is not finite.
+ *     7. pf.normalize(): p_i <- p_i lik_i, then p_i /= sum p; when sum p <= 0 every p_i = 1/N.
+ *     8. forceSIR: SIRUpdate().  Else varP = sqrt(sum (p_i - 1/N)^2 / N); varP > SIR_varP_threshold or sinceSIR >
+ *        SIR_max_iters_wo_resampling: SIRUpdate(), sinceSIR = 0; else sinceSIR++.  SIRUpdate is systematic (low-variance)
+ *        resampling with one uniform offset; afterwards every p = 1/N.
+ *   - pf.getMean(): translation sum p_i t_i; rotation AngleAxis(atan2(sum p sin r, sum p cos r), X) * (.. Y) * (.. Z) over
+ *     each particle's T.rotation().eulerAngles(0,1,2).
+ * DEVIATIONS:
+ *   - random numbers: a counter-based generator -- synth.hash_uniform / hash_normal (SplitMix64, Box-Muller) keyed by (seed,
+ *     filter slot, the filter's draw counter, particle or cell, draw index); a filter's draws do not depend on the batch it runs
+ *     in.  Upstream uses rand() (srand(time(NULL))).  The draw counter counts the filter's initialize and update calls.  SIR's
+ *     thresholds are (u0 + k) / N with one u0 ~ U[0, 1) per update.
+ *   - the map is read in place, not copied into a LazyGrid of the filter's resolution: ndtgpu_mcl_create refuses a map set whose
+ *     cell size differs from params->map_res (NDTGPU_ERR_INVALID).
+ *   - resampling sums: cumulative weights are exact 64-bit fixed-point sums (units of 2^-52), so resampling is order-free.
+ *   - updateAndPredict (the non-Eff variant) and the OctTree are not ported.
+ * Calls on one handle are ordered (each waits, on the device, for the previous one, whatever stream that one named); the
+ * borrowed map set is read by the update's likelihood kernel: the caller orders any rebuild of it before or after an update,
+ * as for the matcher.  Scans of unequal length: pad with NaN points. */
+typedef struct ndtgpu_mcl ndtgpu_mcl;
+typedef struct {
+    double map_res;                      /* NDTMCL3D(map_resolution, ..) (:174 `resolution`); 0 = the map set's cell size */
+    double sensor_res;                   /* resolution_sensor of the local scan map (= map_resolution upstream); 0 = map_res */
+    double scan_size[3];                 /* local map extent guessSize(0,0,0, 100,100,8) [m] (recalled); every 2D scan is served by
+                                          * a planar extent, e.g. {60, 60, 1}: 100 x 100 x 8 m costs 40 MB of build scratch per
+                                          * filter at 0.2 m */
+    double range_limit;                  /* loadPointCloud's range limit; <= 0: none (recalled: upstream passes none) */
+    double zfilt_min;                    /* NDTMCL3D(.., zfilter) (:174: -5) */
+    double motion_model[36];             /* row-major 6x6 (:183 getParam("motion_model"); defaults recalled) */
+    double motion_model_offset[6];       /* (:184 getParam("motion_model_offset"); defaults recalled) */
+    int32_t force_sir;                   /* forceSIR (:175-176, default false) */
+    int32_t sir_max_iters_wo_resampling; /* SIR_max_iters_wo_resampling (:179, 25) */
+    double sir_varp_threshold;           /* SIR_varP_threshold (:178, 0.006) */
+    uint32_t max_scan_cells;             /* cell capacity of each local scan map (ndtgpu_grid_params.max_cells; 0 = default) */
+    uint32_t pad_;
+    uint64_t seed;                       /* the random-number key (see DEVIATIONS) */
+} ndtgpu_mcl_params;
+void ndtgpu_default_mcl_params(ndtgpu_mcl_params *p);
+typedef struct {
+    double var_p;            /* varP of the last update (computed also when force_sir) */
+    double lik_sum;          /* sum of the particles' lik */
+    int64_t terms;           /* (particle, scan cell) terms scored */
+    uint64_t draws;          /* the filter's draw counter (initialize and update calls so far) */
+    int32_t resampled;       /* the last update ran SIRUpdate */
+    int32_t since_sir;       /* sinceSIR after it */
+    int32_t n_scan_cells;    /* Gaussian cells of the local scan map */
+    int32_t overflow;        /* the local scan map needed more than max_scan_cells cells (the rest were not scored) */
+} ndtgpu_mcl_result;
+/* n_particles 1 .. 65536 per filter, n_filters * n_particles <= 2^24; map_idx: HOST, n_filters map indices of map_set */
+ndtgpu_status ndtgpu_mcl_create(ndtgpu_mapset *map_set, const uint32_t *map_idx, const ndtgpu_mcl_params *params, size_t n_filters,
+                                size_t n_particles, ndtgpu_mcl **out);
+ndtgpu_status ndtgpu_mcl_destroy(ndtgpu_mcl *h);
+/* initializeFilter for filters [first, first + count): pose6 / sigma6 HOST, count x (x, y, z, r, p, t).  Synchronous. */
+ndtgpu_status ndtgpu_mcl_initialize(ndtgpu_mcl *h, size_t first, size_t count, const double *pose6, const double *sigma6);
+/* installs particle sets (pf.pcloud[i].T / .p): T16 HOST count x n_particles x 16 (column-major), weights HOST count x n_particles
+ * (NULL: 1/N).  Synchronous. */
+ndtgpu_status ndtgpu_mcl_set_particles(ndtgpu_mcl *h, size_t first, size_t count, const double *T16, const double *weights);
+/* updateAndPredictEff(Tmotion, cloud, subsample_level) for filters [first, first + count): Tmotion16 HOST count x 16; clouds
+ * DEVICE, n_points records `stride_bytes` apart, clouds `map_stride_bytes` apart (base frame).  subsample_level is a per-call
+ * argument as upstream's is.  Asynchronous on `stream`: local-map build, predict, likelihood, normalise and SIR, no host
+ * synchronisation. */
+ndtgpu_status ndtgpu_mcl_update(ndtgpu_mcl *h, size_t first, size_t count, const double *Tmotion16, double subsample_level,
+                                const void *xyz_dev, size_t n_points, size_t stride_bytes, size_t map_stride_bytes,
+                                ndtgpu_stream stream);
+/* the same with the clouds in HOST memory; synchronous */
+ndtgpu_status ndtgpu_mcl_update_host(ndtgpu_mcl *h, size_t first, size_t count, const double *Tmotion16, double subsample_level,
+                                     const void *xyz_host, size_t n_points, size_t stride_bytes, size_t map_stride_bytes);
+/* pf.pcloud after the handle's last call: T16 count x n_particles x 16, weights and lik count x n_particles (HOST; any may be
+ * NULL; lik: the last update's likelihoods).  Waits for the handle. */
+ndtgpu_status ndtgpu_mcl_particles(ndtgpu_mcl *h, size_t first, size_t count, double *T16, double *weights, double *lik);
+/* pf.getMean() of filters [first, first + count): T16_mean HOST count x 16; results (may be NULL) the records of each filter's
+ * last update.  Waits for the handle. */
+ndtgpu_status ndtgpu_mcl_mean(ndtgpu_mcl *h, size_t first, size_t count, double *T16_mean, ndtgpu_mcl_result *results);
+
 /* single pair convenience == graph.cpp:273 */
 ndtgpu_status ndtgpu_match_d2d(ndtgpu_mapset *target_set, size_t target_map, ndtgpu_mapset *source_set,
                                size_t source_map, double T16[16], const ndtgpu_match_params *prm,

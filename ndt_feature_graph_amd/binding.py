@@ -10,7 +10,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _SO = os.path.join(_HERE, "libndtgpu.so")
 _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hip", "ndt_pack.hip", "ndt_fuser.hip", "ndtgpu_api.hip",
-            "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip"]
+            "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip",
+            "ndt_mcl.hip", "ndtgpu_mcl.hip"]
 
 STATUS = {0: "OK", -1: "ERR_INVALID", -2: "ERR_HIP", -3: "ERR_NO_DEVICE", -4: "ERR_CAPACITY", -5: "ERR_ALLOC"}
 
@@ -134,7 +135,8 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_fuser_initialize_batch_host", "ndtgpu_fuser_update_batch_host", "ndtgpu_registrar_inject_abort",
            "ndtgpu_register_batch_cov_device", "ndtgpu_register_batch_cov_host", "ndtgpu_default_resolutions",
            "ndtgpu_multires_create", "ndtgpu_multires_destroy", "ndtgpu_register_multires_device", "ndtgpu_register_multires_host",
-           "ndtgpu_multires_get_info"]
+           "ndtgpu_multires_get_info", "ndtgpu_default_mcl_params", "ndtgpu_mcl_create", "ndtgpu_mcl_destroy", "ndtgpu_mcl_initialize",
+           "ndtgpu_mcl_set_particles", "ndtgpu_mcl_update", "ndtgpu_mcl_update_host", "ndtgpu_mcl_particles", "ndtgpu_mcl_mean"]
 
 _lib = None
 
@@ -245,6 +247,16 @@ def lib():
                                                   vp, C.c_size_t, C.POINTER(MatchParams), C.c_int, vp, vp]
     L.ndtgpu_register_multires_host.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(CellParams),
                                                 dp, C.c_size_t, C.POINTER(MatchParams), C.c_int, vp]
+    L.ndtgpu_default_mcl_params.restype = None
+    L.ndtgpu_default_mcl_params.argtypes = [C.POINTER(MclParams)]
+    L.ndtgpu_mcl_create.argtypes = [vp, u32p, C.POINTER(MclParams), C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.ndtgpu_mcl_destroy.argtypes = [vp]
+    L.ndtgpu_mcl_initialize.argtypes = [vp, C.c_size_t, C.c_size_t, dp, dp]
+    L.ndtgpu_mcl_set_particles.argtypes = [vp, C.c_size_t, C.c_size_t, dp, dp]
+    L.ndtgpu_mcl_update.argtypes = [vp, C.c_size_t, C.c_size_t, dp, C.c_double, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp]
+    L.ndtgpu_mcl_update_host.argtypes = [vp, C.c_size_t, C.c_size_t, dp, C.c_double, vp, C.c_size_t, C.c_size_t, C.c_size_t]
+    L.ndtgpu_mcl_particles.argtypes = [vp, C.c_size_t, C.c_size_t, dp, dp, dp]
+    L.ndtgpu_mcl_mean.argtypes = [vp, C.c_size_t, C.c_size_t, dp, vp]
     _lib = L
     return L
 
@@ -799,6 +811,127 @@ class MultiRes:
                                                    4 * w * npts, float(range_limit), C.byref(cp), _dp(Tc), n, C.byref(p),
                                                    1 if use_initial_guess else 0, C.c_void_p(res.ctypes.data)))
         return np.transpose(Tc.reshape(n, 4, 4), (0, 2, 1)).copy(), res.reshape(n, self.n_levels)
+
+
+class MclParams(C.Structure):
+    _fields_ = [("map_res", C.c_double), ("sensor_res", C.c_double), ("scan_size", C.c_double * 3), ("range_limit", C.c_double),
+                ("zfilt_min", C.c_double), ("motion_model", C.c_double * 36), ("motion_model_offset", C.c_double * 6),
+                ("force_sir", C.c_int32), ("sir_max_iters_wo_resampling", C.c_int32), ("sir_varp_threshold", C.c_double),
+                ("max_scan_cells", C.c_uint32), ("pad_", C.c_uint32), ("seed", C.c_uint64)]
+
+
+class MclResult(C.Structure):
+    _fields_ = [("var_p", C.c_double), ("lik_sum", C.c_double), ("terms", C.c_int64), ("draws", C.c_uint64), ("resampled", C.c_int32),
+                ("since_sir", C.c_int32), ("n_scan_cells", C.c_int32), ("overflow", C.c_int32)]
+
+
+MCL_RESULT_DTYPE = np.dtype([("var_p", "<f8"), ("lik_sum", "<f8"), ("terms", "<i8"), ("draws", "<u8"), ("resampled", "<i4"),
+                             ("since_sir", "<i4"), ("n_scan_cells", "<i4"), ("overflow", "<i4")])
+assert MCL_RESULT_DTYPE.itemsize == C.sizeof(MclResult)
+
+
+def mcl_params(**fields):
+    """ndtgpu_default_mcl_params with fields replaced (motion_model: 36 values row-major, scan_size / motion_model_offset: 3 / 6)"""
+    p = MclParams()
+    lib().ndtgpu_default_mcl_params(C.byref(p))
+    for k, v in fields.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown MCL parameter %r" % k)
+        if k in ("scan_size", "motion_model", "motion_model_offset"):
+            getattr(p, k)[:] = [float(x) for x in np.asarray(v, dtype=np.float64).ravel()]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+class MCL:
+    """ndtgpu_mcl: a bank of n_filters NDTMCL3D particle filters of n_particles particles; filter k localises in map map_idx[k]
+    of the borrowed MapSet map_set (include/ndtgpu.h).  Poses are 4x4 (math convention) in and out."""
+
+    def __init__(self, map_set, map_idx, n_particles, **params):
+        idx = np.ascontiguousarray(np.atleast_1d(map_idx), dtype=np.uint32)
+        p = mcl_params(**params)
+        h = C.c_void_p()
+        _check(lib().ndtgpu_mcl_create(map_set.h, idx.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(p), idx.shape[0], int(n_particles),
+                                       C.byref(h)))
+        self.h, self.map_set, self.n_filters, self.n_particles = h, map_set, int(idx.shape[0]), int(n_particles)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ndtgpu_mcl_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _cm(T, n):
+        """[n, 4, 4] math convention -> [n, 16] column-major"""
+        return np.ascontiguousarray(np.transpose(np.asarray(T, dtype=np.float64).reshape(n, 4, 4), (0, 2, 1))).reshape(n, 16)
+
+    def initialize(self, pose6, sigma6, first=0):
+        """initializeFilter(x, y, z, r, p, t, sx, sy, sz, sr, sp, st) for filters [first, first + count): pose6 / sigma6 [count, 6]"""
+        ps, sg = _f64(pose6).reshape(-1, 6), _f64(sigma6).reshape(-1, 6)
+        assert ps.shape == sg.shape
+        _check(lib().ndtgpu_mcl_initialize(self.h, int(first), ps.shape[0], _dp(ps), _dp(sg)))
+
+    def set_particles(self, T, weights=None, first=0):
+        """pf.pcloud[i].T / .p: T [count, N, 4, 4], weights [count, N] (None: 1/N)"""
+        T = np.asarray(T, dtype=np.float64)
+        n = int(T.size // 16)
+        if T.size != 16 * n or n == 0 or n % self.n_particles:
+            raise ValueError("set_particles: T must hold whole sets of n_particles 4 x 4 poses")
+        count = n // self.n_particles
+        Tc = self._cm(T, n)
+        w = None
+        if weights is not None:
+            w = _f64(weights)
+            if w.size != n:
+                raise ValueError("set_particles: weights must hold one value per particle")
+            w = w.reshape(n)
+        _check(lib().ndtgpu_mcl_set_particles(self.h, int(first), count, _dp(Tc), None if w is None else _dp(w)))
+
+    def update(self, Tmotion, xyz, subsample_level=1.0, first=0, stream=None):
+        """updateAndPredictEff(Tmotion, cloud, subsample_level) for filters [first, first + count): Tmotion [count, 4, 4]; xyz [count, N,
+        3 or 4] float32 in the base frame -- a torch CUDA tensor (asynchronous on `stream`) or a NumPy array (host path, synchronous)"""
+        if xyz.ndim == 2:
+            xyz = xyz[None]
+        count, npts, w = int(xyz.shape[0]), int(xyz.shape[1]), int(xyz.shape[2])
+        assert w in (3, 4)
+        Tm = self._cm(Tmotion, count)
+        if hasattr(xyz, "data_ptr"):
+            import torch
+            assert xyz.dtype == torch.float32 and xyz.is_cuda and xyz.is_contiguous()
+            if stream is None:
+                stream = torch.cuda.current_stream()
+            _check(lib().ndtgpu_mcl_update(self.h, int(first), count, _dp(Tm), float(subsample_level), C.c_void_p(xyz.data_ptr()), npts,
+                                           4 * w, 4 * w * npts, _stream_ptr(stream)))
+        else:
+            a = np.ascontiguousarray(xyz, dtype=np.float32)
+            _check(lib().ndtgpu_mcl_update_host(self.h, int(first), count, _dp(Tm), float(subsample_level), C.c_void_p(a.ctypes.data),
+                                                npts, 4 * w, 4 * w * npts))
+
+    def particles(self, first=0, count=None):
+        """(T [count, N, 4, 4], weights [count, N], lik [count, N]) of filters [first, first + count)"""
+        count = self.n_filters - first if count is None else int(count)
+        n = count * self.n_particles
+        T = np.zeros((n, 16))
+        w = np.zeros(n)
+        lik = np.zeros(n)
+        _check(lib().ndtgpu_mcl_particles(self.h, int(first), count, _dp(T), _dp(w), _dp(lik)))
+        T = np.transpose(T.reshape(n, 4, 4), (0, 2, 1)).reshape(count, self.n_particles, 4, 4)
+        return T, w.reshape(count, self.n_particles), lik.reshape(count, self.n_particles)
+
+    def mean(self, first=0, count=None):
+        """pf.getMean() [count, 4, 4] and the last update's records (MCL_RESULT_DTYPE [count])"""
+        count = self.n_filters - first if count is None else int(count)
+        T = np.zeros((count, 16))
+        res = np.zeros(count, dtype=MCL_RESULT_DTYPE)
+        _check(lib().ndtgpu_mcl_mean(self.h, int(first), count, _dp(T), C.c_void_p(res.ctypes.data)))
+        return np.transpose(T.reshape(count, 4, 4), (0, 2, 1)).copy(), res
 
 
 class FuserParams(C.Structure):
