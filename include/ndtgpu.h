@@ -757,6 +757,103 @@ ndtgpu_status ndtgpu_mcl_particles(ndtgpu_mcl *h, size_t first, size_t count, do
  * last update.  Waits for the handle. */
 ndtgpu_status ndtgpu_mcl_mean(ndtgpu_mcl *h, size_t first, size_t count, double *T16_mean, ndtgpu_mcl_result *results);
 
+/* ---- SE(2) pose-graph optimisation of registered links: a bank of graphs ---------------------------------------------------
+ * The offline mapper (ndt_feature/src/ndt_feature_graph_opt.cpp) ends in :147 graph.force2D() and the loop :152-164 --
+ * clearAllLinks, appendLinks(incremental_links), getValidLinks, appendLinks(links), optimizeGraphUsingISAM(graph) -- whose last
+ * call (ndt_offline_mapper.h:40-107) turns the links into node poses with iSAM.  ndtgpu_pgo_* is that call for a bank of
+ * n_graphs independent graphs (the same nodes under several getValidLinks thresholds, several robots or bags, the replay's
+ * 5000 nodes), and it takes the registrar's poses and covariances where they are, in device memory.
+ * Semantics (restated):
+ *   - a graph has n_nodes unknowns p_i = (x, y, t).  Poses enter as (x, y, yaw) with yaw = getRobustYawFromAffine3d
+ *     (utils.h:30-40; convertEigenAffine3dToIsamPose2d, ndt_offline_mapper.h:8-15) and leave the same way; T16_out is
+ *     convertIsamPose2dToEigenAffine3d (ndt_offline_mapper.h:17-26): Translation(x, y, 0) * Rz(t).
+ *   - the prior (Pose2d_Factor, :61) acts on node 0: e = p_0 - origin, the angle wrapped to (-pi, pi]; origin is node 0's pose
+ *     when the graph is set (:59).
+ *   - each link (ref, mov, z) (Pose2d_Pose2d_Factor, :79, :90): e = (p_mov ominus p_ref) - z, the angle wrapped, with
+ *     ominus = (c dx + s dy, -s dx + c dy, wrap(t_mov - t_ref)), c / s the cosine / sine of t_ref, (dx, dy) the translation
+ *     difference (Pose2d::ominus).
+ *   - the cost is sum e^T W e, W an information matrix per factor (its symmetric part is used); W = NULL is 100 * I3, which is
+ *     what :45, :61, :79 and :90 give every factor.
+ *   - slam.batch_optimization() (:97) is Gauss-Newton on this cost, iSAM's default method; after each step the angles are
+ *     wrapped to (-pi, pi].  The Jacobians here are analytic.
+ * PROVENANCE: iSAM (isam/isam.h) is not vendored by the reference; the factors' errors and the batch method are restated from
+ * memory.
+ * DEVIATIONS:
+ *   - the stop rule and its defaults are OURS and explicit (ndtgpu_pgo_params), not iSAM's: stop when the largest absolute
+ *     component of a Gauss-Newton update is <= eps_step, or after max_iterations updates.
+ *   - each linear system is solved by conjugate gradients preconditioned with the inverses of the 3x3 diagonal blocks, from
+ *     zero, to the relative residual eps_linear or max_linear_iterations -- not by sparse QR.  A solve that stops at the cap
+ *     still gives its iterate as the step.
+ *   - upstream adds every link with score < 0 twice (:74-82 and again in :86-93).  The entries here take an edge list as
+ *     given; the host mirror's optimizeGraphUsingISAM (host/ndt_feature_graph_gpu.h) reproduces the doubling.
+ * Device form (csrc/ndt_pgo.hip, ndt_pgo_kernel): one workgroup of 1024 threads optimises one graph from start to finish, `count`
+ * graphs are `count` workgroups of one launch.  Nothing but the workgroup barrier orders its passes: no grid barrier, no queue,
+ * no spin on memory, no atomics; every sum has one fixed order, so a graph's poses and result are the same bits whichever
+ * batch it runs in, whatever first / count are.  A multi-workgroup form for ONE large graph is not written (the
+ * untried lead).
+ * Measured on MI355X (tools/pgo_cost.py; grid-world graphs of 0.5 m cells, start 0.2 m / 0.1 rad off, defaults): 500 nodes and
+ * 1886 links: 5 updates, 1082 inner iterations, 13.8 ms; 256 such graphs in one launch: 25.8 ms (0.10 ms per graph; 5-6 updates,
+ * at most 1306 inner iterations); the replay's size, 5000 nodes and 43.5 k links: 5 updates, 2506 inner iterations, 740 ms,
+ * converged -- no inner solve reached max_linear_iterations.  The NumPy model (dense solve) takes 0.18 s at 500 nodes on one
+ * core. */
+typedef struct ndtgpu_pgo ndtgpu_pgo;
+typedef struct {
+    int32_t max_iterations;          /* Gauss-Newton updates at most (ours: 50) */
+    int32_t max_linear_iterations;   /* conjugate-gradient iterations per update at most (ours: 2000) */
+    double eps_step;                 /* stop when the largest |component| of the update is <= this (ours: 1e-8; m and rad) */
+    double eps_linear;               /* the inner solve's relative residual |r| / |b| (ours: 1e-8) */
+    double prior_information[9];     /* the prior's W, row-major (100 * I3: ndt_offline_mapper.h:45, :61) */
+} ndtgpu_pgo_params;
+/* the defaults above: max_iterations, max_linear_iterations, eps_step and eps_linear are OURS, not iSAM's */
+void ndtgpu_default_pgo_params(ndtgpu_pgo_params *p);
+enum {
+    NDTGPU_PGO_CONVERGED = 0,        /* the last update was within eps_step */
+    NDTGPU_PGO_MAX_ITERATIONS = 1,   /* max_iterations updates without meeting eps_step */
+    NDTGPU_PGO_LINEAR_CAP = 2,       /* in place of 0 or 1: an inner solve of the run stopped at max_linear_iterations */
+    NDTGPU_PGO_NOT_FINITE = 3        /* an input or the cost is not finite: the poses are the last iterate with a finite cost
+                                      * (the poses as set where the input is at fault) */
+};
+typedef struct {
+    int32_t exit_code;               /* NDTGPU_PGO_* */
+    int32_t iterations;              /* Gauss-Newton updates taken */
+    int32_t linear_iterations;       /* conjugate-gradient iterations, all updates together */
+    int32_t pad_;
+    double cost_initial;             /* sum e^T W e at the poses as set */
+    double cost_final;               /* ... at the poses returned */
+    double max_step;                 /* the largest |component| of the last update */
+    int32_t n_nodes;
+    int32_t n_edges;
+} ndtgpu_pgo_result;
+/* room for n_graphs graphs of up to max_nodes nodes and max_edges links each (n_graphs, max_nodes >= 1; max_nodes <= 2^24,
+ * max_edges <= 2^27) */
+ndtgpu_status ndtgpu_pgo_create(size_t n_graphs, size_t max_nodes, size_t max_edges, ndtgpu_pgo **out);
+ndtgpu_status ndtgpu_pgo_destroy(ndtgpu_pgo *h);
+/* installs graph g.  All arrays HOST: pose3 n_nodes x (x, y, yaw), node 0's is the prior's origin; ref_idx / mov_idx n_edges
+ * node indices; meas3 n_edges x (x, y, yaw); info9 n_edges x 9 row-major or NULL (100 * I3 for every link).
+ * NDTGPU_ERR_INVALID -- checked before the handle is read and the device is looked for -- where an index is out of range, where
+ * ref == mov, and where a node is not connected to node 0 (union-find on the host): such a node would make the system
+ * singular.  The node-to-edge adjacency (CSR, ascending edge order) is built here.  Synchronous. */
+ndtgpu_status ndtgpu_pgo_set_graph(ndtgpu_pgo *h, size_t g, size_t n_nodes, const double *pose3, size_t n_edges,
+                                   const uint32_t *ref_idx, const uint32_t *mov_idx, const double *meas3, const double *info9);
+/* the same with the links where ndtgpu_register_batch_cov_device left them: pose3, ref_idx, mov_idx HOST; T16_dev (n_edges x 16,
+ * column-major), cov36_dev (n_edges x 36) and cov_flags_dev (n_edges) DEVICE and complete when the call is made (after
+ * ndtgpu_registrar_sync, or ordered by the caller's own means).  A small kernel (ndt_pgo_links_kernel) turns each T16 into
+ * (x, y, robust yaw) and inverts the (x, y, yaw) block of cov36 -- rows / columns 0, 1, 5, its symmetric part -- into the link's
+ * information; the covariance 0.02 * I3 stands in where the flags say NDTGPU_COV_SINGULAR, NDTGPU_COV_POSE_UNCHANGED or
+ * NDTGPU_COV_NOT_COMPUTED (the reference does the same after "NOTHING HAPPENED", ndt_feature_graph.cpp:283-310) and where the
+ * block does not invert (not positive definite, or an inverse that is not finite).  cov36_dev == NULL gives every link
+ * 100 * I3 (cov_flags_dev is then not read).  No link value visits the host.  Returns when the kernel has run. */
+ndtgpu_status ndtgpu_pgo_set_links_device(ndtgpu_pgo *h, size_t g, size_t n_nodes, const double *pose3, size_t n_edges,
+                                          const uint32_t *ref_idx, const uint32_t *mov_idx, const double *T16_dev,
+                                          const double *cov36_dev, const int32_t *cov_flags_dev);
+/* optimises graphs [first, first + count), each of which has been set, in ONE launch, asynchronous on `stream`; prm NULL: the
+ * defaults.  Calls on one handle are ordered (each waits, on the device, for the previous one, whatever stream that one named).
+ * A graph that ends with NDTGPU_PGO_NOT_FINITE does not fail the call or touch the other graphs. */
+ndtgpu_status ndtgpu_pgo_optimize(ndtgpu_pgo *h, size_t first, size_t count, const ndtgpu_pgo_params *prm, ndtgpu_stream stream);
+/* graph g's poses: pose3_out HOST n_nodes x (x, y, yaw); T16_out HOST n_nodes x 16 column-major or NULL; result may be NULL.
+ * Waits for the handle. */
+ndtgpu_status ndtgpu_pgo_poses(ndtgpu_pgo *h, size_t g, double *pose3_out, double *T16_out, ndtgpu_pgo_result *result);
+
 /* single pair convenience == graph.cpp:273 */
 ndtgpu_status ndtgpu_match_d2d(ndtgpu_mapset *target_set, size_t target_map, ndtgpu_mapset *source_set,
                                size_t source_map, double T16[16], const ndtgpu_match_params *prm,

@@ -11,7 +11,7 @@ _ROOT = os.path.dirname(_HERE)
 _SO = os.path.join(_HERE, "libndtgpu.so")
 _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hip", "ndt_pack.hip", "ndt_fuser.hip", "ndtgpu_api.hip",
             "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip",
-            "ndt_mcl.hip", "ndtgpu_mcl.hip"]
+            "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndtgpu_pgo.hip"]
 
 STATUS = {0: "OK", -1: "ERR_INVALID", -2: "ERR_HIP", -3: "ERR_NO_DEVICE", -4: "ERR_CAPACITY", -5: "ERR_ALLOC"}
 
@@ -136,7 +136,9 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_register_batch_cov_device", "ndtgpu_register_batch_cov_host", "ndtgpu_default_resolutions",
            "ndtgpu_multires_create", "ndtgpu_multires_destroy", "ndtgpu_register_multires_device", "ndtgpu_register_multires_host",
            "ndtgpu_multires_get_info", "ndtgpu_default_mcl_params", "ndtgpu_mcl_create", "ndtgpu_mcl_destroy", "ndtgpu_mcl_initialize",
-           "ndtgpu_mcl_set_particles", "ndtgpu_mcl_update", "ndtgpu_mcl_update_host", "ndtgpu_mcl_particles", "ndtgpu_mcl_mean"]
+           "ndtgpu_mcl_set_particles", "ndtgpu_mcl_update", "ndtgpu_mcl_update_host", "ndtgpu_mcl_particles", "ndtgpu_mcl_mean",
+           "ndtgpu_default_pgo_params", "ndtgpu_pgo_create", "ndtgpu_pgo_destroy", "ndtgpu_pgo_set_graph", "ndtgpu_pgo_set_links_device",
+           "ndtgpu_pgo_optimize", "ndtgpu_pgo_poses"]
 
 _lib = None
 
@@ -257,6 +259,14 @@ def lib():
     L.ndtgpu_mcl_update_host.argtypes = [vp, C.c_size_t, C.c_size_t, dp, C.c_double, vp, C.c_size_t, C.c_size_t, C.c_size_t]
     L.ndtgpu_mcl_particles.argtypes = [vp, C.c_size_t, C.c_size_t, dp, dp, dp]
     L.ndtgpu_mcl_mean.argtypes = [vp, C.c_size_t, C.c_size_t, dp, vp]
+    L.ndtgpu_default_pgo_params.restype = None
+    L.ndtgpu_default_pgo_params.argtypes = [C.POINTER(PgoParams)]
+    L.ndtgpu_pgo_create.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.ndtgpu_pgo_destroy.argtypes = [vp]
+    L.ndtgpu_pgo_set_graph.argtypes = [vp, C.c_size_t, C.c_size_t, dp, C.c_size_t, u32p, u32p, dp, dp]
+    L.ndtgpu_pgo_set_links_device.argtypes = [vp, C.c_size_t, C.c_size_t, dp, C.c_size_t, u32p, u32p, vp, vp, vp]
+    L.ndtgpu_pgo_optimize.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(PgoParams), vp]
+    L.ndtgpu_pgo_poses.argtypes = [vp, C.c_size_t, dp, dp, C.POINTER(PgoResult)]
     _lib = L
     return L
 
@@ -932,6 +942,109 @@ class MCL:
         res = np.zeros(count, dtype=MCL_RESULT_DTYPE)
         _check(lib().ndtgpu_mcl_mean(self.h, int(first), count, _dp(T), C.c_void_p(res.ctypes.data)))
         return np.transpose(T.reshape(count, 4, 4), (0, 2, 1)).copy(), res
+
+
+class PgoParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("max_linear_iterations", C.c_int32), ("eps_step", C.c_double), ("eps_linear", C.c_double),
+                ("prior_information", C.c_double * 9)]
+
+
+class PgoResult(C.Structure):
+    _fields_ = [("exit_code", C.c_int32), ("iterations", C.c_int32), ("linear_iterations", C.c_int32), ("pad_", C.c_int32),
+                ("cost_initial", C.c_double), ("cost_final", C.c_double), ("max_step", C.c_double), ("n_nodes", C.c_int32),
+                ("n_edges", C.c_int32)]
+
+
+# ndtgpu_pgo_result.exit_code (include/ndtgpu.h NDTGPU_PGO_*)
+PGO_CONVERGED, PGO_MAX_ITERATIONS, PGO_LINEAR_CAP, PGO_NOT_FINITE = 0, 1, 2, 3
+
+
+def pgo_params(**fields):
+    """ndtgpu_default_pgo_params with fields replaced (prior_information: 9 values row-major)"""
+    p = PgoParams()
+    lib().ndtgpu_default_pgo_params(C.byref(p))
+    for k, v in fields.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown PGO parameter %r" % k)
+        if k == "prior_information":
+            p.prior_information[:] = [float(x) for x in np.asarray(v, dtype=np.float64).ravel()]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+class PGO:
+    """ndtgpu_pgo: a bank of n_graphs SE(2) pose graphs of up to max_nodes nodes and max_edges links, optimised one workgroup per
+    graph (include/ndtgpu.h: optimizeGraphUsingISAM).  Poses are (x, y, yaw) rows."""
+
+    def __init__(self, n_graphs, max_nodes, max_edges):
+        h = C.c_void_p()
+        _check(lib().ndtgpu_pgo_create(int(n_graphs), int(max_nodes), int(max_edges), C.byref(h)))
+        self.h, self.n_graphs = h, int(n_graphs)
+        self._n_nodes = [0] * int(n_graphs)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ndtgpu_pgo_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _graph(poses, ref, mov):
+        ps = _f64(poses).reshape(-1, 3)
+        ri = np.ascontiguousarray(ref, dtype=np.uint32).reshape(-1)
+        mi = np.ascontiguousarray(mov, dtype=np.uint32).reshape(-1)
+        if ri.shape != mi.shape:
+            raise ValueError("PGO: one ref and one mov index per link")
+        u32p = C.POINTER(C.c_uint32)
+        return ps, ri, mi, ri.ctypes.data_as(u32p), mi.ctypes.data_as(u32p)
+
+    def set_graph(self, g, poses, ref, mov, meas, info=None):
+        """graph g: poses [n, 3] (node 0's is the prior's origin), links ref -> mov with meas [m, 3] and info [m, 3, 3] (None: 100 I)"""
+        ps, ri, mi, rp, mp = self._graph(poses, ref, mov)
+        z = _f64(meas).reshape(-1, 3)
+        W = None if info is None else _f64(info).reshape(-1, 9)
+        if z.shape[0] != ri.shape[0] or (W is not None and W.shape[0] != ri.shape[0]):
+            raise ValueError("PGO.set_graph: one measurement (and information matrix) per link")
+        _check(lib().ndtgpu_pgo_set_graph(self.h, int(g), ps.shape[0], _dp(ps), ri.shape[0], rp, mp, _dp(z), None if W is None else _dp(W)))
+        self._n_nodes[int(g)] = ps.shape[0]
+
+    def set_links_device(self, g, poses, ref, mov, T16_dev, cov36_dev=None, cov_flags_dev=None):
+        """graph g with its links as ndtgpu_register_batch_cov_device left them: torch CUDA tensors T16_dev float64 [m, 16],
+        cov36_dev float64 [m, 36] and cov_flags_dev int32 [m] (both None: 100 I for every link), complete when the call is made"""
+        ps, ri, mi, rp, mp = self._graph(poses, ref, mov)
+        m = ri.shape[0]
+        assert T16_dev.is_cuda and T16_dev.is_contiguous() and T16_dev.numel() >= 16 * m
+        if cov36_dev is not None:
+            assert cov36_dev.is_cuda and cov36_dev.is_contiguous() and cov36_dev.numel() >= 36 * m
+            assert cov_flags_dev is not None and cov_flags_dev.is_cuda and cov_flags_dev.numel() >= m
+        _check(lib().ndtgpu_pgo_set_links_device(self.h, int(g), ps.shape[0], _dp(ps), m, rp, mp, C.c_void_p(T16_dev.data_ptr()),
+                                                 None if cov36_dev is None else C.c_void_p(cov36_dev.data_ptr()),
+                                                 None if cov36_dev is None else C.c_void_p(cov_flags_dev.data_ptr())))
+        self._n_nodes[int(g)] = ps.shape[0]
+
+    def optimize(self, first=0, count=None, stream=None, **params):
+        """graphs [first, first + count) in one launch, asynchronous on `stream`; keyword arguments: fields of ndtgpu_pgo_params"""
+        count = self.n_graphs - first if count is None else int(count)
+        p = pgo_params(**params)
+        _check(lib().ndtgpu_pgo_optimize(self.h, int(first), count, C.byref(p), _stream_ptr(stream)))
+
+    def poses(self, g, with_T=False):
+        """(poses [n, 3], result dict) of graph g, with_T: (poses, T [n, 4, 4], result); waits for the handle"""
+        n = self._n_nodes[int(g)]
+        ps = np.zeros((max(n, 1), 3))
+        T = np.zeros((max(n, 1), 16)) if with_T else None
+        r = PgoResult()
+        _check(lib().ndtgpu_pgo_poses(self.h, int(g), _dp(ps), None if T is None else _dp(T), C.byref(r)))
+        res = {k: getattr(r, k) for k, _ in PgoResult._fields_ if k != "pad_"}
+        if with_T:
+            return ps, np.transpose(T.reshape(-1, 4, 4), (0, 2, 1)).copy(), res
+        return ps, res
 
 
 class FuserParams(C.Structure):

@@ -1,0 +1,257 @@
+// ndtgpu_pgo.hip -- C-ABI (include/ndtgpu.h) of the SE(2) pose-graph optimiser: optimizeGraphUsingISAM
+// (ndt_feature/include/ndt_feature/ndt_offline_mapper.h:40-107; call site ndt_feature/src/ndt_feature_graph_opt.cpp:152-164) for
+// a bank of independent graphs.  Host side only: the handle, the checks of a graph (index range, self links, connectivity by
+// union-find), the node-to-edge adjacency and the order of the launches; the optimisation runs in csrc/ndt_pgo.hip.
+#include "ndtgpu_host.h"
+#include "ndt_pgo.h"
+
+#include <new>
+#include <numeric>
+
+struct ndtgpu_pgo {
+    size_t G = 0;
+    NdtPgoView v{};
+    std::vector<uint32_t> n_nodes;         // per graph, 0: not set
+    hipEvent_t used = nullptr;             // recorded after the last launch of a call
+    bool used_valid = false;
+    hipStream_t hst = nullptr;             // the synchronous entries' stream
+};
+
+static void sym6(const double *W9, double *W6)
+{
+    W6[0] = W9[0]; W6[1] = 0.5 * (W9[1] + W9[3]); W6[2] = 0.5 * (W9[2] + W9[6]);
+    W6[3] = W9[4]; W6[4] = 0.5 * (W9[5] + W9[7]); W6[5] = W9[8];
+}
+
+// what set_graph / set_links_device check before the handle is read: indices, self links, every node connected to node 0
+static ndtgpu_status pgo_check_graph(const char *what, size_t n_nodes, const double *pose3, size_t n_edges, const uint32_t *ref_idx,
+                                     const uint32_t *mov_idx)
+{
+    const std::string w(what);
+    if (n_nodes == 0 || !pose3 || (n_edges && (!ref_idx || !mov_idx)))
+        return fail(NDTGPU_ERR_INVALID, (w + ": poses and link indices are required").c_str());
+    if (n_nodes > (1u << 24) || n_edges > (1u << 27)) return fail(NDTGPU_ERR_INVALID, (w + ": graph too large").c_str());
+    std::vector<uint32_t> parent(n_nodes);
+    std::iota(parent.begin(), parent.end(), 0u);
+    auto find = [&](uint32_t a) {
+        while (parent[a] != a) {
+            parent[a] = parent[parent[a]];
+            a = parent[a];
+        }
+        return a;
+    };
+    for (size_t e = 0; e < n_edges; e++) {
+        if (ref_idx[e] >= n_nodes || mov_idx[e] >= n_nodes) return fail(NDTGPU_ERR_INVALID, (w + ": link index out of range").c_str());
+        if (ref_idx[e] == mov_idx[e]) return fail(NDTGPU_ERR_INVALID, (w + ": a link joins a node to itself").c_str());
+        const uint32_t a = find(ref_idx[e]), b = find(mov_idx[e]);
+        if (a != b) parent[std::max(a, b)] = std::min(a, b);
+    }
+    for (size_t i = 1; i < n_nodes; i++)
+        if (find((uint32_t)i) != 0) return fail(NDTGPU_ERR_INVALID, (w + ": a node is not connected to node 0").c_str());
+    return NDTGPU_OK;
+}
+
+extern "C" {
+
+void ndtgpu_default_pgo_params(ndtgpu_pgo_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    // the stop rule is ours, not iSAM's
+    p->max_iterations = 50;
+    p->max_linear_iterations = 2000;
+    p->eps_step = 1e-8;
+    p->eps_linear = 1e-8;
+    p->prior_information[0] = p->prior_information[4] = p->prior_information[8] = 100.0;   // ndt_offline_mapper.h:45, :61
+}
+
+ndtgpu_status ndtgpu_pgo_destroy(ndtgpu_pgo *h)
+{
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo_destroy: null");
+    if (h->used_valid) (void)hipEventSynchronize(h->used);
+    if (h->hst) (void)hipStreamSynchronize(h->hst);
+    void *bufs[] = {h->v.state, h->v.pose, h->v.origin, h->v.ref, h->v.mov, h->v.meas, h->v.info, h->v.adj_off, h->v.adj, h->v.jac,
+                    h->v.te, h->v.node};
+    for (void *b : bufs)
+        if (b) (void)hipFree(b);
+    if (h->used) (void)hipEventDestroy(h->used);
+    if (h->hst) (void)hipStreamDestroy(h->hst);
+    delete h;
+    return NDTGPU_OK;
+}
+
+ndtgpu_status ndtgpu_pgo_create(size_t n_graphs, size_t max_nodes, size_t max_edges, ndtgpu_pgo **out)
+{
+    if (!out) return fail(NDTGPU_ERR_INVALID, "pgo_create: out is NULL");
+    *out = nullptr;
+    if (n_graphs == 0 || n_graphs > (1u << 24) || max_nodes == 0 || max_nodes > (1u << 24) || max_edges > (1u << 27))
+        return fail(NDTGPU_ERR_INVALID, "pgo_create: n_graphs and max_nodes must be 1 .. 2^24, max_edges <= 2^27");
+    if (!have_device()) return fail(NDTGPU_ERR_NO_DEVICE, "pgo_create: no HIP device");
+    ndtgpu_pgo *h = new (std::nothrow) ndtgpu_pgo();
+    if (!h) return fail(NDTGPU_ERR_ALLOC, "pgo_create: host alloc");
+    h->G = n_graphs;
+    h->n_nodes.assign(n_graphs, 0);
+    NdtPgoView &v = h->v;
+    v.max_nodes = max_nodes;
+    v.max_edges = max_edges;
+    const size_t G = n_graphs, E = std::max<size_t>(max_edges, 1);     // (no zero-byte allocations)
+    hipError_t e = hipSuccess;
+    if (e == hipSuccess) e = hipMalloc((void **)&v.state, G * sizeof(ndtgpu_pgo_result));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.pose, G * 3 * max_nodes * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.origin, G * 3 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.ref, G * E * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.mov, G * E * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.meas, G * 3 * E * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.info, G * 6 * E * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.adj_off, G * (max_nodes + 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.adj, G * 2 * E * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.jac, G * 4 * E * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.te, G * 3 * E * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.node, G * NDT_PGO_NODE_DOUBLES * max_nodes * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(v.state, 0, G * sizeof(ndtgpu_pgo_result));
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->used, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->hst, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        ndtgpu_pgo_destroy(h);
+        return fail(NDTGPU_ERR_ALLOC, "pgo_create: device buffers", e);
+    }
+    *out = h;
+    return NDTGPU_OK;
+}
+
+// poses, indices and the adjacency of graph g onto the device, on the handle's stream behind its previous call; meas / info are
+// the caller's to fill on the same stream before pgo_installed
+static ndtgpu_status pgo_install(ndtgpu_pgo *h, const char *what, size_t g, size_t n_nodes, const double *pose3, size_t n_edges,
+                                 const uint32_t *ref_idx, const uint32_t *mov_idx)
+{
+    const std::string w(what);
+    if (g >= h->G) return fail(NDTGPU_ERR_INVALID, (w + ": graph index out of range").c_str());
+    if (n_nodes > h->v.max_nodes || n_edges > h->v.max_edges)
+        return fail(NDTGPU_ERR_CAPACITY, (w + ": more nodes or links than the handle was created for").c_str());
+    // (values that are not finite are not refused here: the kernel reports NDTGPU_PGO_NOT_FINITE for that graph)
+    // node -> incident edges, CSR; a node's entries in ascending edge order
+    std::vector<uint32_t> off(n_nodes + 1, 0), adj(2 * n_edges);
+    for (size_t e = 0; e < n_edges; e++) {
+        off[ref_idx[e] + 1]++;
+        off[mov_idx[e] + 1]++;
+    }
+    for (size_t i = 0; i < n_nodes; i++) off[i + 1] += off[i];
+    std::vector<uint32_t> at(off.begin(), off.end() - 1);
+    for (size_t e = 0; e < n_edges; e++) {
+        adj[at[ref_idx[e]]++] = (uint32_t)(e << 1);
+        adj[at[mov_idx[e]]++] = (uint32_t)(e << 1) | 1u;
+    }
+    std::vector<int32_t> ri(ref_idx, ref_idx + n_edges), mi(mov_idx, mov_idx + n_edges);
+    ndtgpu_pgo_result st{};
+    st.n_nodes = (int32_t)n_nodes;
+    st.n_edges = (int32_t)n_edges;
+    const NdtPgoView &v = h->v;
+    h->n_nodes[g] = 0;
+    if (h->used_valid) HIP_TRY(hipStreamWaitEvent(h->hst, h->used, 0));
+    HIP_TRY(hipMemcpyAsync(v.pose + g * 3 * v.max_nodes, pose3, 3 * n_nodes * sizeof(double), hipMemcpyHostToDevice, h->hst));
+    HIP_TRY(hipMemcpyAsync(v.origin + g * 3, pose3, 3 * sizeof(double), hipMemcpyHostToDevice, h->hst));
+    HIP_TRY(hipMemcpyAsync(v.adj_off + g * (v.max_nodes + 1), off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->hst));
+    if (n_edges) {
+        HIP_TRY(hipMemcpyAsync(v.ref + g * v.max_edges, ri.data(), n_edges * sizeof(int32_t), hipMemcpyHostToDevice, h->hst));
+        HIP_TRY(hipMemcpyAsync(v.mov + g * v.max_edges, mi.data(), n_edges * sizeof(int32_t), hipMemcpyHostToDevice, h->hst));
+        HIP_TRY(hipMemcpyAsync(v.adj + g * 2 * v.max_edges, adj.data(), adj.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->hst));
+    }
+    HIP_TRY(hipMemcpyAsync(v.state + g, &st, sizeof st, hipMemcpyHostToDevice, h->hst));
+    HIP_TRY(hipStreamSynchronize(h->hst));               // (the staging vectors above end with this function)
+    return NDTGPU_OK;
+}
+
+static ndtgpu_status pgo_installed(ndtgpu_pgo *h, size_t g, size_t n_nodes)
+{
+    HIP_TRY(hipEventRecord(h->used, h->hst));
+    h->used_valid = true;
+    HIP_TRY(hipStreamSynchronize(h->hst));
+    h->n_nodes[g] = (uint32_t)n_nodes;
+    return NDTGPU_OK;
+}
+
+ndtgpu_status ndtgpu_pgo_set_graph(ndtgpu_pgo *h, size_t g, size_t n_nodes, const double *pose3, size_t n_edges,
+                                   const uint32_t *ref_idx, const uint32_t *mov_idx, const double *meas3, const double *info9)
+{
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo_set_graph: null handle");
+    if (n_edges && !meas3) return fail(NDTGPU_ERR_INVALID, "pgo_set_graph: meas3 is required");
+    ndtgpu_status rc = pgo_check_graph("pgo_set_graph", n_nodes, pose3, n_edges, ref_idx, mov_idx);
+    if (rc != NDTGPU_OK) return rc;
+    if ((rc = pgo_install(h, "pgo_set_graph", g, n_nodes, pose3, n_edges, ref_idx, mov_idx)) != NDTGPU_OK) return rc;
+    if (n_edges) {
+        std::vector<double> W(6 * n_edges);
+        static const double I100[9] = {100, 0, 0, 0, 100, 0, 0, 0, 100};
+        for (size_t e = 0; e < n_edges; e++) sym6(info9 ? info9 + 9 * e : I100, &W[6 * e]);
+        const NdtPgoView &v = h->v;
+        HIP_TRY(hipMemcpyAsync(v.meas + g * 3 * v.max_edges, meas3, 3 * n_edges * sizeof(double), hipMemcpyHostToDevice, h->hst));
+        HIP_TRY(hipMemcpyAsync(v.info + g * 6 * v.max_edges, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice, h->hst));
+        HIP_TRY(hipStreamSynchronize(h->hst));
+    }
+    return pgo_installed(h, g, n_nodes);
+}
+
+ndtgpu_status ndtgpu_pgo_set_links_device(ndtgpu_pgo *h, size_t g, size_t n_nodes, const double *pose3, size_t n_edges,
+                                          const uint32_t *ref_idx, const uint32_t *mov_idx, const double *T16_dev,
+                                          const double *cov36_dev, const int32_t *cov_flags_dev)
+{
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo_set_links_device: null handle");
+    if (n_edges && (!T16_dev || (cov36_dev && !cov_flags_dev)))
+        return fail(NDTGPU_ERR_INVALID, "pgo_set_links_device: T16_dev is required, and cov_flags_dev with cov36_dev");
+    ndtgpu_status rc = pgo_check_graph("pgo_set_links_device", n_nodes, pose3, n_edges, ref_idx, mov_idx);
+    if (rc != NDTGPU_OK) return rc;
+    if ((rc = pgo_install(h, "pgo_set_links_device", g, n_nodes, pose3, n_edges, ref_idx, mov_idx)) != NDTGPU_OK) return rc;
+    hipError_t e = ndt_pgo_launch_links(h->v, g, n_edges, T16_dev, cov36_dev, cov_flags_dev, h->hst);
+    if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "pgo_set_links_device: launch", e);
+    return pgo_installed(h, g, n_nodes);
+}
+
+ndtgpu_status ndtgpu_pgo_optimize(ndtgpu_pgo *h, size_t first, size_t count, const ndtgpu_pgo_params *prm, ndtgpu_stream stream)
+{
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo_optimize: null handle");
+    if (count == 0 || first >= h->G || count > h->G - first)
+        return fail(NDTGPU_ERR_INVALID, "pgo_optimize: graphs [first, first + count) out of range");
+    ndtgpu_pgo_params p;
+    ndtgpu_default_pgo_params(&p);
+    if (prm) p = *prm;
+    bool ok = p.max_iterations >= 0 && p.max_linear_iterations >= 0 && p.eps_step >= 0.0 && p.eps_linear >= 0.0;   // (NaN fails)
+    for (double w : p.prior_information) ok = ok && std::isfinite(w);
+    if (!ok) return fail(NDTGPU_ERR_INVALID, "pgo_optimize: bad parameter (caps and tolerances >= 0, a finite prior)");
+    for (size_t g = first; g < first + count; g++)
+        if (!h->n_nodes[g]) return fail(NDTGPU_ERR_INVALID, "pgo_optimize: a graph of the range has not been set");
+    NdtPgoParamsDev d;
+    d.max_iterations = p.max_iterations;
+    d.max_linear_iterations = p.max_linear_iterations;
+    d.eps_step = p.eps_step;
+    d.eps_linear = p.eps_linear;
+    sym6(p.prior_information, d.prior);
+    hipStream_t st = (hipStream_t)stream;
+    if (h->used_valid) HIP_TRY(hipStreamWaitEvent(st, h->used, 0));   // (the previous call may have run on another stream)
+    hipError_t e = ndt_pgo_launch(h->v, first, count, d, st);
+    if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "pgo_optimize: launch", e);
+    HIP_TRY(hipEventRecord(h->used, st));
+    h->used_valid = true;
+    return NDTGPU_OK;
+}
+
+ndtgpu_status ndtgpu_pgo_poses(ndtgpu_pgo *h, size_t g, double *pose3_out, double *T16_out, ndtgpu_pgo_result *result)
+{
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo_poses: null handle");
+    if (g >= h->G || !h->n_nodes[g]) return fail(NDTGPU_ERR_INVALID, "pgo_poses: no such graph, or it has not been set");
+    if (h->used_valid) HIP_TRY(hipEventSynchronize(h->used));
+    const size_t n = h->n_nodes[g];
+    std::vector<double> p(3 * n);
+    HIP_TRY(hipMemcpy(p.data(), h->v.pose + g * 3 * h->v.max_nodes, p.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (pose3_out) memcpy(pose3_out, p.data(), p.size() * sizeof(double));
+    if (T16_out)
+        for (size_t i = 0; i < n; i++) {                 // convertIsamPose2dToEigenAffine3d: Translation(x, y, 0) * Rz(t)
+            double *T = T16_out + 16 * i;
+            const double c = std::cos(p[3 * i + 2]), s = std::sin(p[3 * i + 2]);
+            for (int k = 0; k < 16; k++) T[k] = 0.0;
+            T[0] = c; T[1] = s; T[4] = -s; T[5] = c; T[10] = 1.0;
+            T[12] = p[3 * i]; T[13] = p[3 * i + 1]; T[15] = 1.0;
+        }
+    if (result) HIP_TRY(hipMemcpy(result, h->v.state + g, sizeof *result, hipMemcpyDeviceToHost));
+    return NDTGPU_OK;
+}
+
+}   // extern "C"

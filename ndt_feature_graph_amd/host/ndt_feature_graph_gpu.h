@@ -4,6 +4,7 @@
 //   ndt_feature::NDTFeatureFuserHMT   ndt_feature_fuser_hmt.h:36-334 (Params, initialize, update)
 //   ndt_feature::NDTFeatureLink / NDTFeatureNode / overlapNDTOccupancyScore   ndt_feature_link.h:9-56, ndt_feature_node.h:38-252
 //   ndt_feature::NDTFeatureGraph      ndt_feature_graph.h:20-280 (initialize, update, updateLink[s]UsingNDTRegistration, ...)
+//   ndt_feature::optimizeGraphUsingISAM   ndt_offline_mapper.h:8-26, 40-107 (on the device: ndtgpu_pgo_*)
 // Class, member and parameter names are the reference's, so that its callers compile against this header.  What is behind them
 // is not the reference's control flow retyped but the batched device entries:
 //   * NDTFeatureFuserHMT::initialize / update are ONE C-ABI call each (ndtgpu_fuser_initialize_batch / ndtgpu_fuser_update_batch
@@ -801,5 +802,54 @@ protected:
     Eigen::Affine3d sensor_pose_, Tnow;
     double distance_moved_in_last_node_;
 };
+
+// convertEigenAffine3dToIsamPose2d / convertIsamPose2dToEigenAffine3d (ndt_offline_mapper.h:8-26); isam::Pose2d is (x, y, t)
+inline Pose2d convertEigenAffine3dToIsamPose2d(const Eigen::Affine3d &a)
+{
+    return Pose2d(a.translation()(0), a.translation()(1), getRobustYawFromAffine3d(a));
+}
+inline Eigen::Affine3d convertIsamPose2dToEigenAffine3d(const Pose2d &p)
+{
+    return ndtgpu_host::affine_from_pose(p(0), p(1), 0., 0., 0., p(2));
+}
+
+// optimizeGraphUsingISAM (ndt_offline_mapper.h:40-107; called at ndt_feature_graph_opt.cpp:164) on the device: one graph of a
+// ndtgpu_pgo bank (include/ndtgpu.h gives the factors, the Gauss-Newton stop rule and what differs from iSAM).  As upstream: node
+// 0's pose is the prior (:59-63), the links with score < 0 are added first (:74-82) and then EVERY link, those again (:86-93),
+// every factor at the information 100 * I3 (:45), and the poses go back with setPose (:101-104).  `params` / `result` are
+// additions: the stop rule's parameters (NULL: the defaults) and the optimiser's report.
+inline void optimizeGraphUsingISAM(NDTFeatureGraphInterface &graph, const ndtgpu_pgo_params *params = nullptr,
+                                   ndtgpu_pgo_result *result = nullptr)
+{
+    const size_t n = graph.getNbNodes();
+    if (n == 0) return;
+    std::vector<double> pose(3 * n), meas;
+    std::vector<uint32_t> ref, mov;
+    for (size_t i = 0; i < n; i++) {
+        const Pose2d p = convertEigenAffine3dToIsamPose2d(graph.getNodeInterface(i).getPose());
+        for (int a = 0; a < 3; a++) pose[3 * i + a] = p(a);
+    }
+    for (int pass = 0; pass < 2; pass++)
+        for (size_t i = 0; i < graph.getNbLinks(); i++) {
+            const NDTFeatureLinkInterface &link = graph.getLinkInterface(i);
+            if (pass == 0 && !(link.getScore() < 0.)) continue;
+            const Pose2d z = convertEigenAffine3dToIsamPose2d(link.getRelPose());
+            ref.push_back((uint32_t)link.getRefIdx());
+            mov.push_back((uint32_t)link.getMovIdx());
+            for (int a = 0; a < 3; a++) meas.push_back(z(a));
+        }
+    ndtgpu_pgo *h = nullptr;
+    ndtgpu_host::check(ndtgpu_pgo_create(1, n, ref.size(), &h), "ndtgpu_pgo_create");
+    ndtgpu_status rc = ndtgpu_pgo_set_graph(h, 0, n, pose.data(), ref.size(), ref.data(), mov.data(), meas.data(), nullptr);
+    if (rc == NDTGPU_OK) rc = ndtgpu_pgo_optimize(h, 0, 1, params, nullptr);
+    ndtgpu_pgo_result r;
+    if (rc == NDTGPU_OK) rc = ndtgpu_pgo_poses(h, 0, pose.data(), nullptr, &r);
+    const std::string err = rc == NDTGPU_OK ? "" : ndtgpu_last_error();
+    ndtgpu_pgo_destroy(h);
+    if (rc != NDTGPU_OK) throw ndtgpu_host::Error(rc, "optimizeGraphUsingISAM: " + err);
+    if (result) *result = r;
+    for (size_t i = 0; i < n; i++)
+        graph.getNodeInterface(i).setPose(convertIsamPose2dToEigenAffine3d(Pose2d(pose[3 * i], pose[3 * i + 1], pose[3 * i + 2])));
+}
 
 }  // namespace ndt_feature
