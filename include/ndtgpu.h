@@ -872,6 +872,10 @@ ndtgpu_status ndtgpu_mapset_counters(ndtgpu_mapset *set, size_t map, uint32_t ou
 /* kernel names as they appear in rocprofv3 --kernel-trace, for bench.py / profiles/ */
 const char *ndtgpu_kernel_name(int which); /* 0 build, 1 match, 2 derivatives */
 
+/* test aid: resources the library currently owns, process-wide */
+ndtgpu_status ndtgpu_live_resources(uint64_t counts[4]);
+/* device buffers, pinned buffers, events, streams */
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,7 +138,7 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_multires_get_info", "ndtgpu_default_mcl_params", "ndtgpu_mcl_create", "ndtgpu_mcl_destroy", "ndtgpu_mcl_initialize",
            "ndtgpu_mcl_set_particles", "ndtgpu_mcl_update", "ndtgpu_mcl_update_host", "ndtgpu_mcl_particles", "ndtgpu_mcl_mean",
            "ndtgpu_default_pgo_params", "ndtgpu_pgo_create", "ndtgpu_pgo_destroy", "ndtgpu_pgo_set_graph", "ndtgpu_pgo_set_links_device",
-           "ndtgpu_pgo_optimize", "ndtgpu_pgo_poses"]
+           "ndtgpu_pgo_optimize", "ndtgpu_pgo_poses", "ndtgpu_live_resources"]
 
 _lib = None
 
@@ -267,6 +267,8 @@ def lib():
     L.ndtgpu_pgo_set_links_device.argtypes = [vp, C.c_size_t, C.c_size_t, dp, C.c_size_t, u32p, u32p, vp, vp, vp]
     L.ndtgpu_pgo_optimize.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(PgoParams), vp]
     L.ndtgpu_pgo_poses.argtypes = [vp, C.c_size_t, dp, dp, C.POINTER(PgoResult)]
+    if hasattr(L, "ndtgpu_live_resources"):            # (NDTGPU_LIB may name a build from before this entry existed)
+        L.ndtgpu_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -278,6 +280,13 @@ def _check(rc):
 
 def device_count():
     return lib().ndtgpu_device_count()
+
+
+def live_resources():
+    """test aid (ndtgpu_live_resources): what the library owns right now, process-wide -- (device buffers, pinned buffers, events, streams)"""
+    c = (C.c_uint64 * 4)()
+    _check(lib().ndtgpu_live_resources(c))
+    return tuple(int(x) for x in c)
 
 
 def _dp(a):

@@ -24,11 +24,11 @@ ndtgpu_status mapset_build_core(ndtgpu_mapset *s, size_t first, size_t count, co
     if (cell) cp = *cell;
     if (s->v.occ && count)   // a rebuilt map starts from cells without readings
         HIP_TRY(hipMemsetAsync(s->v.occ + first * (size_t)s->v.grid.slots, 0, count * (size_t)s->v.grid.slots * sizeof(float), st));
-    if (s->profiling && !s->profile_span) HIP_TRY(hipEventRecord(s->ev[0], st));
+    if (s->profiling && !s->profile_span) HIP_TRY(s->ev[0].record(st));
     hipError_t e = ndt_launch_build(s->v, first, count, xyz_dev, n_points, stride_bytes, map_stride_bytes, range_limit,
                          orig_dev, cp.n_min, cp.eval_factor, s->nice_range(first, count), st);
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "mapset_build: launch", e);
-    if (s->profiling && !s->profile_span) { HIP_TRY(hipEventRecord(s->ev[1], st)); s->ev_valid[0] = true; }
+    if (s->profiling && !s->profile_span) HIP_TRY(s->ev[1].record(st));
     return s->touch(st);
 }
 
@@ -65,6 +65,13 @@ extern "C" {
 // (bumped whenever a kernel changes: bench.py only quotes PMC figures taken with the same version)
 const char *ndtgpu_version(void) { return "ndtgpu 0.6.6 (gfx950)"; }
 const char *ndtgpu_last_error(void) { return g_err.c_str(); }
+
+ndtgpu_status ndtgpu_live_resources(uint64_t counts[4])
+{
+    if (!counts) return fail(NDTGPU_ERR_INVALID, "live_resources: null");
+    for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed);
+    return NDTGPU_OK;
+}
 
 int ndtgpu_device_count(void)
 {
@@ -130,33 +137,27 @@ ndtgpu_status ndtgpu_mapset_create(const ndtgpu_grid_params *grid, size_t n_maps
         for (int a = 0; a < 3; a++) s->centres_host[m * 3 + a] = grid->centre[a];
     s->nice_host.assign(n_maps, ndt_grid_is_nice(g, grid->centre) ? 1 : 0);
 
-    hipError_t e;
-#define ALLOC(ptr, bytes)                                                          \
-    if ((e = hipMalloc((void **)&(ptr), (bytes))) != hipSuccess) {                 \
-        ndtgpu_mapset_destroy(s);                                                  \
-        return fail(NDTGPU_ERR_ALLOC, "mapset_create: hipMalloc " #ptr, e);        \
-    }
-    ALLOC(s->v.rankmap, n_maps * ndt_rm_stride(g) * sizeof(uint2));
-    ALLOC(s->v.wtable, n_maps * (size_t)g.slots * sizeof(int32_t));
-    ALLOC(s->v.bitmap, n_maps * (size_t)((g.slots + 31) / 32) * sizeof(uint32_t));
-    ALLOC(s->v.cells, n_maps * (size_t)cap * sizeof(NdtCell));
-    ALLOC(s->v.acc, n_maps * (size_t)cap * sizeof(NdtAcc));
-    ALLOC(s->v.acc_slot, n_maps * (size_t)cap * sizeof(uint32_t));
-    ALLOC(s->v.rank_agg, n_maps * (size_t)(NDT_RANK_SEGS + 2) * sizeof(uint32_t));
-    ALLOC(s->v.counters, n_maps * sizeof(NdtMapCounters));
-    ALLOC(s->v.centres, n_maps * 3 * sizeof(double));
+    NdtSetView &v = s->v;
+#define ALLOC(buf, n) CREATE_TRY(s, NDTGPU_ERR_ALLOC, "mapset_create: device buffer " #buf, s->buf.alloc((n), &v.buf))
+    ALLOC(rankmap, n_maps * ndt_rm_stride(g));
+    ALLOC(wtable, n_maps * (size_t)g.slots);
+    ALLOC(bitmap, n_maps * (size_t)((g.slots + 31) / 32));
+    ALLOC(cells, n_maps * (size_t)cap);
+    ALLOC(acc, n_maps * (size_t)cap);
+    ALLOC(acc_slot, n_maps * (size_t)cap);
+    ALLOC(rank_agg, n_maps * (size_t)(NDT_RANK_SEGS + 2));
+    ALLOC(counters, n_maps);
+    ALLOC(centres, n_maps * 3);
 #undef ALLOC
-    if ((e = hipMemset(s->v.rankmap, 0, n_maps * ndt_rm_stride(g) * sizeof(uint2))) != hipSuccess ||
-        (e = hipMemset(s->v.wtable, 0xFF, n_maps * (size_t)g.slots * sizeof(int32_t))) != hipSuccess ||
-        (e = hipMemset(s->v.bitmap, 0, n_maps * (size_t)((g.slots + 31) / 32) * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMemset(s->v.acc, 0, n_maps * (size_t)cap * sizeof(NdtAcc))) != hipSuccess ||
-        (e = hipMemset(s->v.counters, 0, n_maps * sizeof(NdtMapCounters))) != hipSuccess ||
-        (e = hipMemset(s->v.rank_agg, 0, n_maps * (size_t)(NDT_RANK_SEGS + 2) * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMemcpy(s->v.centres, s->centres_host.data(), n_maps * 3 * sizeof(double), hipMemcpyHostToDevice)) !=
-            hipSuccess) {
-        ndtgpu_mapset_destroy(s);
-        return fail(NDTGPU_ERR_HIP, "mapset_create: init", e);
-    }
+#define INIT(expr) CREATE_TRY(s, NDTGPU_ERR_HIP, "mapset_create: init", expr)
+    INIT(hipMemset(v.rankmap, 0, n_maps * ndt_rm_stride(g) * sizeof(uint2)));
+    INIT(hipMemset(v.wtable, 0xFF, n_maps * (size_t)g.slots * sizeof(int32_t)));
+    INIT(hipMemset(v.bitmap, 0, n_maps * (size_t)((g.slots + 31) / 32) * sizeof(uint32_t)));
+    INIT(hipMemset(v.acc, 0, n_maps * (size_t)cap * sizeof(NdtAcc)));
+    INIT(hipMemset(v.counters, 0, n_maps * sizeof(NdtMapCounters)));
+    INIT(hipMemset(v.rank_agg, 0, n_maps * (size_t)(NDT_RANK_SEGS + 2) * sizeof(uint32_t)));
+    INIT(hipMemcpy(v.centres, s->centres_host.data(), n_maps * 3 * sizeof(double), hipMemcpyHostToDevice));
+#undef INIT
     *out = s;
     return NDTGPU_OK;
 }
@@ -164,38 +165,7 @@ ndtgpu_status ndtgpu_mapset_create(const ndtgpu_grid_params *grid, size_t n_maps
 ndtgpu_status ndtgpu_mapset_destroy(ndtgpu_mapset *s)
 {
     if (!s) return NDTGPU_OK;
-    (void)hipDeviceSynchronize();
-    if (s->pin) (void)hipHostFree(s->pin);
-    for (auto &m : s->marks) (void)hipEventDestroy(m.ev);
-    for (int k = 0; k < ndtgpu_mapset::HOST_SLOTS; k++) {
-        if (s->host_ring[k]) (void)hipHostFree(s->host_ring[k]);
-        if (s->host_ev[k]) (void)hipEventDestroy(s->host_ev[k]);
-    }
-    if (s->stage_free_ev) (void)hipEventDestroy(s->stage_free_ev);
-    if (s->host_copy_stream) (void)hipStreamDestroy(s->host_copy_stream);
-    if (s->host_build_stream) (void)hipStreamDestroy(s->host_build_stream);
-    if (s->v.rankmap) (void)hipFree(s->v.rankmap);
-    if (s->v.wtable) (void)hipFree(s->v.wtable);
-    if (s->v.bitmap) (void)hipFree(s->v.bitmap);
-    if (s->v.cells) (void)hipFree(s->v.cells);
-    if (s->v.acc) (void)hipFree(s->v.acc);
-    if (s->v.acc_slot) (void)hipFree(s->v.acc_slot);
-    if (s->v.rank_agg) (void)hipFree(s->v.rank_agg);
-    if (s->v.counters) (void)hipFree(s->v.counters);
-    if (s->v.centres) (void)hipFree(s->v.centres);
-    if (s->v.occ) (void)hipFree(s->v.occ);
-    if (s->v.occ_delta) (void)hipFree(s->v.occ_delta);
-    if (s->v.occ_touched) (void)hipFree(s->v.occ_touched);
-    if (s->v.cells_alt) (void)hipFree(s->v.cells_alt);
-    if (s->v.cell_sel) (void)hipFree(s->v.cell_sel);
-    if (s->stage) (void)hipFree(s->stage);
-    if (s->work) (void)hipFree(s->work);
-    if (s->coop_work) (void)hipFree(s->coop_work);
-    if (s->work_ev) (void)hipEventDestroy(s->work_ev);
-    if (s->origins_dev) (void)hipFree(s->origins_dev);
-    if (s->origins_ev) (void)hipEventDestroy(s->origins_ev);
-    for (int k = 0; k < 4; k++)
-        if (s->ev[k]) (void)hipEventDestroy(s->ev[k]);
+    (void)hipDeviceSynchronize();       // (work on the caller's streams included)
     delete s;
     return NDTGPU_OK;
 }
@@ -227,8 +197,8 @@ static ndtgpu_status upload_origins(ndtgpu_mapset *s, const double *range_origin
     if (!range_origins || !count) return NDTGPU_OK;
     ndtgpu_status orc = s->origins_reserve(count * 3, st);
     if (orc != NDTGPU_OK) return orc;
-    HIP_TRY(hipMemcpyAsync(s->origins_dev, range_origins, count * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-    *orig_dev = s->origins_dev;
+    HIP_TRY(hipMemcpyAsync(s->origins.get(), range_origins, count * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    *orig_dev = s->origins.get();
     return NDTGPU_OK;
 }
 
@@ -242,7 +212,7 @@ ndtgpu_status ndtgpu_mapset_build(ndtgpu_mapset *s, size_t first, size_t count, 
     ndtgpu_status rc = upload_origins(s, range_origins, count, st, &orig_dev);
     if (rc != NDTGPU_OK) return rc;
     rc = mapset_build_core(s, first, count, xyz_dev, n_points, stride_bytes, map_stride_bytes, range_limit, orig_dev, cell, st);
-    if (orig_dev) { const ndtgpu_status urc = s->origins_used(st); if (rc == NDTGPU_OK) rc = urc; }
+    if (orig_dev && s->origins_used.record(st) != hipSuccess && rc == NDTGPU_OK) rc = fail(NDTGPU_ERR_HIP, "mapset_build: origins event");
     return rc;
 }
 
@@ -251,17 +221,17 @@ ndtgpu_status ndtgpu_profiling_enable(ndtgpu_mapset *s, int on)
     if (!s) return fail(NDTGPU_ERR_INVALID, "profiling_enable: null");
     if (on)
         for (int k = 0; k < 4; k++)
-            if (!s->ev[k]) HIP_TRY(hipEventCreate(&s->ev[k]));
+            HIP_TRY(s->ev[k].create(hipEventDefault));
     s->profiling = on != 0;
     return NDTGPU_OK;
 }
 
 ndtgpu_status ndtgpu_last_kernel_ms(ndtgpu_mapset *s, int which, float *ms)
 {
-    if (!s || !ms || which < 0 || which > 1 || !s->ev_valid[which])
+    if (!s || !ms || which < 0 || which > 1 || !s->ev[2 * which + 1].valid())
         return fail(NDTGPU_ERR_INVALID, "last_kernel_ms: nothing recorded");
-    HIP_TRY(hipEventSynchronize(s->ev[2 * which + 1]));
-    HIP_TRY(hipEventElapsedTime(ms, s->ev[2 * which], s->ev[2 * which + 1]));
+    HIP_TRY(s->ev[2 * which + 1].sync());
+    HIP_TRY(hipEventElapsedTime(ms, s->ev[2 * which].get(), s->ev[2 * which + 1].get()));
     return NDTGPU_OK;
 }
 
@@ -282,7 +252,7 @@ static ndtgpu_status stage_host_clouds(ndtgpu_mapset *s, const void *xyz_host, s
     ndtgpu_status rc = s->ensure_stage(bytes);
     if (rc != NDTGPU_OK) return rc;
     // the staging area may still be read by the kernels of the previous call (another stream): order behind them
-    if (s->stage_free_valid) HIP_TRY(hipStreamWaitEvent(st, s->stage_free_ev, 0));
+    HIP_TRY(s->stage_free.order(st));
     const size_t slot = ndtgpu_mapset::HOST_SLOT_BYTES;
     const char *force = getenv("NDTGPU_HOST_PIPE");            // 0: never the ring, 1: always (tests)
     // (the ring cuts the input into chunks of WHOLE clouds that lie one after the other: clouds that overlap in memory --
@@ -290,12 +260,12 @@ static ndtgpu_status stage_host_clouds(ndtgpu_mapset *s, const void *xyz_host, s
     const bool ring = n_points && map_stride_bytes >= cloud_bytes && map_stride_bytes <= slot && cloud_bytes <= slot &&
                       (force ? atoi(force) != 0 : bytes >= (24u << 20));
     if (!ring) {
-        if (n_points) HIP_TRY(hipMemcpyAsync(s->stage, xyz_host, bytes, hipMemcpyHostToDevice, st));   // (pageable: returns when read)
-        rc = launch(0, count, s->stage);
+        if (n_points) HIP_TRY(hipMemcpyAsync(s->stage.get(), xyz_host, bytes, hipMemcpyHostToDevice, st));   // (pageable: returns when read)
+        rc = launch(0, count, s->stage.get());
     } else {
         rc = s->ensure_host_ring();
         if (rc != NDTGPU_OK) return rc;
-        if (s->stage_free_valid) HIP_TRY(hipStreamWaitEvent(s->host_copy_stream, s->stage_free_ev, 0));
+        HIP_TRY(s->stage_free.order(s->host_copy_stream.get()));
         // clouds per chunk: a chunk of `per` clouds occupies (per - 1) * map_stride_bytes + cloud_bytes of its slot
         const size_t per = std::max<size_t>(1, std::min(count, 1 + (slot - cloud_bytes) / map_stride_bytes));
         const size_t n_chunks = (count + per - 1) / per;
@@ -311,14 +281,14 @@ static ndtgpu_status stage_host_clouds(ndtgpu_mapset *s, const void *xyz_host, s
         };
         // a slot that an earlier CALL sent off may still be in flight
         for (int k = 0; k < R; k++)
-            if (s->host_ev_used[k]) { HIP_TRY(hipEventSynchronize(s->host_ev[k])); s->host_ev_used[k] = false; }
+            if (s->host_ev[k].valid()) { HIP_TRY(s->host_ev[k].sync()); s->host_ev[k].clear(); }
         std::vector<std::thread> workers;
         for (int w = 0; w < n_workers; w++)
             workers.emplace_back([&, w]() {
                 for (size_t c = (size_t)w; c < n_chunks && !stop.load(std::memory_order_relaxed); c += (size_t)n_workers) {
                     while ((long)c >= allowed.load(std::memory_order_acquire) && !stop.load(std::memory_order_relaxed)) std::this_thread::yield();
                     if (stop.load(std::memory_order_relaxed)) break;
-                    memcpy(s->host_ring[c % R], (const char *)xyz_host + c * per * map_stride_bytes, chunk_bytes(c));
+                    memcpy(s->host_ring[c % R].get(), (const char *)xyz_host + c * per * map_stride_bytes, chunk_bytes(c));
                     staged[c].store(1, std::memory_order_release);
                 }
             });
@@ -326,36 +296,34 @@ static ndtgpu_status stage_host_clouds(ndtgpu_mapset *s, const void *xyz_host, s
         ndtgpu_status lrc = NDTGPU_OK;
         // (profiling: one bracket around all chunks' launches -- ndtgpu_last_kernel_ms then reports the whole build, copies
         //  that the chunks wait for included -- instead of the last chunk's alone)
-        const bool span = s->profiling && s->ev[0] && s->ev[1];
-        if (span) { herr = hipEventRecord(s->ev[0], st); s->profile_span = true; }
+        const bool span = s->profiling && s->ev[0].get() && s->ev[1].get();
+        if (span) { herr = s->ev[0].record(st); s->profile_span = true; }
         for (size_t c = 0; c < n_chunks && herr == hipSuccess && lrc == NDTGPU_OK; c++) {
             while (!staged[c].load(std::memory_order_acquire)) std::this_thread::yield();
             const int k = (int)(c % R);
-            char *dst = (char *)s->stage + c * per * map_stride_bytes;
-            herr = hipMemcpyAsync(dst, s->host_ring[k], chunk_bytes(c), hipMemcpyHostToDevice, s->host_copy_stream);
-            if (herr == hipSuccess) herr = hipEventRecord(s->host_ev[k], s->host_copy_stream);
-            if (herr == hipSuccess) { s->host_ev_used[k] = true; herr = hipStreamWaitEvent(st, s->host_ev[k], 0); }
+            char *dst = s->stage.get() + c * per * map_stride_bytes;
+            herr = hipMemcpyAsync(dst, s->host_ring[k].get(), chunk_bytes(c), hipMemcpyHostToDevice, s->host_copy_stream.get());
+            if (herr == hipSuccess) herr = s->host_ev[k].record(s->host_copy_stream.get());
+            if (herr == hipSuccess) herr = s->host_ev[k].order(st);
             if (herr == hipSuccess) lrc = launch(c * per, std::min(per, count - c * per), dst);
             // chunk c + R will reuse this slot: it may be written once this copy has left the host.  (The calling thread
             // waits here while the workers fill the other slots and the device builds chunk c under the next copies.)
             if (c + R < n_chunks && herr == hipSuccess) {
-                herr = hipEventSynchronize(s->host_ev[k]);
-                s->host_ev_used[k] = false;
+                herr = s->host_ev[k].sync();
+                s->host_ev[k].clear();
                 allowed.store((long)(c + R) + 1, std::memory_order_release);
             }
         }
         if (span) {
             s->profile_span = false;
-            if (herr == hipSuccess && lrc == NDTGPU_OK && hipEventRecord(s->ev[1], st) == hipSuccess) s->ev_valid[0] = true;
+            if (herr == hipSuccess && lrc == NDTGPU_OK) (void)s->ev[1].record(st);
         }
         if (herr != hipSuccess || lrc != NDTGPU_OK) stop.store(1);
         for (auto &t : workers) t.join();
         rc = herr != hipSuccess ? fail(NDTGPU_ERR_HIP, "host clouds: staging copy", herr) : lrc;
     }
     // (also after a failure: chunks that were launched before it may still be reading the staging area)
-    if (!s->stage_free_ev && hipEventCreateWithFlags(&s->stage_free_ev, hipEventDisableTiming) != hipSuccess) s->stage_free_ev = nullptr;
-    if (s->stage_free_ev && hipEventRecord(s->stage_free_ev, st) == hipSuccess) s->stage_free_valid = true;
-    else if (rc == NDTGPU_OK) return fail(NDTGPU_ERR_HIP, "host clouds: event");
+    if (s->stage_free.record(st) != hipSuccess && rc == NDTGPU_OK) return fail(NDTGPU_ERR_HIP, "host clouds: event");
     return rc;
 }
 
@@ -377,7 +345,7 @@ ndtgpu_status ndtgpu_mapset_build_host_async(ndtgpu_mapset *s, size_t first, siz
                                return mapset_build_core(s, first + c0, cnt, dev, n_points, stride_bytes, map_stride_bytes,
                                                         range_limit, orig_dev ? orig_dev + 3 * c0 : nullptr, cell, st);
                            });
-    if (orig_dev) { const ndtgpu_status urc = s->origins_used(st); if (rc == NDTGPU_OK) rc = urc; }
+    if (orig_dev && s->origins_used.record(st) != hipSuccess && rc == NDTGPU_OK) rc = fail(NDTGPU_ERR_HIP, "mapset_build: origins event");
     return rc;
 }
 
@@ -390,9 +358,9 @@ ndtgpu_status ndtgpu_mapset_build_host(ndtgpu_mapset *s, size_t first, size_t co
     if (rc != NDTGPU_OK) return rc;
     { ndtgpu_status wrc_ = s->wait_all(); if (wrc_ != NDTGPU_OK) return wrc_; }             // (earlier work on these maps, whatever stream it used)
     rc = ndtgpu_mapset_build_host_async(s, first, count, xyz_host, n_points, stride_bytes, map_stride_bytes, range_limit,
-                                        range_origins, cell, (ndtgpu_stream)s->host_build_stream);
+                                        range_origins, cell, (ndtgpu_stream)s->host_build_stream.get());
     if (rc != NDTGPU_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(s->host_build_stream));       // the stream the maps were built on: no device-wide wait
+    HIP_TRY(hipStreamSynchronize(s->host_build_stream.get()));       // the stream the maps were built on: no device-wide wait
     return NDTGPU_OK;
 }
 
@@ -478,8 +446,8 @@ ndtgpu_status ndtgpu_mapset_set_cells(ndtgpu_mapset *s, size_t map, const double
     if (uniq.size() > s->v.grid.max_cells) return fail(NDTGPU_ERR_CAPACITY, "set_cells: more cells than max_cells");
     ndtgpu_status rc = s->ensure_stage(std::max<size_t>(uniq.size() * sizeof(NdtCell), 16));
     if (rc != NDTGPU_OK) return rc;
-    if (!uniq.empty()) HIP_TRY(hipMemcpy(s->stage, uniq.data(), uniq.size() * sizeof(NdtCell), hipMemcpyHostToDevice));
-    hipError_t e = ndt_launch_install_cells(s->v, map, (const NdtCell *)s->stage, uniq.size(), nullptr);
+    if (!uniq.empty()) HIP_TRY(hipMemcpy(s->stage.get(), uniq.data(), uniq.size() * sizeof(NdtCell), hipMemcpyHostToDevice));
+    hipError_t e = ndt_launch_install_cells(s->v, map, (const NdtCell *)s->stage.get(), uniq.size(), nullptr);
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "set_cells: launch", e);
     HIP_TRY(hipStreamSynchronize(nullptr));
     return NDTGPU_OK;
@@ -493,8 +461,8 @@ ndtgpu_status ndtgpu_mapset_discard_cells(ndtgpu_mapset *s, size_t map, const fl
     ndtgpu_status rc = s->ensure_stage(n_points * 3 * sizeof(float));
     if (rc != NDTGPU_OK) return rc;
     { ndtgpu_status wrc_ = s->wait_all(); if (wrc_ != NDTGPU_OK) return wrc_; }
-    HIP_TRY(hipMemcpy(s->stage, xyz, n_points * 3 * sizeof(float), hipMemcpyHostToDevice));
-    hipError_t e = ndt_launch_discard(s->v, map, (const float *)s->stage, n_points, nullptr);
+    HIP_TRY(hipMemcpy(s->stage.get(), xyz, n_points * 3 * sizeof(float), hipMemcpyHostToDevice));
+    hipError_t e = ndt_launch_discard(s->v, map, (const float *)s->stage.get(), n_points, nullptr);
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "discard_cells: launch", e);
     HIP_TRY(hipStreamSynchronize(nullptr));
     return NDTGPU_OK;
@@ -506,30 +474,28 @@ ndtgpu_status ndtgpu_mapset_enable_occupancy(ndtgpu_mapset *s)
     if (s->v.occ) return NDTGPU_OK;
     const size_t slots = (size_t)s->v.grid.slots, cap = s->v.grid.max_cells, n = s->n_maps;
     { ndtgpu_status wrc_ = s->wait_all(); if (wrc_ != NDTGPU_OK) return wrc_; }
-    float *occ = nullptr;
-    long long *delta = nullptr;
-    NdtCell *alt = nullptr;
-    uint32_t *sel = nullptr;
-    unsigned char *touched = nullptr;
+    // (locals until all of them exist: a failure leaves the set as it was, without occupancies)
+    DeviceBuffer<float> occ;
+    DeviceBuffer<long long> delta;
+    DeviceBuffer<unsigned char> touched;
+    DeviceBuffer<NdtCell> alt;
+    DeviceBuffer<uint32_t> sel;
     const size_t blocks = (slots + 255) / 256;
     hipError_t e;
-    if ((e = hipMalloc((void **)&occ, n * slots * sizeof(float))) != hipSuccess ||
-        (e = hipMalloc((void **)&delta, n * slots * sizeof(long long))) != hipSuccess ||
-        (e = hipMalloc((void **)&touched, n * blocks)) != hipSuccess ||
-        (e = hipMemset(touched, 0, n * blocks)) != hipSuccess ||
-        (e = hipMalloc((void **)&alt, n * cap * sizeof(NdtCell))) != hipSuccess ||
-        (e = hipMalloc((void **)&sel, n * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMemset(occ, 0, n * slots * sizeof(float))) != hipSuccess ||
-        (e = hipMemset(delta, 0, n * slots * sizeof(long long))) != hipSuccess ||
-        (e = hipMemset(sel, 0, n * sizeof(uint32_t))) != hipSuccess) {
-        if (occ) (void)hipFree(occ);
-        if (delta) (void)hipFree(delta);
-        if (touched) (void)hipFree(touched);
-        if (alt) (void)hipFree(alt);
-        if (sel) (void)hipFree(sel);
+    if ((e = occ.alloc(n * slots)) != hipSuccess ||
+        (e = delta.alloc(n * slots)) != hipSuccess ||
+        (e = touched.alloc(n * blocks)) != hipSuccess ||
+        (e = hipMemset(touched.get(), 0, n * blocks)) != hipSuccess ||
+        (e = alt.alloc(n * cap)) != hipSuccess ||
+        (e = sel.alloc(n)) != hipSuccess ||
+        (e = hipMemset(occ.get(), 0, n * slots * sizeof(float))) != hipSuccess ||
+        (e = hipMemset(delta.get(), 0, n * slots * sizeof(long long))) != hipSuccess ||
+        (e = hipMemset(sel.get(), 0, n * sizeof(uint32_t))) != hipSuccess)
         return fail(NDTGPU_ERR_ALLOC, "enable_occupancy: device memory", e);
-    }
-    s->v.occ = occ; s->v.occ_delta = delta; s->v.occ_touched = touched; s->v.cells_alt = alt; s->v.cell_sel = sel;
+    s->occ = std::move(occ); s->occ_delta = std::move(delta); s->occ_touched = std::move(touched);
+    s->cells_alt = std::move(alt); s->cell_sel = std::move(sel);
+    s->v.occ = s->occ.get(); s->v.occ_delta = s->occ_delta.get(); s->v.occ_touched = s->occ_touched.get();
+    s->v.cells_alt = s->cells_alt.get(); s->v.cell_sel = s->cell_sel.get();
     return NDTGPU_OK;
 }
 
@@ -561,15 +527,16 @@ ndtgpu_status ndtgpu_mapset_add_cloud(ndtgpu_mapset *s, size_t first, size_t cou
         ndtgpu_status orc = s->origins_reserve(count * 3, st);
         if (orc != NDTGPU_OK) return orc;
     }
-    HIP_TRY(hipMemcpyAsync(s->origins_dev, origins, count * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->origins.get(), origins, count * 3 * sizeof(double), hipMemcpyHostToDevice, st));
     NdtFuseParams p;
     p.maxz = fp.maxz; p.sensor_noise = fp.sensor_noise; p.maxnumpoints = fp.maxnumpoints;
     p.occupancy_limit = fp.occupancy_limit; p.eval_factor = fp.eval_factor; p.n_min = fp.n_min;
-    hipError_t e = ndt_launch_fuse(s->v, first, count, xyz_dev, n_points, stride_bytes, map_stride_bytes, s->origins_dev, p,
+    hipError_t e = ndt_launch_fuse(s->v, first, count, xyz_dev, n_points, stride_bytes, map_stride_bytes, s->origins.get(), p,
                                    s->nice_range(first, count), st);
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "add_cloud: launch", e);
     { ndtgpu_status trc = s->touch(st); if (trc != NDTGPU_OK) return trc; }
-    return s->origins_used(st);
+    HIP_TRY(s->origins_used.record(st));
+    return NDTGPU_OK;
 }
 
 ndtgpu_status ndtgpu_mapset_add_cloud_host_async(ndtgpu_mapset *s, size_t first, size_t count, const void *xyz_host,
@@ -594,9 +561,9 @@ ndtgpu_status ndtgpu_mapset_add_cloud_host(ndtgpu_mapset *s, size_t first, size_
     if (rc != NDTGPU_OK) return rc;
     { ndtgpu_status wrc_ = s->wait_all(); if (wrc_ != NDTGPU_OK) return wrc_; }
     rc = ndtgpu_mapset_add_cloud_host_async(s, first, count, xyz_host, n_points, stride_bytes, map_stride_bytes, origins, prm,
-                                            (ndtgpu_stream)s->host_build_stream);
+                                            (ndtgpu_stream)s->host_build_stream.get());
     if (rc != NDTGPU_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(s->host_build_stream));
+    HIP_TRY(hipStreamSynchronize(s->host_build_stream.get()));
     return NDTGPU_OK;
 }
 
@@ -677,7 +644,7 @@ ndtgpu_status ndtgpu_overlap_score_batch(ndtgpu_mapset *rs, const uint32_t *ridx
     std::vector<unsigned> offs(U + 1, 0u);
     if (U) {
         // pass 1: how many cells with a reading every listed map has (before the buffer is laid out for good: it may move)
-        char *b0 = (char *)rs->stage;
+        char *b0 = rs->stage.get();
         HIP_TRY(hipMemcpyAsync(b0 + off_u, list_maps.data(), U * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         hipError_t e0 = ndt_launch_occ_count(ms->v, 0, (const uint32_t *)(b0 + off_u), U, (unsigned *)(b0 + off_o), st);
         if (e0 != hipSuccess) return fail(NDTGPU_ERR_HIP, "overlap_score: count launch", e0);
@@ -690,7 +657,7 @@ ndtgpu_status ndtgpu_overlap_score_batch(ndtgpu_mapset *rs, const uint32_t *ridx
         rc = rs->ensure_stage(off_p + (size_t)at * 8u);
         if (rc != NDTGPU_OK) return rc;
     }
-    char *base = (char *)rs->stage;
+    char *base = rs->stage.get();
     HIP_TRY(hipMemcpyAsync(base + off_T, T16, bT, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(base + off_r, ridx, bI, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(base + off_m, midx, bI, hipMemcpyHostToDevice, st));
@@ -753,13 +720,12 @@ ndtgpu_status ndtgpu_mapset_occupied_cells_max(ndtgpu_mapset *s, size_t first, s
     *max_occupied = 0;
     if (count == 0) return NDTGPU_OK;
     hipStream_t st = (hipStream_t)stream;
-    unsigned *counts_dev = nullptr;
-    HIP_TRY(hipMalloc((void **)&counts_dev, count * sizeof(unsigned)));
+    DeviceBuffer<unsigned> counts_dev;
+    HIP_TRY(counts_dev.alloc(count));
     std::vector<unsigned> counts(count);
-    hipError_t e = ndt_launch_occ_count(s->v, first, nullptr, count, counts_dev, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), counts_dev, count * sizeof(unsigned), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(counts_dev);
+    hipError_t e = ndt_launch_occ_count(s->v, first, nullptr, count, counts_dev.get(), st);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), counts_dev.get(), count * sizeof(unsigned), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);      // (counts_dev is free once the stream has drained)
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "occupied_cells_max", e);
     for (unsigned c : counts) *max_occupied = std::max<uint32_t>(*max_occupied, c);
     return NDTGPU_OK;

@@ -13,31 +13,30 @@ extern "C" {
 struct ndtgpu_fuser_bank {
     ndtgpu_fuser_params prm{};
     size_t n = 0;
-    ndtgpu_mapset *nodes = nullptr, *scans = nullptr;
-    bool own_nodes = false;
+    ndtgpu_mapset *nodes = nullptr;               // the node maps: the caller's (borrowed), or own_nodes (below)
     struct HostState {
         NdtFuserState s{};
         double Todom[16];
         bool is_init = false;
     };
     std::vector<HostState> st;
-    NdtFuserState *st_dev = nullptr;
-    double *sensor_pose_dev = nullptr;
+    DeviceBuffer<NdtFuserState> st_dev;
+    DeviceBuffer<double> sensor_pose_dev;
     // staging of one call: a pinned block and its device twin
     //   [count] Tscan16 | Tmotion16 | Test16 | Q36 | origins3 | centres3 | feat cells (40 x 18) | feat offsets | idx | spose16 | fuse origins3 |
     //   match results | cov36 | cov flags | results
-    char *pin = nullptr, *dev = nullptr;
-    size_t stage_bytes = 0;
-    float *xyz_a = nullptr, *xyz_b = nullptr;     // the scans in the node frame before / after the registration (packed xyz)
-    size_t xyz_cap = 0;
-    void *xyz_in = nullptr;                       // host clouds (the *_host entries) on their way in
-    size_t xyz_in_bytes = 0;
-    hipStream_t own_st = nullptr;
-    hipEvent_t done_ev = nullptr;
-    bool in_flight = false;
+    PinnedBuffer<char> pin;
+    DeviceBuffer<char> dev;
+    DeviceBuffer<float> xyz_a, xyz_b;             // the scans in the node frame before / after the registration (packed xyz)
+    DeviceBuffer<char> xyz_in;                    // host clouds (the *_host entries) on their way in
+    Fence done;                                   // recorded behind the last call's launches; valid: that call is in flight
     size_t fl_first = 0, fl_count = 0;
     size_t off_res = 0, off_pin_res = 0;          // where the in-flight call's results sit in the staging block
     hipStream_t fl_stream = nullptr;
+    // the owned map sets after the buffers: they go first, and ndtgpu_mapset_destroy's hipDeviceSynchronize covers the buffers
+    // above too, also after a call that failed midway on a stream of the caller's and never recorded `done`
+    MapsetOwner own_nodes, scans;
+    Stream own_st;                                // the *_host entries' stream (last: ndtgpu_resource.h)
 };
 
 namespace {
@@ -159,18 +158,7 @@ ndtgpu_status ndtgpu_fuser_prepare(const ndtgpu_fuser_params *prm, const double 
 ndtgpu_status ndtgpu_fuser_bank_destroy(ndtgpu_fuser_bank *b)
 {
     if (!b) return NDTGPU_OK;
-    if (b->in_flight && b->done_ev) (void)hipEventSynchronize(b->done_ev);
-    if (b->done_ev) (void)hipEventDestroy(b->done_ev);
-    if (b->scans) (void)ndtgpu_mapset_destroy(b->scans);
-    if (b->own_nodes && b->nodes) (void)ndtgpu_mapset_destroy(b->nodes);
-    if (b->st_dev) (void)hipFree(b->st_dev);
-    if (b->sensor_pose_dev) (void)hipFree(b->sensor_pose_dev);
-    if (b->pin) (void)hipHostFree(b->pin);
-    if (b->dev) (void)hipFree(b->dev);
-    if (b->xyz_a) (void)hipFree(b->xyz_a);
-    if (b->xyz_b) (void)hipFree(b->xyz_b);
-    if (b->xyz_in) (void)hipFree(b->xyz_in);
-    if (b->own_st) { (void)hipStreamSynchronize(b->own_st); (void)hipStreamDestroy(b->own_st); }
+    (void)b->done.sync();                         // (the call in flight, on whatever stream)
     delete b;
     return NDTGPU_OK;
 }
@@ -197,8 +185,8 @@ ndtgpu_status ndtgpu_fuser_bank_create(const ndtgpu_fuser_params *prm, size_t n_
         g.res = prm->resolution;
         g.size[0] = prm->map_size_x; g.size[1] = prm->map_size_y; g.size[2] = prm->map_size_z;
         g.max_cells = prm->max_cells;
-        rc = ndtgpu_mapset_create(&g, n_fusers, &b->nodes);
-        b->own_nodes = rc == NDTGPU_OK;
+        rc = mapset_create_owned(&g, n_fusers, b->own_nodes);
+        b->nodes = b->own_nodes.get();
     }
     if (rc == NDTGPU_OK) rc = ndtgpu_mapset_enable_occupancy(b->nodes);
     if (rc == NDTGPU_OK) {
@@ -208,18 +196,15 @@ ndtgpu_status ndtgpu_fuser_bank_create(const ndtgpu_fuser_params *prm, size_t n_
         g.size[0] = g.size[1] = prm->sensor_range + 3.0 * prm->resolution;
         g.size[2] = prm->map_size_z;
         g.max_cells = prm->max_cells;
-        rc = ndtgpu_mapset_create(&g, n_fusers, &b->scans);
+        rc = mapset_create_owned(&g, n_fusers, b->scans);
     }
-    hipError_t e = hipSuccess;
-    if (rc == NDTGPU_OK) e = hipMalloc((void **)&b->st_dev, n_fusers * sizeof(NdtFuserState));
-    if (rc == NDTGPU_OK && e == hipSuccess) e = hipMalloc((void **)&b->sensor_pose_dev, 16 * sizeof(double));
-    if (rc == NDTGPU_OK && e == hipSuccess) e = hipMemcpy(b->sensor_pose_dev, prm->sensor_pose, 16 * sizeof(double), hipMemcpyHostToDevice);
-    if (rc == NDTGPU_OK && e == hipSuccess) e = hipEventCreateWithFlags(&b->done_ev, hipEventDisableTiming);
-    if (rc != NDTGPU_OK || e != hipSuccess) {
-        const std::string why = rc != NDTGPU_OK ? g_err : std::string("fuser_bank_create: ") + hipGetErrorString(e);
-        ndtgpu_fuser_bank_destroy(b);
-        return fail(rc != NDTGPU_OK ? rc : NDTGPU_ERR_HIP, why.c_str());
-    }
+    if (rc != NDTGPU_OK) { delete b; return rc; }
+#define TRY(expr) CREATE_TRY(b, NDTGPU_ERR_HIP, "fuser_bank_create", expr)
+    TRY(b->st_dev.alloc(n_fusers));
+    TRY(b->sensor_pose_dev.alloc(16));
+    TRY(hipMemcpy(b->sensor_pose_dev.get(), prm->sensor_pose, 16 * sizeof(double), hipMemcpyHostToDevice));
+    TRY(b->done.create());
+#undef TRY
     *out = b;
     return NDTGPU_OK;
 }
@@ -228,45 +213,31 @@ ndtgpu_status ndtgpu_fuser_bank_mapsets(ndtgpu_fuser_bank *b, ndtgpu_mapset **no
 {
     if (!b) return fail(NDTGPU_ERR_INVALID, "fuser_bank_mapsets: null");
     if (node_maps) *node_maps = b->nodes;
-    if (scan_maps) *scan_maps = b->scans;
+    if (scan_maps) *scan_maps = b->scans.get();
     return NDTGPU_OK;
 }
 
 // the host's copy of the pose state catches up with the device: waits for the call in flight
 static ndtgpu_status fuser_catch_up(ndtgpu_fuser_bank *b)
 {
-    if (!b->in_flight) return NDTGPU_OK;
-    HIP_TRY(hipEventSynchronize(b->done_ev));
-    b->in_flight = false;
+    if (!b->done.valid()) return NDTGPU_OK;
+    HIP_TRY(b->done.sync());
+    b->done.clear();
     if (b->fl_count) {
         std::vector<NdtFuserState> tmp(b->fl_count);
-        HIP_TRY(hipMemcpy(tmp.data(), b->st_dev + b->fl_first, b->fl_count * sizeof(NdtFuserState), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(tmp.data(), b->st_dev.get() + b->fl_first, b->fl_count * sizeof(NdtFuserState), hipMemcpyDeviceToHost));
         for (size_t k = 0; k < b->fl_count; k++) b->st[b->fl_first + k].s = tmp[k];
     }
     return NDTGPU_OK;
 }
 
+// room for a call's staging block and moved scans (no launch uses the old blocks: every caller has caught up with the call in flight)
 static ndtgpu_status fuser_stage(ndtgpu_fuser_bank *b, size_t bytes, size_t count, size_t n_points)
 {
-    if (bytes > b->stage_bytes) {
-        if (b->pin) (void)hipHostFree(b->pin);
-        if (b->dev) (void)hipFree(b->dev);
-        b->pin = b->dev = nullptr;
-        b->stage_bytes = 0;
-        HIP_TRY(hipHostMalloc((void **)&b->pin, bytes, hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&b->dev, bytes));
-        b->stage_bytes = bytes;
-    }
-    const size_t need = count * n_points * 3;
-    if (need > b->xyz_cap) {
-        if (b->xyz_a) (void)hipFree(b->xyz_a);
-        if (b->xyz_b) (void)hipFree(b->xyz_b);
-        b->xyz_a = b->xyz_b = nullptr;
-        b->xyz_cap = 0;
-        HIP_TRY(hipMalloc((void **)&b->xyz_a, need * sizeof(float)));
-        HIP_TRY(hipMalloc((void **)&b->xyz_b, need * sizeof(float)));
-        b->xyz_cap = need;
-    }
+    HIP_TRY(b->pin.reserve(bytes));
+    HIP_TRY(b->dev.reserve(bytes));
+    HIP_TRY(b->xyz_a.reserve(count * n_points * 3));
+    HIP_TRY(b->xyz_b.reserve(count * n_points * 3));
     return NDTGPU_OK;
 }
 
@@ -288,7 +259,7 @@ ndtgpu_status ndtgpu_fuser_initialize_batch(ndtgpu_fuser_bank *b, size_t first, 
     // Tnow = initPos; the map is centred on it (z = 0) and receives the cloud from where the sensor stood
     rc = ndtgpu_mapset_clear(b->nodes, first, count);
     if (rc != NDTGPU_OK) return rc;
-    double *Tinit = (double *)(b->pin + L.Tscan), *orig = (double *)(b->pin + L.forigin), *Tsens = (double *)(b->pin + L.Tmotion);
+    double *Tinit = (double *)(b->pin.get() + L.Tscan), *orig = (double *)(b->pin.get() + L.forigin), *Tsens = (double *)(b->pin.get() + L.Tmotion);
     for (size_t k = 0; k < count; k++) {
         ndtgpu_fuser_bank::HostState &h = b->st[first + k];
         const double *T0 = initPose16 + 16 * k;
@@ -307,23 +278,22 @@ ndtgpu_status ndtgpu_fuser_initialize_batch(ndtgpu_fuser_bank *b, size_t first, 
         ndt_pose_mul(T0, b->prm.sensor_pose, Ts);              // Tnow_sensor: the origin the readings were taken from
         for (int a = 0; a < 3; a++) orig[3 * k + a] = Ts[12 + a];
     }
-    HIP_TRY(hipMemcpyAsync(b->dev, b->pin, L.total, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b->dev.get(), b->pin.get(), L.total, hipMemcpyHostToDevice, st));
     {
         std::vector<NdtFuserState> tmp(count);
         for (size_t k = 0; k < count; k++) tmp[k] = b->st[first + k].s;
-        HIP_TRY(hipMemcpy(b->st_dev + first, tmp.data(), count * sizeof(NdtFuserState), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(b->st_dev.get() + first, tmp.data(), count * sizeof(NdtFuserState), hipMemcpyHostToDevice));
     }
-    hipError_t e = ndt_launch_cloud_transform(xyz_dev, count, n_points, stride_bytes, map_stride_bytes, (const double *)(b->dev + L.Tmotion),
-                                              (const double *)(b->dev + L.Tscan), 16, b->xyz_b, st);
+    hipError_t e = ndt_launch_cloud_transform(xyz_dev, count, n_points, stride_bytes, map_stride_bytes, (const double *)(b->dev.get() + L.Tmotion),
+                                              (const double *)(b->dev.get() + L.Tscan), 16, b->xyz_b.get(), st);
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "fuser_initialize: transform", e);
     NdtFuseParams fp;
     fp.maxz = 100.0; fp.sensor_noise = 0.1; fp.maxnumpoints = 1e5; fp.occupancy_limit = 255.0; fp.eval_factor = 1000.0; fp.n_min = 3;   // :92-94
-    e = ndt_launch_fuse(b->nodes->v, first, count, b->xyz_b, n_points, 12, n_points * 12, (const double *)(b->dev + L.forigin), fp,
+    e = ndt_launch_fuse(b->nodes->v, first, count, b->xyz_b.get(), n_points, 12, n_points * 12, (const double *)(b->dev.get() + L.forigin), fp,
                         b->nodes->nice_range(first, count), st);
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "fuser_initialize: fuse launch", e);
     { ndtgpu_status trc = b->nodes->touch(st); if (trc != NDTGPU_OK) return trc; }
-    HIP_TRY(hipEventRecord(b->done_ev, st));
-    b->in_flight = true;
+    HIP_TRY(b->done.record(st));
     b->fl_first = first; b->fl_count = 0;                      // (the host state is already what the device holds)
     b->fl_stream = st;
     return NDTGPU_OK;
@@ -349,10 +319,10 @@ ndtgpu_status ndtgpu_fuser_update_batch(ndtgpu_fuser_bank *b, size_t first, size
     rc = fuser_stage(b, L.total, count, n_points);
     if (rc != NDTGPU_OK) return rc;
     // ---- host: what depends on the odometry increment and the current pose only -----------------------------------------
-    double *Tscan = (double *)(b->pin + L.Tscan), *Tm = (double *)(b->pin + L.Tmotion), *Te = (double *)(b->pin + L.Test),
-           *Q = (double *)(b->pin + L.Q), *orig = (double *)(b->pin + L.origin), *cen = (double *)(b->pin + L.centre),
-           *fc = (double *)(b->pin + L.feat);
-    uint32_t *foff = (uint32_t *)(b->pin + L.foff), *idx = (uint32_t *)(b->pin + L.idx);
+    double *Tscan = (double *)(b->pin.get() + L.Tscan), *Tm = (double *)(b->pin.get() + L.Tmotion), *Te = (double *)(b->pin.get() + L.Test),
+           *Q = (double *)(b->pin.get() + L.Q), *orig = (double *)(b->pin.get() + L.origin), *cen = (double *)(b->pin.get() + L.centre),
+           *fc = (double *)(b->pin.get() + L.feat);
+    uint32_t *foff = (uint32_t *)(b->pin.get() + L.foff), *idx = (uint32_t *)(b->pin.get() + L.idx);
     for (size_t k = 0; k < count; k++) {
         ndtgpu_fuser_bank::HostState &h = b->st[first + k];
         const double *T = Tmotion16 + 16 * k;
@@ -381,21 +351,21 @@ ndtgpu_status ndtgpu_fuser_update_batch(ndtgpu_fuser_bank *b, size_t first, size
         b->scans->nice_host[first + k] = ndt_grid_is_nice(b->scans->v.grid, pp.scan_centre) ? 1 : 0;
     }
     foff[count] = (uint32_t)(40 * count);
-    HIP_TRY(hipMemcpyAsync(b->dev, b->pin, L.res, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b->scans->v.centres + first * 3, b->dev + L.centre, count * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b->dev.get(), b->pin.get(), L.res, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b->scans->v.centres + first * 3, b->dev.get() + L.centre, count * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
     // ---- device -------------------------------------------------------------------------------------------------------
     // the scan in the node map's frame (:190), its NDT map on the node map's lattice (:201-227)
-    hipError_t e = ndt_launch_cloud_transform(xyz_dev, count, n_points, stride_bytes, map_stride_bytes, (const double *)(b->dev + L.Tscan),
-                                              nullptr, 16, b->xyz_a, st);
+    hipError_t e = ndt_launch_cloud_transform(xyz_dev, count, n_points, stride_bytes, map_stride_bytes, (const double *)(b->dev.get() + L.Tscan),
+                                              nullptr, 16, b->xyz_a.get(), st);
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "fuser_update: transform", e);
-    rc = mapset_build_core(b->scans, first, count, b->xyz_a, n_points, 12, n_points * 12, P.sensor_range, (const double *)(b->dev + L.origin),
+    rc = mapset_build_core(b->scans.get(), first, count, b->xyz_a.get(), n_points, 12, n_points * 12, P.sensor_range, (const double *)(b->dev.get() + L.origin),
                            nullptr, st);
     if (rc != NDTGPU_OK) return rc;
     if (P.discard_cells && n_points > 0) {
         // :229-232 -- ndt_feature::discardCell(ndglobal, cloud.front()) and (.., cloud.back()): the cells of the scan map that hold the
         // first and the last point of the (moved) scan lose their Gaussian
         for (size_t k = 0; k < count; k++) {
-            const float *c0 = b->xyz_a + k * n_points * 3;
+            const float *c0 = b->xyz_a.get() + k * n_points * 3;
             e = ndt_launch_discard(b->scans->v, first + k, c0, 1, st);
             if (e == hipSuccess) e = ndt_launch_discard(b->scans->v, first + k, c0 + (n_points - 1) * 3, 1, st);
             if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "fuser_update: discard launch", e);
@@ -409,17 +379,17 @@ ndtgpu_status ndtgpu_fuser_update_batch(ndtgpu_fuser_bank *b, size_t first, size
     mp.use_initial_guess = 1;
     NdtMatchParamsDev pd = to_dev(&mp);
     pd.fusion_flags = feat ? (flags | (P.step_control_fusion ? 4 : 0)) : flags;
-    const uint32_t *idx_dev = (const uint32_t *)(b->dev + L.idx);
-    rc = match_device_core(b->nodes, idx_dev, b->scans, idx_dev, (double *)(b->dev + L.Test), count, pd,
-                           (ndtgpu_match_result *)(b->dev + L.match), flags ? (const double *)(b->dev + L.Q) : nullptr, st,
-                           feat ? (const unsigned *)(b->dev + L.foff) : nullptr, feat ? (const double *)(b->dev + L.feat) : nullptr);
+    const uint32_t *idx_dev = (const uint32_t *)(b->dev.get() + L.idx);
+    rc = match_device_core(b->nodes, idx_dev, b->scans.get(), idx_dev, (double *)(b->dev.get() + L.Test), count, pd,
+                           (ndtgpu_match_result *)(b->dev.get() + L.match), flags ? (const double *)(b->dev.get() + L.Q) : nullptr, st,
+                           feat ? (const unsigned *)(b->dev.get() + L.foff) : nullptr, feat ? (const double *)(b->dev.get() + L.feat) : nullptr);
     if (rc != NDTGPU_OK) return rc;
     // NDTMatcherD2D::covariance at the registered pose (:403-405; a default-constructed matcher: n_neighbours 2)
     if (P.compute_cov) {
         ndtgpu_match_params cp;
         ndtgpu_default_match_params(&cp);
-        e = ndt_launch_covariance(b->nodes->v, idx_dev, b->scans->v, idx_dev, (const double *)(b->dev + L.Test), count, cp.n_neighbours,
-                                  cp.lfd1, cp.lfd2, P.covariance_mode, (double *)(b->dev + L.cov), (int *)(b->dev + L.covflag), st);
+        e = ndt_launch_covariance(b->nodes->v, idx_dev, b->scans->v, idx_dev, (const double *)(b->dev.get() + L.Test), count, cp.n_neighbours,
+                                  cp.lfd1, cp.lfd2, P.covariance_mode, (double *)(b->dev.get() + L.cov), (int *)(b->dev.get() + L.covflag), st);
         if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "fuser_update: covariance launch", e);
     }
     // the post-registration step (:361-480), the scan in the frame of the new pose, the fuse-in (:485-486)
@@ -428,25 +398,24 @@ ndtgpu_status ndtgpu_fuser_update_batch(ndtgpu_fuser_bank *b, size_t first, size
     pol.translation_fuse_delta = 0.05; pol.rotation_fuse_delta = 0.01;                   // ndt_feature_fuser_hmt.h:222-223
     pol.check_consistency = P.check_consistency; pol.fuse_incomplete = P.fuse_incomplete; pol.all_matches_valid = P.all_matches_valid;
     pol.force_odom_as_est = P.force_odom_as_est; pol.compute_cov = P.compute_cov;
-    e = ndt_launch_fuser_post(pol, b->sensor_pose_dev, b->st_dev + first, (const double *)(b->dev + L.Tmotion), (const double *)(b->dev + L.Test),
-                              (const NdtMatchResultDev *)(b->dev + L.match), P.compute_cov ? (const double *)(b->dev + L.cov) : nullptr,
-                              P.compute_cov ? (const int *)(b->dev + L.covflag) : nullptr, count, (double *)(b->dev + L.spose),
-                              (double *)(b->dev + L.forigin), (NdtFuserResultDev *)(b->dev + L.res), st);
+    e = ndt_launch_fuser_post(pol, b->sensor_pose_dev.get(), b->st_dev.get() + first, (const double *)(b->dev.get() + L.Tmotion), (const double *)(b->dev.get() + L.Test),
+                              (const NdtMatchResultDev *)(b->dev.get() + L.match), P.compute_cov ? (const double *)(b->dev.get() + L.cov) : nullptr,
+                              P.compute_cov ? (const int *)(b->dev.get() + L.covflag) : nullptr, count, (double *)(b->dev.get() + L.spose),
+                              (double *)(b->dev.get() + L.forigin), (NdtFuserResultDev *)(b->dev.get() + L.res), st);
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "fuser_update: post launch", e);
     if (update_ndt_map) {
-        e = ndt_launch_cloud_transform(xyz_dev, count, n_points, stride_bytes, map_stride_bytes, (const double *)(b->dev + L.spose), nullptr, 16,
-                                       b->xyz_b, st);
+        e = ndt_launch_cloud_transform(xyz_dev, count, n_points, stride_bytes, map_stride_bytes, (const double *)(b->dev.get() + L.spose), nullptr, 16,
+                                       b->xyz_b.get(), st);
         if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "fuser_update: transform", e);
         NdtFuseParams fp;
         fp.maxz = 25.0; fp.sensor_noise = 0.06; fp.maxnumpoints = 1e5; fp.occupancy_limit = 255.0; fp.eval_factor = 1000.0; fp.n_min = 3;   // :485-486
-        e = ndt_launch_fuse(b->nodes->v, first, count, b->xyz_b, n_points, 12, n_points * 12, (const double *)(b->dev + L.forigin), fp,
+        e = ndt_launch_fuse(b->nodes->v, first, count, b->xyz_b.get(), n_points, 12, n_points * 12, (const double *)(b->dev.get() + L.forigin), fp,
                             b->nodes->nice_range(first, count), st);
         if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "fuser_update: fuse launch", e);
         { ndtgpu_status trc = b->nodes->touch(st); if (trc != NDTGPU_OK) return trc; }
     }
-    HIP_TRY(hipMemcpyAsync(b->pin + L.res, b->dev + L.res, count * sizeof(NdtFuserResultDev), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(b->done_ev, st));
-    b->in_flight = true;
+    HIP_TRY(hipMemcpyAsync(b->pin.get() + L.res, b->dev.get() + L.res, count * sizeof(NdtFuserResultDev), hipMemcpyDeviceToHost, st));
+    HIP_TRY(b->done.record(st));
     b->fl_first = first; b->fl_count = count;
     b->off_pin_res = L.res;
     b->fl_stream = st;
@@ -462,16 +431,11 @@ static ndtgpu_status fuser_clouds_in(ndtgpu_fuser_bank *b, size_t count, const v
     if (count > 1 && map_stride_bytes < n_points * stride_bytes) return fail(NDTGPU_ERR_INVALID, "fuser: clouds must not overlap");
     ndtgpu_status rc = fuser_catch_up(b);          // (the previous call may still read the buffer)
     if (rc != NDTGPU_OK) return rc;
-    if (!b->own_st) HIP_TRY(hipStreamCreateWithFlags(&b->own_st, hipStreamNonBlocking));
+    if (!b->own_st.get()) HIP_TRY(b->own_st.create(hipStreamNonBlocking));
     const size_t bytes = (count - 1) * map_stride_bytes + n_points * stride_bytes;
-    if (bytes > b->xyz_in_bytes) {
-        if (b->xyz_in) (void)hipFree(b->xyz_in);
-        b->xyz_in = nullptr; b->xyz_in_bytes = 0;
-        HIP_TRY(hipMalloc(&b->xyz_in, bytes));
-        b->xyz_in_bytes = bytes;
-    }
-    HIP_TRY(hipMemcpyAsync(b->xyz_in, xyz_host, bytes, hipMemcpyHostToDevice, b->own_st));
-    *xyz_dev = b->xyz_in;
+    HIP_TRY(b->xyz_in.reserve(bytes));             // (nothing reads the old block: caught up above)
+    HIP_TRY(hipMemcpyAsync(b->xyz_in.get(), xyz_host, bytes, hipMemcpyHostToDevice, b->own_st.get()));
+    *xyz_dev = b->xyz_in.get();
     return NDTGPU_OK;
 }
 
@@ -482,7 +446,7 @@ ndtgpu_status ndtgpu_fuser_initialize_batch_host(ndtgpu_fuser_bank *b, size_t fi
     const void *dev = nullptr;
     ndtgpu_status rc = fuser_clouds_in(b, count, xyz_host, n_points, stride_bytes, map_stride_bytes, &dev);
     if (rc != NDTGPU_OK) return rc;
-    return ndtgpu_fuser_initialize_batch(b, first, count, initPose16, dev, n_points, stride_bytes, map_stride_bytes, (ndtgpu_stream)b->own_st);
+    return ndtgpu_fuser_initialize_batch(b, first, count, initPose16, dev, n_points, stride_bytes, map_stride_bytes, (ndtgpu_stream)b->own_st.get());
 }
 
 ndtgpu_status ndtgpu_fuser_update_batch_host(ndtgpu_fuser_bank *b, size_t first, size_t count, const double *Tmotion16,
@@ -494,13 +458,12 @@ ndtgpu_status ndtgpu_fuser_update_batch_host(ndtgpu_fuser_bank *b, size_t first,
     ndtgpu_status rc = fuser_clouds_in(b, count, xyz_host, n_points, stride_bytes, map_stride_bytes, &dev);
     if (rc != NDTGPU_OK) return rc;
     return ndtgpu_fuser_update_batch(b, first, count, Tmotion16, dev, n_points, stride_bytes, map_stride_bytes, update_ndt_map,
-                                     (ndtgpu_stream)b->own_st);
+                                     (ndtgpu_stream)b->own_st.get());
 }
 
 ndtgpu_status ndtgpu_fuser_poses(ndtgpu_fuser_bank *b, size_t first, size_t count, double *Tnow16, ndtgpu_fuser_result *results)
 {
     if (!b || first + count > b->n || (count && !Tnow16)) return fail(NDTGPU_ERR_INVALID, "fuser_poses: bad argument");
-    const bool had = b->in_flight && b->fl_count > 0;
     const size_t f0 = b->fl_first, fc = b->fl_count, off = b->off_pin_res;
     ndtgpu_status rc = fuser_catch_up(b);
     if (rc != NDTGPU_OK) return rc;
@@ -508,11 +471,10 @@ ndtgpu_status ndtgpu_fuser_poses(ndtgpu_fuser_bank *b, size_t first, size_t coun
     if (results) {
         // the records of the LAST update call, for the slots it covered (zeroes elsewhere)
         memset(results, 0, count * sizeof *results);
-        (void)had;
         if (fc)
             for (size_t k = 0; k < count; k++) {
                 const size_t slot = first + k;
-                if (slot >= f0 && slot < f0 + fc) memcpy(&results[k], b->pin + off + (slot - f0) * sizeof(NdtFuserResultDev), sizeof(NdtFuserResultDev));
+                if (slot >= f0 && slot < f0 + fc) memcpy(&results[k], b->pin.get() + off + (slot - f0) * sizeof(NdtFuserResultDev), sizeof(NdtFuserResultDev));
             }
     }
     return NDTGPU_OK;

@@ -3,6 +3,7 @@
 // side only and internal: not installed, and nothing declared here is exported from libndtgpu.so.
 #pragma once
 #include "../../include/ndtgpu.h"
+#include "ndtgpu_resource.h"
 #include "ndt_math.h"
 #include "ndt_solver.h"
 #include "ndt_pose.h"
@@ -12,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -58,7 +60,19 @@ inline int env_int(const char *name, int fallback)
 struct CoopOrder;     // (ndtgpu_matcher.hip: the last grid-barrier launch of a device)
 
 struct ndtgpu_mapset {
+    // what the kernels receive: filled from the owners below (create, enable_occupancy).  Stays the FIRST member: the debug
+    // entries of ndt_match.hip read a handle as its view
     NdtSetView v{};
+    DeviceBuffer<uint2> rankmap;
+    DeviceBuffer<int32_t> wtable;
+    DeviceBuffer<uint32_t> bitmap, acc_slot, rank_agg, cell_sel;
+    DeviceBuffer<NdtCell> cells, cells_alt;
+    DeviceBuffer<NdtAcc> acc;
+    DeviceBuffer<NdtMapCounters> counters;
+    DeviceBuffer<double> centres;
+    DeviceBuffer<float> occ;
+    DeviceBuffer<long long> occ_delta;
+    DeviceBuffer<unsigned char> occ_touched;
     size_t n_maps = 0;
     std::vector<double> centres_host;
     std::vector<unsigned char> nice_host;   // per map: fp32 cell offsets are exact (ndt_grid_is_nice)
@@ -68,11 +82,11 @@ struct ndtgpu_mapset {
             if (!nice_host[m]) return 0;
         return 1;
     }
-    // Streams that may still hold work on this set (writers: builds, unpack, add_cloud; readers: matcher launches): one event
-    // per recently used stream, recorded AFTER the launch.  The host-synchronous entries wait for these events -- not for
+    // Streams that may still hold work on this set (writers: builds, unpack, add_cloud; readers: matcher launches): one fence
+    // per recently used stream, recorded AFTER the launch.  The host-synchronous entries wait for these fences -- not for
     // stream handles, which the caller may have destroyed since, and not only for the last writer (a matcher that still reads
     // the maps on another stream is waited for as well).
-    struct StreamMark { hipStream_t st; hipEvent_t ev; };
+    struct StreamMark { hipStream_t st; Fence ev; };
     std::vector<StreamMark> marks;
     bool null_stream_used = false;       // the null stream needs no event: its handle is always valid (and an event record
                                          // costs the reference's one-pair-at-a-time call shape ~10 us of its 0.37 ms)
@@ -80,16 +94,14 @@ struct ndtgpu_mapset {
     {
         if (st == nullptr) { null_stream_used = true; return NDTGPU_OK; }
         for (StreamMark &m : marks)
-            if (m.st == st) { HIP_TRY(hipEventRecord(m.ev, st)); return NDTGPU_OK; }
+            if (m.st == st) { HIP_TRY(m.ev.record(st)); return NDTGPU_OK; }
         if (marks.size() >= 8) {                 // many streams over time: retire the oldest entry once its work is done
-            HIP_TRY(hipEventSynchronize(marks.front().ev));
-            (void)hipEventDestroy(marks.front().ev);
+            HIP_TRY(marks.front().ev.sync());
             marks.erase(marks.begin());
         }
-        StreamMark m{st, nullptr};
-        HIP_TRY(hipEventCreateWithFlags(&m.ev, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(m.ev, st));
-        marks.push_back(m);
+        StreamMark m{st, {}};
+        HIP_TRY(m.ev.record(st));
+        marks.push_back(std::move(m));
         return NDTGPU_OK;
     }
     // ... for work that is about to be enqueued on `st`: what was recorded on `st` itself is ordered by the stream
@@ -97,122 +109,104 @@ struct ndtgpu_mapset {
     {
         if (null_stream_used && st != nullptr) { HIP_TRY(hipStreamSynchronize(nullptr)); null_stream_used = false; }
         for (StreamMark &m : marks)
-            if (m.st != st) HIP_TRY(hipEventSynchronize(m.ev));
+            if (m.st != st) HIP_TRY(m.ev.sync());
         return NDTGPU_OK;
     }
     ndtgpu_status wait_all()
     {
         if (null_stream_used) { HIP_TRY(hipStreamSynchronize(nullptr)); null_stream_used = false; }
-        for (StreamMark &m : marks) HIP_TRY(hipEventSynchronize(m.ev));
+        for (StreamMark &m : marks) HIP_TRY(m.ev.sync());
         return NDTGPU_OK;
     }
     // staging buffers reused across calls
-    void *stage = nullptr;
-    size_t stage_bytes = 0;
-    double *origins_dev = nullptr;
-    size_t origins_cap = 0;
-    hipEvent_t origins_ev = nullptr;   // recorded after the last launch that reads origins_dev (it may be on another stream)
-    bool origins_ev_valid = false;
-    // room for `n` doubles in origins_dev, ordered behind its last reader: `st` waits for that launch before the buffer is
+    DeviceBuffer<char> stage;
+    Fence stage_free;                    // recorded after the last kernel that reads the staged clouds of a host-cloud call
+    ndtgpu_status ensure_stage(size_t bytes)
+    {
+        if (bytes <= stage.capacity()) return NDTGPU_OK;
+        HIP_TRY(stage_free.sync());      // (those kernels may still read the block that is replaced)
+        stage_free.clear();
+        HIP_TRY(stage.reserve(bytes));
+        return NDTGPU_OK;
+    }
+    DeviceBuffer<double> origins;
+    Fence origins_used;                  // recorded after the last launch that reads `origins` (it may be on another stream)
+    // room for `n` doubles in `origins`, ordered behind its last reader: `st` waits for that launch before the buffer is
     // overwritten (or the host does, before it is replaced)
     ndtgpu_status origins_reserve(size_t n, hipStream_t st)
     {
-        if (origins_cap < n) {
-            if (origins_ev_valid) HIP_TRY(hipEventSynchronize(origins_ev));
-            if (origins_dev) (void)hipFree(origins_dev);
-            origins_dev = nullptr;
-            origins_cap = 0;
-            HIP_TRY(hipMalloc((void **)&origins_dev, n * sizeof(double)));
-            origins_cap = n;
-        } else if (origins_ev_valid) {
-            HIP_TRY(hipStreamWaitEvent(st, origins_ev, 0));
-        }
-        return NDTGPU_OK;
-    }
-    ndtgpu_status origins_used(hipStream_t st)
-    {
-        if (!origins_ev) HIP_TRY(hipEventCreateWithFlags(&origins_ev, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(origins_ev, st));
-        origins_ev_valid = true;
+        if (origins.capacity() < n) HIP_TRY(origins.reserve(n, origins_used));
+        else HIP_TRY(origins_used.order(st));
         return NDTGPU_OK;
     }
     // workgroups the persistent matcher launches with this set as target get at most (0: one per CU).  The registrar keeps its
     // matcher launches on part of the chip: the rest stays free for the next sub-batch's builds while a launch runs
     unsigned match_groups = 0;
-    // matcher work area: ticket counters, parked list, parked solver states
-    void *work = nullptr;
-    size_t work_bytes = 0;
-    hipEvent_t work_ev = nullptr;      // recorded after the last launch that uses `work`
-    bool work_ev_valid = false;
-    hipStream_t work_stream = nullptr;
-    // profiling hooks: [0,1] bracket the build kernel, [2,3] the match kernel
+    // matcher work area: ticket counters, parked list, parked solver states (match_device_core)
+    DeviceBuffer<char> work;
+    Fence work_used;                     // recorded after the last launch that uses `work`
+    hipStream_t work_stream = nullptr;   // ... the stream it was recorded on
+    // profiling hooks: [0,1] bracket the build kernel, [2,3] the match kernel (timed events, made by ndtgpu_profiling_enable;
+    // ndtgpu_last_kernel_ms(which) reads a bracket whose end, ev[2 which + 1], is valid)
     bool profiling = false;
     bool profile_span = false;         // a chunked host build is ONE bracket: the chunks' launches do not re-record the events
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool ev_valid[2] = {false, false};
-
-    ndtgpu_status ensure_work(size_t bytes)
-    {
-        if (bytes <= work_bytes) return NDTGPU_OK;
-        if (work) (void)hipFree(work);
-        work = nullptr;
-        work_bytes = 0;
-        HIP_TRY(hipMalloc(&work, bytes));
-        work_bytes = bytes;
-        return NDTGPU_OK;
-    }
+    Fence ev[4];
     // work area of the grid-barrier matcher (a control block + partial sums per registration); its kernels leave the
     // control blocks zeroed, so a call only clears what it cannot know to be clean
-    void *coop_work = nullptr;
-    size_t coop_bytes = 0, coop_clean_stride = 0, coop_clean_upto = 0;
+    DeviceBuffer<char> coop_work;
+    size_t coop_clean_stride = 0, coop_clean_upto = 0;
     // (both defined in ndtgpu_matcher.hip: a block that grows is freed once the device's last grid-barrier launch, which may
     //  still use it, has ended)
     ndtgpu_status ensure_coop(size_t bytes, const CoopOrder &last);
     // pinned host mirror of small staging blocks (poses, indices, results of a host-pointer matcher call): copies from /
     // to pinned memory are truly asynchronous and skip the runtime's own bounce buffer
-    void *pin = nullptr;
-    size_t pin_bytes = 0;
+    PinnedBuffer<char> pin;
     ndtgpu_status ensure_pin(size_t bytes, const CoopOrder &last);
     // Host clouds (the reference's call sites hand over pcl::PointCloud on the host): a ring of pinned slots that host
     // threads fill from the caller's pageable memory while earlier slots travel to the device and earlier chunks of
-    // maps are being built (stage_host_clouds below).  The copies run on a stream of their own.
+    // maps are being built (stage_host_clouds).  The copies run on a stream of their own.
     static constexpr int HOST_SLOTS = 6;
     static constexpr size_t HOST_SLOT_BYTES = 16u << 20;
-    void *host_ring[HOST_SLOTS] = {};
-    hipEvent_t host_ev[HOST_SLOTS] = {};
-    bool host_ev_used[HOST_SLOTS] = {};
-    hipStream_t host_copy_stream = nullptr;
-    hipStream_t host_build_stream = nullptr;  // the synchronous host-cloud entries build on a stream of their own (no device-wide wait)
+    PinnedBuffer<char> host_ring[HOST_SLOTS];
+    Fence host_ev[HOST_SLOTS];           // recorded behind a slot's copy to the device; valid: the slot may still be in flight
+    // (the streams last: ndtgpu_resource.h)
+    Stream host_copy_stream;
+    Stream host_build_stream;            // the synchronous host-cloud entries build on a stream of their own (no device-wide wait)
     ndtgpu_status ensure_host_build_stream()
     {
-        if (!host_build_stream) HIP_TRY(hipStreamCreateWithFlags(&host_build_stream, hipStreamNonBlocking));
+        if (!host_build_stream.get()) HIP_TRY(host_build_stream.create(hipStreamNonBlocking));
         return NDTGPU_OK;
     }
-    hipEvent_t stage_free_ev = nullptr;      // recorded after the last kernel that reads the staged clouds
-    bool stage_free_valid = false;
     ndtgpu_status ensure_host_ring()
     {
-        if (host_copy_stream) return NDTGPU_OK;
+        if (host_copy_stream.get()) return NDTGPU_OK;
         for (int k = 0; k < HOST_SLOTS; k++) {
-            HIP_TRY(hipHostMalloc(&host_ring[k], HOST_SLOT_BYTES, hipHostMallocDefault));
-            HIP_TRY(hipEventCreateWithFlags(&host_ev[k], hipEventDisableTiming));
+            HIP_TRY(host_ring[k].alloc(HOST_SLOT_BYTES));
+            HIP_TRY(host_ev[k].create());
         }
-        HIP_TRY(hipEventCreateWithFlags(&stage_free_ev, hipEventDisableTiming));
-        HIP_TRY(hipStreamCreateWithFlags(&host_copy_stream, hipStreamNonBlocking));
-        return NDTGPU_OK;
-    }
-    ndtgpu_status ensure_stage(size_t bytes)
-    {
-        if (bytes <= stage_bytes) return NDTGPU_OK;
-        if (stage_free_valid) { HIP_TRY(hipEventSynchronize(stage_free_ev)); stage_free_valid = false; }
-        if (stage) (void)hipFree(stage);
-        stage = nullptr;
-        stage_bytes = 0;
-        HIP_TRY(hipMalloc(&stage, bytes));
-        stage_bytes = bytes;
+        HIP_TRY(stage_free.create());
+        HIP_TRY(host_copy_stream.create(hipStreamNonBlocking));
         return NDTGPU_OK;
     }
 };
+
+// a map set that another handle owns (registrar, fuser bank, multires, MCL)
+struct MapsetDestroy { void operator()(ndtgpu_mapset *s) const { (void)ndtgpu_mapset_destroy(s); } };
+using MapsetOwner = std::unique_ptr<ndtgpu_mapset, MapsetDestroy>;
+inline ndtgpu_status mapset_create_owned(const ndtgpu_grid_params *grid, size_t n_maps, MapsetOwner &out)
+{
+    ndtgpu_mapset *s = nullptr;
+    const ndtgpu_status rc = ndtgpu_mapset_create(grid, n_maps, &s);
+    out.reset(s);
+    return rc;
+}
+
+// In a create function: a HIP call that fails deletes the half-built handle and returns `status` with the message `what`.
+#define CREATE_TRY(handle, status, what, expr)                              \
+    do {                                                                    \
+        hipError_t _e = (expr);                                             \
+        if (_e != hipSuccess) { delete (handle); return fail((status), (what), _e); } \
+    } while (0)
 
 // Consecutive regions of one staging block, each on a 256-byte boundary: take(bytes) returns where the region starts; `at` is
 // where the next one would.

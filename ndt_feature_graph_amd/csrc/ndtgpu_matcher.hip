@@ -64,6 +64,8 @@ ndtgpu_status match_params_dev(const ndtgpu_match_params *prm, int fusion_flags,
 // launch waits (on its stream, not on the host) for the event of the one before it.
 static std::mutex g_coop_mutex;
 // (per device: an event belongs to the device it was created on, and launches on one device need not wait for another's)
+// Static storage, so a raw event handle and no Fence: these live until the process ends, when the HIP runtime may already be
+// gone -- nothing here is destroyed, and ndtgpu_live_resources does not count it.
 struct CoopOrder {
     hipEvent_t ev = nullptr;       // recorded behind the device's last asynchronous grid-barrier launch
     bool valid = false;
@@ -79,25 +81,18 @@ static CoopOrder &coop_order()     // (the current device's; read and written un
 
 ndtgpu_status ndtgpu_mapset::ensure_coop(size_t bytes, const CoopOrder &last)
 {
-    if (bytes <= coop_bytes) return NDTGPU_OK;
+    if (bytes <= coop_work.capacity()) return NDTGPU_OK;
     if (last.valid) HIP_TRY(hipEventSynchronize(last.ev));      // an asynchronous launch may still use the area
-    if (coop_work) (void)hipFree(coop_work);
-    coop_work = nullptr;
-    coop_bytes = coop_clean_upto = 0;
-    HIP_TRY(hipMalloc(&coop_work, bytes));
-    coop_bytes = bytes;
+    coop_clean_upto = 0;
+    HIP_TRY(coop_work.reserve(bytes));
     return NDTGPU_OK;
 }
 
 ndtgpu_status ndtgpu_mapset::ensure_pin(size_t bytes, const CoopOrder &last)
 {
-    if (bytes <= pin_bytes) return NDTGPU_OK;
+    if (bytes <= pin.capacity()) return NDTGPU_OK;
     if (last.valid) HIP_TRY(hipEventSynchronize(last.ev));      // a grid-barrier kernel may still write into the block
-    if (pin) (void)hipHostFree(pin);
-    pin = nullptr;
-    pin_bytes = 0;
-    HIP_TRY(hipHostMalloc(&pin, bytes, hipHostMallocDefault));
-    pin_bytes = bytes;
+    HIP_TRY(pin.reserve(bytes));
     return NDTGPU_OK;
 }
 
@@ -193,15 +188,15 @@ static ndtgpu_status coop_enqueue(ndtgpu_mapset *ts, ndtgpu_mapset *ss, const ui
     hipError_t e;
     if (pl.pool) {
         if (clear) {
-            HIP_TRY(hipMemsetAsync(ts->coop_work, 0, ndt_match_pool_ctrl_bytes(), st));
-            HIP_TRY(hipMemset2DAsync((char *)ts->coop_work + ndt_match_pool_ctrl_bytes(), pl.stride, 0, ndt_match_pool_head_bytes(), n_pairs, st));
+            HIP_TRY(hipMemsetAsync(ts->coop_work.get(), 0, ndt_match_pool_ctrl_bytes(), st));
+            HIP_TRY(hipMemset2DAsync((char *)ts->coop_work.get() + ndt_match_pool_ctrl_bytes(), pl.stride, 0, ndt_match_pool_head_bytes(), n_pairs, st));
         }
         e = ndt_launch_match_pool(ts->v, tidx_dev, ss->v, sidx_dev, T16_dev, n_pairs, p, res_dev, Q36_dev, pl.groups, pl.per_group,
-                                  ts->coop_work, pl.stride, st);
+                                  ts->coop_work.get(), pl.stride, st);
     } else {
-        if (clear) HIP_TRY(hipMemset2DAsync(ts->coop_work, pl.stride, 0, ndt_match_coop_ctrl_bytes(), n_pairs, st));
+        if (clear) HIP_TRY(hipMemset2DAsync(ts->coop_work.get(), pl.stride, 0, ndt_match_coop_ctrl_bytes(), n_pairs, st));
         e = ndt_launch_match_coop(ts->v, tidx_dev, ss->v, sidx_dev, T16_dev, 0, n_pairs, p, res_dev, Q36_dev, pl.groups,
-                                  pl.per_group, ts->coop_work, pl.stride, pl.checked, st, done_host);
+                                  pl.per_group, ts->coop_work.get(), pl.stride, pl.checked, st, done_host);
     }
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "match: grid-barrier launch", e);
     if (record) {     // (a caller that waits for its launch under the mutex leaves nothing for later launches to wait for)
@@ -225,7 +220,7 @@ ndtgpu_status match_device_core(ndtgpu_mapset *ts, const uint32_t *tidx_dev, ndt
     // persistent workgroups, one per CU (8 waves x 256 VGPRs), each with `slots` registrations in flight whose evaluation
     // shares its waves take in turn (csrc/ndt_match.hip); pairs are pulled from a ticket counter.
     unsigned n_groups = (unsigned)std::min<size_t>(n_pairs, (size_t)device_cus());
-    // (a stream that owns only part of the chip -- hipExtStreamCreateWithCUMask, bench.py --cu-split -- wants one workgroup
+    // (a stream that owns only part of the chip -- a CU-masked stream, bench.py --cu-split -- wants one workgroup
     //  per CU it has, not per CU of the device)
     if (ts->match_groups) n_groups = (unsigned)std::min<size_t>(n_pairs, (size_t)ts->match_groups);
     // (more workgroups than CUs: narrow-workgroup builds of the kernel, -DNDT_MATCH_THREADS=256, of which two share a CU)
@@ -233,20 +228,15 @@ ndtgpu_status match_device_core(ndtgpu_mapset *ts, const uint32_t *tidx_dev, ndt
     const unsigned double_thresh = knobs.double_thresh_set ? knobs.double_thresh : n_groups;
     // The work area (ticket counters, parked solver states) belongs to the target set: a launch on another stream
     // waits for the previous one, and growing the area waits for everything that may still use the old one.
-    if (ts->work_ev_valid && ts->work_stream != st) HIP_TRY(hipStreamWaitEvent(st, ts->work_ev, 0));
-    const size_t need = ndt_match_work_bytes(n_pairs, (size_t)n_groups * knobs.slots);
-    if (need > ts->work_bytes && ts->work_ev_valid) HIP_TRY(hipEventSynchronize(ts->work_ev));
-    ndtgpu_status wrc = ts->ensure_work(need);
-    if (wrc != NDTGPU_OK) return wrc;
-    if (ts->profiling) HIP_TRY(hipEventRecord(ts->ev[2], st));
+    if (ts->work_stream != st) HIP_TRY(ts->work_used.order(st));
+    HIP_TRY(ts->work.reserve(ndt_match_work_bytes(n_pairs, (size_t)n_groups * knobs.slots), ts->work_used));
+    if (ts->profiling) HIP_TRY(ts->ev[2].record(st));
     hipError_t e = ndt_launch_match(ts->v, tidx_dev, ss->v, sidx_dev, T16_dev, n_pairs, p,
                                     reinterpret_cast<NdtMatchResultDev *>(results_dev), Q36_dev, feat_off_dev, feat_cells_dev,
-                                    n_groups, knobs.park_iters, knobs.slots, double_thresh, ts->work, st, cov_mode, cov36_dev, cov_flags_dev);
+                                    n_groups, knobs.park_iters, knobs.slots, double_thresh, ts->work.get(), st, cov_mode, cov36_dev, cov_flags_dev);
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "match: launch", e);
-    if (ts->profiling) { HIP_TRY(hipEventRecord(ts->ev[3], st)); ts->ev_valid[1] = true; }
-    if (!ts->work_ev) HIP_TRY(hipEventCreateWithFlags(&ts->work_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(ts->work_ev, st));
-    ts->work_ev_valid = true;
+    if (ts->profiling) HIP_TRY(ts->ev[3].record(st));
+    HIP_TRY(ts->work_used.record(st));
     ts->work_stream = st;
     // the launch reads both sets' maps: host-synchronous rebuilds of either wait for it
     { ndtgpu_status trc = ts->touch(st); if (trc != NDTGPU_OK) return trc; }
@@ -276,7 +266,7 @@ ndtgpu_status match_batch_device_ex(ndtgpu_mapset *ts, const uint32_t *tidx_dev,
     if (rc != NDTGPU_OK) return rc;
     ts->coop_clean_stride = pl.stride;
     ts->coop_clean_upto = 0;                            // (nobody will look how this launch ended: the next call clears)
-    ts->ev_valid[1] = false;
+    ts->ev[3].clear();
     if (cov_mode >= 0) HIP_TRY(hipMemcpyAsync(T16_save_dev, T16_dev, n_pairs * 16 * sizeof(double), hipMemcpyDeviceToDevice, st));
     rc = coop_enqueue(ts, ss, tidx_dev, sidx_dev, T16_dev, reinterpret_cast<NdtMatchResultDev *>(results_dev), nullptr,
                       n_pairs, p, pl, true, true, order, st);
@@ -307,7 +297,7 @@ static ndtgpu_status match_persistent_host(ndtgpu_mapset *ts, const uint32_t *ti
                  off_Fo = L.take(bFo), off_Fc = L.take(bFc);
     ndtgpu_status rc = ts->ensure_stage(off_Fc + bFc);
     if (rc != NDTGPU_OK) return rc;
-    char *base = (char *)ts->stage;
+    char *base = ts->stage.get();
     HIP_TRY(hipMemcpyAsync(base + off_T, T16, bT, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(base + off_ti, tidx, bI, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(base + off_si, sidx, bI, hipMemcpyHostToDevice, st));
@@ -324,7 +314,7 @@ static ndtgpu_status match_persistent_host(ndtgpu_mapset *ts, const uint32_t *ti
     unsigned aborted = 0;
     HIP_TRY(hipMemcpyAsync(T16, base + off_T, bT, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(results, base + off_R, bR, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&aborted, (char *)ts->work + ndt_match_abort_offset(), sizeof aborted, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&aborted, ts->work.get() + ndt_match_abort_offset(), sizeof aborted, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (aborted) return fail(NDTGPU_ERR_HIP, "match: the persistent matcher gave up (a wave found no work for ~1 s)");
     return NDTGPU_OK;
@@ -340,7 +330,7 @@ static ndtgpu_status match_host_driven(ndtgpu_mapset *ts, const uint32_t *tidx, 
     const unsigned max_groups = 128;
     ndtgpu_status rc = ts->ensure_stage(max_groups * 32 * sizeof(double));
     if (rc != NDTGPU_OK) return rc;
-    double *partials_dev = (double *)ts->stage;
+    double *partials_dev = (double *)ts->stage.get();
     std::vector<double> partials(max_groups * 32);
     for (size_t k = 0; k < n_pairs; k++) {
         long long terms_g = 0, terms_h = 0;
@@ -350,7 +340,7 @@ static ndtgpu_status match_host_driven(ndtgpu_mapset *ts, const uint32_t *tidx, 
         unsigned groups = (cs.n_cells + 511u) / 512u;
         if (groups < 1) groups = 1;
         if (groups > max_groups) groups = max_groups;
-        ts->ev_valid[1] = false;
+        ts->ev[3].clear();
         MatchState ms;
         NewtonWs ws;
         match_state_init(ms, T16 + 16 * k, p, Q36 ? Q36 + 36 * k : nullptr);
@@ -411,7 +401,7 @@ static ndtgpu_status match_coop_host(ndtgpu_mapset *ts, const uint32_t *tidx, nd
         if (rc != NDTGPU_OK) return rc;
         rc = ts->ensure_pin(off_ctrl + bCtrl, order);
         if (rc != NDTGPU_OK) return rc;
-        pin = (char *)ts->pin;
+        pin = ts->pin.get();
         memcpy(pin + off_T, T16, bT);
         memcpy(pin + off_ti, tidx, bI);
         memcpy(pin + off_si, sidx, bI);
@@ -424,7 +414,7 @@ static ndtgpu_status match_coop_host(ndtgpu_mapset *ts, const uint32_t *tidx, nd
         // event, like any asynchronous one.  The task pool keeps its staging copies and waits for the stream.
         const bool direct = !pl.pool;
         unsigned *ctrl = reinterpret_cast<unsigned *>(pin + off_ctrl), *flags = ctrl + 4 * n_pairs;
-        char *base = direct ? pin : (char *)ts->stage;
+        char *base = direct ? pin : ts->stage.get();
         if (direct) for (size_t k = 0; k < n_pairs; k++) __atomic_store_n(&flags[k], 0u, __ATOMIC_RELEASE);
         else HIP_TRY(hipMemcpyAsync(base, pin, total, hipMemcpyHostToDevice, st));
         // only blocks this set has not seen finish cleanly at this stride are cleared
@@ -461,7 +451,7 @@ static ndtgpu_status match_coop_host(ndtgpu_mapset *ts, const uint32_t *tidx, nd
         }
         ts->coop_clean_upto = bad.empty() ? clean_before : 0;
     }
-    ts->ev_valid[1] = false;          // (ndtgpu_last_kernel_ms(1): no persistent launch was timed by this call)
+    ts->ev[3].clear();          // (ndtgpu_last_kernel_ms(1): no persistent launch was timed by this call)
     memcpy(T16, pin + off_T, bT);
     memcpy(results, pin + off_R, bR);
     // A registration whose grid barrier gave up (it cannot with a co-resident grid; the bounded spin stays as a guard
@@ -558,8 +548,8 @@ ndtgpu_status ndtgpu_derivatives(ndtgpu_mapset *t, size_t tmap, const double *sr
     size_t bytes = cells.size() * sizeof(NdtCell) + 32 * sizeof(double);
     ndtgpu_status rc = t->ensure_stage(bytes);
     if (rc != NDTGPU_OK) return rc;
-    double *out_dev = (double *)t->stage;
-    NdtCell *src_dev = (NdtCell *)((char *)t->stage + 32 * sizeof(double));
+    double *out_dev = (double *)t->stage.get();
+    NdtCell *src_dev = (NdtCell *)(t->stage.get() + 32 * sizeof(double));
     { ndtgpu_status wrc_ = t->wait_all(); if (wrc_ != NDTGPU_OK) return wrc_; }
     if (!cells.empty()) HIP_TRY(hipMemcpy(src_dev, cells.data(), cells.size() * sizeof(NdtCell), hipMemcpyHostToDevice));
     hipError_t e = ndt_launch_derivatives(t->v, tmap, src_dev, cells.size(), n_neighbours, compute_hessian, lfd1, lfd2,
@@ -589,10 +579,10 @@ ndtgpu_status ndtgpu_match_aborted(ndtgpu_mapset *ts, int *aborted)
 {
     if (!ts || !aborted) return fail(NDTGPU_ERR_INVALID, "match_aborted: bad argument");
     *aborted = 0;
-    if (!ts->work) return NDTGPU_OK;                     // no persistent launch has used this set as a target
+    if (!ts->work.get()) return NDTGPU_OK;                     // no persistent launch has used this set as a target
     { ndtgpu_status wrc_ = ts->wait_all(); if (wrc_ != NDTGPU_OK) return wrc_; }
     unsigned w = 0;
-    HIP_TRY(hipMemcpy(&w, (char *)ts->work + ndt_match_abort_offset(), sizeof w, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&w, ts->work.get() + ndt_match_abort_offset(), sizeof w, hipMemcpyDeviceToHost));
     *aborted = w != 0u;
     return NDTGPU_OK;
 }
@@ -684,7 +674,7 @@ ndtgpu_status ndtgpu_covariance_batch(ndtgpu_mapset *ts, const uint32_t *tidx, n
     const size_t off_T = L.take(bT), off_t = L.take(bI), off_s = L.take(bI), off_c = L.take(bC), off_f = L.take(n_links * sizeof(int));
     ndtgpu_status rc = ts->ensure_stage(off_f + n_links * sizeof(int));
     if (rc != NDTGPU_OK) return rc;
-    char *base = (char *)ts->stage;
+    char *base = ts->stage.get();
     HIP_TRY(hipMemcpyAsync(base + off_T, T16, bT, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(base + off_t, tidx, bI, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(base + off_s, sidx, bI, hipMemcpyHostToDevice, st));

@@ -9,11 +9,11 @@
 
 struct ndtgpu_mcl {
     ndtgpu_mapset *map = nullptr;          // borrowed
-    ndtgpu_mapset *scan = nullptr;         // the local scan maps, one per filter
     ndtgpu_mcl_params prm{};
     size_t F = 0;
     unsigned N = 0;
     unsigned chunk = 0, n_chunks = 0;      // scan cells per likelihood chunk, chunks per filter (fixed per handle)
+    // what the kernels receive: plain pointers, filled from the owners below at create
     uint32_t *map_idx = nullptr;           // device [F]
     rigid *T = nullptr, *T_tmp = nullptr;  // device [F][N]
     double *w = nullptr, *lik = nullptr;   // device [F][N]
@@ -23,15 +23,21 @@ struct ndtgpu_mcl {
     NdtMclMotion *motion = nullptr;        // device [F]
     double *pose12 = nullptr;              // device [F][12]
     double *mean16 = nullptr;              // device [F][16]
-    NdtMclMotion *pin_motion[2] = {};      // pinned host staging of the motion records, two calls in flight
-    hipEvent_t pin_ev[2] = {};
-    bool pin_ev_valid[2] = {};
+    DeviceBuffer<uint32_t> map_idx_buf;
+    DeviceBuffer<rigid> T_buf, T_tmp_buf;
+    DeviceBuffer<double> w_buf, lik_buf, partial_buf, pose12_buf, mean16_buf;
+    DeviceBuffer<long long> cum_buf;
+    DeviceBuffer<NdtMclState> state_buf;
+    DeviceBuffer<NdtMclMotion> motion_buf;
+    PinnedBuffer<NdtMclMotion> pin_motion[2];   // pinned host staging of the motion records, two calls in flight
+    Fence pin_used[2];                     // ... recorded behind a slot's copy to the device
     int pin_slot = 0;
-    hipEvent_t used = nullptr;             // recorded after the last launch of a call
-    bool used_valid = false;
-    hipStream_t hst = nullptr;             // the synchronous entries' stream
-    void *h_cloud = nullptr;               // update_host's device copy of the clouds
-    size_t h_cloud_bytes = 0;
+    Fence used;                            // recorded after the last launch of a call
+    DeviceBuffer<char> h_cloud;            // update_host's device copy of the clouds
+    MapsetOwner scan;                      // the local scan maps, one per filter.  After the buffers: it goes first, and
+                                           // ndtgpu_mapset_destroy's hipDeviceSynchronize covers them too, also after a call
+                                           // that failed midway on a stream of the caller's and never recorded `used`
+    Stream hst;                            // the synchronous entries' stream (last: ndtgpu_resource.h)
 };
 
 extern "C" {
@@ -66,19 +72,8 @@ void ndtgpu_default_mcl_params(ndtgpu_mcl_params *p)
 ndtgpu_status ndtgpu_mcl_destroy(ndtgpu_mcl *h)
 {
     if (!h) return fail(NDTGPU_ERR_INVALID, "mcl_destroy: null");
-    if (h->used_valid) (void)hipEventSynchronize(h->used);
-    if (h->hst) (void)hipStreamSynchronize(h->hst);
-    if (h->scan) ndtgpu_mapset_destroy(h->scan);
-    void *bufs[] = {h->map_idx, h->T, h->T_tmp, h->w, h->lik, h->partial, h->cum, h->state, h->motion, h->pose12, h->mean16, h->h_cloud};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    for (int k = 0; k < 2; k++) {
-        if (h->pin_ev[k]) (void)hipEventSynchronize(h->pin_ev[k]);
-        if (h->pin_motion[k]) (void)hipHostFree(h->pin_motion[k]);
-        if (h->pin_ev[k]) (void)hipEventDestroy(h->pin_ev[k]);
-    }
-    if (h->used) (void)hipEventDestroy(h->used);
-    if (h->hst) (void)hipStreamDestroy(h->hst);
+    (void)h->used.sync();                  // (the last call may have run on a stream of the caller's)
+    for (Fence &p : h->pin_used) (void)p.sync();   // (... and a call that failed behind its copy from the pinned block never recorded `used`)
     delete h;
     return NDTGPU_OK;
 }
@@ -122,48 +117,43 @@ ndtgpu_status ndtgpu_mcl_create(ndtgpu_mapset *map_set, const uint32_t *map_idx,
     g.centre[0] = g.centre[1] = g.centre[2] = 0.0;
     for (int a = 0; a < 3; a++) g.size[a] = p.scan_size[a];
     g.max_cells = p.max_scan_cells;
-    ndtgpu_status rc = ndtgpu_mapset_create(&g, n_filters, &h->scan);
-    if (rc != NDTGPU_OK) { ndtgpu_mcl_destroy(h); return rc; }
+    ndtgpu_status rc = mapset_create_owned(&g, n_filters, h->scan);
+    if (rc != NDTGPU_OK) { delete h; return rc; }
     // chunks of the scan cells: at most NDT_MCL_MAX_CHUNKS per filter, whole LDS stages each
     const unsigned cap = h->scan->v.grid.max_cells;
     const unsigned per = (cap + NDT_MCL_MAX_CHUNKS - 1) / NDT_MCL_MAX_CHUNKS;
     h->chunk = std::max(1u, (per + NDT_MCL_STAGE - 1) / NDT_MCL_STAGE) * NDT_MCL_STAGE;
     h->n_chunks = std::max(1u, (cap + h->chunk - 1) / h->chunk);
     const size_t FN = n_filters * n_particles;
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = hipMalloc((void **)&h->map_idx, n_filters * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->T, FN * sizeof(rigid));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->T_tmp, FN * sizeof(rigid));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->w, FN * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->lik, FN * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->partial, FN * h->n_chunks * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->cum, FN * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->state, n_filters * sizeof(NdtMclState));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->motion, n_filters * sizeof(NdtMclMotion));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->pose12, n_filters * 12 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->mean16, n_filters * 16 * sizeof(double));
-    for (int k = 0; k < 2 && e == hipSuccess; k++) {
-        e = hipHostMalloc((void **)&h->pin_motion[k], n_filters * sizeof(NdtMclMotion), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&h->pin_ev[k], hipEventDisableTiming);
+#define TRY(expr) CREATE_TRY(h, NDTGPU_ERR_ALLOC, "mcl_create: device buffers", expr)
+    TRY(h->map_idx_buf.alloc(n_filters, &h->map_idx));
+    TRY(h->T_buf.alloc(FN, &h->T));
+    TRY(h->T_tmp_buf.alloc(FN, &h->T_tmp));
+    TRY(h->w_buf.alloc(FN, &h->w));
+    TRY(h->lik_buf.alloc(FN, &h->lik));
+    TRY(h->partial_buf.alloc(FN * h->n_chunks, &h->partial));
+    TRY(h->cum_buf.alloc(FN, &h->cum));
+    TRY(h->state_buf.alloc(n_filters, &h->state));
+    TRY(h->motion_buf.alloc(n_filters, &h->motion));
+    TRY(h->pose12_buf.alloc(n_filters * 12, &h->pose12));
+    TRY(h->mean16_buf.alloc(n_filters * 16, &h->mean16));
+    for (int k = 0; k < 2; k++) {
+        TRY(h->pin_motion[k].alloc(n_filters));
+        TRY(h->pin_used[k].create());
     }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->used, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->hst, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMemcpy(h->map_idx, map_idx, n_filters * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(h->state, 0, n_filters * sizeof(NdtMclState));
-    if (e == hipSuccess) e = hipMemset(h->lik, 0, FN * sizeof(double));
-    if (e == hipSuccess) {
-        // until initialize / set_particles: every particle at the origin with weight 1/N
-        std::vector<rigid> T0(n_particles, rigid{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}});
-        std::vector<double> w0(n_particles, 1.0 / (double)n_particles);
-        for (size_t f = 0; f < n_filters && e == hipSuccess; f++) {
-            e = hipMemcpy(h->T + f * n_particles, T0.data(), n_particles * sizeof(rigid), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(h->w + f * n_particles, w0.data(), n_particles * sizeof(double), hipMemcpyHostToDevice);
-        }
+    TRY(h->used.create());
+    TRY(h->hst.create(hipStreamNonBlocking));
+    TRY(hipMemcpy(h->map_idx, map_idx, n_filters * sizeof(uint32_t), hipMemcpyHostToDevice));
+    TRY(hipMemset(h->state, 0, n_filters * sizeof(NdtMclState)));
+    TRY(hipMemset(h->lik, 0, FN * sizeof(double)));
+    // until initialize / set_particles: every particle at the origin with weight 1/N
+    std::vector<rigid> T0(n_particles, rigid{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}});
+    std::vector<double> w0(n_particles, 1.0 / (double)n_particles);
+    for (size_t f = 0; f < n_filters; f++) {
+        TRY(hipMemcpy(h->T + f * n_particles, T0.data(), n_particles * sizeof(rigid), hipMemcpyHostToDevice));
+        TRY(hipMemcpy(h->w + f * n_particles, w0.data(), n_particles * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (e != hipSuccess) {
-        ndtgpu_mcl_destroy(h);
-        return fail(NDTGPU_ERR_ALLOC, "mcl_create: device buffers", e);
-    }
+#undef TRY
     *out = h;
     return NDTGPU_OK;
 }
@@ -173,19 +163,6 @@ static ndtgpu_status mcl_range(const ndtgpu_mcl *h, size_t first, size_t count, 
     if (!h) return fail(NDTGPU_ERR_INVALID, (std::string(what) + ": null handle").c_str());
     if (count == 0 || first >= h->F || count > h->F - first)
         return fail(NDTGPU_ERR_INVALID, (std::string(what) + ": filters [first, first + count) out of range").c_str());
-    return NDTGPU_OK;
-}
-
-// the synchronous entries: on the handle's stream, behind the previous call
-static ndtgpu_status mcl_begin_sync(ndtgpu_mcl *h)
-{
-    if (h->used_valid) HIP_TRY(hipStreamWaitEvent(h->hst, h->used, 0));
-    return NDTGPU_OK;
-}
-static ndtgpu_status mcl_end(ndtgpu_mcl *h, hipStream_t st)
-{
-    HIP_TRY(hipEventRecord(h->used, st));
-    h->used_valid = true;
     return NDTGPU_OK;
 }
 
@@ -200,12 +177,12 @@ ndtgpu_status ndtgpu_mcl_initialize(ndtgpu_mcl *h, size_t first, size_t count, c
             buf[k * 12 + d] = pose6[k * 6 + d];
             buf[k * 12 + 6 + d] = sigma6[k * 6 + d];
         }
-    if ((rc = mcl_begin_sync(h)) != NDTGPU_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(h->pose12, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice, h->hst));
-    hipError_t e = ndt_mcl_launch_init(first, count, h->N, h->pose12, h->prm.seed, h->state, h->T, h->w, h->hst);
+    HIP_TRY(h->used.order(h->hst.get()));     // (the synchronous entries run on the handle's stream, behind the previous call)
+    HIP_TRY(hipMemcpyAsync(h->pose12, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice, h->hst.get()));
+    hipError_t e = ndt_mcl_launch_init(first, count, h->N, h->pose12, h->prm.seed, h->state, h->T, h->w, h->hst.get());
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "mcl_initialize: launch", e);
-    if ((rc = mcl_end(h, h->hst)) != NDTGPU_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(h->hst));
+    HIP_TRY(h->used.record(h->hst.get()));
+    HIP_TRY(hipStreamSynchronize(h->hst.get()));
     return NDTGPU_OK;
 }
 
@@ -221,31 +198,30 @@ ndtgpu_status ndtgpu_mcl_set_particles(ndtgpu_mcl *h, size_t first, size_t count
         ndt_rigid_from16(T16 + 16 * k, T[k]);
         w[k] = weights ? weights[k] : 1.0 / (double)h->N;
     }
-    if ((rc = mcl_begin_sync(h)) != NDTGPU_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(h->T + first * h->N, T.data(), n * sizeof(rigid), hipMemcpyHostToDevice, h->hst));
-    HIP_TRY(hipMemcpyAsync(h->w + first * h->N, w.data(), n * sizeof(double), hipMemcpyHostToDevice, h->hst));
-    if ((rc = mcl_end(h, h->hst)) != NDTGPU_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(h->hst));
+    HIP_TRY(h->used.order(h->hst.get()));     // (the synchronous entries run on the handle's stream, behind the previous call)
+    HIP_TRY(hipMemcpyAsync(h->T + first * h->N, T.data(), n * sizeof(rigid), hipMemcpyHostToDevice, h->hst.get()));
+    HIP_TRY(hipMemcpyAsync(h->w + first * h->N, w.data(), n * sizeof(double), hipMemcpyHostToDevice, h->hst.get()));
+    HIP_TRY(h->used.record(h->hst.get()));
+    HIP_TRY(hipStreamSynchronize(h->hst.get()));
     return NDTGPU_OK;
 }
 
 static ndtgpu_status mcl_update_core(ndtgpu_mcl *h, size_t first, size_t count, const double *Tmotion16, double subsample_level,
                                      const void *xyz_dev, size_t n_points, size_t stride_bytes, size_t map_stride_bytes, hipStream_t st)
 {
-    if (h->used_valid) HIP_TRY(hipStreamWaitEvent(st, h->used, 0));   // (the previous call may have run on another stream)
+    HIP_TRY(h->used.order(st));   // (the previous call may have run on another stream)
     // the motion records: pinned staging, one of two slots (its previous copy has long been queued)
     const int s = h->pin_slot;
     h->pin_slot ^= 1;
-    if (h->pin_ev_valid[s]) HIP_TRY(hipEventSynchronize(h->pin_ev[s]));
+    HIP_TRY(h->pin_used[s].sync());
     for (size_t k = 0; k < count; k++)
-        ndt_mcl_motion(Tmotion16 + 16 * k, h->prm.motion_model, h->prm.motion_model_offset, h->pin_motion[s][k]);
-    HIP_TRY(hipMemcpyAsync(h->motion + first, h->pin_motion[s], count * sizeof(NdtMclMotion), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(h->pin_ev[s], st));
-    h->pin_ev_valid[s] = true;
+        ndt_mcl_motion(Tmotion16 + 16 * k, h->prm.motion_model, h->prm.motion_model_offset, h->pin_motion[s].get()[k]);
+    HIP_TRY(hipMemcpyAsync(h->motion + first, h->pin_motion[s].get(), count * sizeof(NdtMclMotion), hipMemcpyHostToDevice, st));
+    HIP_TRY(h->pin_used[s].record(st));
 
     ndtgpu_cell_params cp;
     ndtgpu_default_cell_params(&cp);
-    ndtgpu_status rc = mapset_build_core(h->scan, first, count, xyz_dev, n_points, stride_bytes, map_stride_bytes, h->prm.range_limit,
+    ndtgpu_status rc = mapset_build_core(h->scan.get(), first, count, xyz_dev, n_points, stride_bytes, map_stride_bytes, h->prm.range_limit,
                                          nullptr, &cp, st);
     if (rc != NDTGPU_OK) return rc;
     NdtMclParamsDev pd;
@@ -264,7 +240,8 @@ static ndtgpu_status mcl_update_core(ndtgpu_mcl *h, size_t first, size_t count, 
                                      h->partial, h->cum, st);
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "mcl_update: launch", e);
     if ((rc = h->map->touch(st)) != NDTGPU_OK) return rc;
-    return mcl_end(h, st);
+    HIP_TRY(h->used.record(st));
+    return NDTGPU_OK;
 }
 
 static ndtgpu_status mcl_update_check(ndtgpu_mcl *h, size_t first, size_t count, const double *Tmotion16, const void *xyz,
@@ -295,19 +272,12 @@ ndtgpu_status ndtgpu_mcl_update_host(ndtgpu_mcl *h, size_t first, size_t count, 
     ndtgpu_status rc = mcl_update_check(h, first, count, Tmotion16, xyz_host, n_points, stride_bytes);
     if (rc != NDTGPU_OK) return rc;
     const size_t bytes = n_points ? (count - 1) * map_stride_bytes + n_points * stride_bytes : 0;
-    if (bytes > h->h_cloud_bytes) {
-        if (h->used_valid) HIP_TRY(hipEventSynchronize(h->used));
-        if (h->h_cloud) (void)hipFree(h->h_cloud);
-        h->h_cloud = nullptr;
-        h->h_cloud_bytes = 0;
-        HIP_TRY(hipMalloc(&h->h_cloud, bytes));
-        h->h_cloud_bytes = bytes;
-    }
-    if ((rc = mcl_begin_sync(h)) != NDTGPU_OK) return rc;
-    if (bytes) HIP_TRY(hipMemcpyAsync(h->h_cloud, xyz_host, bytes, hipMemcpyHostToDevice, h->hst));
-    rc = mcl_update_core(h, first, count, Tmotion16, subsample_level, h->h_cloud, n_points, stride_bytes, map_stride_bytes, h->hst);
+    HIP_TRY(h->h_cloud.reserve(bytes, h->used));     // (the last update may still read the block that is replaced)
+    HIP_TRY(h->used.order(h->hst.get()));     // (the synchronous entries run on the handle's stream, behind the previous call)
+    if (bytes) HIP_TRY(hipMemcpyAsync(h->h_cloud.get(), xyz_host, bytes, hipMemcpyHostToDevice, h->hst.get()));
+    rc = mcl_update_core(h, first, count, Tmotion16, subsample_level, h->h_cloud.get(), n_points, stride_bytes, map_stride_bytes, h->hst.get());
     if (rc != NDTGPU_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(h->hst));
+    HIP_TRY(hipStreamSynchronize(h->hst.get()));
     return NDTGPU_OK;
 }
 
@@ -315,7 +285,7 @@ ndtgpu_status ndtgpu_mcl_particles(ndtgpu_mcl *h, size_t first, size_t count, do
 {
     ndtgpu_status rc = mcl_range(h, first, count, "mcl_particles");
     if (rc != NDTGPU_OK) return rc;
-    if (h->used_valid) HIP_TRY(hipEventSynchronize(h->used));
+    HIP_TRY(h->used.sync());
     const size_t n = count * h->N, off = first * h->N;
     if (T16) {
         std::vector<rigid> T(n);
@@ -331,16 +301,16 @@ ndtgpu_status ndtgpu_mcl_mean(ndtgpu_mcl *h, size_t first, size_t count, double 
 {
     ndtgpu_status rc = mcl_range(h, first, count, "mcl_mean");
     if (rc != NDTGPU_OK) return rc;
-    if ((rc = mcl_begin_sync(h)) != NDTGPU_OK) return rc;
+    HIP_TRY(h->used.order(h->hst.get()));     // (the synchronous entries run on the handle's stream, behind the previous call)
     if (T16_mean) {
-        hipError_t e = ndt_mcl_launch_mean(first, count, h->N, h->T, h->w, h->mean16, h->hst);
+        hipError_t e = ndt_mcl_launch_mean(first, count, h->N, h->T, h->w, h->mean16, h->hst.get());
         if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "mcl_mean: launch", e);
-        HIP_TRY(hipMemcpyAsync(T16_mean, h->mean16, count * 16 * sizeof(double), hipMemcpyDeviceToHost, h->hst));
+        HIP_TRY(hipMemcpyAsync(T16_mean, h->mean16, count * 16 * sizeof(double), hipMemcpyDeviceToHost, h->hst.get()));
     }
     std::vector<NdtMclState> st(count);
-    HIP_TRY(hipMemcpyAsync(st.data(), h->state + first, count * sizeof(NdtMclState), hipMemcpyDeviceToHost, h->hst));
-    if ((rc = mcl_end(h, h->hst)) != NDTGPU_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(h->hst));
+    HIP_TRY(hipMemcpyAsync(st.data(), h->state + first, count * sizeof(NdtMclState), hipMemcpyDeviceToHost, h->hst.get()));
+    HIP_TRY(h->used.record(h->hst.get()));
+    HIP_TRY(hipStreamSynchronize(h->hst.get()));
     if (results)
         for (size_t k = 0; k < count; k++) {
             ndtgpu_mcl_result &r = results[k];

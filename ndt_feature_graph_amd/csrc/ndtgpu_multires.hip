@@ -12,25 +12,26 @@ struct ndtgpu_multires {
     double res[NDTGPU_MAX_LEVELS] = {};
     ndtgpu_grid_params grid{};
     size_t per = 0;                                        // pairs per sub-batch
-    ndtgpu_mapset *tset[NDTGPU_MAX_LEVELS] = {}, *sset[NDTGPU_MAX_LEVELS] = {};
     // device, per sub-batch pair: iota (target index), source index, Temp / X (16 doubles each), {Tacc, Tinit} (32), stopped,
     // the matcher's results of one level
-    uint32_t *iota = nullptr, *sidx = nullptr;
-    double *temp = nullptr, *xf = nullptr, *state = nullptr;
-    int *stopped = nullptr;
-    NdtMatchResultDev *res_lvl = nullptr;
+    DeviceBuffer<uint32_t> iota, sidx;
+    DeviceBuffer<double> temp, xf, state;
+    DeviceBuffer<int> stopped;
+    DeviceBuffer<NdtMatchResultDev> res_lvl;
     // the moved source clouds, packed xyz (ping-pong: a level reads one and writes the other)
-    float *cloud[2] = {nullptr, nullptr};
+    DeviceBuffer<float> cloud[2];
     size_t cloud_points = 0;                               // n_points the buffers hold per pair
-    hipEvent_t used = nullptr;                             // recorded after the last launch of a call (every internal buffer
-    bool used_valid = false;                               // and map set is free once it has passed)
+    Fence used;                                            // recorded after the last launch of a call (every internal buffer
+                                                           // and map set is free once it has passed)
     uint64_t levels_fused = 0, levels_unfused = 0;         // source builds so far: moved on load / moved, then built
-    // host entry: staging on a stream of its own
-    hipStream_t hst = nullptr;
-    void *h_tg = nullptr, *h_sc = nullptr;
-    size_t h_cloud_bytes = 0;
-    double *h_T = nullptr;
-    ndtgpu_match_result *h_res = nullptr;
+    // host entry: staging on a stream of its own (last: ndtgpu_resource.h)
+    DeviceBuffer<char> h_tg, h_sc;
+    DeviceBuffer<double> h_T;
+    DeviceBuffer<ndtgpu_match_result> h_res;
+    // the level map sets after the buffers: they go first, and ndtgpu_mapset_destroy's hipDeviceSynchronize covers the buffers
+    // above too, also after a call that failed midway on a stream of the caller's and never recorded `used`
+    MapsetOwner tset[NDTGPU_MAX_LEVELS], sset[NDTGPU_MAX_LEVELS];
+    Stream hst;
 };
 
 void ndtgpu_default_resolutions(double res[4], int *n_levels)
@@ -43,18 +44,7 @@ void ndtgpu_default_resolutions(double res[4], int *n_levels)
 ndtgpu_status ndtgpu_multires_destroy(ndtgpu_multires *mr)
 {
     if (!mr) return NDTGPU_ERR_INVALID;
-    if (mr->used_valid) (void)hipEventSynchronize(mr->used);
-    if (mr->hst) (void)hipStreamSynchronize(mr->hst);
-    for (int j = 0; j < NDTGPU_MAX_LEVELS; j++) {
-        if (mr->tset[j]) ndtgpu_mapset_destroy(mr->tset[j]);
-        if (mr->sset[j]) ndtgpu_mapset_destroy(mr->sset[j]);
-    }
-    void *bufs[] = {mr->iota, mr->sidx, mr->temp, mr->xf, mr->state, mr->stopped, mr->res_lvl, mr->cloud[0], mr->cloud[1],
-                    mr->h_tg, mr->h_sc, mr->h_T, mr->h_res};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (mr->used) (void)hipEventDestroy(mr->used);
-    if (mr->hst) (void)hipStreamDestroy(mr->hst);
+    (void)mr->used.sync();                 // (the last call may have run on a stream of the caller's)
     delete mr;
     return NDTGPU_OK;
 }
@@ -79,42 +69,34 @@ ndtgpu_status ndtgpu_multires_create(const ndtgpu_grid_params *grid, const doubl
         mr->res[j] = resolutions[j];
         ndtgpu_grid_params g = *grid;
         g.res = resolutions[j];
-        ndtgpu_status rc = ndtgpu_mapset_create(&g, p, &mr->tset[j]);
-        if (rc == NDTGPU_OK) rc = ndtgpu_mapset_create(&g, p, &mr->sset[j]);
-        if (rc != NDTGPU_OK) { ndtgpu_multires_destroy(mr); return rc; }
+        ndtgpu_status rc = mapset_create_owned(&g, p, mr->tset[j]);
+        if (rc == NDTGPU_OK) rc = mapset_create_owned(&g, p, mr->sset[j]);
+        if (rc != NDTGPU_OK) { delete mr; return rc; }
     }
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = hipMalloc((void **)&mr->iota, p * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&mr->sidx, p * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&mr->temp, p * 16 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&mr->xf, p * 16 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&mr->state, p * 32 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&mr->stopped, p * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&mr->res_lvl, p * sizeof(NdtMatchResultDev));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&mr->used, hipEventDisableTiming);
-    if (e == hipSuccess) {
-        std::vector<uint32_t> iota(p);
-        for (size_t k = 0; k < p; k++) iota[k] = (uint32_t)k;
-        e = hipMemcpy(mr->iota, iota.data(), p * sizeof(uint32_t), hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        ndtgpu_multires_destroy(mr);
-        return fail(NDTGPU_ERR_ALLOC, "multires_create: device buffers", e);
-    }
+#define TRY(expr) CREATE_TRY(mr, NDTGPU_ERR_ALLOC, "multires_create: device buffers", expr)
+    TRY(mr->iota.alloc(p));
+    TRY(mr->sidx.alloc(p));
+    TRY(mr->temp.alloc(p * 16));
+    TRY(mr->xf.alloc(p * 16));
+    TRY(mr->state.alloc(p * 32));
+    TRY(mr->stopped.alloc(p));
+    TRY(mr->res_lvl.alloc(p));
+    TRY(mr->used.create());
+    std::vector<uint32_t> iota(p);
+    for (size_t k = 0; k < p; k++) iota[k] = (uint32_t)k;
+    TRY(hipMemcpy(mr->iota.get(), iota.data(), p * sizeof(uint32_t), hipMemcpyHostToDevice));
+#undef TRY
     *out = mr;
     return NDTGPU_OK;
 }
 
+// room for n_points per pair in both cloud buffers; the last call's launches may still use the ones that are replaced
 static ndtgpu_status ensure_clouds(ndtgpu_multires *mr, size_t n_points)
 {
     if (n_points <= mr->cloud_points) return NDTGPU_OK;
-    if (mr->used_valid) HIP_TRY(hipEventSynchronize(mr->used));
-    for (float *&c : mr->cloud) {
-        if (c) (void)hipFree(c);
-        c = nullptr;
-    }
+    HIP_TRY(mr->used.sync());
     mr->cloud_points = 0;
-    for (float *&c : mr->cloud) HIP_TRY(hipMalloc((void **)&c, mr->per * n_points * 3 * sizeof(float)));
+    for (DeviceBuffer<float> &c : mr->cloud) HIP_TRY(c.reserve(mr->per * n_points * 3));
     mr->cloud_points = n_points;
     return NDTGPU_OK;
 }
@@ -130,17 +112,17 @@ static ndtgpu_status multires_subbatch(ndtgpu_multires *mr, const char *tg, cons
     if (cell) cp = *cell;
     const int L = mr->n_levels;
     NdtMatchResultDev *res_out = reinterpret_cast<NdtMatchResultDev *>(results_dev);
-    hipError_t e = ndt_launch_multires_step(p, -1, 0, L, 0, use_initial_guess, T16_dev, mr->temp, mr->xf, mr->state, mr->stopped,
-                                            mr->sidx, mr->res_lvl, res_out, st);
+    hipError_t e = ndt_launch_multires_step(p, -1, 0, L, 0, use_initial_guess, T16_dev, mr->temp.get(), mr->xf.get(), mr->state.get(), mr->stopped.get(),
+                                            mr->sidx.get(), mr->res_lvl.get(), res_out, st);
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "multires: init launch", e);
     // the source cloud the first level moves: the caller's, or its range-filtered packed copy
     const char *in = sc;
     size_t in_stride = stride_bytes, in_map_stride = map_stride_bytes;
     int next = 0;
     if (range_limit > 0) {
-        e = ndt_launch_multires_range(sc, p, n_points, stride_bytes, map_stride_bytes, range_limit, mr->cloud[0], st);
+        e = ndt_launch_multires_range(sc, p, n_points, stride_bytes, map_stride_bytes, range_limit, mr->cloud[0].get(), st);
         if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "multires: range filter launch", e);
-        in = (const char *)mr->cloud[0];
+        in = (const char *)mr->cloud[0].get();
         in_stride = 12;
         in_map_stride = n_points * 12;
         next = 1;
@@ -148,15 +130,15 @@ static ndtgpu_status multires_subbatch(ndtgpu_multires *mr, const char *tg, cons
     for (int i = 0; i < L; i++) {
         const int j = L - 1 - i;                           // list position: from the last entry to the first
         const bool last = i == L - 1;
-        ndtgpu_mapset *ts = mr->tset[j], *ss = mr->sset[j];
+        ndtgpu_mapset *ts = mr->tset[j].get(), *ss = mr->sset[j].get();
         ndtgpu_status rc = mapset_build_core(ts, 0, p, tg, n_points, stride_bytes, map_stride_bytes, range_limit, nullptr, cell, st);
         if (rc != NDTGPU_OK) return rc;
-        float *out = mr->cloud[next];
+        float *out = mr->cloud[next].get();
         e = hipErrorNotSupported;
         if (fused) {
             if (ss->v.occ) HIP_TRY(hipMemsetAsync(ss->v.occ, 0, p * (size_t)ss->v.grid.slots * sizeof(float), st));
             e = ndt_launch_build_flat_xf(ss->v, 0, p, in, n_points, in_stride, in_map_stride, cp.n_min, cp.eval_factor,
-                                         ss->nice_range(0, p), mr->xf, last ? nullptr : out, st);
+                                         ss->nice_range(0, p), mr->xf.get(), last ? nullptr : out, st);
             if (e != hipSuccess && e != hipErrorNotSupported) return fail(NDTGPU_ERR_HIP, "multires: source build launch", e);
             if (e == hipSuccess) {
                 mr->levels_fused++;
@@ -166,7 +148,7 @@ static ndtgpu_status multires_subbatch(ndtgpu_multires *mr, const char *tg, cons
         }
         if (e == hipErrorNotSupported) {
             // the move, then the general build on the moved clouds
-            e = ndt_launch_cloud_transform(in, p, n_points, in_stride, in_map_stride, mr->xf, nullptr, 16, out, st);
+            e = ndt_launch_cloud_transform(in, p, n_points, in_stride, in_map_stride, mr->xf.get(), nullptr, 16, out, st);
             if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "multires: transform launch", e);
             rc = mapset_build_core(ss, 0, p, out, n_points, 12, n_points * 12, 0.0, nullptr, cell, st);
             if (rc != NDTGPU_OK) return rc;
@@ -176,15 +158,14 @@ static ndtgpu_status multires_subbatch(ndtgpu_multires *mr, const char *tg, cons
         in_stride = 12;
         in_map_stride = n_points * 12;
         next ^= 1;
-        rc = match_batch_device_ex(ts, mr->iota, ss, mr->sidx, mr->temp, p, &mp, reinterpret_cast<ndtgpu_match_result *>(mr->res_lvl),
+        rc = match_batch_device_ex(ts, mr->iota.get(), ss, mr->sidx.get(), mr->temp.get(), p, &mp, reinterpret_cast<ndtgpu_match_result *>(mr->res_lvl.get()),
                                    st, -1, nullptr, nullptr, nullptr);
         if (rc != NDTGPU_OK) return rc;
-        e = ndt_launch_multires_step(p, i, j, L, last ? 1 : 0, use_initial_guess, T16_dev, mr->temp, mr->xf, mr->state, mr->stopped,
-                                     mr->sidx, mr->res_lvl, res_out, st);
+        e = ndt_launch_multires_step(p, i, j, L, last ? 1 : 0, use_initial_guess, T16_dev, mr->temp.get(), mr->xf.get(), mr->state.get(), mr->stopped.get(),
+                                     mr->sidx.get(), mr->res_lvl.get(), res_out, st);
         if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "multires: level step launch", e);
     }
-    HIP_TRY(hipEventRecord(mr->used, st));
-    mr->used_valid = true;
+    HIP_TRY(mr->used.record(st));
     return NDTGPU_OK;
 }
 
@@ -228,7 +209,7 @@ ndtgpu_status ndtgpu_register_multires_device(ndtgpu_multires *mr, const void *t
     rc = ensure_clouds(mr, n_points);
     if (rc != NDTGPU_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (mr->used_valid) HIP_TRY(hipStreamWaitEvent(st, mr->used, 0));   // (the previous call may have run on another stream)
+    HIP_TRY(mr->used.order(st));   // (the previous call may have run on another stream)
     const bool fused = fused_enabled();
     for (size_t off = 0; off < n_pairs; off += mr->per) {
         const size_t p = std::min(mr->per, n_pairs - off);
@@ -252,36 +233,31 @@ ndtgpu_status ndtgpu_register_multires_host(ndtgpu_multires *mr, const void *tar
     if (n_pairs == 0) return NDTGPU_OK;
     rc = ensure_clouds(mr, n_points);
     if (rc != NDTGPU_OK) return rc;
-    if (!mr->hst) HIP_TRY(hipStreamCreateWithFlags(&mr->hst, hipStreamNonBlocking));
-    hipStream_t st = mr->hst;
-    if (mr->used_valid) HIP_TRY(hipStreamWaitEvent(st, mr->used, 0));
+    if (!mr->hst.get()) HIP_TRY(mr->hst.create(hipStreamNonBlocking));
+    hipStream_t st = mr->hst.get();
+    HIP_TRY(mr->used.order(st));
     // one sub-batch of clouds at a time: p clouds map_stride_bytes apart, the last one n_points records long
     const size_t cloud_bytes = (mr->per - 1) * map_stride_bytes + n_points * stride_bytes;
-    if (cloud_bytes > mr->h_cloud_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (mr->h_tg) (void)hipFree(mr->h_tg);
-        if (mr->h_sc) (void)hipFree(mr->h_sc);
-        mr->h_tg = mr->h_sc = nullptr;
-        mr->h_cloud_bytes = 0;
-        HIP_TRY(hipMalloc(&mr->h_tg, cloud_bytes));
-        HIP_TRY(hipMalloc(&mr->h_sc, cloud_bytes));
-        mr->h_cloud_bytes = cloud_bytes;
+    if (cloud_bytes > std::min(mr->h_tg.capacity(), mr->h_sc.capacity())) {
+        HIP_TRY(hipStreamSynchronize(st));                 // (the copies and builds of the last call read the old blocks)
+        HIP_TRY(mr->h_tg.reserve(cloud_bytes));
+        HIP_TRY(mr->h_sc.reserve(cloud_bytes));
     }
-    if (!mr->h_T) HIP_TRY(hipMalloc((void **)&mr->h_T, mr->per * 16 * sizeof(double)));
-    if (!mr->h_res) HIP_TRY(hipMalloc((void **)&mr->h_res, mr->per * NDTGPU_MAX_LEVELS * sizeof(ndtgpu_match_result)));
+    HIP_TRY(mr->h_T.reserve(mr->per * 16));
+    HIP_TRY(mr->h_res.reserve(mr->per * NDTGPU_MAX_LEVELS));
     const bool fused = fused_enabled();
     const size_t L = (size_t)mr->n_levels;
     for (size_t off = 0; off < n_pairs; off += mr->per) {
         const size_t p = std::min(mr->per, n_pairs - off);
         const size_t bytes = (p - 1) * map_stride_bytes + n_points * stride_bytes;
-        HIP_TRY(hipMemcpyAsync(mr->h_tg, (const char *)targets_host + off * map_stride_bytes, bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(mr->h_sc, (const char *)sources_host + off * map_stride_bytes, bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(mr->h_T, T16 + off * 16, p * 16 * sizeof(double), hipMemcpyHostToDevice, st));
-        rc = multires_subbatch(mr, (const char *)mr->h_tg, (const char *)mr->h_sc, n_points, stride_bytes, map_stride_bytes, range_limit,
-                               cell, mr->h_T, p, mp, use_initial_guess ? 1 : 0, mr->h_res, fused, st);
+        HIP_TRY(hipMemcpyAsync(mr->h_tg.get(), (const char *)targets_host + off * map_stride_bytes, bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(mr->h_sc.get(), (const char *)sources_host + off * map_stride_bytes, bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(mr->h_T.get(), T16 + off * 16, p * 16 * sizeof(double), hipMemcpyHostToDevice, st));
+        rc = multires_subbatch(mr, mr->h_tg.get(), mr->h_sc.get(), n_points, stride_bytes, map_stride_bytes, range_limit,
+                               cell, mr->h_T.get(), p, mp, use_initial_guess ? 1 : 0, mr->h_res.get(), fused, st);
         if (rc != NDTGPU_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(T16 + off * 16, mr->h_T, p * 16 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(results + off * L, mr->h_res, p * L * sizeof(ndtgpu_match_result), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(T16 + off * 16, mr->h_T.get(), p * 16 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(results + off * L, mr->h_res.get(), p * L * sizeof(ndtgpu_match_result), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     return NDTGPU_OK;

@@ -10,11 +10,14 @@
 
 struct ndtgpu_pgo {
     size_t G = 0;
-    NdtPgoView v{};
+    NdtPgoView v{};                        // what the kernels receive: filled from the owners below at create
+    DeviceBuffer<ndtgpu_pgo_result> state;
+    DeviceBuffer<double> pose, origin, meas, info, jac, te, node;
+    DeviceBuffer<int32_t> ref, mov;
+    DeviceBuffer<uint32_t> adj_off, adj;
     std::vector<uint32_t> n_nodes;         // per graph, 0: not set
-    hipEvent_t used = nullptr;             // recorded after the last launch of a call
-    bool used_valid = false;
-    hipStream_t hst = nullptr;             // the synchronous entries' stream
+    Fence used;                            // recorded after the last launch of a call
+    Stream hst;                            // the synchronous entries' stream (last: ndtgpu_resource.h)
 };
 
 static void sym6(const double *W9, double *W6)
@@ -68,14 +71,7 @@ void ndtgpu_default_pgo_params(ndtgpu_pgo_params *p)
 ndtgpu_status ndtgpu_pgo_destroy(ndtgpu_pgo *h)
 {
     if (!h) return fail(NDTGPU_ERR_INVALID, "pgo_destroy: null");
-    if (h->used_valid) (void)hipEventSynchronize(h->used);
-    if (h->hst) (void)hipStreamSynchronize(h->hst);
-    void *bufs[] = {h->v.state, h->v.pose, h->v.origin, h->v.ref, h->v.mov, h->v.meas, h->v.info, h->v.adj_off, h->v.adj, h->v.jac,
-                    h->v.te, h->v.node};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (h->used) (void)hipEventDestroy(h->used);
-    if (h->hst) (void)hipStreamDestroy(h->hst);
+    (void)h->used.sync();                  // (the last call may have run on a stream of the caller's)
     delete h;
     return NDTGPU_OK;
 }
@@ -95,26 +91,23 @@ ndtgpu_status ndtgpu_pgo_create(size_t n_graphs, size_t max_nodes, size_t max_ed
     v.max_nodes = max_nodes;
     v.max_edges = max_edges;
     const size_t G = n_graphs, E = std::max<size_t>(max_edges, 1);     // (no zero-byte allocations)
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = hipMalloc((void **)&v.state, G * sizeof(ndtgpu_pgo_result));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.pose, G * 3 * max_nodes * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.origin, G * 3 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.ref, G * E * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.mov, G * E * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.meas, G * 3 * E * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.info, G * 6 * E * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.adj_off, G * (max_nodes + 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.adj, G * 2 * E * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.jac, G * 4 * E * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.te, G * 3 * E * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.node, G * NDT_PGO_NODE_DOUBLES * max_nodes * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(v.state, 0, G * sizeof(ndtgpu_pgo_result));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->used, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->hst, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        ndtgpu_pgo_destroy(h);
-        return fail(NDTGPU_ERR_ALLOC, "pgo_create: device buffers", e);
-    }
+#define TRY(expr) CREATE_TRY(h, NDTGPU_ERR_ALLOC, "pgo_create: device buffers", expr)
+    TRY(h->state.alloc(G, &v.state));
+    TRY(h->pose.alloc(G * 3 * max_nodes, &v.pose));
+    TRY(h->origin.alloc(G * 3, &v.origin));
+    TRY(h->ref.alloc(G * E, &v.ref));
+    TRY(h->mov.alloc(G * E, &v.mov));
+    TRY(h->meas.alloc(G * 3 * E, &v.meas));
+    TRY(h->info.alloc(G * 6 * E, &v.info));
+    TRY(h->adj_off.alloc(G * (max_nodes + 1), &v.adj_off));
+    TRY(h->adj.alloc(G * 2 * E, &v.adj));
+    TRY(h->jac.alloc(G * 4 * E, &v.jac));
+    TRY(h->te.alloc(G * 3 * E, &v.te));
+    TRY(h->node.alloc(G * NDT_PGO_NODE_DOUBLES * max_nodes, &v.node));
+    TRY(hipMemset(v.state, 0, G * sizeof(ndtgpu_pgo_result)));
+    TRY(h->used.create());
+    TRY(h->hst.create(hipStreamNonBlocking));
+#undef TRY
     *out = h;
     return NDTGPU_OK;
 }
@@ -147,25 +140,24 @@ static ndtgpu_status pgo_install(ndtgpu_pgo *h, const char *what, size_t g, size
     st.n_edges = (int32_t)n_edges;
     const NdtPgoView &v = h->v;
     h->n_nodes[g] = 0;
-    if (h->used_valid) HIP_TRY(hipStreamWaitEvent(h->hst, h->used, 0));
-    HIP_TRY(hipMemcpyAsync(v.pose + g * 3 * v.max_nodes, pose3, 3 * n_nodes * sizeof(double), hipMemcpyHostToDevice, h->hst));
-    HIP_TRY(hipMemcpyAsync(v.origin + g * 3, pose3, 3 * sizeof(double), hipMemcpyHostToDevice, h->hst));
-    HIP_TRY(hipMemcpyAsync(v.adj_off + g * (v.max_nodes + 1), off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->hst));
+    HIP_TRY(h->used.order(h->hst.get()));
+    HIP_TRY(hipMemcpyAsync(v.pose + g * 3 * v.max_nodes, pose3, 3 * n_nodes * sizeof(double), hipMemcpyHostToDevice, h->hst.get()));
+    HIP_TRY(hipMemcpyAsync(v.origin + g * 3, pose3, 3 * sizeof(double), hipMemcpyHostToDevice, h->hst.get()));
+    HIP_TRY(hipMemcpyAsync(v.adj_off + g * (v.max_nodes + 1), off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->hst.get()));
     if (n_edges) {
-        HIP_TRY(hipMemcpyAsync(v.ref + g * v.max_edges, ri.data(), n_edges * sizeof(int32_t), hipMemcpyHostToDevice, h->hst));
-        HIP_TRY(hipMemcpyAsync(v.mov + g * v.max_edges, mi.data(), n_edges * sizeof(int32_t), hipMemcpyHostToDevice, h->hst));
-        HIP_TRY(hipMemcpyAsync(v.adj + g * 2 * v.max_edges, adj.data(), adj.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->hst));
+        HIP_TRY(hipMemcpyAsync(v.ref + g * v.max_edges, ri.data(), n_edges * sizeof(int32_t), hipMemcpyHostToDevice, h->hst.get()));
+        HIP_TRY(hipMemcpyAsync(v.mov + g * v.max_edges, mi.data(), n_edges * sizeof(int32_t), hipMemcpyHostToDevice, h->hst.get()));
+        HIP_TRY(hipMemcpyAsync(v.adj + g * 2 * v.max_edges, adj.data(), adj.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->hst.get()));
     }
-    HIP_TRY(hipMemcpyAsync(v.state + g, &st, sizeof st, hipMemcpyHostToDevice, h->hst));
-    HIP_TRY(hipStreamSynchronize(h->hst));               // (the staging vectors above end with this function)
+    HIP_TRY(hipMemcpyAsync(v.state + g, &st, sizeof st, hipMemcpyHostToDevice, h->hst.get()));
+    HIP_TRY(hipStreamSynchronize(h->hst.get()));               // (the staging vectors above end with this function)
     return NDTGPU_OK;
 }
 
 static ndtgpu_status pgo_installed(ndtgpu_pgo *h, size_t g, size_t n_nodes)
 {
-    HIP_TRY(hipEventRecord(h->used, h->hst));
-    h->used_valid = true;
-    HIP_TRY(hipStreamSynchronize(h->hst));
+    HIP_TRY(h->used.record(h->hst.get()));
+    HIP_TRY(hipStreamSynchronize(h->hst.get()));
     h->n_nodes[g] = (uint32_t)n_nodes;
     return NDTGPU_OK;
 }
@@ -183,9 +175,9 @@ ndtgpu_status ndtgpu_pgo_set_graph(ndtgpu_pgo *h, size_t g, size_t n_nodes, cons
         static const double I100[9] = {100, 0, 0, 0, 100, 0, 0, 0, 100};
         for (size_t e = 0; e < n_edges; e++) sym6(info9 ? info9 + 9 * e : I100, &W[6 * e]);
         const NdtPgoView &v = h->v;
-        HIP_TRY(hipMemcpyAsync(v.meas + g * 3 * v.max_edges, meas3, 3 * n_edges * sizeof(double), hipMemcpyHostToDevice, h->hst));
-        HIP_TRY(hipMemcpyAsync(v.info + g * 6 * v.max_edges, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice, h->hst));
-        HIP_TRY(hipStreamSynchronize(h->hst));
+        HIP_TRY(hipMemcpyAsync(v.meas + g * 3 * v.max_edges, meas3, 3 * n_edges * sizeof(double), hipMemcpyHostToDevice, h->hst.get()));
+        HIP_TRY(hipMemcpyAsync(v.info + g * 6 * v.max_edges, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice, h->hst.get()));
+        HIP_TRY(hipStreamSynchronize(h->hst.get()));
     }
     return pgo_installed(h, g, n_nodes);
 }
@@ -200,7 +192,7 @@ ndtgpu_status ndtgpu_pgo_set_links_device(ndtgpu_pgo *h, size_t g, size_t n_node
     ndtgpu_status rc = pgo_check_graph("pgo_set_links_device", n_nodes, pose3, n_edges, ref_idx, mov_idx);
     if (rc != NDTGPU_OK) return rc;
     if ((rc = pgo_install(h, "pgo_set_links_device", g, n_nodes, pose3, n_edges, ref_idx, mov_idx)) != NDTGPU_OK) return rc;
-    hipError_t e = ndt_pgo_launch_links(h->v, g, n_edges, T16_dev, cov36_dev, cov_flags_dev, h->hst);
+    hipError_t e = ndt_pgo_launch_links(h->v, g, n_edges, T16_dev, cov36_dev, cov_flags_dev, h->hst.get());
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "pgo_set_links_device: launch", e);
     return pgo_installed(h, g, n_nodes);
 }
@@ -225,11 +217,10 @@ ndtgpu_status ndtgpu_pgo_optimize(ndtgpu_pgo *h, size_t first, size_t count, con
     d.eps_linear = p.eps_linear;
     sym6(p.prior_information, d.prior);
     hipStream_t st = (hipStream_t)stream;
-    if (h->used_valid) HIP_TRY(hipStreamWaitEvent(st, h->used, 0));   // (the previous call may have run on another stream)
+    HIP_TRY(h->used.order(st));   // (the previous call may have run on another stream)
     hipError_t e = ndt_pgo_launch(h->v, first, count, d, st);
     if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "pgo_optimize: launch", e);
-    HIP_TRY(hipEventRecord(h->used, st));
-    h->used_valid = true;
+    HIP_TRY(h->used.record(st));
     return NDTGPU_OK;
 }
 
@@ -237,7 +228,7 @@ ndtgpu_status ndtgpu_pgo_poses(ndtgpu_pgo *h, size_t g, double *pose3_out, doubl
 {
     if (!h) return fail(NDTGPU_ERR_INVALID, "pgo_poses: null handle");
     if (g >= h->G || !h->n_nodes[g]) return fail(NDTGPU_ERR_INVALID, "pgo_poses: no such graph, or it has not been set");
-    if (h->used_valid) HIP_TRY(hipEventSynchronize(h->used));
+    HIP_TRY(h->used.sync());
     const size_t n = h->n_nodes[g];
     std::vector<double> p(3 * n);
     HIP_TRY(hipMemcpy(p.data(), h->v.pose + g * 3 * h->v.max_nodes, p.size() * sizeof(double), hipMemcpyDeviceToHost));

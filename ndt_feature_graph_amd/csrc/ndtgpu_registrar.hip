@@ -35,45 +35,30 @@ struct ndtgpu_registrar {
     size_t per = 0;
     int depth = 0;
     ndtgpu_registrar_params prm{};     // as given to ndtgpu_registrar_create_ex (zeros resolved)
-    std::vector<ndtgpu_mapset *> sets;
-    std::vector<hipStream_t> streams;
-    std::vector<hipEvent_t> built;
-    // completion events, one per sub-batch, in a ring of 4 x depth: sub-batch j records done[j % ring] -- an entry always
+    std::vector<MapsetOwner> sets;
+    std::vector<Fence> built;
+    // completion fences, one per sub-batch, in a ring of 4 x depth: sub-batch j records done[j % ring] -- an entry always
     // belongs to stream j % depth, so whoever waits on an entry that a later sub-batch has re-recorded waits for a superset
-    std::vector<hipEvent_t> done;
-    hipEvent_t in_ev = nullptr;
+    std::vector<Fence> done;
+    Fence in_ev;
     int last_built = -1;
-    uint32_t *iota = nullptr;          // device: 0 .. 2 per - 1 (target indices: iota, source indices: iota + p)
+    DeviceBuffer<uint32_t> iota;       // device: 0 .. 2 per - 1 (target indices: iota, source indices: iota + p)
     size_t submitted = 0;              // sub-batches so far
     // stream-fed form (csrc/ndt_match.hip, ndt_match_stream_kernel): build streams, ONE matcher stream on which an instance of
     // the matcher serves batch after batch from a queue in device memory
-    void *queue = nullptr;
-    hipStream_t bst = nullptr, bst2 = nullptr, pst = nullptr, mst = nullptr;   // builds (two, in turn), publishes (in order), matcher
+    DeviceBuffer<char> queue;
     int mst_prio = 0;                  // the matcher stream's priority: a stream of the caller's at this priority may share its hardware queue
-    hipStream_t hst = nullptr;         // the drain helper of ndtgpu_registrar_sync
     size_t helped = 0;                 // sub-batches submitted when the last helper was launched
-    std::vector<hipEvent_t> trace_ev;  // NDTGPU_REG_TRACE: start / end of the build of the last 64 sub-batches
+    std::vector<Fence> trace_ev;       // NDTGPU_REG_TRACE: start / end of the build of the last 64 sub-batches (timed)
     size_t trace_first = (size_t)-1;   // ... the first sub-batch that has them
-    std::vector<hipEvent_t> pub_ev;
+    std::vector<Fence> pub_ev;
     unsigned stream_groups = 0;        // workgroups (= CUs) of a matcher instance; 0: to be measured on the next sub-batch
     int stream_slots = 2;              // registrations in flight per workgroup of an instance (2, or 3 with half the hit list each)
     int device = 0;
-    hipEvent_t probe_ev[2] = {nullptr, nullptr};
-    std::vector<std::pair<unsigned, hipStream_t>> masked;      // streams that own the first F CUs of the mask (the split's build probes)
-    ndtgpu_status masked_stream(unsigned n_cus, hipStream_t *out)
-    {
-        for (auto &m : masked) if (m.first == n_cus) { *out = m.second; return NDTGPU_OK; }
-        std::vector<uint32_t> mask(((size_t)n_cu + 31) / 32, 0u);
-        for (unsigned i = 0; i < n_cus && i < (unsigned)n_cu; i++) mask[i / 32] |= 1u << (i % 32);
-        hipStream_t st = nullptr;
-        HIP_TRY(hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data()));
-        masked.emplace_back(n_cus, st);
-        *out = st;
-        return NDTGPU_OK;
-    }
+    Fence probe_ev[2];                 // (timed)
     int stream_nn = -1;
     int stream_cov = 0;                // the running instances' kind: 1 = with the covariance tail (an instance is compiled for one)
-    double *cov_save = nullptr;        // per-batch form, grid-barrier / pool sub-batches with a covariance: the initial guesses of
+    DeviceBuffer<double> cov_save;     // per-batch form, grid-barrier / pool sub-batches with a covariance: the initial guesses of
     size_t cov_save_pairs = 0;         // slot k at [k * per * 16] (the match overwrites them; ndt_cov_flags_kernel compares)
     int n_cu = 256;
     // the split of the chip is measured on a sub-batch and re-measured when the maps change: per slot the map counters of
@@ -85,7 +70,7 @@ struct ndtgpu_registrar {
                                        // again at every change)
     double recal_ref = 0.0;
     size_t calib_at = 0;               // ... and its number
-    unsigned long long *stat_host = nullptr; // [depth][2], pinned: {Gaussian cells of the slot's maps, sub-batch + 1} written by a
+    PinnedBuffer<unsigned long long> stat_host; // [depth][2]: {Gaussian cells of the slot's maps, sub-batch + 1} written by a
                                              // one-workgroup kernel behind the build (no copy engine, no event: a device-to-host
                                              // copy per sub-batch cost the pipeline a quarter of its rate, measured)
     std::vector<long long> stat_seq;   // sub-batch whose counters slot k was asked for (-1: none / consumed)
@@ -93,48 +78,37 @@ struct ndtgpu_registrar {
     std::vector<double> recent_cells;  // mean cells per map of the last sub-batches seen (at most `depth`)
     // host clouds (ndtgpu_register_batch_host): per slot a device staging area for the scans of a sub-batch, one for the
     // poses / results of a call, a copy stream
-    std::vector<void *> hstage;
-    std::vector<size_t> hstage_bytes;
-    void *hio = nullptr;
-    size_t hio_bytes = 0;
-    hipStream_t hcopy = nullptr;
+    std::vector<DeviceBuffer<char>> hstage;
+    DeviceBuffer<char> hio;
     bool profiling = false;
-    struct ProfMark { hipEvent_t e[4]; long long seq; };   // build start / end, matcher start / end (events), or the queue's stamps of `seq`
+    struct ProfMark { Fence e[4]; long long seq; };   // build start / end, matcher start / end (timed events), or the queue's stamps of `seq`
     std::vector<ProfMark> marks;
+    // the streams last (ndtgpu_resource.h): one per map set; stream-fed form: builds (two, in turn), publishes (in order), matcher;
+    // the drain helper of ndtgpu_registrar_sync; the host entries' copy stream
+    std::vector<Stream> streams;
+    Stream bst, bst2, pst, mst, hst, hcopy;
+    std::vector<std::pair<unsigned, Stream>> masked;      // streams that own the first F CUs of the mask (the split's build probes)
+    ndtgpu_status masked_stream(unsigned n_cus, hipStream_t *out)
+    {
+        for (auto &m : masked) if (m.first == n_cus) { *out = m.second.get(); return NDTGPU_OK; }
+        std::vector<uint32_t> mask(((size_t)n_cu + 31) / 32, 0u);
+        for (unsigned i = 0; i < n_cus && i < (unsigned)n_cu; i++) mask[i / 32] |= 1u << (i % 32);
+        Stream st;
+        HIP_TRY(st.create_cu_mask((uint32_t)mask.size(), mask.data()));
+        *out = st.get();
+        masked.emplace_back(n_cus, std::move(st));
+        return NDTGPU_OK;
+    }
 };
 
 
 ndtgpu_status ndtgpu_registrar_destroy(ndtgpu_registrar *r)
 {
     if (!r) return NDTGPU_OK;
-    for (hipStream_t st : r->streams)
-        if (st) (void)hipStreamSynchronize(st);
-    for (auto &m : r->marks)
-        for (hipEvent_t e : m.e) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : r->built) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : r->done) if (e) (void)hipEventDestroy(e);
-    if (r->in_ev) (void)hipEventDestroy(r->in_ev);
-    if (r->hcopy) { (void)hipStreamSynchronize(r->hcopy); (void)hipStreamDestroy(r->hcopy); }
-    if (r->bst) (void)hipStreamSynchronize(r->bst);
-    if (r->bst2) (void)hipStreamSynchronize(r->bst2);
-    if (r->pst) { (void)hipStreamSynchronize(r->pst); (void)hipStreamDestroy(r->pst); }
-    if (r->hst) { (void)hipStreamSynchronize(r->hst); (void)hipStreamDestroy(r->hst); }
-    if (r->mst) { (void)hipStreamSynchronize(r->mst); (void)hipStreamDestroy(r->mst); }
-    if (r->bst) (void)hipStreamDestroy(r->bst);
-    if (r->bst2) (void)hipStreamDestroy(r->bst2);
-    for (hipEvent_t e : r->pub_ev) if (e) (void)hipEventDestroy(e);
-    if (r->stat_host) (void)hipHostFree(r->stat_host);
-    for (auto &m : r->masked) if (m.second) { (void)hipStreamSynchronize(m.second); (void)hipStreamDestroy(m.second); }
-    for (hipEvent_t e : r->probe_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : r->trace_ev) if (e) (void)hipEventDestroy(e);
-    if (r->queue) (void)hipFree(r->queue);
-    for (void *q : r->hstage) if (q) (void)hipFree(q);
-    if (r->hio) (void)hipFree(r->hio);
-    for (ndtgpu_mapset *s : r->sets) (void)ndtgpu_mapset_destroy(s);
-    for (hipStream_t st : r->streams)
-        if (st) (void)hipStreamDestroy(st);
-    if (r->iota) (void)hipFree(r->iota);
-    if (r->cov_save) (void)hipFree(r->cov_save);
+    // every stream drained before the first one goes (a device-side wait on one of them ends with the matcher's progress on another)
+    for (Stream &st : r->streams) (void)hipStreamSynchronize(st.get());
+    for (Stream *st : {&r->hcopy, &r->bst, &r->bst2, &r->pst, &r->hst, &r->mst})
+        if (st->get()) (void)hipStreamSynchronize(st->get());
     delete r;
     return NDTGPU_OK;
 }
@@ -186,87 +160,77 @@ ndtgpu_status ndtgpu_registrar_create_ex(const ndtgpu_grid_params *grid, const n
     r->depth = depth;
     r->n_cu = device_cus();
     (void)hipGetDevice(&r->device);
-    r->sets.assign(depth, nullptr);
-    r->streams.assign(depth, nullptr);
-    r->built.assign(depth, nullptr);
-    r->done.assign(4 * (size_t)depth, nullptr);
-    hipError_t e = hipSuccess;
-    ndtgpu_status rc = NDTGPU_OK;
-    for (int k = 0; k < depth && rc == NDTGPU_OK && e == hipSuccess; k++) {
-        rc = ndtgpu_mapset_create(grid, 2 * pairs_per_batch, &r->sets[k]);
-        if (rc != NDTGPU_OK) break;
+    r->sets.resize(depth);
+    r->streams.resize(depth);
+    r->built.resize(depth);
+    r->done.resize(4 * (size_t)depth);
+#define TRY(expr) CREATE_TRY(r, NDTGPU_ERR_HIP, "registrar_create", expr)
+    for (int k = 0; k < depth; k++) {
+        const ndtgpu_status rc = mapset_create_owned(grid, 2 * pairs_per_batch, r->sets[k]);
+        if (rc != NDTGPU_OK) { delete r; return rc; }
         // Pipelined (depth > 1), a matcher launch keeps to half of the CUs: its persistent workgroups hold a CU each, whole, until
         // their registrations are done, and with all CUs taken the next sub-batch's builds would wait for the launch's first
         // exits (measured, 1024 pairs per sub-batch: 470 k registrations/s with 256 workgroups, 488 k with 128..160)
         if (depth > 1) r->sets[k]->match_groups = P.matcher_groups ? P.matcher_groups : (unsigned)(r->n_cu / 2);
-        e = hipStreamCreateWithFlags(&r->streams[k], hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&r->built[k], hipEventDisableTiming);
+        TRY(r->streams[k].create(hipStreamNonBlocking));
+        TRY(r->built[k].create());
     }
-    for (size_t k = 0; k < r->done.size() && rc == NDTGPU_OK && e == hipSuccess; k++)
-        e = hipEventCreateWithFlags(&r->done[k], hipEventDisableTiming);
+    for (Fence &d : r->done) TRY(d.create());
     // The stream-fed matcher: pipelined registrars of small maps.  It needs a hardware queue of its own for the matcher stream:
     // the registrar orders map-set reuse with device-side wait kernels that only end when the running instance makes progress,
     // so an instance launch must never sit in a queue behind such a kernel.  What keeps the streams apart is a priority of
     // their own each -- a device that offers one priority level only (lo == hi) keeps the form with one matcher launch per
     // sub-batch (ordered by events), as does NDTGPU_REG_PRIO=0.
-    if (rc == NDTGPU_OK && e == hipSuccess) {
-        int lo = 0, hi = 0;
-        const bool prio_ok = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi && env_int("NDTGPU_REG_PRIO", 1) != 0;
-        const bool can = depth > 1 && (unsigned)depth <= ndt_stream_ring() && r->sets[0]->v.grid.max_cells < 16384u && prio_ok;
-        if (P.matcher_form == NDTGPU_MATCHER_STREAM_FED && !can) {
-            ndtgpu_registrar_destroy(r);
-            return fail(NDTGPU_ERR_INVALID, "registrar_create: the stream-fed matcher needs 2 <= depth <= 8, max_cells < 16384 and a device "
-                                            "with more than one stream priority");
-        }
-        if (P.matcher_form != NDTGPU_MATCHER_PER_BATCH && can) {
-            r->stream_groups = P.matcher_groups;            // 0: measured on the first sub-batch
-            r->stream_slots = P.matcher_slots ? P.matcher_slots : 2;   // (auto: decided with the split, by the cells per map)
-            e = hipMalloc(&r->queue, ndt_stream_queue_bytes());
-            if (e == hipSuccess) e = hipMemset(r->queue, 0, ndt_stream_queue_bytes());
-            const unsigned ring_linger[2] = {(unsigned)depth, 100u * P.linger_us};   // 100 MHz ticks (measured: no gain from 300 / 1000 us; default 0)
-            if (e == hipSuccess) e = hipMemcpy((char *)r->queue + ndt_stream_ring_offset(), ring_linger, sizeof ring_linger, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->bst, hipStreamNonBlocking);
-            // Two build streams that take the sub-batches in turn (build_streams = 1: one): a build launch is one
-            // workgroup per map and every map costs about the same, so on F free CUs it takes ceil(maps / 4 F) whole rounds
-            // (measured: 1.47 ms beside a matcher instance on 128 CUs, 1.85 ms beside one on 129); with the next launch's
-            // workgroups filling the last, nearly empty round the build side runs at its average rate whatever F is.
-            // Publishes stay in order on a stream of their own.
-            if (P.build_streams == 0) P.build_streams = depth >= 3 ? 2 : 1;
-            if (depth < 3) P.build_streams = 1;
-            if (e == hipSuccess && P.build_streams == 2) e = hipStreamCreateWithFlags(&r->bst2, hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipStreamCreateWithPriority(&r->pst, hipStreamNonBlocking, lo);
-            // (a priority of its own: the runtime then never maps the two streams onto one hardware queue, where the build of
-            //  batch k + 1 would sit behind the running matcher instance)
-            if (e == hipSuccess) e = hipStreamCreateWithPriority(&r->mst, hipStreamNonBlocking, hi);
-            r->mst_prio = hi;
-            if (e == hipSuccess) (void)hipStreamGetPriority(r->mst, &r->mst_prio);
-            r->pub_ev.assign(depth, nullptr);
-            for (int k = 0; k < depth && e == hipSuccess; k++) e = hipEventCreateWithFlags(&r->pub_ev[k], hipEventDisableTiming);
-            // the side channel of the map statistics
-            if (e == hipSuccess && P.matcher_groups == 0 && P.recalibrate_pct > 0) {
-                e = hipHostMalloc((void **)&r->stat_host, (size_t)depth * 2 * sizeof(unsigned long long), hipHostMallocDefault);
-                if (e == hipSuccess) memset(r->stat_host, 0, (size_t)depth * 2 * sizeof(unsigned long long));
-                r->stat_seq.assign(depth, -1);
-                r->stat_maps.assign(depth, 0u);
-            }
-        } else {
-            P.build_streams = 0;
-        }
-        P.matcher_form = r->queue ? NDTGPU_MATCHER_STREAM_FED : NDTGPU_MATCHER_PER_BATCH;
+    int lo = 0, hi = 0;
+    const bool prio_ok = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi && env_int("NDTGPU_REG_PRIO", 1) != 0;
+    const bool can = depth > 1 && (unsigned)depth <= ndt_stream_ring() && r->sets[0]->v.grid.max_cells < 16384u && prio_ok;
+    if (P.matcher_form == NDTGPU_MATCHER_STREAM_FED && !can) {
+        delete r;
+        return fail(NDTGPU_ERR_INVALID, "registrar_create: the stream-fed matcher needs 2 <= depth <= 8, max_cells < 16384 and a device "
+                                        "with more than one stream priority");
     }
+    if (P.matcher_form != NDTGPU_MATCHER_PER_BATCH && can) {
+        r->stream_groups = P.matcher_groups;            // 0: measured on the first sub-batch
+        r->stream_slots = P.matcher_slots ? P.matcher_slots : 2;   // (auto: decided with the split, by the cells per map)
+        TRY(r->queue.alloc(ndt_stream_queue_bytes()));
+        TRY(hipMemset(r->queue.get(), 0, ndt_stream_queue_bytes()));
+        const unsigned ring_linger[2] = {(unsigned)depth, 100u * P.linger_us};   // 100 MHz ticks (measured: no gain from 300 / 1000 us; default 0)
+        TRY(hipMemcpy(r->queue.get() + ndt_stream_ring_offset(), ring_linger, sizeof ring_linger, hipMemcpyHostToDevice));
+        TRY(r->bst.create(hipStreamNonBlocking));
+        // Two build streams that take the sub-batches in turn (build_streams = 1: one): a build launch is one
+        // workgroup per map and every map costs about the same, so on F free CUs it takes ceil(maps / 4 F) whole rounds
+        // (measured: 1.47 ms beside a matcher instance on 128 CUs, 1.85 ms beside one on 129); with the next launch's
+        // workgroups filling the last, nearly empty round the build side runs at its average rate whatever F is.
+        // Publishes stay in order on a stream of their own.
+        if (P.build_streams == 0) P.build_streams = depth >= 3 ? 2 : 1;
+        if (depth < 3) P.build_streams = 1;
+        if (P.build_streams == 2) TRY(r->bst2.create(hipStreamNonBlocking));
+        TRY(r->pst.create(hipStreamNonBlocking, lo));
+        // (a priority of its own: the runtime then never maps the two streams onto one hardware queue, where the build of
+        //  batch k + 1 would sit behind the running matcher instance)
+        TRY(r->mst.create(hipStreamNonBlocking, hi));
+        r->mst_prio = hi;
+        (void)hipStreamGetPriority(r->mst.get(), &r->mst_prio);
+        r->pub_ev.resize(depth);
+        for (Fence &e : r->pub_ev) TRY(e.create());
+        // the side channel of the map statistics
+        if (P.matcher_groups == 0 && P.recalibrate_pct > 0) {
+            TRY(r->stat_host.alloc((size_t)depth * 2));
+            memset(r->stat_host.get(), 0, (size_t)depth * 2 * sizeof(unsigned long long));
+            r->stat_seq.assign(depth, -1);
+            r->stat_maps.assign(depth, 0u);
+        }
+    } else {
+        P.build_streams = 0;
+    }
+    P.matcher_form = r->queue.get() ? NDTGPU_MATCHER_STREAM_FED : NDTGPU_MATCHER_PER_BATCH;
     r->prm = P;
-    if (rc == NDTGPU_OK && e == hipSuccess) e = hipEventCreateWithFlags(&r->in_ev, hipEventDisableTiming);
-    if (rc == NDTGPU_OK && e == hipSuccess) e = hipMalloc((void **)&r->iota, (2 * pairs_per_batch + 4) * sizeof(uint32_t));
-    if (rc == NDTGPU_OK && e == hipSuccess) {
-        std::vector<uint32_t> h(2 * pairs_per_batch);
-        for (size_t i = 0; i < h.size(); i++) h[i] = (uint32_t)i;
-        e = hipMemcpy(r->iota, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    }
-    if (rc != NDTGPU_OK || e != hipSuccess) {
-        const std::string why = rc != NDTGPU_OK ? g_err : std::string("registrar_create: ") + hipGetErrorString(e);
-        ndtgpu_registrar_destroy(r);
-        return fail(rc != NDTGPU_OK ? rc : NDTGPU_ERR_HIP, why.c_str());
-    }
+    TRY(r->in_ev.create());
+    TRY(r->iota.alloc(2 * pairs_per_batch + 4));
+    std::vector<uint32_t> h(2 * pairs_per_batch);
+    for (size_t i = 0; i < h.size(); i++) h[i] = (uint32_t)i;
+    TRY(hipMemcpy(r->iota.get(), h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+#undef TRY
     *out = r;
     return NDTGPU_OK;
 }
@@ -284,16 +248,16 @@ ndtgpu_status ndtgpu_registrar_get_info(const ndtgpu_registrar *r, ndtgpu_regist
 {
     if (!r || !info) return fail(NDTGPU_ERR_INVALID, "registrar_get_info: null argument");
     info->matcher_form = r->prm.matcher_form;
-    info->matcher_groups = r->queue ? r->stream_groups : r->sets[0]->match_groups;
+    info->matcher_groups = r->queue.get() ? r->stream_groups : r->sets[0]->match_groups;
     info->build_streams = r->prm.build_streams;
     info->calibrations = r->calibrations;
     info->submitted = (uint64_t)r->submitted;
     info->cells_per_map = r->calib_cells;
-    info->matcher_slots = r->queue ? r->stream_slots : 2;
+    info->matcher_slots = r->queue.get() ? r->stream_slots : 2;
     info->resident_groups = 0;
-    if (r->queue) {                                         // (a 4-byte read on the null stream; the registrar's streams do not block it)
+    if (r->queue.get()) {                                         // (a 4-byte read on the null stream; the registrar's streams do not block it)
         unsigned live = 0u;
-        HIP_TRY(hipMemcpy(&live, (const char *)r->queue + ndt_stream_live_offset(), sizeof live, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&live, r->queue.get() + ndt_stream_live_offset(), sizeof live, hipMemcpyDeviceToHost));
         info->resident_groups = (int32_t)live;
     }
     return NDTGPU_OK;
@@ -303,16 +267,16 @@ ndtgpu_status ndtgpu_registrar_get_info(const ndtgpu_registrar *r, ndtgpu_regist
 ndtgpu_status ndtgpu_registrar_inject_abort(ndtgpu_registrar *r)
 {
     if (!r) return fail(NDTGPU_ERR_INVALID, "registrar_inject_abort: null");
-    if (!r->queue) return fail(NDTGPU_ERR_INVALID, "registrar_inject_abort: not the stream-fed form");
+    if (!r->queue.get()) return fail(NDTGPU_ERR_INVALID, "registrar_inject_abort: not the stream-fed form");
     const unsigned one = 1u;
-    HIP_TRY(hipMemcpy((char *)r->queue + ndt_stream_abort_offset(), &one, sizeof one, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r->queue.get() + ndt_stream_abort_offset(), &one, sizeof one, hipMemcpyHostToDevice));
     return NDTGPU_OK;
 }
 
 ndtgpu_status ndtgpu_registrar_mapset(ndtgpu_registrar *r, int slot, ndtgpu_mapset **set)
 {
     if (!r || !set || slot < 0 || slot >= r->depth) return fail(NDTGPU_ERR_INVALID, "registrar_mapset: bad argument");
-    *set = r->sets[slot];
+    *set = r->sets[slot].get();
     return NDTGPU_OK;
 }
 
@@ -329,28 +293,26 @@ ndtgpu_status ndtgpu_registrar_kernel_ms(ndtgpu_registrar *r, float mean_ms[2], 
     const size_t n = r->marks.size();
     double sum[2] = {0.0, 0.0};
     size_t cnt[2] = {0, 0};
-    if (r->queue && n) {                    // the stamps are complete once the matcher side is
+    if (r->queue.get() && n) {                    // the stamps are complete once the matcher side is
         ndtgpu_status rc = ndtgpu_registrar_sync(r);
         if (rc != NDTGPU_OK) return rc;
     }
     for (size_t k = 0; k < n; k++) {
         ndtgpu_registrar::ProfMark &m = r->marks[k];
-        HIP_TRY(hipEventSynchronize(m.e[m.seq >= 0 ? 1 : 3]));
+        HIP_TRY(m.e[m.seq >= 0 ? 1 : 3].sync());
         float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, m.e[0], m.e[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, m.e[0].get(), m.e[1].get()));
         sum[0] += ms; cnt[0]++;
         if (m.seq < 0) {
-            HIP_TRY(hipEventElapsedTime(&ms, m.e[2], m.e[3]));
+            HIP_TRY(hipEventElapsedTime(&ms, m.e[2].get(), m.e[3].get()));
             sum[1] += ms; cnt[1]++;
         } else if ((size_t)m.seq + ndt_stream_stamps() > r->submitted) {
             // stream-fed form: what the queue saw of the sub-batch -- published (its maps built) until its last registration finished
             unsigned long long st[2] = {0, 0};
-            HIP_TRY(ndt_stream_read_stamps(r->queue, (unsigned)m.seq, st));
+            HIP_TRY(ndt_stream_read_stamps(r->queue.get(), (unsigned)m.seq, st));
             if (st[1] > st[0]) { sum[1] += (double)(st[1] - st[0]) * 1e-5; cnt[1]++; }
         }
     }
-    for (auto &m : r->marks)
-        for (hipEvent_t e : m.e) if (e) (void)hipEventDestroy(e);
     r->marks.clear();
     *launches = (int32_t)n;
     mean_ms[0] = cnt[0] ? (float)(sum[0] / (double)cnt[0]) : 0.f;
@@ -375,12 +337,12 @@ static ndtgpu_status register_batch_core(ndtgpu_registrar *r, const void *target
     if (n_pairs == 0) return NDTGPU_OK;
     NdtMatchParamsDev pdev;
     { ndtgpu_status prc = match_params_dev(prm, 0, pdev); if (prc != NDTGPU_OK) return prc; }
-    HIP_TRY(hipEventRecord(r->in_ev, (hipStream_t)stream));
+    HIP_TRY(r->in_ev.record((hipStream_t)stream));
     auto new_mark = [&](long long seq, ndtgpu_registrar::ProfMark **out_mark) -> ndtgpu_status {
         ndtgpu_registrar::ProfMark m{};
         m.seq = seq;
-        for (int k = 0; k < (seq >= 0 ? 2 : 4); k++) HIP_TRY(hipEventCreate(&m.e[k]));
-        r->marks.push_back(m);
+        for (int k = 0; k < (seq >= 0 ? 2 : 4); k++) HIP_TRY(m.e[k].create(hipEventDefault));
+        r->marks.push_back(std::move(m));
         *out_mark = &r->marks.back();
         return NDTGPU_OK;
     };
@@ -394,14 +356,14 @@ static ndtgpu_status register_batch_core(ndtgpu_registrar *r, const void *target
             rc = ndtgpu_mapset_build(set, p, p, sc, n_points, stride_bytes, map_stride_bytes, range_limit, nullptr, cell, st);
         return rc;
     };
-    if (r->queue) {
+    if (r->queue.get()) {
         // ---- stream-fed form: builds on one stream, batches published to the running matcher instance -------------------
         auto drain = [&]() -> ndtgpu_status {
-            HIP_TRY(hipStreamSynchronize(r->bst));
-            if (r->bst2) HIP_TRY(hipStreamSynchronize(r->bst2));
-            HIP_TRY(hipStreamSynchronize(r->pst));
-            HIP_TRY(hipStreamSynchronize(r->mst));
-            if (r->hst) HIP_TRY(hipStreamSynchronize(r->hst));
+            HIP_TRY(hipStreamSynchronize(r->bst.get()));
+            if (r->bst2.get()) HIP_TRY(hipStreamSynchronize(r->bst2.get()));
+            HIP_TRY(hipStreamSynchronize(r->pst.get()));
+            HIP_TRY(hipStreamSynchronize(r->mst.get()));
+            if (r->hst.get()) HIP_TRY(hipStreamSynchronize(r->hst.get()));
             return NDTGPU_OK;
         };
         // (an instance is compiled for one neighbourhood size, and with or without the covariance tail)
@@ -414,18 +376,18 @@ static ndtgpu_status register_batch_core(ndtgpu_registrar *r, const void *target
             const size_t p = std::min(r->per, n_pairs - off);
             const size_t j = r->submitted;
             const int slot = (int)(j % (size_t)r->depth);
-            ndtgpu_mapset *set = r->sets[slot];
-            hipStream_t st = (r->bst2 && (j & 1u)) ? r->bst2 : r->bst;
+            ndtgpu_mapset *set = r->sets[slot].get();
+            hipStream_t st = (r->bst2.get() && (j & 1u)) ? r->bst2.get() : r->bst.get();
             // ---- have the maps changed?  The counters of earlier builds that have arrived on the host say how many Gaussian
             // cells a map holds now; when the mean over the last sub-batches has left the figure the split was measured at by
             // more than recalibrate_pct, the pipeline is drained once and this sub-batch measures the split again (a
             // registrar that moves from halls to clutter would otherwise keep 128 matcher CUs where 200 are right).
-            if (r->stat_host && r->stream_groups != 0u) {
+            if (r->stat_host.get() && r->stream_groups != 0u) {
                 // (back-pressure: the host runs at most `depth` sub-batches ahead of the builds -- without it a caller that
                 //  never waits would have submitted everything before the first counters arrive)
-                if (j >= (size_t)r->depth) HIP_TRY(hipEventSynchronize(r->built[slot]));
+                if (j >= (size_t)r->depth) HIP_TRY(r->built[slot].sync());
                 for (int k = 0; k < r->depth; k++) {
-                    volatile unsigned long long *sh = r->stat_host + 2 * k;
+                    volatile unsigned long long *sh = r->stat_host.get() + 2 * k;
                     if (r->stat_seq[k] < 0 || sh[1] != (unsigned long long)r->stat_seq[k] + 1ull) continue;
                     std::atomic_thread_fence(std::memory_order_acquire);
                     if (r->stat_maps[k]) {
@@ -448,7 +410,7 @@ static ndtgpu_status register_batch_core(ndtgpu_registrar *r, const void *target
                     }
                 }
             }
-            HIP_TRY(hipStreamWaitEvent(st, r->in_ev, 0));
+            HIP_TRY(r->in_ev.order(st));
             if (r->stream_groups == 0u) {
                 // ---- a sub-batch that measures the split of the chip (the first of a registrar's life; later ones after a
                 // drain, see above): its maps are built and its pairs registered with nothing else on the device (the whole
@@ -456,20 +418,20 @@ static ndtgpu_status register_batch_core(ndtgpu_registrar *r, const void *target
                 // registrations M -- and a matcher instance gets n_cu M / (M + B) CUs from then on: 128 of 256 on the bench's
                 // halls, 200 on a cluttered scene whose maps hold five times the cells.  Costs one synchronisation.
                 ndtgpu_registrar::ProfMark *mk0 = nullptr;
-                if (r->profiling) { ndtgpu_status mrc = new_mark(-1, &mk0); if (mrc != NDTGPU_OK) return mrc; HIP_TRY(hipEventRecord(mk0->e[0], st)); }
+                if (r->profiling) { ndtgpu_status mrc = new_mark(-1, &mk0); if (mrc != NDTGPU_OK) return mrc; HIP_TRY(mk0->e[0].record(st)); }
                 ndtgpu_status rc0 = build_pairs(set, off, p, st);
                 if (rc0 != NDTGPU_OK) return rc0;
-                if (mk0) { HIP_TRY(hipEventRecord(mk0->e[1], st)); HIP_TRY(hipEventRecord(mk0->e[2], st)); }
+                if (mk0) { HIP_TRY(mk0->e[1].record(st)); HIP_TRY(mk0->e[2].record(st)); }
                 const unsigned saved_groups = set->match_groups;
                 set->match_groups = 0;                            // (the whole chip)
-                rc0 = match_batch_device_ex(set, r->iota, set, r->iota + p, T16_dev + off * 16, p, prm, results_dev + off, st, cov_mode,
+                rc0 = match_batch_device_ex(set, r->iota.get(), set, r->iota.get() + p, T16_dev + off * 16, p, prm, results_dev + off, st, cov_mode,
                                             with_cov ? cov36_dev + off * 36 : nullptr, with_cov ? cov_flags_dev + off : nullptr, nullptr);
                 set->match_groups = saved_groups;
                 if (rc0 != NDTGPU_OK) return rc0;
-                if (mk0) HIP_TRY(hipEventRecord(mk0->e[3], st));
-                hipError_t se = ndt_stream_skip(r->queue, (unsigned)j, st);
+                if (mk0) HIP_TRY(mk0->e[3].record(st));
+                hipError_t se = ndt_stream_skip(r->queue.get(), (unsigned)j, st);
                 if (se != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: calibration", se);
-                HIP_TRY(hipEventRecord(r->built[slot], st));
+                HIP_TRY(r->built[slot].record(st));
                 HIP_TRY(hipStreamSynchronize(st));
                 std::vector<NdtMapCounters> ctr(2 * p);
                 std::vector<ndtgpu_match_result> res(p);
@@ -525,7 +487,7 @@ static ndtgpu_status register_batch_core(ndtgpu_registrar *r, const void *target
                 // had three), and a quarter more or less decides between two splits (halls 120 instead of 128 CUs on one box in
                 // three: -5 %; clutter 184 instead of 160: 103 against 127 k registrations/s).  A build launch takes whole rounds,
                 // so the only splits worth having are those that leave the builds just enough CUs for k rounds, k = 1, 2, ...:
-                // the sub-batch is built again on a stream that owns exactly those CUs (hipExtStreamCreateWithCUMask: mask bits
+                // the sub-batch is built again on a stream that owns exactly those CUs (Stream::create_cu_mask: mask bits
                 // are dealt to the XCDs in turn, like the CUs a matcher instance leaves), timed with events, and the split whose
                 // slower side -- that time, or the registrations' CU-clocks over the matcher's CUs -- is fastest wins.  A few
                 // build launches, once per measurement; NDTGPU_REG_PROBE=0 keeps the model above.
@@ -545,16 +507,17 @@ static ndtgpu_status register_batch_core(ndtgpu_registrar *r, const void *target
                         hipStream_t ms_st = nullptr;
                         ndtgpu_status prc = r->masked_stream((unsigned)n_cu - g, &ms_st);
                         if (prc != NDTGPU_OK) return prc;
-                        if (!r->probe_ev[0]) { HIP_TRY(hipEventCreate(&r->probe_ev[0])); HIP_TRY(hipEventCreate(&r->probe_ev[1])); }
+                        HIP_TRY(r->probe_ev[0].create(hipEventDefault));
+                        HIP_TRY(r->probe_ev[1].create(hipEventDefault));
                         float best = 0.f;
                         for (int rep = 0; rep < 2; rep++) {                    // (the first launch on a new stream pays for the stream)
-                            HIP_TRY(hipEventRecord(r->probe_ev[0], ms_st));
+                            HIP_TRY(r->probe_ev[0].record(ms_st));
                             prc = build_pairs(set, off, p, ms_st);
                             if (prc != NDTGPU_OK) return prc;
-                            HIP_TRY(hipEventRecord(r->probe_ev[1], ms_st));
-                            HIP_TRY(hipEventSynchronize(r->probe_ev[1]));
+                            HIP_TRY(r->probe_ev[1].record(ms_st));
+                            HIP_TRY(r->probe_ev[1].sync());
                             float e = 0.f;
-                            HIP_TRY(hipEventElapsedTime(&e, r->probe_ev[0], r->probe_ev[1]));
+                            HIP_TRY(hipEventElapsedTime(&e, r->probe_ev[0].get(), r->probe_ev[1].get()));
                             if (rep == 0 || e < best) best = e;
                         }
                         *ms = (double)best;
@@ -597,9 +560,8 @@ static ndtgpu_status register_batch_core(ndtgpu_registrar *r, const void *target
                     }
                     // (the probe streams go at once: each is a hardware queue of its own and of no use until the next measurement;
                     //  creating them is most of what a measurement costs, ~50 ms with three or four candidates)
-                    for (auto &m : r->masked) if (m.second) { (void)hipStreamSynchronize(m.second); (void)hipStreamDestroy(m.second); }
                     r->masked.clear();
-                    HIP_TRY(hipEventRecord(r->built[slot], st));               // (the maps were rebuilt: same contents)
+                    HIP_TRY(r->built[slot].record(st));               // (the maps were rebuilt: same contents)
                 }
                 r->calibrations++;
                 // three registrations per workgroup (hit lists of 640 entries per share) where the maps are small -- up to 448 cells: the
@@ -620,67 +582,72 @@ static ndtgpu_status register_batch_core(ndtgpu_registrar *r, const void *target
             // (Depth: a batch is complete 3-5 ms after its publication; with 8 map sets the builds never wait for that, 4 cost
             //  ~5 % on the bench -- include/ndtgpu.h.)
             if (j >= (size_t)r->depth) {
-                hipError_t we = ndt_stream_wait(r->queue, (unsigned)r->depth, (unsigned)(j - (size_t)r->depth), st);
+                hipError_t we = ndt_stream_wait(r->queue.get(), (unsigned)r->depth, (unsigned)(j - (size_t)r->depth), st);
                 if (we != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: wait launch", we);
             }
             ndtgpu_registrar::ProfMark *mk = nullptr;
-            if (r->profiling) { ndtgpu_status mrc = new_mark((long long)j, &mk); if (mrc != NDTGPU_OK) return mrc; HIP_TRY(hipEventRecord(mk->e[0], st)); }
+            if (r->profiling) { ndtgpu_status mrc = new_mark((long long)j, &mk); if (mrc != NDTGPU_OK) return mrc; HIP_TRY(mk->e[0].record(st)); }
             const bool tracing = getenv("NDTGPU_REG_TRACE") != nullptr;
             if (tracing) {
-                if (r->trace_ev.empty()) { r->trace_ev.assign(128, nullptr); for (hipEvent_t &e : r->trace_ev) HIP_TRY(hipEventCreate(&e)); }
-                HIP_TRY(hipEventRecord(r->trace_ev[2 * (j % 64)], st));
+                if (r->trace_ev.empty()) {
+                    std::vector<Fence> ev(128);
+                    for (Fence &e : ev) HIP_TRY(e.create(hipEventDefault));
+                    r->trace_ev = std::move(ev);                                      // (all 128 or none)
+                }
+                HIP_TRY(r->trace_ev[2 * (j % 64)].record(st));
                 if (r->trace_first == (size_t)-1) r->trace_first = j;
             }
             ndtgpu_status rc = build_pairs(set, off, p, st);
             if (rc != NDTGPU_OK) return rc;
-            if (tracing) HIP_TRY(hipEventRecord(r->trace_ev[2 * (j % 64) + 1], st));
-            if (mk) HIP_TRY(hipEventRecord(mk->e[1], st));
-            if (r->stat_host && r->stat_seq[slot] < 0 && j % 3u == 0u) {
+            if (tracing) HIP_TRY(r->trace_ev[2 * (j % 64) + 1].record(st));
+            if (mk) HIP_TRY(mk->e[1].record(st));
+            if (r->stat_host.get() && r->stat_seq[slot] < 0 && j % 3u == 0u) {
                 // (how many Gaussian cells the maps of this build hold: one small kernel behind it writes the sum to the host.
                 //  Every third sub-batch: the launch costs the build stream a few microseconds -- 2 % of the bench's rate when
                 //  every sub-batch had one -- and an odd period does not lock onto callers that alternate between two scenes)
                 hipLaunchKernelGGL(ndt_reg_stats_kernel, dim3(1), dim3(256), 0, st, set->v.counters, (unsigned)(2 * p), (unsigned long long)j,
-                                   r->stat_host + 2 * slot);
+                                   r->stat_host.get() + 2 * slot);
                 HIP_TRY(hipGetLastError());
                 r->stat_seq[slot] = (long long)j;
                 r->stat_maps[slot] = (unsigned)(2 * p);
             }
-            HIP_TRY(hipEventRecord(r->built[slot], st));
-            HIP_TRY(hipStreamWaitEvent(r->pst, r->built[slot], 0));
-            hipError_t pe = ndt_stream_publish(r->queue, set->v, T16_dev + off * 16, reinterpret_cast<NdtMatchResultDev *>(results_dev + off),
-                                               pdev, (unsigned)p, (unsigned)j, r->pst, with_cov ? cov_mode : -1,
+            HIP_TRY(r->built[slot].record(st));
+            HIP_TRY(r->built[slot].order(r->pst.get()));
+            hipError_t pe = ndt_stream_publish(r->queue.get(), set->v, T16_dev + off * 16, reinterpret_cast<NdtMatchResultDev *>(results_dev + off),
+                                               pdev, (unsigned)p, (unsigned)j, r->pst.get(), with_cov ? cov_mode : -1,
                                                with_cov ? cov36_dev + off * 36 : nullptr, with_cov ? cov_flags_dev + off : nullptr);
             if (pe != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: publish", pe);
-            HIP_TRY(hipEventRecord(r->pub_ev[slot], r->pst));
+            HIP_TRY(r->pub_ev[slot].record(r->pst.get()));
             // every published batch is followed by an instance launch: it starts when the running instance has ended (and
             // then serves this batch and whatever is published while it runs), or finds the batch taken and leaves
-            HIP_TRY(hipStreamWaitEvent(r->mst, r->pub_ev[slot], 0));
-            pe = ndt_launch_match_stream(r->queue, pdev.n_neighbours, r->stream_slots, r->stream_groups, r->mst, r->stream_cov);
+            HIP_TRY(r->pub_ev[slot].order(r->mst.get()));
+            pe = ndt_launch_match_stream(r->queue.get(), pdev.n_neighbours, r->stream_slots, r->stream_groups, r->mst.get(), r->stream_cov);
             if (pe != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: matcher launch", pe);
             r->submitted++;
             if (ticket) *ticket = (uint64_t)r->submitted;
         }
         return NDTGPU_OK;
     }
-    if (with_cov && !r->cov_save) {
-        // (only grid-barrier / pool sub-batches read it -- sets of large maps, at most half as many pairs as CUs)
+    if (with_cov && !r->cov_save.get()) {
+        // (only grid-barrier / pool sub-batches read it -- sets of large maps, at most half as many pairs as CUs.  Made once and
+        //  never replaced: nothing to wait for)
         const size_t n = std::min(r->per, (size_t)r->n_cu);
-        HIP_TRY(hipMalloc((void **)&r->cov_save, (size_t)r->depth * n * 16 * sizeof(double)));
+        HIP_TRY(r->cov_save.reserve((size_t)r->depth * n * 16));
         r->cov_save_pairs = n;
     }
     for (size_t off = 0; off < n_pairs; off += r->per) {
         const size_t p = std::min(r->per, n_pairs - off);
         const int slot = (int)(r->submitted % (size_t)r->depth);
-        hipStream_t st = r->streams[slot];
-        ndtgpu_mapset *set = r->sets[slot];
-        HIP_TRY(hipStreamWaitEvent(st, r->in_ev, 0));
-        if (r->last_built >= 0 && r->last_built != slot) HIP_TRY(hipStreamWaitEvent(st, r->built[r->last_built], 0));
+        hipStream_t st = r->streams[slot].get();
+        ndtgpu_mapset *set = r->sets[slot].get();
+        HIP_TRY(r->in_ev.order(st));
+        if (r->last_built >= 0 && r->last_built != slot) HIP_TRY(r->built[r->last_built].order(st));
         ndtgpu_registrar::ProfMark *mk = nullptr;
-        if (r->profiling) { ndtgpu_status mrc = new_mark(-1, &mk); if (mrc != NDTGPU_OK) return mrc; HIP_TRY(hipEventRecord(mk->e[0], st)); }
+        if (r->profiling) { ndtgpu_status mrc = new_mark(-1, &mk); if (mrc != NDTGPU_OK) return mrc; HIP_TRY(mk->e[0].record(st)); }
         ndtgpu_status rc = build_pairs(set, off, p, st);
         if (rc != NDTGPU_OK) return rc;
-        if (mk) { HIP_TRY(hipEventRecord(mk->e[1], st)); HIP_TRY(hipEventRecord(mk->e[2], st)); }
-        HIP_TRY(hipEventRecord(r->built[slot], st));
+        if (mk) { HIP_TRY(mk->e[1].record(st)); HIP_TRY(mk->e[2].record(st)); }
+        HIP_TRY(r->built[slot].record(st));
         r->last_built = slot;
         // `built` releases the next sub-batch's build AND, on this stream, this sub-batch's matcher.  The matcher's persistent
         // workgroups (one per CU, all registers and LDS of it) must not be placed first: the build would then only get the CUs
@@ -689,14 +656,14 @@ static ndtgpu_status register_batch_core(ndtgpu_registrar *r, const void *target
         // microseconds the next build's dispatch needs to get ahead (NDTGPU_REG_GAP: their number).
         if (r->depth > 1) {
             const int n_gap = env_int("NDTGPU_REG_GAP", 2);
-            for (int g = 0; g < n_gap; g++) HIP_TRY(hipMemsetAsync(r->iota + 2 * r->per, 0, 4, st));
+            for (int g = 0; g < n_gap; g++) HIP_TRY(hipMemsetAsync(r->iota.get() + 2 * r->per, 0, 4, st));
         }
-        rc = match_batch_device_ex(set, r->iota, set, r->iota + p, T16_dev + off * 16, p, prm, results_dev + off, st, cov_mode,
+        rc = match_batch_device_ex(set, r->iota.get(), set, r->iota.get() + p, T16_dev + off * 16, p, prm, results_dev + off, st, cov_mode,
                                    with_cov ? cov36_dev + off * 36 : nullptr, with_cov ? cov_flags_dev + off : nullptr,
-                                   with_cov && p <= r->cov_save_pairs ? r->cov_save + (size_t)slot * r->cov_save_pairs * 16 : nullptr);
+                                   with_cov && p <= r->cov_save_pairs ? r->cov_save.get() + (size_t)slot * r->cov_save_pairs * 16 : nullptr);
         if (rc != NDTGPU_OK) return rc;
-        if (mk) HIP_TRY(hipEventRecord(mk->e[3], st));
-        HIP_TRY(hipEventRecord(r->done[r->submitted % r->done.size()], st));
+        if (mk) HIP_TRY(mk->e[3].record(st));
+        HIP_TRY(r->done[r->submitted % r->done.size()].record(st));
         r->submitted++;
         if (ticket) *ticket = (uint64_t)r->submitted;      // "every sub-batch before this count"
     }
@@ -731,7 +698,7 @@ ndtgpu_status ndtgpu_registrar_wait_stream(ndtgpu_registrar *r, uint64_t ticket,
 {
     if (!r || ticket > (uint64_t)r->submitted) return fail(NDTGPU_ERR_INVALID, "registrar_wait_stream: bad argument");
     const size_t end = ticket ? (size_t)ticket : r->submitted;
-    if (r->queue) {
+    if (r->queue.get()) {
         // The wait is a device-side kernel that ends when the running matcher instance has made the batch complete: it must not
         // sit in the hardware queue the instance launches go through.  The runtime keeps streams of different priorities on
         // different queues; a stream of the matcher stream's priority (the highest the device offers) is refused.
@@ -743,44 +710,44 @@ ndtgpu_status ndtgpu_registrar_wait_stream(ndtgpu_registrar *r, uint64_t ticket,
         }
         // the last `depth` sub-batches before `end` (a sub-batch is only published once the one `depth` before it is complete)
         for (size_t j = end > (size_t)r->depth ? end - (size_t)r->depth : 0; j < end; j++) {
-            hipError_t we = ndt_stream_wait(r->queue, (unsigned)r->depth, (unsigned)j, (hipStream_t)stream);
+            hipError_t we = ndt_stream_wait(r->queue.get(), (unsigned)r->depth, (unsigned)j, (hipStream_t)stream);
             if (we != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: wait launch", we);
         }
         return NDTGPU_OK;
     }
     // the newest sub-batch before `end` on every internal stream (earlier ones precede it in stream order)
     for (size_t j = end > (size_t)r->depth ? end - (size_t)r->depth : 0; j < end; j++)
-        HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, r->done[j % r->done.size()], 0));
+        HIP_TRY(r->done[j % r->done.size()].order((hipStream_t)stream));
     return NDTGPU_OK;
 }
 
 ndtgpu_status ndtgpu_registrar_sync(ndtgpu_registrar *r)
 {
     if (!r) return fail(NDTGPU_ERR_INVALID, "registrar_sync: null");
-    if (r->queue) {
+    if (r->queue.get()) {
         // Nothing more is coming before this call returns: once the last sub-batch has been published the CUs that were kept
         // for the builds are free, and a second instance on those takes its share of what is left to register.
         // (nothing more is coming before this call returns: instances do not linger behind the last published batch)
         if (r->submitted) {
-            hipError_t fe = ndt_stream_final(r->queue, (unsigned)r->submitted, r->pst);
+            hipError_t fe = ndt_stream_final(r->queue.get(), (unsigned)r->submitted, r->pst.get());
             if (fe != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: final launch", fe);
         }
         if (r->submitted > r->helped && r->stream_groups && r->stream_nn >= 0 && !getenv("NDTGPU_REG_NO_HELPER")) {
             const int n_cu = r->n_cu;
             if ((unsigned)n_cu > r->stream_groups + 8u) {
-                if (!r->hst) HIP_TRY(hipStreamCreateWithFlags(&r->hst, hipStreamNonBlocking));
-                HIP_TRY(hipStreamWaitEvent(r->hst, r->pub_ev[(r->submitted - 1) % (size_t)r->depth], 0));
-                hipError_t he = ndt_launch_match_stream(r->queue, r->stream_nn, r->stream_slots, (unsigned)n_cu - r->stream_groups, r->hst,
+                if (!r->hst.get()) HIP_TRY(r->hst.create(hipStreamNonBlocking));
+                HIP_TRY(r->pub_ev[(r->submitted - 1) % (size_t)r->depth].order(r->hst.get()));
+                hipError_t he = ndt_launch_match_stream(r->queue.get(), r->stream_nn, r->stream_slots, (unsigned)n_cu - r->stream_groups, r->hst.get(),
                                                         r->stream_cov);
                 if (he != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: helper launch", he);
             }
             r->helped = r->submitted;
         }
-        HIP_TRY(hipStreamSynchronize(r->bst));
-        if (r->bst2) HIP_TRY(hipStreamSynchronize(r->bst2));
-        HIP_TRY(hipStreamSynchronize(r->pst));
-        HIP_TRY(hipStreamSynchronize(r->mst));
-        if (r->hst) HIP_TRY(hipStreamSynchronize(r->hst));
+        HIP_TRY(hipStreamSynchronize(r->bst.get()));
+        if (r->bst2.get()) HIP_TRY(hipStreamSynchronize(r->bst2.get()));
+        HIP_TRY(hipStreamSynchronize(r->pst.get()));
+        HIP_TRY(hipStreamSynchronize(r->mst.get()));
+        if (r->hst.get()) HIP_TRY(hipStreamSynchronize(r->hst.get()));
         if (getenv("NDTGPU_REG_TRACE") && r->submitted) {
             // (experiments: when the last batches were published -- their maps built -- and when their last registration finished,
             //  in microseconds after the first of them)
@@ -788,13 +755,13 @@ ndtgpu_status ndtgpu_registrar_sync(ndtgpu_registrar *r)
             unsigned long long t0 = 0;
             for (size_t k = r->submitted - nb; k < r->submitted; k++) {
                 unsigned long long st[2] = {0, 0};
-                HIP_TRY(ndt_stream_read_stamps(r->queue, (unsigned)k, st));
+                HIP_TRY(ndt_stream_read_stamps(r->queue.get(), (unsigned)k, st));
                 if (!t0) t0 = st[0];
                 float b0 = 0.f, b1 = 0.f;          // the build's start and end, against the end of the first listed build (~ its publication)
                 const size_t kref = std::max(r->submitted - nb, r->trace_first);
                 if (!r->trace_ev.empty() && k >= kref) {
-                    (void)hipEventElapsedTime(&b0, r->trace_ev[2 * (kref % 64) + 1], r->trace_ev[2 * (k % 64)]);
-                    (void)hipEventElapsedTime(&b1, r->trace_ev[2 * (kref % 64) + 1], r->trace_ev[2 * (k % 64) + 1]);
+                    (void)hipEventElapsedTime(&b0, r->trace_ev[2 * (kref % 64) + 1].get(), r->trace_ev[2 * (k % 64)].get());
+                    (void)hipEventElapsedTime(&b1, r->trace_ev[2 * (kref % 64) + 1].get(), r->trace_ev[2 * (k % 64) + 1].get());
                     (void)hipGetLastError();
                 }
                 if (k == kref) t0 = st[0];
@@ -803,21 +770,21 @@ ndtgpu_status ndtgpu_registrar_sync(ndtgpu_registrar *r)
             }
         }
         unsigned aborted = 0;
-        HIP_TRY(hipMemcpy(&aborted, (char *)r->queue + ndt_stream_abort_offset(), sizeof aborted, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&aborted, r->queue.get() + ndt_stream_abort_offset(), sizeof aborted, hipMemcpyDeviceToHost));
         if (aborted) {
             // Reported ONCE: the registrations of the batches that were cut short carry exit_code -4 (every result starts as
             // "not run" when its batch is published), the queue is put back to "everything submitted is over", and the
             // registrar can be used again.
-            HIP_TRY(ndt_stream_reset(r->queue, (unsigned)r->submitted, (unsigned)r->depth));
+            HIP_TRY(ndt_stream_reset(r->queue.get(), (unsigned)r->submitted, (unsigned)r->depth));
             return fail(NDTGPU_ERR_HIP, "registrar: the stream-fed matcher gave up (no work, or no progress behind a wait, for ~30 s); "
                                         "registrations that did not run report exit_code -4");
         }
         return NDTGPU_OK;
     }
-    for (int k = 0; k < r->depth; k++) HIP_TRY(hipStreamSynchronize(r->streams[k]));
+    for (int k = 0; k < r->depth; k++) HIP_TRY(hipStreamSynchronize(r->streams[k].get()));
     for (int k = 0; k < r->depth && (size_t)k < r->submitted; k++) {
         int aborted = 0;
-        ndtgpu_status rc = ndtgpu_match_aborted(r->sets[k], &aborted);
+        ndtgpu_status rc = ndtgpu_match_aborted(r->sets[k].get(), &aborted);
         if (rc != NDTGPU_OK) return rc;
         if (aborted) return fail(NDTGPU_ERR_HIP, "registrar: a matcher launch gave up (a wave found no work for ~1 s)");
     }
@@ -839,26 +806,23 @@ static ndtgpu_status register_batch_host_core(ndtgpu_registrar *r, const void *t
     const bool with_cov = cov_mode >= 0;
     if (with_cov && n_pairs && (!cov36 || !cov_flags)) return fail(NDTGPU_ERR_INVALID, "register_batch_cov_host: bad argument (cov36 / cov_flags)");
     if (n_pairs == 0) return NDTGPU_OK;
-    if (!r->hcopy) HIP_TRY(hipStreamCreateWithFlags(&r->hcopy, hipStreamNonBlocking));
-    if (r->hstage.empty()) { r->hstage.assign(r->depth, nullptr); r->hstage_bytes.assign(r->depth, 0); }
+    if (!r->hcopy.get()) HIP_TRY(r->hcopy.create(hipStreamNonBlocking));
+    if (r->hstage.empty()) r->hstage.resize(r->depth);
     const size_t bT = n_pairs * 16 * sizeof(double), bR = n_pairs * sizeof(ndtgpu_match_result);
     // (with the covariance: 36 doubles and a flag word per pair behind the results)
     const size_t bC = with_cov ? n_pairs * 36 * sizeof(double) : 0, bF = with_cov ? n_pairs * sizeof(int32_t) : 0;
     StageLayout io;
     const size_t offT = io.take(bT), offR = io.take(bR), offC = io.take(bC);
     const size_t offF = offC + bC, need_io = with_cov ? offF + bF : offR + bR;
-    if (r->hio_bytes < need_io) {
-        HIP_TRY(hipStreamSynchronize(r->hcopy));
-        if (r->hio) (void)hipFree(r->hio);
-        r->hio = nullptr; r->hio_bytes = 0;
-        HIP_TRY(hipMalloc(&r->hio, need_io));
-        r->hio_bytes = need_io;
+    if (r->hio.capacity() < need_io) {
+        HIP_TRY(hipStreamSynchronize(r->hcopy.get()));          // (the last call's copies)
+        HIP_TRY(r->hio.reserve(need_io));
     }
-    double *T_dev = (double *)((char *)r->hio + offT);
-    ndtgpu_match_result *R_dev = (ndtgpu_match_result *)((char *)r->hio + offR);
-    double *C_dev = with_cov ? (double *)((char *)r->hio + offC) : nullptr;
-    int32_t *F_dev = with_cov ? (int32_t *)((char *)r->hio + offF) : nullptr;
-    HIP_TRY(hipMemcpyAsync(T_dev, T16, bT, hipMemcpyHostToDevice, r->hcopy));
+    double *T_dev = (double *)(r->hio.get() + offT);
+    ndtgpu_match_result *R_dev = (ndtgpu_match_result *)(r->hio.get() + offR);
+    double *C_dev = with_cov ? (double *)(r->hio.get() + offC) : nullptr;
+    int32_t *F_dev = with_cov ? (int32_t *)(r->hio.get() + offF) : nullptr;
+    HIP_TRY(hipMemcpyAsync(T_dev, T16, bT, hipMemcpyHostToDevice, r->hcopy.get()));
     const size_t cloud_bytes = n_points * stride_bytes;
     for (size_t off = 0; off < n_pairs; off += r->per) {
         const size_t p = std::min(r->per, n_pairs - off);
@@ -866,21 +830,16 @@ static ndtgpu_status register_batch_host_core(ndtgpu_registrar *r, const void *t
         const size_t half = (p - 1) * map_stride_bytes + cloud_bytes, half_al = p * map_stride_bytes;   // targets, then sources
         const size_t need = half_al + half;
         // the staging area of this slot is read by the build of the sub-batch that used it last: wait for that build
-        if (r->submitted >= (size_t)r->depth) HIP_TRY(hipEventSynchronize(r->built[slot]));
-        if (r->hstage_bytes[slot] < need) {
-            if (r->hstage[slot]) (void)hipFree(r->hstage[slot]);
-            r->hstage[slot] = nullptr; r->hstage_bytes[slot] = 0;
-            HIP_TRY(hipMalloc(&r->hstage[slot], need));
-            r->hstage_bytes[slot] = need;
-        }
-        char *tg = (char *)r->hstage[slot], *sc = tg + half_al;        // sources follow targets: ONE build launch per sub-batch
+        if (r->submitted >= (size_t)r->depth) HIP_TRY(r->built[slot].sync());
+        HIP_TRY(r->hstage[slot].reserve(need));
+        char *tg = r->hstage[slot].get(), *sc = tg + half_al;        // sources follow targets: ONE build launch per sub-batch
         if (n_points) {
-            HIP_TRY(hipMemcpyAsync(tg, (const char *)targets_host + off * map_stride_bytes, half, hipMemcpyHostToDevice, r->hcopy));
-            HIP_TRY(hipMemcpyAsync(sc, (const char *)sources_host + off * map_stride_bytes, half, hipMemcpyHostToDevice, r->hcopy));
+            HIP_TRY(hipMemcpyAsync(tg, (const char *)targets_host + off * map_stride_bytes, half, hipMemcpyHostToDevice, r->hcopy.get()));
+            HIP_TRY(hipMemcpyAsync(sc, (const char *)sources_host + off * map_stride_bytes, half, hipMemcpyHostToDevice, r->hcopy.get()));
         }
         // (p <= pairs_per_batch: ONE sub-batch, in this slot, behind these copies)
         ndtgpu_status rc = register_batch_core(r, tg, sc, n_points, stride_bytes, map_stride_bytes, range_limit, cell, T_dev + off * 16, p,
-                                               prm, R_dev + off, (ndtgpu_stream)r->hcopy, nullptr, cov_mode,
+                                               prm, R_dev + off, (ndtgpu_stream)r->hcopy.get(), nullptr, cov_mode,
                                                with_cov ? C_dev + off * 36 : nullptr, with_cov ? F_dev + off : nullptr);
         if (rc != NDTGPU_OK) return rc;
     }
