@@ -876,6 +876,114 @@ const char *ndtgpu_kernel_name(int which); /* 0 build, 1 match, 2 derivatives */
 ndtgpu_status ndtgpu_live_resources(uint64_t counts[4]);
 /* device buffers, pinned buffers, events, streams */
 
+/* ---- feature-set RANSAC matching: the seed of every loop-closure link -------------------------------------------------------
+ * The offline mapper's first step, computeAllPossibleLinks (ndt_feature_graph.cpp:395-405; ndt_feature_graph_opt.cpp:95 builds the
+ * graph it runs on), calls computeLink (ndt_feature_graph.cpp:162-177) for every pair of nodes, and computeLink seeds link.T with
+ * matchNodesUsingFeatureMap (ndt_feature_node.h:256) -> matchFeatureMap (ndt_feature_map.h:104-122): flirtlib's
+ * RansacFeatureSetMatcher(0.0599, 0.9, 0.1, 0.6, 0.0499, false).matchSets(ref, mov, transform, matches) on BetaGrid descriptors
+ * under SymmetricChi2Distance.  The fuser makes the same call for the correspondences of its feature term
+ * (ndt_feature_fuser_hmt.cpp:251 with the matcher member of ndt_feature_fuser_hmt.h:213; the flirtlib <-> Eigen conversions are
+ * flirtlib_utils.h:32-42), which ndtgpu_match_fusion_feat_batch consumes.  ndtgpu_featbank_* is that call for a batch of
+ * (ref, mov) pairs of feature sets kept in device memory, one workgroup per pair, all pairs in one launch.
+ * PROVENANCE: flirtlib is not vendored by the reference -- only its call sites and parameters are.  The algorithm below is
+ * restated from memory, as perception_oru's is; no program text of either is copied.
+ * Semantics (restated).  A feature set holds n points, each a position (x, y, theta) and a descriptor of desc_len doubles
+ * (BetaGrid: bin_rho 4 x bin_phi 12 = 48).  For a pair (ref, mov):
+ *   1. descriptor distance d(a, b) = 0.5 * sum_k (a_k - b_k)^2 / (a_k + b_k) over the bins with a_k + b_k > 0, summed in
+ *      ascending k.
+ *   2. candidates: for every mov point i in ascending order the ref point j of smallest distance (strict <, ascending j: the
+ *      lowest j wins ties); (i, j) is kept where the distance is < distance_threshold.  n_c of them.  n_c < 2, or
+ *      n_c * inlier_probability < 2, or an empty set: NDTGPU_FEATMATCH_TOO_FEW.
+ *   3. H = ceil(log(1 - success_probability) / log(1 - inlier_probability^2)) hypotheses (230 at the defaults); hypothesis h
+ *      pairs the candidates a = floor(u(seed, 0, h) * n_c) and b = floor(u(seed, 1, h) * (n_c - 1)), plus 1 if b >= a, with u
+ *      the counter-based uniform of the Monte Carlo localisation (csrc/ndt_mcl.h ndt_hash_uniform).
+ *   4. rigidity: f, g the squared distances between the two mov and between the two ref points; the hypothesis is skipped
+ *      where f + g == 0 or (f - g)^2 / (8 (f + g)) > rigidity_threshold.
+ *   5. pose from correspondences (compute2DPose), p the mov and q the ref points: centroids subtracted, A = sum dp . dq,
+ *      B = sum (dp.x dq.y - dp.y dq.x), h = sqrt(A^2 + B^2), (c, s) = (A / h, B / h) or (1, 0) where h == 0,
+ *      t = mean_q - R mean_p.  The pose maps mov into ref: computeLink's link.T.
+ *   6. verification (verifyHypothesis) over ALL mov points: the point moved by the hypothesis, its nearest ref point by squared
+ *      Euclidean distance (strict <, ascending j); d^2 < acceptance_threshold adds d^2 to the score and (i, j) to the inliers,
+ *      otherwise acceptance_threshold is added.  The threshold is compared with the SQUARED distance, as upstream.
+ *   7. the best hypothesis has the smallest score, ties to the lowest h.  Every hypothesis skipped:
+ *      NDTGPU_FEATMATCH_NO_HYPOTHESIS (upstream: a NaN transform, and matchFeatureMap returns max()).
+ *   8. refinement: step 5 over the best hypothesis's inliers, then step 6 with that pose: the reported score, pose and
+ *      correspondences (ascending i).
+ * DEVIATIONS:
+ *   - upstream draws the two samples from a default-seeded boost::mt19937 and redraws the second until it differs from the
+ *     first; here the draws are counter-based, so a pair's samples depend on (seed, h, n_c) alone -- not on the pairs matched
+ *     before it.
+ *   - the rotation is carried as (c, s); theta = atan2(s, c) is only reported.
+ *   - only the non-adaptive matcher (the `false` of the constructor call) is offered: params.adaptive != 0 is refused.
+ *   - a best hypothesis with an empty inlier set (possible only with thresholds far from the defaults) keeps its own pose in
+ *     step 8.
+ *   - desc_len <= 128 and max_points <= 1024 (the kernel's LDS tiles).
+ * A pair that ends with a status other than NDTGPU_FEATMATCH_OK has score 1e17, the identity pose and no correspondences.
+ * Device form (csrc/ndt_featmatch.hip, ndt_featmatch_kernel): one workgroup of 256 threads per pair.  Both sets' positions are
+ * staged in LDS; step 2 streams the ref descriptors through an LDS tile with a lane per mov point and compacts the kept
+ * candidates in order with a prefix sum; steps 3-7 run one wave per hypothesis, four at a time, the ref positions read from LDS
+ * by every lane at once; step 8 is two more sweeps by the whole workgroup.  Every sum has one fixed order that depends on the
+ * pair's own sizes only, so a pair's outputs are the same bits whichever batch, position or batch size it runs in.  No
+ * environment switches.
+ * Measured on MI355X (tools/featmatch_cost.py, builder-run; defaults, 230 hypotheses, 60 % of a pair's points in common): 1024
+ * pairs of sets of 64 / 256 / 1024 points: 1.23 / 5.77 / 88.2 ms; the replay's 44 486 gated edges at 128 points: 79.8 ms.  No
+ * baseline exists: flirtlib cannot be built here. */
+typedef struct ndtgpu_featbank ndtgpu_featbank;
+typedef struct {
+    double acceptance_threshold;     /* on the squared distance of a moved point to its nearest ref point (0.0599) */
+    double success_probability;      /* (0.9) */
+    double inlier_probability;       /* (0.1) */
+    double distance_threshold;       /* on the descriptor distance of a candidate (0.6) */
+    double rigidity_threshold;       /* (0.0499) */
+    uint64_t seed;                   /* the key of the sample draws (see DEVIATIONS; 0) */
+    int32_t adaptive;                /* must be 0: the adaptive matcher is not offered */
+    int32_t pad_;
+} ndtgpu_featmatch_params;
+/* ndt_feature_map.h:104-122: RansacFeatureSetMatcher(0.0599, 0.9, 0.1, 0.6, 0.0499, false) */
+void ndtgpu_default_featmatch_params(ndtgpu_featmatch_params *p);
+enum {
+    NDTGPU_FEATMATCH_OK = 0,
+    NDTGPU_FEATMATCH_TOO_FEW = 1,         /* step 2: too few candidates, or an empty set */
+    NDTGPU_FEATMATCH_NO_HYPOTHESIS = 2,   /* step 7: no sample passed the rigidity test */
+    NDTGPU_FEATMATCH_BAD_INDEX = 3        /* a set index of the pair is >= n_sets (checked on the device) */
+};
+typedef struct {
+    double score;                    /* step 8's score; 1e17 unless status is OK */
+    double x, y, theta;              /* the pose that maps mov into ref; theta = atan2(s, c) */
+    double c, s;                     /* its rotation as carried */
+    int32_t n_candidates;            /* n_c */
+    int32_t n_hypotheses;            /* H */
+    int32_t n_tested;                /* hypotheses that passed the rigidity test */
+    int32_t best_hypothesis;         /* h of the best one, -1 where there is none */
+    int32_t n_inliers;               /* correspondences reported */
+    int32_t status;                  /* NDTGPU_FEATMATCH_* */
+} ndtgpu_featmatch_result;
+/* room for n_sets feature sets of up to max_points points (1 .. 1024) with descriptors of desc_len doubles (1 .. 128); every set
+ * starts empty */
+ndtgpu_status ndtgpu_featbank_create(size_t n_sets, size_t max_points, size_t desc_len, ndtgpu_featbank **out);
+ndtgpu_status ndtgpu_featbank_destroy(ndtgpu_featbank *h);
+/* installs set k.  HOST arrays: pos3 n x (x, y, theta), desc n x desc_len row-major.  n <= max_points (NDTGPU_ERR_CAPACITY
+ * otherwise); n = 0 empties the set (pos3 / desc may then be NULL).  The arguments are checked before the handle is read and the
+ * device is looked for.  Synchronous. */
+ndtgpu_status ndtgpu_featbank_set(ndtgpu_featbank *h, size_t k, size_t n, const double *pos3, const double *desc);
+/* matches n_pairs pairs (ref_idx[p], mov_idx[p]) of sets, HOST index arrays, in ONE launch, asynchronous on `stream`; prm NULL:
+ * the defaults.  The results stay in the handle for ndtgpu_featbank_results.  Calls on one handle are ordered (each waits, on
+ * the device, for the previous one, whatever stream that one named). */
+ndtgpu_status ndtgpu_featbank_match(ndtgpu_featbank *h, const uint32_t *ref_idx, const uint32_t *mov_idx, size_t n_pairs,
+                                    const ndtgpu_featmatch_params *prm, ndtgpu_stream stream);
+/* the same on DEVICE arrays: ref_idx_dev / mov_idx_dev n_pairs set indices; results_dev n_pairs records; T16_dev n_pairs x 16
+ * doubles, column-major 4x4 built from (c, s, x, y) without trigonometry -- it can be handed to ndtgpu_match_batch_device as
+ * the initial guesses unchanged; corr_dev n_pairs x max_points x 2 uint32 (mov_i, ref_j), a pair's entries beyond its n_inliers
+ * unspecified.  T16_dev and corr_dev may be NULL. */
+ndtgpu_status ndtgpu_featbank_match_device(ndtgpu_featbank *h, const uint32_t *ref_idx_dev, const uint32_t *mov_idx_dev,
+                                           size_t n_pairs, const ndtgpu_featmatch_params *prm,
+                                           ndtgpu_featmatch_result *results_dev, double *T16_dev, uint32_t *corr_dev,
+                                           ndtgpu_stream stream);
+/* pairs [first, first + count) of the last ndtgpu_featbank_match: HOST results count records, T16 count x 16, corr
+ * count x max_points x 2 (any may be NULL).  Waits for that call. */
+ndtgpu_status ndtgpu_featbank_results(ndtgpu_featbank *h, size_t first, size_t count, ndtgpu_featmatch_result *results, double *T16,
+                                      uint32_t *corr);
+
 #ifdef __cplusplus
 }
 #endif

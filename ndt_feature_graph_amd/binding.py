@@ -11,7 +11,7 @@ _ROOT = os.path.dirname(_HERE)
 _SO = os.path.join(_HERE, "libndtgpu.so")
 _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hip", "ndt_pack.hip", "ndt_fuser.hip", "ndtgpu_api.hip",
             "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip",
-            "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndtgpu_pgo.hip"]
+            "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip"]
 
 STATUS = {0: "OK", -1: "ERR_INVALID", -2: "ERR_HIP", -3: "ERR_NO_DEVICE", -4: "ERR_CAPACITY", -5: "ERR_ALLOC"}
 
@@ -138,7 +138,9 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_multires_get_info", "ndtgpu_default_mcl_params", "ndtgpu_mcl_create", "ndtgpu_mcl_destroy", "ndtgpu_mcl_initialize",
            "ndtgpu_mcl_set_particles", "ndtgpu_mcl_update", "ndtgpu_mcl_update_host", "ndtgpu_mcl_particles", "ndtgpu_mcl_mean",
            "ndtgpu_default_pgo_params", "ndtgpu_pgo_create", "ndtgpu_pgo_destroy", "ndtgpu_pgo_set_graph", "ndtgpu_pgo_set_links_device",
-           "ndtgpu_pgo_optimize", "ndtgpu_pgo_poses", "ndtgpu_live_resources"]
+           "ndtgpu_pgo_optimize", "ndtgpu_pgo_poses", "ndtgpu_live_resources",
+           "ndtgpu_default_featmatch_params", "ndtgpu_featbank_create", "ndtgpu_featbank_destroy", "ndtgpu_featbank_set",
+           "ndtgpu_featbank_match", "ndtgpu_featbank_match_device", "ndtgpu_featbank_results"]
 
 _lib = None
 
@@ -267,6 +269,14 @@ def lib():
     L.ndtgpu_pgo_set_links_device.argtypes = [vp, C.c_size_t, C.c_size_t, dp, C.c_size_t, u32p, u32p, vp, vp, vp]
     L.ndtgpu_pgo_optimize.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(PgoParams), vp]
     L.ndtgpu_pgo_poses.argtypes = [vp, C.c_size_t, dp, dp, C.POINTER(PgoResult)]
+    L.ndtgpu_default_featmatch_params.restype = None
+    L.ndtgpu_default_featmatch_params.argtypes = [C.POINTER(FeatMatchParams)]
+    L.ndtgpu_featbank_create.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.ndtgpu_featbank_destroy.argtypes = [vp]
+    L.ndtgpu_featbank_set.argtypes = [vp, C.c_size_t, C.c_size_t, dp, dp]
+    L.ndtgpu_featbank_match.argtypes = [vp, u32p, u32p, C.c_size_t, C.POINTER(FeatMatchParams), vp]
+    L.ndtgpu_featbank_match_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(FeatMatchParams), vp, vp, vp, vp]
+    L.ndtgpu_featbank_results.argtypes = [vp, C.c_size_t, C.c_size_t, vp, dp, u32p]
     if hasattr(L, "ndtgpu_live_resources"):            # (NDTGPU_LIB may name a build from before this entry existed)
         L.ndtgpu_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
@@ -1054,6 +1064,100 @@ class PGO:
         if with_T:
             return ps, np.transpose(T.reshape(-1, 4, 4), (0, 2, 1)).copy(), res
         return ps, res
+
+
+class FeatMatchParams(C.Structure):
+    _fields_ = [("acceptance_threshold", C.c_double), ("success_probability", C.c_double), ("inlier_probability", C.c_double),
+                ("distance_threshold", C.c_double), ("rigidity_threshold", C.c_double), ("seed", C.c_uint64), ("adaptive", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+class FeatMatchResult(C.Structure):
+    _fields_ = [("score", C.c_double), ("x", C.c_double), ("y", C.c_double), ("theta", C.c_double), ("c", C.c_double), ("s", C.c_double),
+                ("n_candidates", C.c_int32), ("n_hypotheses", C.c_int32), ("n_tested", C.c_int32), ("best_hypothesis", C.c_int32),
+                ("n_inliers", C.c_int32), ("status", C.c_int32)]
+
+
+FEATMATCH_RESULT_DTYPE = np.dtype([("score", "<f8"), ("x", "<f8"), ("y", "<f8"), ("theta", "<f8"), ("c", "<f8"), ("s", "<f8"),
+                                   ("n_candidates", "<i4"), ("n_hypotheses", "<i4"), ("n_tested", "<i4"), ("best_hypothesis", "<i4"),
+                                   ("n_inliers", "<i4"), ("status", "<i4")])
+# ndtgpu_featmatch_result.status (include/ndtgpu.h NDTGPU_FEATMATCH_*)
+FEATMATCH_OK, FEATMATCH_TOO_FEW, FEATMATCH_NO_HYPOTHESIS, FEATMATCH_BAD_INDEX = 0, 1, 2, 3
+
+
+def featmatch_params(**fields):
+    """ndtgpu_default_featmatch_params with fields replaced"""
+    p = FeatMatchParams()
+    lib().ndtgpu_default_featmatch_params(C.byref(p))
+    for k, v in fields.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown feature-match parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+class FeatureMatcher:
+    """ndtgpu_featbank: n_sets feature sets of up to max_points points (position (x, y, theta) + descriptor of desc_len doubles) in
+    device memory, and the RANSAC matching of pairs of them, one workgroup per pair (include/ndtgpu.h: matchFeatureMap)."""
+
+    def __init__(self, n_sets, max_points, desc_len=48):
+        h = C.c_void_p()
+        _check(lib().ndtgpu_featbank_create(int(n_sets), int(max_points), int(desc_len), C.byref(h)))
+        self.h, self.n_sets, self.max_points, self.desc_len = h, int(n_sets), int(max_points), int(desc_len)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ndtgpu_featbank_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set(self, k, pos, desc):
+        """set k: pos [n, 3] (x, y, theta), desc [n, desc_len]; n = 0 empties it"""
+        ps = _f64(pos).reshape(-1, 3)
+        ds = _f64(desc).reshape(-1, self.desc_len)
+        if ps.shape[0] != ds.shape[0]:
+            raise ValueError("FeatureMatcher.set: one descriptor per point")
+        n = ps.shape[0]
+        _check(lib().ndtgpu_featbank_set(self.h, int(k), n, _dp(ps) if n else None, _dp(ds) if n else None))
+
+    def match(self, ref_idx, mov_idx, stream=None, **params):
+        """pairs (ref_idx[p], mov_idx[p]) in one launch -> (results [n] FEATMATCH_RESULT_DTYPE, T [n, 4, 4] mov -> ref, list of n
+        correspondence arrays [n_inliers, 2] uint32 (mov_i, ref_j)); keyword arguments: fields of ndtgpu_featmatch_params"""
+        ri = np.ascontiguousarray(ref_idx, dtype=np.uint32).reshape(-1)
+        mi = np.ascontiguousarray(mov_idx, dtype=np.uint32).reshape(-1)
+        if ri.shape != mi.shape:
+            raise ValueError("FeatureMatcher.match: one ref and one mov index per pair")
+        n = ri.shape[0]
+        u32p = C.POINTER(C.c_uint32)
+        p = featmatch_params(**params)
+        _check(lib().ndtgpu_featbank_match(self.h, ri.ctypes.data_as(u32p), mi.ctypes.data_as(u32p), n, C.byref(p), _stream_ptr(stream)))
+        res = np.zeros(n, dtype=FEATMATCH_RESULT_DTYPE)
+        T = np.zeros((n, 16))
+        corr = np.zeros((n, self.max_points, 2), dtype=np.uint32)
+        _check(lib().ndtgpu_featbank_results(self.h, 0, n, C.c_void_p(res.ctypes.data), _dp(T), corr.ctypes.data_as(u32p)))
+        return res, np.transpose(T.reshape(n, 4, 4), (0, 2, 1)).copy(), [corr[k, :res["n_inliers"][k]].copy() for k in range(n)]
+
+    def match_device(self, ref_idx_dev, mov_idx_dev, results_dev, T16_dev=None, corr_dev=None, stream=None, **params):
+        """the same on torch CUDA tensors, asynchronous on `stream`: ref_idx_dev / mov_idx_dev int32 [n] (read as uint32),
+        results_dev uint8 [n * sizeof(ndtgpu_featmatch_result)], T16_dev float64 [n, 16] (column-major, ready for
+        match_batch_device), corr_dev int32 [n, max_points, 2]"""
+        n = int(ref_idx_dev.numel())
+        assert ref_idx_dev.is_cuda and mov_idx_dev.is_cuda and ref_idx_dev.element_size() == 4 and mov_idx_dev.element_size() == 4
+        assert mov_idx_dev.numel() == n and ref_idx_dev.is_contiguous() and mov_idx_dev.is_contiguous()
+        assert results_dev.is_cuda and results_dev.is_contiguous() and results_dev.numel() * results_dev.element_size() >= n * C.sizeof(FeatMatchResult)
+        if T16_dev is not None:
+            assert T16_dev.is_cuda and T16_dev.is_contiguous() and T16_dev.element_size() == 8 and T16_dev.numel() >= 16 * n
+        if corr_dev is not None:
+            assert corr_dev.is_cuda and corr_dev.is_contiguous() and corr_dev.element_size() == 4 and corr_dev.numel() >= 2 * n * self.max_points
+        p = featmatch_params(**params)
+        _check(lib().ndtgpu_featbank_match_device(self.h, C.c_void_p(ref_idx_dev.data_ptr()), C.c_void_p(mov_idx_dev.data_ptr()), n, C.byref(p),
+                                                  C.c_void_p(results_dev.data_ptr()), None if T16_dev is None else C.c_void_p(T16_dev.data_ptr()),
+                                                  None if corr_dev is None else C.c_void_p(corr_dev.data_ptr()), _stream_ptr(stream)))
 
 
 class FuserParams(C.Structure):

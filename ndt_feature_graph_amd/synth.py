@@ -291,3 +291,47 @@ def pair_3d(seeds, rings=64, azimuths=3125, device="cpu"):
     g = torch.tensor([PAIR_OFFSET_3D[i] + GUESS_PERTURB_3D[i] for i in range(6)], dtype=torch.float64,
                      device=device)[None, :].expand(B, -1)
     return dict(fixed=fixed, moving=moving, T_gt=Toff, T_init=pose6_to_T(g))
+
+
+# ----------------------------------------------------------------------------------------
+# feature sets (interest points with histogram descriptors) for the RANSAC feature matcher
+# ----------------------------------------------------------------------------------------
+
+def feature_sets(seed, n_ref, n_mov, n_common, T, pos_noise=0.01, desc_noise=0.02, desc_len=48, extent=10.0, peak=16.0):
+    """A (ref, mov) pair of feature sets with a planted pose T = (x, y, theta) that maps mov into ref.
+
+    ref: n_ref points uniform in [-extent, extent]^2 with random headings and random histograms normalised to sum 1.
+    mov: n_common of the ref points (a seeded selection, so correspondence is not the identity) moved by T^-1 with N(0, pos_noise^2)
+    position noise and |N(0, desc_noise^2)| / desc_len descriptor noise per bin (renormalised), then n_mov - n_common outliers at
+    random positions whose histograms are PEAKED (u^peak, normalised): their chi-square distance to the flat random histograms
+    of ref is often above the matcher's 0.6 threshold, which two flat random histograms (about 0.17) never are.
+    Returns dict(ref_pos [n_ref, 3], ref_desc [n_ref, desc_len], mov_pos, mov_desc, common [n_common] the ref index of mov point m),
+    float64 / int64 tensors."""
+    assert 0 <= n_common <= min(n_ref, n_mov)
+    i_ref = torch.arange(n_ref, dtype=torch.int64)
+    i_mov = torch.arange(n_mov, dtype=torch.int64)
+    k = torch.arange(desc_len, dtype=torch.int64)
+
+    def hist(stream, idx, power):
+        h = hash_uniform(seed, stream, idx[:, None] * desc_len + k[None, :]) ** power
+        return h / h.sum(dim=1, keepdim=True)
+
+    ref_pos = torch.stack([(2.0 * hash_uniform(seed, 101, i_ref) - 1.0) * extent, (2.0 * hash_uniform(seed, 102, i_ref) - 1.0) * extent,
+                           (2.0 * hash_uniform(seed, 103, i_ref) - 1.0) * math.pi], dim=-1)
+    ref_desc = hist(104, i_ref, 1.0)
+    common = torch.argsort(hash_uniform(seed, 105, i_ref))[:n_common]
+    tx, ty, th = (float(v) for v in T)
+    c, s = math.cos(th), math.sin(th)
+    # p_mov = R^T (p_ref - t)
+    dx, dy = ref_pos[common, 0] - tx, ref_pos[common, 1] - ty
+    ic = i_mov[:n_common]
+    com_pos = torch.stack([c * dx + s * dy + pos_noise * hash_normal(seed, 106, ic), -s * dx + c * dy + pos_noise * hash_normal(seed, 108, ic),
+                           ref_pos[common, 2] - th], dim=-1)
+    com_desc = ref_desc[common] + hash_normal(seed, 110, ic[:, None] * desc_len + k[None, :]).abs() * (desc_noise / desc_len)
+    com_desc = com_desc / com_desc.sum(dim=1, keepdim=True)
+    io = i_mov[n_common:]
+    out_pos = torch.stack([(2.0 * hash_uniform(seed, 112, io) - 1.0) * extent, (2.0 * hash_uniform(seed, 113, io) - 1.0) * extent,
+                           (2.0 * hash_uniform(seed, 114, io) - 1.0) * math.pi], dim=-1)
+    out_desc = hist(115, io, peak)
+    return dict(ref_pos=ref_pos, ref_desc=ref_desc, mov_pos=torch.cat([com_pos, out_pos]), mov_desc=torch.cat([com_desc, out_desc]),
+                common=common)
