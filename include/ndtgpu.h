@@ -984,6 +984,114 @@ ndtgpu_status ndtgpu_featbank_match_device(ndtgpu_featbank *h, const uint32_t *r
 ndtgpu_status ndtgpu_featbank_results(ndtgpu_featbank *h, size_t first, size_t count, ndtgpu_featmatch_result *results, double *T16,
                                       uint32_t *corr);
 
+/* ---- laser-scan feature extraction: the interest points and descriptors that the matcher above consumes ---------------------
+ * The reference makes features for every scan it fuses: detector_->detect(*reading, pts) and descriptor_->describe(*p, *reading)
+ * (ndt_feature2d_fuser.cpp:766-779, publish_graph_message.cpp:1401-1404) with the objects of flirtlib_utils.h:15-42 --
+ * SimpleMinMaxPeakFinder(0.34, 0.001), CurvatureDetector(peak, 5, 0.2, 1.4, 2.0) with setUseMaxRange(false) and
+ * BetaGridGenerator(0.02, 1.0, 4, 12) -- on a reading built by flirtlib_ros::fromRos (conversions.cpp:69-82): angles
+ * angle_min + i * angle_increment, the ranges, the sensor at the origin.  ndtgpu_featbank_extract* is that for a batch of scans
+ * in ONE launch, one workgroup per scan; scan b fills set set_idx[b] of the bank, where ndtgpu_featbank_match* finds it with no
+ * host round trip: scan -> features -> RANSAC seed -> D2D registration -> gating -> pose-graph optimisation.
+ * PROVENANCE: flirtlib is not vendored by the reference -- only its call sites and parameters are.  The algorithm below is
+ * restated from memory of what such a detector and descriptor do and is THIS project's specification; no program text of
+ * flirtlib or of the reference is copied.
+ * Semantics (restated).  A scan is n_beams ranges; beam i looks along angle_min + i * angle_increment, and the sensor is at the
+ * origin of the frame the features are reported in.
+ *   1. valid points: beam i is valid iff its range is finite and r_min < r < r_max; the valid points p_k = r (cos, sin) in beam
+ *      order, m of them.  m < 3: NDTGPU_FEATEXTRACT_TOO_FEW_POINTS and an empty set.
+ *   2. chain: d_k = |p_k - p_(k-1)|; a new segment starts at k iff d_k > dmst; the arc length g_0 = 0, g_k = g_(k-1) + d_k.  The
+ *      scan is not closed: beam 0 and the last beam are not neighbours.
+ *   3. scale space: level s = 0 .. scales - 1 has sigma_s = base_sigma * sigma_step^s.  The window of k is the set of j in k's
+ *      segment with |g_j - g_k| <= 3 sigma_s; S_s(k) = sum w_j p_j / sum w_j with w_j = exp(-(g_j - g_k)^2 / (2 sigma_s^2)), both
+ *      sums over the window in ascending j; n_s(k) = S_s(k) - p_k and the response R_s(k) = |n_s(k)| / sigma_s.  k is ELIGIBLE at
+ *      level s iff g_k - g_first >= 3 sigma_s and g_last - g_k >= 3 sigma_s within its segment (the one-sided windows of
+ *      occlusion edges would give responses near 0.8).
+ *   4. peaks (SimpleMinMaxPeakFinder::isPeak as recalled): (s, k) is a peak iff k is eligible at s, R_s(k) > min_value,
+ *      R_s(k) - R_s(k-1) > min_diff and R_s(k) - R_s(k+1) > min_diff; the neighbours' responses whether eligible or not.
+ *   5. one level per point: among the peaks of one k the level of the largest R is kept, ties to the lowest s.
+ *   6. separation: a kept peak k is dropped iff another kept peak k' of step 5 in the same segment has |g_k' - g_k| <
+ *      min_separation and R' > R, or R' == R and k' < k.  One pass over the step-5 set, not iterated.
+ *   7. interest point: position p_k, theta = atan2(n_s(k).y, n_s(k).x) -- it points to the inside of the corner --, level s and
+ *      beam i; the points of a scan in ascending beam order.
+ *   8. BetaGrid descriptor of (x, y, theta), bin_rho * bin_phi bins indexed a * bin_phi + c.  A location q has the bin of
+ *      l = R(-theta)(q - (x, y)), rho = |l|, phi = atan2(l.y, l.x): iff min_rho <= rho < max_rho, a = floor((rho - min_rho) / drho)
+ *      with drho = (max_rho - min_rho) / bin_rho, c = min(floor((phi + pi) / (2 pi / bin_phi)), bin_phi - 1).  HITS: every valid
+ *      point of the scan that has a bin adds 1 to it.  MISSES: the beam of every valid point q is sampled at
+ *      q (1 - u delta / |q|), u = 1, 2, ... while u delta < |q|, delta = drho / 2; a bin holding at least one sample of the beam
+ *      gets ONE miss from it, except the bin that q itself hits.  Bin b holds (hit_b + 1) / (hit_b + miss_b + 2), the mean of the
+ *      Beta posterior; not normalised.
+ * DEVIATIONS:
+ *   - flirtlib's CurvatureDetector smooths over geodesic distances in a minimum spanning tree of the scan points with edges up
+ *     to dmst; here the tree is the chain of consecutive valid beams, broken at gaps above dmst.
+ *   - the response and its normalisation are this project's, and so is what 0.34 means on it: a corner turning more than about
+ *     50 degrees, from sqrt(2 / pi) sin(turn / 2) > 0.34 (a noise-free right angle: 0.564 in the continuum, 0.60-0.61 sampled at
+ *     1 degree).  It is not calibrated against flirtlib.
+ *   - eligibility (step 3) and the separation of step 6 (min_separation) are this project's.
+ *   - the misses come from fixed-step samples of the beam, not from flirtlib's traversal of the grid.
+ *   - limits: bin_rho * bin_phi <= 64, scales <= 8, n_beams <= 2048.
+ * Device form (csrc/ndt_featextract.hip, ndt_featextract_kernel): one workgroup of 256 threads per scan.  Steps 1-2 are ordered
+ * compactions and prefix sums over the workgroup, step 3 a lane per point level by level with the window found by walking from k,
+ * step 8 a wave per keypoint with a lane per beam, the visited bins as a 64-bit mask and integer LDS atomics.  fp64 throughout;
+ * every sum has one fixed order that depends on the scan alone, so a scan's outputs are the same bits in any batch, at any
+ * position and for any batch size.  The set indices of one call must differ from each other.  No environment switches.
+ * Measured on MI355X (tools/featextract_cost.py, builder-run; defaults, synthetic halls, 1024 scans of 360 / 720 / 1440 beams):
+ * the extraction alone 0.22 / 0.46 / 1.41 ms (0.2 / 0.5 / 1.4 us a scan, 6 / 8 / 9 interest points a scan), the extraction and the matching
+ * of the 1023 pairs of consecutive scans 0.40 / 0.64 / 1.59 ms.  No baseline exists: flirtlib cannot be built here. */
+typedef struct {
+    int32_t scales;                  /* levels of the scale space, 1 .. 8 (5) */
+    int32_t bin_rho;                 /* rings of the descriptor (4) */
+    int32_t bin_phi;                 /* sectors of the descriptor (12); bin_rho * bin_phi <= 64 and == the bank's desc_len */
+    int32_t pad_;
+    double base_sigma;               /* sigma of level 0, metres of arc length (0.2) */
+    double sigma_step;               /* ratio of consecutive levels, > 1 (1.4) */
+    double dmst;                     /* a gap between consecutive valid points above this starts a new segment (2.0) */
+    double min_value;                /* a peak's response is above this (0.34) */
+    double min_diff;                 /* ... and above both neighbours' by more than this (0.001) */
+    double min_rho;                  /* the descriptor's inner radius (0.02) */
+    double max_rho;                  /* ... and outer radius (1.0) */
+    double min_separation;           /* step 6, metres of arc length (0.2; this project's) */
+    double r_min;                    /* a valid range is above this (0.5) */
+    double r_max;                    /* ... and below this (30.0) */
+} ndtgpu_featextract_params;
+/* flirtlib_utils.h:15-42; min_separation 0.2; r_min / r_max: the launch files' min and sensor range */
+void ndtgpu_default_featextract_params(ndtgpu_featextract_params *p);
+enum {
+    NDTGPU_FEATEXTRACT_OK = 0,
+    NDTGPU_FEATEXTRACT_TOO_FEW_POINTS = 1,   /* step 1: fewer than 3 valid points; the set is emptied */
+    NDTGPU_FEATEXTRACT_OVERFLOW = 2,         /* n_found > the bank's max_points: the first max_points in beam order are stored */
+    NDTGPU_FEATEXTRACT_BAD_INDEX = 3         /* the scan's set index is >= n_sets (checked on the device); nothing is written */
+};
+typedef struct {
+    int32_t n_valid;                 /* m */
+    int32_t n_segments;
+    int32_t n_peaks;                 /* peaks (s, k) of step 4, every level counted */
+    int32_t n_found;                 /* interest points after step 6 */
+    int32_t n_stored;                /* min(n_found, max_points): the set's count */
+    int32_t status;                  /* NDTGPU_FEATEXTRACT_* */
+} ndtgpu_featextract_result;
+/* extracts n_scans scans, HOST ranges n_scans x n_beams (through a pinned staging buffer) and HOST set indices, in ONE launch,
+ * asynchronous on `stream`; prm NULL: the defaults.  The bank's desc_len must equal bin_rho * bin_phi (NDTGPU_ERR_INVALID).  The
+ * arguments and parameters are checked before the handle is read and the device is looked for.  The records stay in the handle
+ * for ndtgpu_featbank_extract_results.  Ordered against the handle's other calls like ndtgpu_featbank_match. */
+ndtgpu_status ndtgpu_featbank_extract(ndtgpu_featbank *h, const uint32_t *set_idx, const double *ranges, size_t n_scans, size_t n_beams,
+                                      double angle_min, double angle_increment, const ndtgpu_featextract_params *prm,
+                                      ndtgpu_stream stream);
+/* the same on DEVICE arrays, fully asynchronous: set_idx_dev n_scans set indices, ranges_dev n_scans x n_beams; results_dev
+ * n_scans records; beam_dev / level_dev / response_dev n_scans x max_points, a scan's entries beyond its n_stored unspecified
+ * (each may be NULL) */
+ndtgpu_status ndtgpu_featbank_extract_device(ndtgpu_featbank *h, const uint32_t *set_idx_dev, const double *ranges_dev, size_t n_scans,
+                                             size_t n_beams, double angle_min, double angle_increment,
+                                             const ndtgpu_featextract_params *prm, ndtgpu_featextract_result *results_dev,
+                                             uint32_t *beam_dev, int32_t *level_dev, double *response_dev, ndtgpu_stream stream);
+/* scans [first, first + count) of the last ndtgpu_featbank_extract: HOST results count records; beam, level and response
+ * count x max_points (any may be NULL).  Waits for that call. */
+ndtgpu_status ndtgpu_featbank_extract_results(ndtgpu_featbank *h, size_t first, size_t count, ndtgpu_featextract_result *results,
+                                              uint32_t *beam, int32_t *level, double *response);
+/* reads set k back, however it was filled (ndtgpu_featbank_set or an extraction): *n its count, HOST pos3 max_points x 3 and desc
+ * max_points x desc_len of room (either may be NULL), the first *n rows written, the descriptors row-major.  Waits for the
+ * handle's last call. */
+ndtgpu_status ndtgpu_featbank_get(ndtgpu_featbank *h, size_t k, size_t *n, double *pos3, double *desc);
+
 #ifdef __cplusplus
 }
 #endif

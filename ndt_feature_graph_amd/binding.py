@@ -11,7 +11,8 @@ _ROOT = os.path.dirname(_HERE)
 _SO = os.path.join(_HERE, "libndtgpu.so")
 _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hip", "ndt_pack.hip", "ndt_fuser.hip", "ndtgpu_api.hip",
             "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip",
-            "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip"]
+            "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
+            "ndt_featextract.hip"]
 
 STATUS = {0: "OK", -1: "ERR_INVALID", -2: "ERR_HIP", -3: "ERR_NO_DEVICE", -4: "ERR_CAPACITY", -5: "ERR_ALLOC"}
 
@@ -140,7 +141,9 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_default_pgo_params", "ndtgpu_pgo_create", "ndtgpu_pgo_destroy", "ndtgpu_pgo_set_graph", "ndtgpu_pgo_set_links_device",
            "ndtgpu_pgo_optimize", "ndtgpu_pgo_poses", "ndtgpu_live_resources",
            "ndtgpu_default_featmatch_params", "ndtgpu_featbank_create", "ndtgpu_featbank_destroy", "ndtgpu_featbank_set",
-           "ndtgpu_featbank_match", "ndtgpu_featbank_match_device", "ndtgpu_featbank_results"]
+           "ndtgpu_featbank_match", "ndtgpu_featbank_match_device", "ndtgpu_featbank_results",
+           "ndtgpu_default_featextract_params", "ndtgpu_featbank_extract", "ndtgpu_featbank_extract_device",
+           "ndtgpu_featbank_extract_results", "ndtgpu_featbank_get"]
 
 _lib = None
 
@@ -277,6 +280,13 @@ def lib():
     L.ndtgpu_featbank_match.argtypes = [vp, u32p, u32p, C.c_size_t, C.POINTER(FeatMatchParams), vp]
     L.ndtgpu_featbank_match_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(FeatMatchParams), vp, vp, vp, vp]
     L.ndtgpu_featbank_results.argtypes = [vp, C.c_size_t, C.c_size_t, vp, dp, u32p]
+    L.ndtgpu_default_featextract_params.restype = None
+    L.ndtgpu_default_featextract_params.argtypes = [C.POINTER(FeatExtractParams)]
+    L.ndtgpu_featbank_extract.argtypes = [vp, u32p, dp, C.c_size_t, C.c_size_t, C.c_double, C.c_double, C.POINTER(FeatExtractParams), vp]
+    L.ndtgpu_featbank_extract_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_double, C.c_double, C.POINTER(FeatExtractParams),
+                                                 vp, vp, vp, vp, vp]
+    L.ndtgpu_featbank_extract_results.argtypes = [vp, C.c_size_t, C.c_size_t, vp, u32p, C.POINTER(C.c_int32), dp]
+    L.ndtgpu_featbank_get.argtypes = [vp, C.c_size_t, C.POINTER(C.c_size_t), dp, dp]
     if hasattr(L, "ndtgpu_live_resources"):            # (NDTGPU_LIB may name a build from before this entry existed)
         L.ndtgpu_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
@@ -1085,6 +1095,35 @@ FEATMATCH_RESULT_DTYPE = np.dtype([("score", "<f8"), ("x", "<f8"), ("y", "<f8"),
 FEATMATCH_OK, FEATMATCH_TOO_FEW, FEATMATCH_NO_HYPOTHESIS, FEATMATCH_BAD_INDEX = 0, 1, 2, 3
 
 
+class FeatExtractParams(C.Structure):
+    _fields_ = [("scales", C.c_int32), ("bin_rho", C.c_int32), ("bin_phi", C.c_int32), ("pad_", C.c_int32), ("base_sigma", C.c_double),
+                ("sigma_step", C.c_double), ("dmst", C.c_double), ("min_value", C.c_double), ("min_diff", C.c_double),
+                ("min_rho", C.c_double), ("max_rho", C.c_double), ("min_separation", C.c_double), ("r_min", C.c_double),
+                ("r_max", C.c_double)]
+
+
+class FeatExtractResult(C.Structure):
+    _fields_ = [("n_valid", C.c_int32), ("n_segments", C.c_int32), ("n_peaks", C.c_int32), ("n_found", C.c_int32),
+                ("n_stored", C.c_int32), ("status", C.c_int32)]
+
+
+FEATEXTRACT_RESULT_DTYPE = np.dtype([("n_valid", "<i4"), ("n_segments", "<i4"), ("n_peaks", "<i4"), ("n_found", "<i4"),
+                                     ("n_stored", "<i4"), ("status", "<i4")])
+# ndtgpu_featextract_result.status (include/ndtgpu.h NDTGPU_FEATEXTRACT_*)
+FEATEXTRACT_OK, FEATEXTRACT_TOO_FEW_POINTS, FEATEXTRACT_OVERFLOW, FEATEXTRACT_BAD_INDEX = 0, 1, 2, 3
+
+
+def featextract_params(**fields):
+    """ndtgpu_default_featextract_params with fields replaced"""
+    p = FeatExtractParams()
+    lib().ndtgpu_default_featextract_params(C.byref(p))
+    for k, v in fields.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown feature-extraction parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 def featmatch_params(**fields):
     """ndtgpu_default_featmatch_params with fields replaced"""
     p = FeatMatchParams()
@@ -1124,6 +1163,54 @@ class FeatureMatcher:
             raise ValueError("FeatureMatcher.set: one descriptor per point")
         n = ps.shape[0]
         _check(lib().ndtgpu_featbank_set(self.h, int(k), n, _dp(ps) if n else None, _dp(ds) if n else None))
+
+    def get(self, k):
+        """set k as it stands in the bank -> (pos [n, 3], desc [n, desc_len] row-major); waits for the handle"""
+        n = C.c_size_t()
+        ps, ds = np.zeros((self.max_points, 3)), np.zeros((self.max_points, self.desc_len))
+        _check(lib().ndtgpu_featbank_get(self.h, int(k), C.byref(n), _dp(ps), _dp(ds)))
+        return ps[:n.value].copy(), ds[:n.value].copy()
+
+    def extract(self, set_idx, ranges, angle_min, angle_increment, stream=None, **params):
+        """laser scans ranges [n, n_beams] (beam i at angle_min + i * angle_increment) in one launch, scan b into set set_idx[b] ->
+        (records [n] FEATEXTRACT_RESULT_DTYPE, list of n dicts(beam uint32 [n_stored], level int32, response float64)); keyword
+        arguments: fields of ndtgpu_featextract_params"""
+        si = np.ascontiguousarray(set_idx, dtype=np.uint32).reshape(-1)
+        rr = np.ascontiguousarray(ranges, dtype=np.float64)
+        n = si.shape[0]
+        if rr.ndim != 2 or rr.shape[0] != n:
+            raise ValueError("FeatureMatcher.extract: ranges must be [n_scans, n_beams], one row per set index")
+        u32p = C.POINTER(C.c_uint32)
+        p = featextract_params(**params)
+        _check(lib().ndtgpu_featbank_extract(self.h, si.ctypes.data_as(u32p), _dp(rr), n, rr.shape[1], float(angle_min), float(angle_increment),
+                                             C.byref(p), _stream_ptr(stream)))
+        res = np.zeros(n, dtype=FEATEXTRACT_RESULT_DTYPE)
+        beam = np.zeros((n, self.max_points), dtype=np.uint32)
+        level = np.zeros((n, self.max_points), dtype=np.int32)
+        resp = np.zeros((n, self.max_points))
+        _check(lib().ndtgpu_featbank_extract_results(self.h, 0, n, C.c_void_p(res.ctypes.data), beam.ctypes.data_as(u32p),
+                                                     level.ctypes.data_as(C.POINTER(C.c_int32)), _dp(resp)))
+        return res, [dict(beam=beam[b, :res["n_stored"][b]].copy(), level=level[b, :res["n_stored"][b]].copy(),
+                          response=resp[b, :res["n_stored"][b]].copy()) for b in range(n)]
+
+    def extract_device(self, set_idx_dev, ranges_dev, angle_min, angle_increment, results_dev, beam_dev=None, level_dev=None,
+                       response_dev=None, stream=None, **params):
+        """the same on torch CUDA tensors, asynchronous on `stream`: set_idx_dev int32 [n] (read as uint32), ranges_dev float64
+        [n, n_beams], results_dev uint8 [n * sizeof(ndtgpu_featextract_result)], beam_dev / level_dev int32 [n, max_points],
+        response_dev float64 [n, max_points]"""
+        n = int(set_idx_dev.numel())
+        assert set_idx_dev.is_cuda and set_idx_dev.is_contiguous() and set_idx_dev.element_size() == 4
+        assert ranges_dev.is_cuda and ranges_dev.is_contiguous() and ranges_dev.element_size() == 8 and ranges_dev.dim() == 2
+        assert ranges_dev.shape[0] == n
+        assert results_dev.is_cuda and results_dev.is_contiguous() and results_dev.numel() * results_dev.element_size() >= n * C.sizeof(FeatExtractResult)
+        for t, size in ((beam_dev, 4), (level_dev, 4), (response_dev, 8)):
+            if t is not None:
+                assert t.is_cuda and t.is_contiguous() and t.element_size() == size and t.numel() >= n * self.max_points
+        p = featextract_params(**params)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _check(lib().ndtgpu_featbank_extract_device(self.h, ptr(set_idx_dev), ptr(ranges_dev), n, int(ranges_dev.shape[1]), float(angle_min),
+                                                    float(angle_increment), C.byref(p), ptr(results_dev), ptr(beam_dev), ptr(level_dev),
+                                                    ptr(response_dev), _stream_ptr(stream)))
 
     def match(self, ref_idx, mov_idx, stream=None, **params):
         """pairs (ref_idx[p], mov_idx[p]) in one launch -> (results [n] FEATMATCH_RESULT_DTYPE, T [n, 4, 4] mov -> ref, list of n

@@ -7,9 +7,16 @@
 //                                                 ndt_feature_graph.cpp:162-177, and by the fuser, ndt_feature_fuser_hmt.cpp:251)
 //   ndt_feature::computeAllPossibleFeatureLinks   the feature step of computeAllPossibleLinks (ndt_feature_graph.cpp:395-405): every
 //                                                 pair i < j, all of them in ONE device call
-// The detector and the descriptor generator (scan -> interest points) are not part of this: a caller fills InterestPointGPU from
-// flirtlib's points (position, BetaGrid histogram flattened row by row: flirtlib_utils.h:32-42 gives bin_rho 4 x bin_phi 12).
-// NDTFeatureGraph::computeLink (host/ndt_feature_graph_gpu.h) is not wired to this header.
+//   ndt_feature::LaserScanGPU                     the reading flirtlib_ros::fromRos builds (conversions.cpp:69-82): angle_min,
+//                                                 angle_increment and the ranges, the sensor at the origin
+//   ndt_feature::detectAndDescribe                the detect + describe loop of the fuser (ndt_feature2d_fuser.cpp:772-776) for a
+//                                                 batch of scans in ONE device call (include/ndtgpu.h, "laser-scan feature
+//                                                 extraction": the detector and descriptor are restated there, with what
+//                                                 deviates from flirtlib's CurvatureDetector and BetaGridGenerator)
+// A caller may also fill InterestPointGPU from flirtlib's own points (position, BetaGrid histogram flattened row by row:
+// flirtlib_utils.h:32-42 gives bin_rho 4 x bin_phi 12).
+// NOT WIRED: NDTFeatureGraph::computeLink and the fuser's InterestPointVec (host/ndt_feature_graph_gpu.h, still an empty
+// placeholder) do not call this header; a caller chains detectAndDescribe -> NDTFeatureMapGPU::update -> matchFeatureMap itself.
 // There is no CPU fallback: a failed C-ABI call throws ndtgpu_host::Error.
 #pragma once
 #include "lslgeneric_gpu.h"
@@ -41,6 +48,13 @@ public:
 
 private:
     int counter_ = 0;
+};
+
+// sensor_msgs/LaserScan as flirtlib_ros::fromRos reads it (conversions.cpp:69-82): beam i looks along
+// angle_min + i * angle_increment
+struct LaserScanGPU {
+    double angle_min = 0., angle_increment = 0.;
+    std::vector<double> ranges;
 };
 
 struct NDTFeatureMatchLink {
@@ -135,6 +149,56 @@ inline double matchFeatureMap(const NDTFeatureMapGPU &ref, const NDTFeatureMapGP
     if (l.report.status == NDTGPU_FEATMATCH_NO_HYPOTHESIS) return std::numeric_limits<double>::max();
     T = l.T;
     return l.score;
+}
+
+// ndt_feature2d_fuser.cpp:772-776 (detector_->detect(*reading, pts), then descriptor_->describe(*p, *reading) for every point) for
+// a batch of scans in one device call: the interest points of scan b, in ascending beam order, with their BetaGrid descriptors.
+// Every scan must have the first scan's angle_min, angle_increment and number of beams (one call reads one kind of laser).
+// `params` is an addition (NULL: flirtlib_utils.h:15-42); `max_points` is the most a scan may give (more: the first max_points in
+// beam order), `records` the device's record of every scan.
+inline std::vector<InterestPointGPUVec> detectAndDescribe(const std::vector<LaserScanGPU> &scans,
+                                                          const ndtgpu_featextract_params *params = nullptr, size_t max_points = 256,
+                                                          std::vector<ndtgpu_featextract_result> *records = nullptr)
+{
+    std::vector<InterestPointGPUVec> out(scans.size());
+    if (scans.empty()) return out;
+    ndtgpu_featextract_params prm;
+    ndtgpu_default_featextract_params(&prm);
+    if (params) prm = *params;
+    const size_t n = scans.size(), n_beams = scans[0].ranges.size(), desc_len = (size_t)prm.bin_rho * (size_t)prm.bin_phi;
+    std::vector<double> ranges;
+    std::vector<uint32_t> idx(n);
+    for (size_t b = 0; b < n; b++) {
+        if (scans[b].ranges.size() != n_beams || scans[b].angle_min != scans[0].angle_min || scans[b].angle_increment != scans[0].angle_increment)
+            throw ndtgpu_host::Error(NDTGPU_ERR_INVALID, "detectAndDescribe: every scan must have the same angles and number of beams");
+        ranges.insert(ranges.end(), scans[b].ranges.begin(), scans[b].ranges.end());
+        idx[b] = (uint32_t)b;
+    }
+    ndtgpu_featbank *h = nullptr;
+    ndtgpu_host::check(ndtgpu_featbank_create(n, max_points, desc_len ? desc_len : 1, &h), "ndtgpu_featbank_create");
+    std::vector<ndtgpu_featextract_result> res(n);
+    std::vector<double> pos(max_points * 3), desc(max_points * (desc_len ? desc_len : 1));
+    ndtgpu_status rc = ndtgpu_featbank_extract(h, idx.data(), ranges.data(), n, n_beams, scans[0].angle_min, scans[0].angle_increment, &prm,
+                                               nullptr);
+    if (rc == NDTGPU_OK) rc = ndtgpu_featbank_extract_results(h, 0, n, res.data(), nullptr, nullptr, nullptr);
+    for (size_t b = 0; b < n && rc == NDTGPU_OK; b++) {
+        size_t m = 0;
+        rc = ndtgpu_featbank_get(h, b, &m, pos.data(), desc.data());
+        if (rc != NDTGPU_OK) break;
+        out[b].resize(m);
+        for (size_t i = 0; i < m; i++) {
+            InterestPointGPU &p = out[b][i];
+            p.x = pos[3 * i];
+            p.y = pos[3 * i + 1];
+            p.theta = pos[3 * i + 2];
+            p.descriptor.assign(desc.begin() + i * desc_len, desc.begin() + (i + 1) * desc_len);
+        }
+    }
+    const std::string err = rc == NDTGPU_OK ? std::string() : std::string(ndtgpu_last_error());
+    ndtgpu_featbank_destroy(h);
+    if (rc != NDTGPU_OK) throw ndtgpu_host::Error(rc, "detectAndDescribe: " + err);
+    if (records) *records = res;
+    return out;
 }
 
 // every pair i < j of `maps` (ref = i, mov = j, in computeAllPossibleLinks' order) in one device call; a pair with an empty map

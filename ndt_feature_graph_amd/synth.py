@@ -155,6 +155,16 @@ def scan_2d(seeds, poses, n_points, noise_sigma=0.03, z_jitter=0.02, r_max=30.0,
     return out
 
 
+def scan_2d_ranges(seeds, poses, n_beams, **kw):
+    """scan_2d as a laser reading (sensor_msgs/LaserScan, flirtlib_ros::fromRos conversions.cpp:69-82): (ranges float64
+    [B, n_beams], angle_min, angle_increment) with beam i at angle_min + i * angle_increment.  The ranges are the lengths of
+    scan_2d's points, so a dropped beam stays NaN; keyword arguments as scan_2d's."""
+    pts = scan_2d(seeds, poses, n_beams, **kw).to(torch.float64)
+    ranges = torch.sqrt(pts[..., 0] * pts[..., 0] + pts[..., 1] * pts[..., 1])
+    inc = 2.0 * math.pi / n_beams
+    return ranges, 0.5 * inc - math.pi, inc
+
+
 def pose2d_to_T(pose):
     """(x, y, yaw) [B,3] -> 4x4 [B,4,4] float64 (Translation * Rz)."""
     pose = torch.as_tensor(pose, dtype=torch.float64)
