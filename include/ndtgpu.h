@@ -854,6 +854,102 @@ ndtgpu_status ndtgpu_pgo_optimize(ndtgpu_pgo *h, size_t first, size_t count, con
  * Waits for the handle. */
 ndtgpu_status ndtgpu_pgo_poses(ndtgpu_pgo *h, size_t g, double *pose3_out, double *T16_out, ndtgpu_pgo_result *result);
 
+/* ---- world-map assembly: the node maps of a graph, under its poses, merged into one map -------------------------------------
+ * The chain scans -> feature sets -> seeded links -> registered links -> optimised poses ends in node poses; the product the
+ * reference's consumers use is ONE map: ndt_feature_mcl_node.cpp:174 localises in a single saved NDT map,
+ * ndt_feature2d_fuser.cpp:425-432 publishes graph->getMap() moved by graph->getT(), ndt_feature_graph_opt.cpp:178-185 ends by
+ * concatenating every node's getGlobalPointCloud(), and NDTFeatureGraph::fuse() (ndt_feature_graph.h:149-152) is the declared
+ * but empty place for combining nodes.  ndtgpu_world_assemble is that step: it fills `count` destination maps
+ * [dst_first, dst_first + count) of a destination map set (its own grid, centres and max_cells), world w from the node maps
+ * node_idx[node_offsets[w] .. node_offsets[w + 1]) of a source map set, one pose T16 per listed node (node frame -> world
+ * frame; what ndtgpu_pgo_poses returns as T16_out).
+ * Semantics (restated):
+ *   - every Gaussian cell (mu, Sigma, n) of a listed node becomes mu' = R mu + t, Sigma' = R Sigma R^T: pseudoTransformNDT, and
+ *     over a whole map NDTMap::pseudoTransformNDTMap -- the call the fuser comments out at ndt_feature2d_fuser.cpp:471 and
+ *     publish_graph_message.cpp:588.
+ *   - the moved cell is binned by LazyGrid::getIndexForPoint(mu') of the destination grid (per axis
+ *     floor((p - c) / res + 0.5) + size / 2.0 truncated to int, in fp64, not contracted: csrc/ndt_math.h lazygrid_index_half).
+ *   - a mean outside the destination grid is dropped (n_dropped).  A contribution that is not finite, or whose second moment
+ *     would leave the accumulator's room (below), is dropped and counted in n_rejected.
+ *   - the contributions of one world cell merge as pooled sample statistics -- what a chain of NDTCell::updateSampleVariance /
+ *     addDistributionToCell calls gives in exact arithmetic:  N = sum n_i,  mean = sum n_i mu'_i / N,
+ *     (N - 1) C = sum [(n_i - 1) Sigma'_i + n_i (mu'_i - mean)(mu'_i - mean)^T];  then NDTCell::rescaleCovariance once, with
+ *     params.eval_factor.
+ *   - the finalise step's Gaussian threshold is n_min = 2: every contribution already is a Gaussian.  One node under the identity
+ *     pose on an identical grid therefore reproduces itself.
+ *   - the destination maps' previous content is replaced.
+ * PROVENANCE: perception_oru's NDTCell / NDTMap are restated from memory; no program text is copied.
+ * DEVIATIONS:
+ *   - OURS: a source cell with n < 2 counts as n = 2 (ndtgpu_mapset_set_cells installs n = 1; a Gaussian stands for at least two
+ *     points).
+ *   - saturation: params.maxnumpoints (1e5, fuser_hmt.cpp:486; <= 0: never) is applied ONCE at the end, where it only clamps the
+ *     stored n -- mean and covariance do not depend on it.  Upstream saturates at every pairwise merge, which makes its result
+ *     depend on the order of the merges.
+ *   - order independence: a world's cells are the same bits for any order of its nodes in node_idx, in whichever batch it is
+ *     assembled, and on repeated calls (the sums are 64-bit integers; the scales are a function of the world's own nodes).
+ *   - occupancy: where the destination set has occupancies they are what a plain ndtgpu_mapset_build leaves on such a set --
+ *     min(N log(0.6 / 0.4), 255) from the merged N for every touched cell, 0 elsewhere -- and then clamped to
+ *     params.occupancy_limit where that is below 255.  Merging the nodes' own log-odds is out of scope.
+ *   - the map's n_dropped counter (ndtgpu_mapset_counters) holds n_dropped + n_rejected of the world, saturated.
+ * Room of the accumulators (nothing wraps silently).  The scales are ndt_build_shifts of the destination grid for the bound of
+ * a cell's N -- the sum of n over ALL listed cells of the world, counted on the device in a first pass
+ * (ndt_world_count_kernel); 2^32 or more: NDTGPU_ERR_CAPACITY.  They leave one cell^2 of second moment per point (sixteen on
+ * grids with an odd axis, where LazyGrid's truncation lets |u| reach 2): n u_k^2 takes at most 1/4 (4) of it, so a contribution
+ * is admitted where
+ *        (n - 1) |Sigma'_kl| / res_dst^2  <=  (3/4) n     (12 n with an odd axis)      for all six entries,
+ * and rejected otherwise.  A cell built from points of a grid with res_src <= res_dst always passes: its largest eigenvalue is
+ * at most its trace <= 3 (res_src / 2)^2 n / (n - 1), and rescaleCovariance only raises the small eigenvalues.  That is why
+ * res_dst < res_src is refused.
+ * Device form (csrc/ndt_world.hip): sum n_i u_i and sum [(n_i - 1) Sigma'_i / res^2 + n_i u_i u_i^T], u = (mu' - cell origin) /
+ * res, are exactly the "sum u" and "sum u u^T" of a virtual point set, so ndt_world_scatter_kernel -- one lane per source cell,
+ * grid (chunks of a node's cells, listed node) -- writes the destination map's build scratch in the build's own format (NdtAcc
+ * fixed point, every partial rounded once, integer atomics; work table, bitmap and accumulator ids allocated like phase A of
+ * the build), and the build's unmodified finalise, rank and placement launches (csrc/ndt_build.hip ndt_launch_finalise) make
+ * the Gaussians, the rank map and the counters.  Destination overflow (more world cells than max_cells) is the build's:
+ * NdtMapCounters::overflow, reported in the result; the entries that read the map then return NDTGPU_ERR_CAPACITY as after a
+ * build.  Plain launches in stream order; no floating-point atomics, no sort, no grid barrier.
+ * Measured on MI355X (tools/world_cost.py, builder-run): node maps of the replay's layout (bench.py --config 4: 100 x 100 x 1 m at
+ * 0.5 m, one build of a 20 000-point scan each, 246 Gaussian cells on average) into one world of 1360 x 1200 x 2 cells: 64 / 512
+ * / 5000 nodes (11 k / 117 k / 1.23 M contributions -> 428 / 2804 / 24 173 world cells) in 0.18 / 0.23 / 0.88 ms per call, host
+ * wall time around the synchronous call; 64 worlds of 64 nodes (1.02 M contributions) in one call: 0.85 ms.  The only route
+ * without this call -- ndtgpu_mapset_export_cells per node, the NumPy merge of tests/world_model.py, ndtgpu_mapset_set_cells --
+ * takes 100 / 96 / 979 ms and 814 ms on the same box (557 / 413 / 1114 and 953 times as long), yields the same cell counts, and
+ * loses the point counts. */
+typedef struct {
+    double maxnumpoints;             /* end-of-chain clamp of the stored n (1e5, fuser_hmt.cpp:486; <= 0: never) */
+    double eval_factor;              /* NDTCell::rescaleCovariance (1000) */
+    double occupancy_limit;          /* (255) */
+    double reserved_[2];
+} ndtgpu_world_params;
+void ndtgpu_default_world_params(ndtgpu_world_params *p);
+typedef struct {
+    int32_t  n_nodes;                /* listed nodes of the world */
+    int32_t  n_cells;                /* Gaussian cells of the assembled map */
+    int64_t  n_contributions;        /* Gaussian cells of the listed nodes */
+    int64_t  n_dropped;              /* ... whose moved mean lies outside the destination grid */
+    int64_t  n_rejected;             /* ... not finite, or beyond the accumulator's room */
+    int64_t  n_points;               /* sum of merged N (before the maxnumpoints clamp) */
+    int32_t  overflow;               /* NdtMapCounters::overflow of the destination map */
+    int32_t  s1_shift;               /* the accumulators' scales: sum u 2^s1, sum u u^T 2^s2 (cell units) */
+    int32_t  s2_shift;
+    int32_t  pad_;
+} ndtgpu_world_result;
+/* node_offsets (count + 1), node_idx and T16 (16 doubles, column-major, per entry of node_idx from node_offsets[0] on) HOST;
+ * prm NULL: the defaults; results HOST, `count` records, may be NULL.  NDTGPU_ERR_INVALID before any device work: offsets that
+ * are not non-decreasing and dst_set == src_set with a destination map among the listed nodes (both before the device is looked
+ * for and before a handle is read), a node index out of range, destination maps out of range (count <= 65535), destination res
+ * smaller than source res.  Works on `stream` and returns when the maps and results are complete (synchronous, like
+ * ndtgpu_overlap_score_batch).  Temporaries are gone on return; there is no handle: afterwards the destination maps are
+ * ordinary maps of their set (ndtgpu_mapset_num_cells / export_cells / export_occupancy, ndtgpu_mcl_create, ndtgpu_match_*,
+ * ndtgpu_mapset_pack_*). */
+ndtgpu_status ndtgpu_world_assemble(ndtgpu_mapset *dst_set, size_t dst_first, size_t count, ndtgpu_mapset *src_set,
+                                    const uint32_t *node_offsets, const uint32_t *node_idx, const double *T16,
+                                    const ndtgpu_world_params *prm, ndtgpu_world_result *results, ndtgpu_stream stream);
+/* the argument checks of ndtgpu_world_assemble on plain numbers (the sets' map counts and res, same_set: dst_set == src_set):
+ * needs no handle and no device */
+ndtgpu_status ndtgpu_world_check(size_t dst_n_maps, double dst_res, size_t dst_first, size_t count, size_t src_n_maps,
+                                 double src_res, int same_set, const uint32_t *node_offsets, const uint32_t *node_idx);
+
 /* single pair convenience == graph.cpp:273 */
 ndtgpu_status ndtgpu_match_d2d(ndtgpu_mapset *target_set, size_t target_map, ndtgpu_mapset *source_set,
                                size_t source_map, double T16[16], const ndtgpu_match_params *prm,

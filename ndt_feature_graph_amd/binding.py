@@ -12,7 +12,7 @@ _SO = os.path.join(_HERE, "libndtgpu.so")
 _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hip", "ndt_pack.hip", "ndt_fuser.hip", "ndtgpu_api.hip",
             "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip",
             "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
-            "ndt_featextract.hip"]
+            "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip"]
 
 STATUS = {0: "OK", -1: "ERR_INVALID", -2: "ERR_HIP", -3: "ERR_NO_DEVICE", -4: "ERR_CAPACITY", -5: "ERR_ALLOC"}
 
@@ -143,7 +143,8 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_default_featmatch_params", "ndtgpu_featbank_create", "ndtgpu_featbank_destroy", "ndtgpu_featbank_set",
            "ndtgpu_featbank_match", "ndtgpu_featbank_match_device", "ndtgpu_featbank_results",
            "ndtgpu_default_featextract_params", "ndtgpu_featbank_extract", "ndtgpu_featbank_extract_device",
-           "ndtgpu_featbank_extract_results", "ndtgpu_featbank_get"]
+           "ndtgpu_featbank_extract_results", "ndtgpu_featbank_get",
+           "ndtgpu_default_world_params", "ndtgpu_world_assemble", "ndtgpu_world_check"]
 
 _lib = None
 
@@ -287,6 +288,10 @@ def lib():
                                                  vp, vp, vp, vp, vp]
     L.ndtgpu_featbank_extract_results.argtypes = [vp, C.c_size_t, C.c_size_t, vp, u32p, C.POINTER(C.c_int32), dp]
     L.ndtgpu_featbank_get.argtypes = [vp, C.c_size_t, C.POINTER(C.c_size_t), dp, dp]
+    L.ndtgpu_default_world_params.restype = None
+    L.ndtgpu_default_world_params.argtypes = [C.POINTER(WorldParams)]
+    L.ndtgpu_world_assemble.argtypes = [vp, C.c_size_t, C.c_size_t, vp, u32p, u32p, dp, C.POINTER(WorldParams), C.POINTER(WorldResult), vp]
+    L.ndtgpu_world_check.argtypes = [C.c_size_t, C.c_double, C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, C.c_int, u32p, u32p]
     if hasattr(L, "ndtgpu_live_resources"):            # (NDTGPU_LIB may name a build from before this entry existed)
         L.ndtgpu_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
@@ -1074,6 +1079,57 @@ class PGO:
         if with_T:
             return ps, np.transpose(T.reshape(-1, 4, 4), (0, 2, 1)).copy(), res
         return ps, res
+
+
+class WorldParams(C.Structure):
+    _fields_ = [("maxnumpoints", C.c_double), ("eval_factor", C.c_double), ("occupancy_limit", C.c_double), ("reserved_", C.c_double * 2)]
+
+
+class WorldResult(C.Structure):
+    _fields_ = [("n_nodes", C.c_int32), ("n_cells", C.c_int32), ("n_contributions", C.c_int64), ("n_dropped", C.c_int64),
+                ("n_rejected", C.c_int64), ("n_points", C.c_int64), ("overflow", C.c_int32), ("s1_shift", C.c_int32),
+                ("s2_shift", C.c_int32), ("pad_", C.c_int32)]
+
+
+def world_params(**fields):
+    """ndtgpu_default_world_params with fields replaced"""
+    p = WorldParams()
+    lib().ndtgpu_default_world_params(C.byref(p))
+    for k, v in fields.items():
+        if not hasattr(p, k) or k == "reserved_":
+            raise TypeError("unknown world parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def assemble_world(dst, dst_first, src, node_lists, T16_lists, params=None, stream=None):
+    """ndtgpu_world_assemble: destination maps dst_first, dst_first + 1, ... of `dst` become the worlds of node_lists -- world w
+    merges the node maps node_lists[w] of `src` under the poses T16_lists[w] (4 x 4 matrices, node frame -> world frame).
+    params: a WorldParams, a dict of its fields, or None.  Returns one dict per world (ndtgpu_world_result)."""
+    count = len(node_lists)
+    if len(T16_lists) != count:
+        raise ValueError("assemble_world: one list of poses per world")
+    off = np.zeros(count + 1, dtype=np.uint32)
+    idx, Ts = [], []
+    for w in range(count):
+        nodes = [int(k) for k in node_lists[w]]
+        T = _f64(T16_lists[w]).reshape(-1, 4, 4) if len(nodes) else np.zeros((0, 4, 4))
+        if T.shape[0] != len(nodes):
+            raise ValueError("assemble_world: one pose per listed node")
+        idx += nodes
+        Ts.append(np.transpose(T, (0, 2, 1)).reshape(-1, 16))           # column-major
+        off[w + 1] = off[w] + len(nodes)
+    idx = np.asarray(idx + [0], dtype=np.uint32)                        # (never an empty buffer)
+    Tcm = np.ascontiguousarray(np.concatenate(Ts + [np.zeros((1, 16))], axis=0))
+    if params is None or isinstance(params, WorldParams):
+        p = params
+    else:
+        p = world_params(**dict(params))
+    res = (WorldResult * max(count, 1))()
+    u32p = C.POINTER(C.c_uint32)
+    _check(lib().ndtgpu_world_assemble(dst.h, int(dst_first), count, src.h, off.ctypes.data_as(u32p), idx.ctypes.data_as(u32p), _dp(Tcm),
+                                       None if p is None else C.byref(p), res, _stream_ptr(stream)))
+    return [{k: getattr(res[w], k) for k, _ in WorldResult._fields_ if k != "pad_"} for w in range(count)]
 
 
 class FeatMatchParams(C.Structure):

@@ -1331,3 +1331,30 @@ hipError_t ndt_launch_install_cells(const NdtSetView &set, size_t map, const Ndt
                        (unsigned)n_cells);
     return hipGetLastError();
 }
+
+// Build scratch -> cells for maps [first, first + count): the launches that follow the accumulate launch in ndt_launch_build's
+// few-maps path (Gaussians on up to 32 workgroups per map, big grids ranked and placed by launches of their own), with the
+// shifts and n_min the caller filled the scratch for.  For scratch that did not come from a point cloud (csrc/ndt_world.hip):
+// the kernels' point count is 0, so they leave n_dropped = -(sum of the cells' n) for the caller to replace.
+hipError_t ndt_launch_finalise(const NdtSetView &set, size_t first, size_t count, int n_min, double eval_factor, int s1_shift,
+                               int s2_shift, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    const unsigned bm_words = (unsigned)((set.grid.slots + 31) / 32);
+    unsigned fin_parts = (unsigned)((bm_words >= 16384u ? 256u : 64u) / count);
+    if (fin_parts > 32u) fin_parts = 32u;
+    if (fin_parts < 1u) fin_parts = 1u;
+    const int split_rank = (fin_parts > 1u && bm_words >= 16384u) ? 1 : 0;
+    hipLaunchKernelGGL((ndt_build_kernel<0, 2, false, false>), dim3(fin_parts, (unsigned)count), dim3(NDT_FIN_THREADS), 0, stream, set,
+                       (unsigned)first, (const char *)nullptr, 0u, 12u, (size_t)0, 0.0, (const double *)nullptr, n_min, eval_factor,
+                       s1_shift, s2_shift, split_rank, __builtin_inff());
+    if (split_rank) {
+        unsigned parts = fin_parts;                       // (ndt_launch_build's defaults: as many as the Gaussians' launch)
+        hipLaunchKernelGGL((ndt_build_kernel<0, 3, false, false>), dim3(std::min(parts, (unsigned)NDT_RANK_SEGS), (unsigned)count),
+                           dim3(NDT_FIN_THREADS), 0, stream, set, (unsigned)first, (const char *)nullptr, 0u, 12u, (size_t)0, 0.0,
+                           (const double *)nullptr, n_min, eval_factor, s1_shift, s2_shift, 0, __builtin_inff());
+        hipLaunchKernelGGL(ndt_place_cells_kernel, dim3(std::min(parts, 64u), (unsigned)count), dim3(NDT_FIN_THREADS), 0, stream, set,
+                           (unsigned)first);
+    }
+    return hipGetLastError();
+}

@@ -5,6 +5,8 @@
 //   ndt_feature::NDTFeatureLink / NDTFeatureNode / overlapNDTOccupancyScore   ndt_feature_link.h:9-56, ndt_feature_node.h:38-252
 //   ndt_feature::NDTFeatureGraph      ndt_feature_graph.h:20-280 (initialize, update, updateLink[s]UsingNDTRegistration, ...)
 //   ndt_feature::optimizeGraphUsingISAM   ndt_offline_mapper.h:8-26, 40-107 (on the device: ndtgpu_pgo_*)
+//   ndt_feature::assembleWorldMap         the graph's node maps under their poses as ONE map (ndt_feature_graph.h:149-152 fuse(),
+//                                         ndt_feature2d_fuser.cpp:425-432; on the device: ndtgpu_world_assemble)
 // Class, member and parameter names are the reference's, so that its callers compile against this header.  What is behind them
 // is not the reference's control flow retyped but the batched device entries:
 //   * NDTFeatureFuserHMT::initialize / update are ONE C-ABI call each (ndtgpu_fuser_initialize_batch / ndtgpu_fuser_update_batch
@@ -584,6 +586,7 @@ public:
     virtual NDTFeatureLinkInterface &getLinkInterface(size_t idx) { return links_[idx]; }
     virtual const NDTFeatureLinkInterface &getLinkInterface(size_t idx) const { return links_[idx]; }
     NDTFeatureNode &getNode(size_t i) { return nodes_[i]; }
+    const NDTFeatureNode &getNode(size_t i) const { return nodes_[i]; }
     NDTFeatureLink &getLink(size_t i) { return links_[i]; }
     lslgeneric::NDTMap *getMap(int i) { return nodes_[i].map->map; }
     Eigen::Affine3d getT() { return Tnow; }
@@ -850,6 +853,43 @@ inline void optimizeGraphUsingISAM(NDTFeatureGraphInterface &graph, const ndtgpu
     if (result) *result = r;
     for (size_t i = 0; i < n; i++)
         graph.getNodeInterface(i).setPose(convertIsamPose2dToEigenAffine3d(Pose2d(pose[3 * i], pose[3 * i + 1], pose[3 * i + 2])));
+}
+
+// The product of the mapper: ONE map from the graph's node maps under the node poses T -- graph->getMap() moved by getT()
+// (ndt_feature2d_fuser.cpp:425-432), the combination NDTFeatureGraph::fuse() (ndt_feature_graph.h:149-152) declares but leaves
+// empty, the single map ndt_feature_mcl_node.cpp:174 localises in.  On the device in one call: ndtgpu_world_assemble
+// (include/ndtgpu.h "world-map assembly": pseudoTransformNDT of every cell, binned by the world's LazyGrid, cells that share a
+// world cell merged as pooled sample statistics).  `world` has its geometry (guessSize or initialize) and a resolution not below
+// the nodes'; its previous content is replaced.  `node_maps` live in one pool.  Returns the call's report.
+inline ndtgpu_world_result assembleWorldMap(const std::vector<lslgeneric::NDTMap *> &node_maps, const std::vector<Eigen::Affine3d> &poses,
+                                            lslgeneric::NDTMap &world, const ndtgpu_world_params *params = nullptr)
+{
+    if (node_maps.size() != poses.size()) throw ndtgpu_host::Error(NDTGPU_ERR_INVALID, "assembleWorldMap: one pose per node map");
+    const uint32_t off[2] = {0u, (uint32_t)node_maps.size()};
+    std::vector<uint32_t> idx(node_maps.size() + 1, 0u);
+    std::vector<double> T16(16 * (node_maps.size() + 1), 0.);
+    ndtgpu_mapset *src = world.handle();               // (no nodes: any set will do, nothing of it is read)
+    for (size_t i = 0; i < node_maps.size(); i++) {
+        if (i == 0) src = node_maps[0]->handle();
+        else if (node_maps[i]->handle() != src) throw ndtgpu_host::Error(NDTGPU_ERR_INVALID, "assembleWorldMap: the node maps must live in one pool");
+        idx[i] = (uint32_t)node_maps[i]->slot();
+        for (int q = 0; q < 16; q++) T16[16 * i + q] = poses[i].data()[q];
+    }
+    ndtgpu_world_result r;
+    ndtgpu_host::check(ndtgpu_world_assemble(world.handle(), world.slot(), 1, src, off, idx.data(), T16.data(), params, &r, nullptr),
+                       "ndtgpu_world_assemble");
+    return r;
+}
+// every node's map under the node's pose T, in one call
+inline ndtgpu_world_result assembleWorldMap(const NDTFeatureGraph &graph, lslgeneric::NDTMap &world, const ndtgpu_world_params *params = nullptr)
+{
+    std::vector<lslgeneric::NDTMap *> maps;
+    std::vector<Eigen::Affine3d> poses;
+    for (size_t i = 0; i < graph.getNbNodes(); i++) {
+        maps.push_back(graph.getNode(i).map->map);
+        poses.push_back(graph.getNode(i).T);
+    }
+    return assembleWorldMap(maps, poses, world, params);
 }
 
 }  // namespace ndt_feature
