@@ -6,7 +6,7 @@
 // bank; n_scans scans are n_scans workgroups that never look at each other.  Inside a workgroup only __syncthreads orders the
 // phases: no grid barrier, no queue, no spin on memory.  The only atomics are integer adds on LDS counters (step 8), which are
 // exact and free of order.
-//   steps 1-2: the valid beams are compacted in beam order by a ballot prefix per wave and the waves' counts in order; a thread
+//   steps 1-2: the valid beams are compacted in beam order (ndt_block.h: a ballot prefix per wave, the waves' counts in order); a thread
 //     then owns ceil(m / 256) consecutive points: it sums their chord lengths and counts their breaks, the threads' sums are
 //     scanned over the wave (shuffle-up, a fixed tree) and the waves' totals added in order, and a second walk over the same
 //     points writes the arc length g and the segment number of each.
@@ -25,15 +25,14 @@
 // Contraction is off throughout: tests/flirt_model.py restates the arithmetic operation for operation, and the integer outputs
 // rest on comparisons of such values.
 #include "ndt_featextract.h"
-#include "ndt_wave.h"
+#include "ndt_block.h"
 
 #define FX_NO_LEVEL 0xFFu
 
 struct FxFixed {
     unsigned hit[NDT_FEATEXTRACT_WAVES][NDT_FEATEXTRACT_MAX_BINS], miss[NDT_FEATEXTRACT_WAVES][NDT_FEATEXTRACT_MAX_BINS];
     double wsum[NDT_FEATEXTRACT_WAVES];
-    unsigned wcount[2][NDT_FEATEXTRACT_WAVES];
-    unsigned wint[2][NDT_FEATEXTRACT_WAVES];
+    NdtBlockCounts<NDT_FEATEXTRACT_WAVES> wint;
 };
 static_assert(sizeof(FxFixed) <= NDT_FEATEXTRACT_FIXED_BYTES && NDT_FEATEXTRACT_FIXED_BYTES % 16 == 0, "ndt_featextract_lds_bytes");
 
@@ -65,37 +64,6 @@ NDT_D FxLayout fx_layout(unsigned char *base, unsigned nb)
     L.lvl = at;                     at += nb;
     L.flag = at;
     return L;
-}
-
-// Ordered compaction over the workgroup: where `keep`, the number of kept threads below this one; total: all of them.
-// wcount is used in turn with its other half, so one barrier serves.
-NDT_D unsigned fx_block_rank(bool keep, FxFixed &F, int &cpar, unsigned &total)
-{
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long m = ndt_ballot(keep);
-    if (lane == 0) F.wcount[cpar][wave] = (unsigned)__popcll(m);
-    __syncthreads();
-    unsigned below = 0;
-    total = 0;
-    for (unsigned w = 0; w < NDT_FEATEXTRACT_WAVES; w++) {
-        const unsigned c = F.wcount[cpar][w];
-        below += w < wave ? c : 0u;
-        total += c;
-    }
-    cpar ^= 1;
-    return below + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-}
-
-// the sum of an integer over the workgroup, in every thread (exact: its order is free)
-NDT_D unsigned fx_block_count(unsigned c, FxFixed &F, int &ipar)
-{
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    if ((threadIdx.x & 63) == 0) F.wint[ipar][threadIdx.x >> 6] = c;
-    __syncthreads();
-    unsigned n = 0;
-    for (int w = 0; w < NDT_FEATEXTRACT_WAVES; w++) n += F.wint[ipar][w];
-    ipar ^= 1;
-    return n;
 }
 
 // step 3 for point k at the level of `sigma`: n = S - p_k, R = |n| / sigma, and whether k is eligible
@@ -209,13 +177,13 @@ __global__ __launch_bounds__(NDT_FEATEXTRACT_THREADS) void ndt_featextract_kerne
     // ---- step 1: the valid points in beam order ------------------------------------------------------------------------------
     const double *rr = ranges + scan * (size_t)n_beams;
     unsigned m = 0;
-    int cpar = 0, ipar = 0;
+    int ipar = 0;
     for (unsigned base = 0; base < n_beams; base += NDT_FEATEXTRACT_THREADS) {
         const unsigned i = base + tid;
         const double r = i < n_beams ? rr[i] : 0.0;
         const bool ok = i < n_beams && r > prm.r_min && r < prm.r_max;          // (NaN and the infinities fail one of the two)
         unsigned kept;
-        const unsigned at = m + fx_block_rank(ok, F, cpar, kept);
+        const unsigned at = m + ndt_block_rank(ok, F.wint, ipar, kept);
         if (ok) {
             const double phi = angle_min + (double)i * angle_increment;
             L.p[at] = make_double2(r * cos(phi), r * sin(phi));
@@ -253,7 +221,7 @@ __global__ __launch_bounds__(NDT_FEATEXTRACT_THREADS) void ndt_featextract_kerne
     const unsigned incl_breaks = ndt_wave_incl_scan(own_breaks);
     if (lane == 63) {
         F.wsum[wave] = incl;
-        F.wint[ipar][wave] = incl_breaks;
+        F.wint.v[ipar][wave] = incl_breaks;               // (ndt_block.h's discipline: this half, one barrier, then the other)
     }
     __syncthreads();
     double run = 0.0;
@@ -261,9 +229,9 @@ __global__ __launch_bounds__(NDT_FEATEXTRACT_THREADS) void ndt_featextract_kerne
     for (unsigned w = 0; w < NDT_FEATEXTRACT_WAVES; w++) {
         if (w < wave) {
             run += F.wsum[w];
-            seg += F.wint[ipar][w];
+            seg += F.wint.v[ipar][w];
         }
-        n_segments += F.wint[ipar][w];
+        n_segments += F.wint.v[ipar][w];
     }
     ipar ^= 1;
     if (lane > 0) run += before_in_wave;
@@ -310,7 +278,7 @@ __global__ __launch_bounds__(NDT_FEATEXTRACT_THREADS) void ndt_featextract_kerne
         }
         __syncthreads();
     }
-    const unsigned n_peaks = fx_block_count(my_peaks, F, ipar);
+    const unsigned n_peaks = ndt_block_count(my_peaks, F.wint, ipar);
 
     // ---- step 6: one pass over the step-5 set ---------------------------------------------------------------------------------------
     for (unsigned k = tid; k < m; k += NDT_FEATEXTRACT_THREADS) {
@@ -338,7 +306,7 @@ __global__ __launch_bounds__(NDT_FEATEXTRACT_THREADS) void ndt_featextract_kerne
         const unsigned k = base + tid;
         const bool keep = k < m && L.flag[k];
         unsigned kept;
-        const unsigned at = n_found + fx_block_rank(keep, F, cpar, kept);
+        const unsigned at = n_found + ndt_block_rank(keep, F.wint, ipar, kept);
         if (keep) L.kp[at] = (unsigned short)k;
         n_found += kept;
     }

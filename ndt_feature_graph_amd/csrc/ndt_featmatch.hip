@@ -7,11 +7,11 @@
 //   phase A (steps 1-2): a lane per mov point (256 at a time); the ref descriptors stream through an LDS tile of
 //     NDT_FEATMATCH_TILE descriptors laid out [bin][ref], so a lane reads a bin of its own descriptor once per tile (coalesced:
 //     the bank stores descriptors transposed) and the tile's 16 values of the bin from LDS, all lanes the same address.  Each
-//     (mov, ref) distance is summed by ONE lane in ascending bin order.  The kept candidates are compacted in ascending i by a
-//     ballot prefix per wave and the waves' counts in order.
+//     (mov, ref) distance is summed by ONE lane in ascending bin order.  The kept candidates are compacted in ascending i
+//     (ndt_block.h: a ballot prefix per wave, the waves' counts in order).
 //   phase B (steps 3-7): a wave per hypothesis, four at a time.  Lanes stride the mov points, two per lane per pass over the ref
 //     positions in LDS (every lane reads the same address).  A lane's score terms are added in ascending i, then summed over the
-//     wave by the fixed xor butterfly; a wave keeps the best of its hypotheses (ascending h, strict <), the four waves' bests
+//     wave in the order of ndt_block.h; a wave keeps the best of its hypotheses (ascending h, strict <), the four waves' bests
 //     are reduced lexicographically on (score, h).
 //   phase C (step 8): the whole workgroup sweeps with the best hypothesis's pose, refines it over the inliers, sweeps again and
 //     compacts the inliers in ascending i.
@@ -19,7 +19,7 @@
 // Contraction is off throughout: tests/featmatch_model.py restates the arithmetic operation for operation, and the integer
 // outputs (candidates, best hypothesis, inliers) rest on comparisons of such values.
 #include "ndt_featmatch.h"
-#include "ndt_wave.h"
+#include "ndt_block.h"
 
 struct FmPose {
     double c, s, tx, ty;
@@ -31,61 +31,11 @@ struct FmShared {
     unsigned short cand_i[NDT_FEATMATCH_MAX_POINTS], cand_j[NDT_FEATMATCH_MAX_POINTS];
     unsigned short nn[NDT_FEATMATCH_MAX_POINTS];                    // the last sweep's nearest ref point of each mov point
     unsigned char inl[NDT_FEATMATCH_MAX_POINTS];                    // ... and whether it is an inlier
-    double red[2][NDT_FEATMATCH_WAVES][4];
-    unsigned wcount[2][NDT_FEATMATCH_WAVES];
+    NdtBlockSums<NDT_FEATMATCH_WAVES, 4> red;
+    NdtBlockCounts<NDT_FEATMATCH_WAVES> wcount;
     double wbest[NDT_FEATMATCH_WAVES];
     int wbest_h[NDT_FEATMATCH_WAVES], wtested[NDT_FEATMATCH_WAVES];
 };
-
-// the sum of v over the 64 lanes, in every lane: v += lane ^ 32, 16, 8, 4, 2, 1 in that order, in the vector ALU
-NDT_D double fm_wave_sum(double v)
-{
-    v = pl_swap_add(v, v, false);
-    v = pl_swap_add(v, v, true);
-    v += xor_lane<8>(v);
-    v += xor_lane<4>(v);
-    v += xor_lane<2>(v);
-    v += xor_lane<1>(v);
-    return v;
-}
-
-// sums of v[0..N) over the workgroup, in every thread: the butterfly per wave, then the waves' sums in ascending order.  `red`
-// is used in turn with its other half, so one barrier serves.
-template <int N>
-NDT_D void fm_block_sum(double (&v)[N], FmShared &sh, int &par)
-{
-    static_assert(N <= 4, "FmShared::red");
-#pragma unroll
-    for (int k = 0; k < N; k++) v[k] = fm_wave_sum(v[k]);
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < N; k++) sh.red[par][threadIdx.x >> 6][k] = v[k];
-    __syncthreads();
-    for (int k = 0; k < N; k++) {
-        double s = 0.0;
-        for (int w = 0; w < NDT_FEATMATCH_WAVES; w++) s += sh.red[par][w][k];
-        v[k] = s;
-    }
-    par ^= 1;
-}
-
-// Ordered compaction over the workgroup: where `keep`, the number of kept threads below this one; total: all of them.
-// wcount is used in turn with its other half, so one barrier serves.
-NDT_D unsigned fm_block_rank(bool keep, FmShared &sh, int &cpar, unsigned &total)
-{
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long m = ndt_ballot(keep);
-    if (lane == 0) sh.wcount[cpar][wave] = (unsigned)__popcll(m);
-    __syncthreads();
-    unsigned below = 0;
-    total = 0;
-    for (unsigned w = 0; w < NDT_FEATMATCH_WAVES; w++) {
-        const unsigned c = sh.wcount[cpar][w];
-        below += w < wave ? c : 0u;
-        total += c;
-    }
-    cpar ^= 1;
-    return below + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-}
 
 // step 5 over two correspondences (p: mov, q: ref), the sums in the order of the general form
 NDT_D FmPose fm_pose2(double2 p1, double2 p2, double2 q1, double2 q2)
@@ -257,7 +207,7 @@ __global__ __launch_bounds__(NDT_FEATMATCH_THREADS) void ndt_featmatch_kernel(Nd
         }
         const bool keep = live && 0.5 * best < prm.distance_threshold;
         unsigned kept;
-        const unsigned at = n_c + fm_block_rank(keep, sh, cpar, kept);
+        const unsigned at = n_c + ndt_block_rank(keep, sh.wcount, cpar, kept);
         if (keep) {
             sh.cand_i[at] = (unsigned short)i;
             sh.cand_j[at] = (unsigned short)best_j;
@@ -277,7 +227,7 @@ __global__ __launch_bounds__(NDT_FEATMATCH_THREADS) void ndt_featmatch_kernel(Nd
         FmPose T;
         if (!fm_hypothesis(sh, prm, (unsigned)h, n_c, T)) continue;
         tested++;
-        const double score = fm_wave_sum(fm_sweep<false>(sh, n_ref, n_mov, T, prm.acceptance_threshold, lane, 64));
+        const double score = ndt_wave_sum(fm_sweep<false>(sh, n_ref, n_mov, T, prm.acceptance_threshold, lane, 64));
         if (wbest_h < 0 || score < wbest) {
             wbest = score;
             wbest_h = h;
@@ -320,17 +270,8 @@ __global__ __launch_bounds__(NDT_FEATMATCH_THREADS) void ndt_featmatch_kernel(Nd
             m[0] += p.x; m[1] += p.y; m[2] += q.x; m[3] += q.y;
             mine++;
         }
-    fm_block_sum(m, sh, par);
-    unsigned n_in = 0;
-    {
-        // the inlier count: exact, so its order is free
-        unsigned c = mine;
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-        if (lane == 0) sh.wcount[cpar][wave] = c;
-        __syncthreads();
-        for (int w = 0; w < NDT_FEATMATCH_WAVES; w++) n_in += sh.wcount[cpar][w];
-        cpar ^= 1;
-    }
+    ndt_block_sum(m, sh.red, par);
+    const unsigned n_in = ndt_block_count(mine, sh.wcount, cpar);             // (the inlier count)
     if (n_in > 0) {
         const double mpx = m[0] / (double)n_in, mpy = m[1] / (double)n_in, mqx = m[2] / (double)n_in, mqy = m[3] / (double)n_in;
         double ab[2] = {0.0, 0.0};
@@ -341,29 +282,29 @@ __global__ __launch_bounds__(NDT_FEATMATCH_THREADS) void ndt_featmatch_kernel(Nd
                 ab[0] += px * qx + py * qy;
                 ab[1] += px * qy - py * qx;
             }
-        fm_block_sum(ab, sh, par);
+        ndt_block_sum(ab, sh.red, par);
         const double hh = __dsqrt_rn(ab[0] * ab[0] + ab[1] * ab[1]);
         T.c = hh == 0.0 ? 1.0 : ab[0] / hh;
         T.s = hh == 0.0 ? 0.0 : ab[1] / hh;
         T.tx = mqx - (T.c * mpx - T.s * mpy);
         T.ty = mqy - (T.s * mpx + T.c * mpy);
     }
-    double fin[1] = {fm_sweep<true>(sh, n_ref, n_mov, T, prm.acceptance_threshold, tid, NDT_FEATMATCH_THREADS)};
-    fm_block_sum(fin, sh, par);
+    const double mine_fin = fm_sweep<true>(sh, n_ref, n_mov, T, prm.acceptance_threshold, tid, NDT_FEATMATCH_THREADS);
+    const double fin = ndt_block_sum(mine_fin, sh.red, par);
     uint32_t *corr = corr_all ? corr_all + pair * (size_t)MP * 2 : nullptr;
     unsigned n_inliers = 0;
     for (unsigned base = 0; base < n_mov; base += NDT_FEATMATCH_THREADS) {
         const unsigned i = base + tid;
         const bool keep = i < n_mov && sh.inl[i];
         unsigned kept;
-        const unsigned at = n_inliers + fm_block_rank(keep, sh, cpar, kept);
+        const unsigned at = n_inliers + ndt_block_rank(keep, sh.wcount, cpar, kept);
         if (keep && corr) {
             corr[2 * (size_t)at] = i;
             corr[2 * (size_t)at + 1] = sh.nn[i];
         }
         n_inliers += kept;
     }
-    if (tid == 0) fm_write(out, T16, NDTGPU_FEATMATCH_OK, fin[0], T, (int)n_c, H, n_tested, best_h, (int)n_inliers);
+    if (tid == 0) fm_write(out, T16, NDTGPU_FEATMATCH_OK, fin, T, (int)n_c, H, n_tested, best_h, (int)n_inliers);
 }
 
 hipError_t ndt_featmatch_launch(const NdtFeatBankView &v, const uint32_t *ref_idx_dev, const uint32_t *mov_idx_dev, size_t n_pairs,

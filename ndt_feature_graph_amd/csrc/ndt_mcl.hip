@@ -5,8 +5,9 @@
 //
 // Every sum is formed in an order fixed by the handle alone (particle count, chunk size): never by the launch shape, the CU
 // count, the range of filters a call covers or how many filters the handle holds -- a particle's likelihood, weight and pose
-// are the same bits whichever batch it runs in.
+// are the same bits whichever batch it runs in.  The sums over a workgroup are ndt_block.h's, in its order.
 #include "ndt_mcl.h"
+#include "ndt_block.h"
 
 // LazyGrid::getIndexForPoint with the quotient as a product when the cell size is a power of two (the same bits: both are the
 // correctly rounded value of one real number; csrc/ndt_match.hip lazygrid_index_p2)
@@ -17,20 +18,6 @@ NDT_D int mcl_grid_index(double p, double centre, double res, double inv_res, do
     const double v = floor(q + 0.5) + half;
     if (!(v > -2.0e9 && v < 2.0e9)) return -1;
     return (int)v;
-}
-
-// the sum of v over the workgroup, the same on every thread: a fixed shuffle tree per wave, then the waves in order
-template <int NT>
-NDT_D double mcl_block_sum(double v, double *s_red)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const unsigned tid = threadIdx.x;
-    if ((tid & 63u) == 0) s_red[tid >> 6] = v;
-    __syncthreads();
-    double s = s_red[0];
-    for (int w = 1; w < NT / 64; w++) s += s_red[w];
-    __syncthreads();
-    return s;
 }
 
 // initializeFilter: T = Translation(x + sx n0, ..) * AngleAxis(r + sr n3, X) * AngleAxis(p + sp n4, Y) * AngleAxis(t + st n5, Z),
@@ -101,7 +88,7 @@ __global__ __launch_bounds__(NDT_MCL_THREADS) void ndt_mcl_likelihood_kernel(Ndt
 {
 #pragma clang fp contract(off)
     __shared__ double s_cell[9][NDT_MCL_STAGE];
-    __shared__ unsigned s_cnt[NDT_MCL_THREADS / 64];
+    __shared__ NdtBlockCounts<NDT_MCL_THREADS / 64> s_cnt;
     const unsigned per_filter = tiles * n_chunks;
     const unsigned fl = blockIdx.x / per_filter, r = blockIdx.x % per_filter;
     const unsigned tile = r / n_chunks, ck = r % n_chunks;
@@ -166,15 +153,9 @@ __global__ __launch_bounds__(NDT_MCL_THREADS) void ndt_mcl_likelihood_kernel(Ndt
         }
     }
     if (active) partial[((size_t)f * n_chunks + ck) * n_particles + i] = sum;
-    // terms scored: an integer sum (order-free)
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
-    if ((tid & 63u) == 0) s_cnt[tid >> 6] = cnt;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long t = 0;
-        for (int w = 0; w < NDT_MCL_THREADS / 64; w++) t += s_cnt[w];
-        if (t) atomicAdd(&state[f].terms, t);
-    }
+    int par = 0;
+    const unsigned long long t = ndt_block_count(cnt, s_cnt, par);    // terms scored
+    if (tid == 0 && t) atomicAdd(&state[f].terms, t);
 }
 
 // updateAndPredictEff steps 6 (the chunks' sum) - 8, one workgroup per filter: lik, pf.normalize(), varP, the SIR decision and
@@ -190,7 +171,7 @@ __global__ __launch_bounds__(NDT_MCL_NORM_THREADS) void ndt_mcl_normalise_kernel
 {
 #pragma clang fp contract(off)
     constexpr int NT = NDT_MCL_NORM_THREADS;
-    __shared__ double s_red[NT / 64];
+    __shared__ NdtBlockSums<NT / 64, 2> s_red;
     __shared__ long long s_scan[NT];
     __shared__ int s_sir;
     __shared__ double s_u0;
@@ -202,18 +183,19 @@ __global__ __launch_bounds__(NDT_MCL_NORM_THREADS) void ndt_mcl_normalise_kernel
     const unsigned nch = (n_cells + chunk - 1) / chunk;
     const double invN = 1.0 / (double)N;
 
-    double ws = 0.0, ls = 0.0;
+    int par = 0;
+    double wl[2] = {0.0, 0.0};                                    // the sums of the weights and of the likelihoods
     for (unsigned i = tid; i < N; i += NT) {
         double li = 0.0;
         for (unsigned k = 0; k < nch; k++) li += partial[((size_t)f * n_chunks + k) * N + i];
         lik[base + i] = li;
         const double p = w[base + i] * li;
         w[base + i] = p;
-        ws += p;
-        ls += li;
+        wl[0] += p;
+        wl[1] += li;
     }
-    const double S = mcl_block_sum<NT>(ws, s_red);
-    const double lik_sum = mcl_block_sum<NT>(ls, s_red);
+    ndt_block_sum(wl, s_red, par);
+    const double S = wl[0], lik_sum = wl[1];
     double vs = 0.0;
     for (unsigned i = tid; i < N; i += NT) {
         const double p = S > 0.0 ? w[base + i] / S : invN;
@@ -221,7 +203,7 @@ __global__ __launch_bounds__(NDT_MCL_NORM_THREADS) void ndt_mcl_normalise_kernel
         const double d = p - invN;
         vs += d * d;
     }
-    const double var_p = sqrt(mcl_block_sum<NT>(vs, s_red) / (double)N);
+    const double var_p = sqrt(ndt_block_sum(vs, s_red, par) / (double)N);
     if (tid == 0) {
         NdtMclState st = state[f];
         int sir = 0;
@@ -292,10 +274,10 @@ __global__ __launch_bounds__(NDT_MCL_THREADS) void ndt_mcl_mean_kernel(unsigned 
 {
 #pragma clang fp contract(off)
     constexpr int NT = NDT_MCL_THREADS;
-    __shared__ double s_red[NT / 64];
+    __shared__ NdtBlockSums<NT / 64, 9> s_red;
     const unsigned fl = blockIdx.x, f = first + fl, tid = threadIdx.x;
     const size_t base = (size_t)f * n_particles;
-    double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (unsigned i = tid; i < n_particles; i += NT) {
         const rigid P = T[base + i];
         const double p = w[base + i];
@@ -303,13 +285,13 @@ __global__ __launch_bounds__(NDT_MCL_THREADS) void ndt_mcl_mean_kernel(unsigned 
         ndt_rigid_to16(P, P16);
         ndt_euler012(P16, e);
         for (int q = 0; q < 3; q++) {
-            a[q] += p * P.t[q];
-            a[3 + q] += p * cos(e[q]);
-            a[6 + q] += p * sin(e[q]);
+            s[q] += p * P.t[q];
+            s[3 + q] += p * cos(e[q]);
+            s[6 + q] += p * sin(e[q]);
         }
     }
-    double s[9];
-    for (int q = 0; q < 9; q++) s[q] = mcl_block_sum<NT>(a[q], s_red);
+    int par = 0;
+    ndt_block_sum(s, s_red, par);
     if (tid == 0) {
         rigid M;
         ndt_mcl_xyz_rigid(s[0], s[1], s[2], atan2(s[6], s[3]), atan2(s[7], s[4]), atan2(s[8], s[5]), M);

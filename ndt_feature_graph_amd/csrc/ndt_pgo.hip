@@ -5,7 +5,7 @@
 // ndt_pgo_kernel: ONE workgroup of NDT_PGO_THREADS optimises ONE graph from start to finish; `count` graphs are `count`
 // workgroups that never look at each other.  Inside a workgroup only __syncthreads orders the passes: no grid barrier, no
 // queue, no spin on memory, no atomics.  Every sum is taken in one fixed order -- a thread's strided items in ascending order,
-// a butterfly over the wave, the waves' partial sums in ascending order; a node's incident edges in ascending edge order -- so a
+// then over the workgroup in the order of ndt_block.h; a node's incident edges in ascending edge order -- so a
 // graph's result is the same bits whichever batch it runs in.
 //   linearisation (once per Gauss-Newton iteration): a thread per edge (strided) writes c, s, lx, ly -- all that both 3x3
 //     Jacobian blocks hold -- and W e; a thread per node gathers its gradient and its 3x3 diagonal block over the node's
@@ -14,40 +14,9 @@
 // A node is always handled by the same thread, so the vector updates between the passes need no barrier.  The vectors live in a
 // per-graph scratch area in device memory (27 doubles per node, 7 per edge), LDS holds the reductions' partial sums.
 #include "ndt_pgo.h"
+#include "ndt_block.h"
 
-// sums of a and b over the workgroup, in every thread; `red` is used in turn with its other half, so one barrier serves
-__device__ __forceinline__ void pgo_sum2(double &a, double &b, double (*red)[2][NDT_PGO_WAVES], int &par)
-{
-    for (int o = 32; o > 0; o >>= 1) {
-        a += __shfl_xor(a, o);
-        b += __shfl_xor(b, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        red[par][0][threadIdx.x >> 6] = a;
-        red[par][1][threadIdx.x >> 6] = b;
-    }
-    __syncthreads();
-    double sa = 0.0, sb = 0.0;
-    for (int k = 0; k < NDT_PGO_WAVES; k++) {
-        sa += red[par][0][k];
-        sb += red[par][1][k];
-    }
-    a = sa;
-    b = sb;
-    par ^= 1;
-}
-
-// the largest a over the workgroup, in every thread
-__device__ __forceinline__ double pgo_max(double a, double (*red)[2][NDT_PGO_WAVES], int &par)
-{
-    for (int o = 32; o > 0; o >>= 1) a = fmax(a, __shfl_xor(a, o));
-    if ((threadIdx.x & 63) == 0) red[par][0][threadIdx.x >> 6] = a;
-    __syncthreads();
-    double m = 0.0;
-    for (int k = 0; k < NDT_PGO_WAVES; k++) m = fmax(m, red[par][0][k]);
-    par ^= 1;
-    return m;
-}
+typedef NdtBlockSums<NDT_PGO_WAVES, 2> PgoRed;
 
 // y = W x, W symmetric as 6 numbers
 __device__ __forceinline__ void pgo_symv(const double *W, double x0, double x1, double x2, double &y0, double &y1, double &y2)
@@ -95,9 +64,9 @@ __device__ __forceinline__ void pgo_prior_error(const PgoGraph &G, double &e0, d
 
 // per edge: error, Jacobian numbers, W e.  Returns the graph's cost sum e^T W e (prior included) in every thread; its barrier
 // is the one that makes jac / te visible to the gather.
-__device__ double pgo_linearise(const PgoGraph &G, const NdtPgoParamsDev &prm, double (*red)[2][NDT_PGO_WAVES], int &par)
+__device__ double pgo_linearise(const PgoGraph &G, const NdtPgoParamsDev &prm, PgoRed &red, int &par)
 {
-    double cost = 0.0, unused = 0.0;
+    double cost = 0.0;
     if (threadIdx.x == 0) {
         double e0, e1, e2, w0, w1, w2;
         pgo_prior_error(G, e0, e1, e2);
@@ -119,8 +88,7 @@ __device__ double pgo_linearise(const PgoGraph &G, const NdtPgoParamsDev &prm, d
         t[0] = w0; t[1] = w1; t[2] = w2;
         cost += e0 * w0 + e1 * w1 + e2 * w2;
     }
-    pgo_sum2(cost, unused, red, par);
-    return cost;
+    return ndt_block_sum(cost, red, par);
 }
 
 // per node: b = -gradient and the inverse of the 3x3 diagonal block of J^T W J, over the node's incident edges
@@ -165,9 +133,9 @@ __device__ void pgo_gather(const PgoGraph &G, const NdtPgoParamsDev &prm)
 
 // Solves (J^T W J) x = b by preconditioned conjugate gradients from x = 0; returns the iterations taken, `capped` where it
 // stopped at max_linear_iterations with the relative residual still above eps_linear.
-__device__ int pgo_solve(const PgoGraph &G, const NdtPgoParamsDev &prm, double (*red)[2][NDT_PGO_WAVES], int &par, bool &capped)
+__device__ int pgo_solve(const PgoGraph &G, const NdtPgoParamsDev &prm, PgoRed &red, int &par, bool &capped)
 {
-    double rz = 0.0, rr = 0.0;
+    double dot[2] = {0.0, 0.0};                          // r.z and r.r
     for (unsigned i = threadIdx.x; i < G.N; i += NDT_PGO_THREADS) {
         const size_t o = 3 * (size_t)i;
         const double r0 = G.b[o], r1 = G.b[o + 1], r2 = G.b[o + 2];
@@ -176,14 +144,15 @@ __device__ int pgo_solve(const PgoGraph &G, const NdtPgoParamsDev &prm, double (
         G.x[o] = G.x[o + 1] = G.x[o + 2] = 0.0;
         G.r[o] = r0; G.r[o + 1] = r1; G.r[o + 2] = r2;
         G.p[o] = z0; G.p[o + 1] = z1; G.p[o + 2] = z2;
-        rz += r0 * z0 + r1 * z1 + r2 * z2;
-        rr += r0 * r0 + r1 * r1 + r2 * r2;
+        dot[0] += r0 * z0 + r1 * z1 + r2 * z2;
+        dot[1] += r0 * r0 + r1 * r1 + r2 * r2;
     }
-    pgo_sum2(rz, rr, red, par);                          // (its barrier: p is visible to the edge pass)
-    const double tol2 = prm.eps_linear * prm.eps_linear * rr;
+    ndt_block_sum(dot, red, par);                        // (its barrier: p is visible to the edge pass)
+    double rz = dot[0];
+    const double tol2 = prm.eps_linear * prm.eps_linear * dot[1];
     int k = 0;
     capped = false;
-    while (rr > tol2) {
+    while (dot[1] > tol2) {
         if (k >= prm.max_linear_iterations) {
             capped = true;
             break;
@@ -198,7 +167,7 @@ __device__ int pgo_solve(const PgoGraph &G, const NdtPgoParamsDev &prm, double (
             pgo_symv(G.info + 6 * (size_t)e, u0, u1, u2, t[0], t[1], t[2]);
         }
         __syncthreads();
-        double pap = 0.0, unused = 0.0;
+        double pap = 0.0;
         for (unsigned i = threadIdx.x; i < G.N; i += NDT_PGO_THREADS) {
             const size_t o = 3 * (size_t)i;
             double a0 = 0.0, a1 = 0.0, a2 = 0.0;
@@ -218,11 +187,10 @@ __device__ int pgo_solve(const PgoGraph &G, const NdtPgoParamsDev &prm, double (
             G.ap[o] = a0; G.ap[o + 1] = a1; G.ap[o + 2] = a2;
             pap += p0 * a0 + p1 * a1 + p2 * a2;
         }
-        pgo_sum2(pap, unused, red, par);
+        pap = ndt_block_sum(pap, red, par);
         if (!(pap > 0.0)) break;                         // (not positive definite, or not finite: the iterate so far is the step)
         const double alpha = rz / pap;
-        double rz_new = 0.0;
-        rr = 0.0;
+        dot[0] = dot[1] = 0.0;
         for (unsigned i = threadIdx.x; i < G.N; i += NDT_PGO_THREADS) {
             const size_t o = 3 * (size_t)i;
             double r[3], z[3];
@@ -233,12 +201,12 @@ __device__ int pgo_solve(const PgoGraph &G, const NdtPgoParamsDev &prm, double (
             }
             pgo_symv(G.dinv + 6 * (size_t)i, r[0], r[1], r[2], z[0], z[1], z[2]);
             for (int d = 0; d < 3; d++) G.z[o + d] = z[d];
-            rz_new += r[0] * z[0] + r[1] * z[1] + r[2] * z[2];
-            rr += r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+            dot[0] += r[0] * z[0] + r[1] * z[1] + r[2] * z[2];
+            dot[1] += r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
         }
-        pgo_sum2(rz_new, rr, red, par);                  // (its barrier: every edge has read the old p)
-        const double beta = rz_new / rz;
-        rz = rz_new;
+        ndt_block_sum(dot, red, par);                    // (its barrier: every edge has read the old p)
+        const double beta = dot[0] / rz;
+        rz = dot[0];
         for (unsigned i = threadIdx.x; i < G.N; i += NDT_PGO_THREADS) {
             const size_t o = 3 * (size_t)i;
             for (int d = 0; d < 3; d++) G.p[o + d] = G.z[o + d] + beta * G.p[o + d];
@@ -251,7 +219,7 @@ __device__ int pgo_solve(const PgoGraph &G, const NdtPgoParamsDev &prm, double (
 
 __global__ __launch_bounds__(NDT_PGO_THREADS) void ndt_pgo_kernel(NdtPgoView v, size_t first, NdtPgoParamsDev prm)
 {
-    __shared__ double red[2][2][NDT_PGO_WAVES];
+    __shared__ PgoRed red;
     int par = 0;
     const size_t g = first + blockIdx.x;
     ndtgpu_pgo_result *out = v.state + g;
@@ -306,7 +274,7 @@ __global__ __launch_bounds__(NDT_PGO_THREADS) void ndt_pgo_kernel(NdtPgoView v, 
                 G.pose[o + 1] += G.x[o + 1];
                 G.pose[o + 2] = ndt_pgo_wrap(G.pose[o + 2] + G.x[o + 2]);
             }
-            max_step = pgo_max(step, red, par);          // (its barrier: the new poses are visible to the edge pass)
+            max_step = ndt_block_max(step, red, par);    // (its barrier: the new poses are visible to the edge pass)
             iterations++;
             const double cost_new = pgo_linearise(G, prm, red, par);
             if (!(cost_new - cost_new == 0.0)) {         // the step left the finite numbers: back to the last iterate
