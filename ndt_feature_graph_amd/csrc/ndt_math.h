@@ -483,11 +483,13 @@ NDT_HD void ldlt_solve_ws(int n, const double *A, const double *b, double *x, do
 
 // 6x6 version of ldlt_solve with every index a compile-time constant (the matrix lives in registers):
 // the data-dependent pivot only selects which statically indexed swap runs.  Same pivot rule (largest
-// |diagonal| of the remaining block, first one on ties), same elimination and substitution formulas,
-// hence the same arithmetic as ldlt_solve / Eigen's LDLT::solve on a 6x6 system.  Only the lower triangle is
-// stored (21 values): the elimination of the full matrix reads its upper row K, which is the not yet scaled column K
-// by symmetry, and the substitutions only ever read the lower triangle -- same products, same results, a third of
-// the registers.
+// |diagonal| of the remaining block, first one on ties), same elimination and substitution formulas as
+// ldlt_solve / Eigen's LDLT::solve on a 6x6 system.  Only the lower triangle is stored (21 values): the elimination
+// of the full matrix reads its upper row K, which is the not yet scaled column K by symmetry, and the substitutions
+// only ever read the lower triangle -- a third of the registers.  The results are NOT those of ldlt_solve_ws bit for
+// bit: the full-matrix version updates both triangles, with differently rounded products (l * a(K, j) against
+// l(j) * a(i, K)), so the two triangles drift apart by rounding and later pivots and columns see other values.  Both
+// are the same factorisation up to rounding; tests/test_solver_direct.py holds this one to the exact solution.
 // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): loops whose indices are constants from the start.
 // (With `#pragma unroll` the indices only become constants after the unroller has run; by then the optimiser may have
 // merged the branches of a pivot switch into indexed accesses, and the register array goes to the stack.)

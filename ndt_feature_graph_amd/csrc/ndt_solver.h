@@ -204,6 +204,19 @@ NDT_HD int mt_cstep(double &stx, double &fx, double &dx, double &sty, double &fy
     return info;
 }
 
+// step * increment, every product rounded on its own.  The trial pose (mt_request_trial) and the pose apply_step moves to are
+// both pose_to_rigid(step * incr) * T, and final_from_trial / reuse_sums rest on the two being the same bits.  Left to the
+// device compiler the products are contracted into whatever adds them -- the translation of rigid_mul became
+// fma(step, incr, R t) in apply_step and R t + round(step * incr) in mt_request_trial, one ulp apart
+// (tests/test_solver_direct.py, trialpose).  A product computed here has no contraction flag and is fused with nothing --
+// as long as the compiler honours the pragma: hipcc's default, -ffp-contract=fast-honor-pragmas, does (it is what the
+// library and the tests are built with); a build with plain -ffp-contract=fast ignores it, and the two poses may differ again.
+NDT_HD void scaled_increment(const double (&incr)[6], double step, double (&out)[6])
+{
+#pragma clang fp contract(off)
+    for (int a = 0; a < 6; a++) out[a] = step * incr[a];
+}
+
 // head of the More-Thuente while(1) body (fusion.h:523-561): pick the trial step and request its evaluation.
 // A stage of its own (the More-Thuente block is handed over in st.mt): the trial pose costs three rigid transforms
 // in registers.
@@ -236,7 +249,7 @@ NDT_HDN void mt_request_trial(MatchState &st)
         (infoc == 0) || (brackt && (stmax - stmin <= xtol * stmax)))
         stp = stx;
     double pincr[6];
-    for (int a = 0; a < 6; a++) pincr[a] = stp * incr[a];
+    scaled_increment(incr, stp, pincr);
     rigid ps, Te;
     pose_to_rigid(pincr, ps);
     rigid_mul(ps, T, Te);              // trial cells = ps * nextNDT (fusion.h:556-589)
@@ -269,16 +282,14 @@ NDT_HDN void mt_request_trial(MatchState &st)
 NDT_HDN void apply_step(MatchState &st, const NdtMatchParamsDev &prm)
 {
     const double step_size = st.step_size;
-    double incr[6], pl[6];
-    for (int a = 0; a < 6; a++) { incr[a] = st.incr[a]; pl[a] = st.pose_local[a]; }
+    double incr0[6], incr[6], pl[6];
+    for (int a = 0; a < 6; a++) { incr0[a] = st.incr[a]; pl[a] = st.pose_local[a]; }
     const rigid T = st.T;
     const int itr_ctr = st.itr_ctr, itr_max = prm.itr_max;
     const double delta_score = prm.delta_score;
+    scaled_increment(incr0, step_size, incr);
     double inorm = 0;
-    for (int a = 0; a < 6; a++) {
-        incr[a] *= step_size;
-        inorm += incr[a] * incr[a];
-    }
+    for (int a = 0; a < 6; a++) inorm += incr[a] * incr[a];
     inorm = sqrt(inorm);
     for (int a = 0; a < 6; a++) pl[a] += incr[a];   // fusion.h:1045
     rigid TR, Tn;
