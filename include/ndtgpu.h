@@ -950,6 +950,87 @@ ndtgpu_status ndtgpu_world_assemble(ndtgpu_mapset *dst_set, size_t dst_first, si
 ndtgpu_status ndtgpu_world_check(size_t dst_n_maps, double dst_res, size_t dst_first, size_t count, size_t src_n_maps,
                                  double src_res, int same_set, const uint32_t *node_offsets, const uint32_t *node_idx);
 
+/* ---- occupancy-grid export: a map rasterised the way lslgeneric::toOccupancyGrid fills a nav_msgs::OccupancyGrid --------------
+ * What the reference's mapper publishes on a timer, and what navigation stacks and RViz consume (ndt_feature2d_fuser.cpp:428-433:
+ * toOccupancyGrid(graph->getMap(), omap, occ_map_resolution_, world_frame) + moveOccupancyMap(omap, graph->getT()); :450-454 the
+ * same for fuser->map).  ndtgpu_mapset_occupancy_grid* rasterises maps [first, first + count) of a set -- node maps, fused maps,
+ * or a world of ndtgpu_world_assemble -- into int8 grids, one kernel launch for all of them.
+ * Semantics (restated).  A map with centre c, size[] cells per axis of res metres; the pixel size r is occ_resolution:
+ *   - size_m[k] = size[k] * res;  width = (int)(size_m[0] / r), height = (int)(size_m[1] / r);
+ *     origin = (c.x - size_m[0] / 2, c.y - size_m[1] / 2, 0);  data is row-major, data[j * width + i], i along x, j along y.
+ *   - pixel (i, j) is probed at p = (origin.x + (i + 0.5) r, origin.y + (j + 0.5) r, params.z) (params.z 0.0: upstream probes
+ *     pcl::PointXYZ(px, py, 0)), in fp64, not contracted; its cell is LazyGrid::getIndexForPoint(p) -- per axis
+ *     floor((p - c) / res + 0.5) + size / 2.0 truncated to int (csrc/ndt_math.h lazygrid_index_half) with the map's own centre.  A
+ *     point outside the grid gives -1: in z when params.z leaves the grid, and -- LazyGrid's cells are centred on
+ *     c + (k - size / 2) res -- in the last half cell of an axis with an even size, which belongs to no cell.
+ *   - the value of a pixel whose cell has occupancy occ:  occ == 0 (never observed): -1;  occ < 0 (observed free): 0;
+ *     occ > 0 and a Gaussian (mu, Sigma):  l = (p - mu)^T Sigma^-1 (p - mu),  v = 0.5 + 0.5 (exp(-l / 2) + 0.1),
+ *     value = v > 1 ? 100 : (int8)(v * 100), truncated: 55 .. 100;  l not finite: -1;
+ *     occ > 0 and no Gaussian: params.occupied_no_gaussian (100).
+ *   - a set without occupancy arrays (no ndtgpu_mapset_enable_occupancy): a cell with a Gaussian counts as occ > 0, every other
+ *     as occ == 0.  A world of ndtgpu_world_assemble on an occupancy-enabled set holds occ > 0 in touched cells and 0 elsewhere.
+ *   - ndtgpu_occgrid_move is moveOccupancyMap (ros_utils.h:12-18): origin_pose <- T * origin_pose, a 4 x 4 product on the host.  The
+ *     data is not resampled, as in the reference.
+ * PROVENANCE: toOccupancyGrid lives in perception_oru (ndt_map/ndt_conversions.h), which is not part of the reference tree; it is
+ * restated from memory, like NDTCell / NDTMap in SURVEY.md App. A; no program text is copied.  Uncertain in that recollection: what
+ * a cell with occ > 0 and no Gaussian yields (upstream reads the inverse covariance of a cell that has none; a zero matrix gives
+ * v = 1.05, hence 100) -- therefore a parameter.
+ * DEVIATIONS:
+ *   - OURS, pixel count: pixel centres are origin + (i + 0.5) r for exactly width x height pixels.  Upstream advances px += r in a
+ *     floating-point loop, so its pixel count can differ from width * height by a row or a column.
+ *   - OURS, inverse covariance: Sigma^-1 is recomputed from the stored covariance by the adjugate (csrc/ndt_occgrid.h
+ *     ndt_occgrid_inverse), refusing only det <= 0 and a determinant that is not finite (-> -1); upstream keeps V Lambda^-1 V^T from
+ *     rescaleCovariance.  Not the |det| > 1e-12 gate of the matcher's (C_i + C_j)^-1: a wall cell at 0.5 m with eigenvalues
+ *     (0.02, 2e-5, 2e-5) has det 8e-12, and less spread falls below it.
+ *   - a map whose build overflowed max_cells: the synchronous form returns NDTGPU_ERR_CAPACITY like the other readers; the
+ *     asynchronous device form cannot report it and writes -1 to every pixel of that map.
+ * Device form (csrc/ndt_occgrid.hip ndt_occgrid_kernel): grid (tiles of 256 x 4 pixels, map of the call); one lane owns 4 pixels
+ * consecutive in x and writes them as one 32-bit store where the byte address is 4-aligned, with byte stores otherwise (row
+ * tails, rows of a width that is no multiple of 4, a map whose first byte k * width * height is unaligned).  Per pixel one rank-map
+ * word, and where a Gaussian is present its 80-byte cell, inverse, quadratic form and exp.  No atomics, no barriers: the bytes of
+ * a map are the same in any batch and on any call.
+ * Measured on MI355X (tools/occgrid_cost.py, builder-run): the replay's world (5000 node maps assembled into 1360 x 1200 x 2 cells
+ * of 0.5 m, 24 173 Gaussian cells) at 0.1 m (6800 x 6000 = 40.8 M pixels) / 0.05 m (13600 x 12000 = 163.2 M pixels): device form
+ * 0.16 / 0.42 ms (HIP events), host form 13.5 / 49.5 ms (wall: kernel + one copy to pageable memory + the counts); 64 node maps of
+ * 100 x 100 m at 0.05 m (256 M pixels) in one call: 0.58 ms and 75 ms.  The output-write rate is 0.25 / 0.38 / 0.44 TB/s, 4 to 7 %
+ * of the 6.29 TB/s copy ceiling: the kernel is NOT bound by its writes but by the fp64 index arithmetic of every pixel (one IEEE
+ * division each; 99 % of the pixels are empty and cost nothing else).  The route without the call -- ndtgpu_mapset_export_cells + the
+ * NumPy rasteriser of tests/occgrid_model.py -- takes 928 ms for the world at 0.1 m and 77 ms for one node map at 0.05 m on the same
+ * box (69 and 37 times the host form), with no pixel outside the comparison band different. */
+typedef struct {
+    double  z;                       /* height the pixels are probed at (0.0) */
+    int32_t occupied_no_gaussian;    /* value of a cell with occ > 0 and no Gaussian (100); an int8 */
+    int32_t reserved_[5];
+} ndtgpu_occgrid_params;
+void ndtgpu_default_occgrid_params(ndtgpu_occgrid_params *p);
+typedef struct {
+    int32_t width, height;
+    double  resolution;              /* occ_resolution */
+    double  origin[3];               /* of pixel (0, 0)'s lower corner, in the map's frame */
+    int64_t n_unknown, n_free, n_occupied;     /* pixels < 0, == 0, > 0: counted on the host from the copied grid */
+} ndtgpu_occgrid_info;
+/* width, height and origin of the grid of a map with the given geometry: plain numbers, needs no handle and no device (like
+ * ndtgpu_world_check).  NDTGPU_ERR_INVALID: res or occ_resolution not positive and finite, an empty axis, width or height 0,
+ * 2^30 pixels or more along an axis. */
+ndtgpu_status ndtgpu_occgrid_dims(double res, const int32_t cells_per_axis[3], const double centre[3], double occ_resolution,
+                                  int32_t *width, int32_t *height, double origin[3]);
+/* the handle-dependent argument checks of ndtgpu_mapset_occupancy_grid* on plain numbers (the set's map count, the grid's width and
+ * height): needs no handle and no device */
+ndtgpu_status ndtgpu_occgrid_check(size_t n_maps, size_t first, size_t count, int32_t width, int32_t height);
+/* out: `count` grids of width * height bytes back to back, map first + k at out + k * width * height.  prm NULL: the defaults.
+ * NDTGPU_ERR_INVALID before any device work: occ_resolution not finite or <= 0 and a NULL output (both before the device is looked
+ * for and before the handle is read), maps out of range, width or height 0, count * width * height beyond 2^40.
+ * _device: out_dev DEVICE memory; asynchronous on `stream`.  The other form: out_host and info (`count` records, may be NULL)
+ * HOST; works on `stream` and returns when they are complete.  Temporaries are gone on return (ndtgpu_live_resources is
+ * unchanged by a call). */
+ndtgpu_status ndtgpu_mapset_occupancy_grid_device(ndtgpu_mapset *set, size_t first, size_t count, double occ_resolution,
+                                                  const ndtgpu_occgrid_params *prm, int8_t *out_dev, ndtgpu_stream stream);
+ndtgpu_status ndtgpu_mapset_occupancy_grid(ndtgpu_mapset *set, size_t first, size_t count, double occ_resolution,
+                                           const ndtgpu_occgrid_params *prm, int8_t *out_host, ndtgpu_occgrid_info *info,
+                                           ndtgpu_stream stream);
+/* moveOccupancyMap: moved16 = T16 * origin_pose16 (4 x 4, column-major; moved16 may be origin_pose16) */
+void ndtgpu_occgrid_move(const double T16[16], const double origin_pose16[16], double moved16[16]);
+
 /* single pair convenience == graph.cpp:273 */
 ndtgpu_status ndtgpu_match_d2d(ndtgpu_mapset *target_set, size_t target_map, ndtgpu_mapset *source_set,
                                size_t source_map, double T16[16], const ndtgpu_match_params *prm,

@@ -12,7 +12,7 @@ _SO = os.path.join(_HERE, "libndtgpu.so")
 _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hip", "ndt_pack.hip", "ndt_fuser.hip", "ndtgpu_api.hip",
             "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip",
             "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
-            "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip"]
+            "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip", "ndt_occgrid.hip", "ndtgpu_occgrid.hip"]
 
 STATUS = {0: "OK", -1: "ERR_INVALID", -2: "ERR_HIP", -3: "ERR_NO_DEVICE", -4: "ERR_CAPACITY", -5: "ERR_ALLOC"}
 
@@ -144,7 +144,9 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_featbank_match", "ndtgpu_featbank_match_device", "ndtgpu_featbank_results",
            "ndtgpu_default_featextract_params", "ndtgpu_featbank_extract", "ndtgpu_featbank_extract_device",
            "ndtgpu_featbank_extract_results", "ndtgpu_featbank_get",
-           "ndtgpu_default_world_params", "ndtgpu_world_assemble", "ndtgpu_world_check"]
+           "ndtgpu_default_world_params", "ndtgpu_world_assemble", "ndtgpu_world_check",
+           "ndtgpu_default_occgrid_params", "ndtgpu_occgrid_dims", "ndtgpu_mapset_occupancy_grid_device", "ndtgpu_mapset_occupancy_grid",
+           "ndtgpu_occgrid_move", "ndtgpu_occgrid_check"]
 
 _lib = None
 
@@ -292,6 +294,15 @@ def lib():
     L.ndtgpu_default_world_params.argtypes = [C.POINTER(WorldParams)]
     L.ndtgpu_world_assemble.argtypes = [vp, C.c_size_t, C.c_size_t, vp, u32p, u32p, dp, C.POINTER(WorldParams), C.POINTER(WorldResult), vp]
     L.ndtgpu_world_check.argtypes = [C.c_size_t, C.c_double, C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, C.c_int, u32p, u32p]
+    L.ndtgpu_default_occgrid_params.restype = None
+    L.ndtgpu_default_occgrid_params.argtypes = [C.POINTER(OccGridParams)]
+    L.ndtgpu_occgrid_dims.argtypes = [C.c_double, C.POINTER(C.c_int32), dp, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp]
+    L.ndtgpu_mapset_occupancy_grid_device.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(OccGridParams), vp, vp]
+    L.ndtgpu_mapset_occupancy_grid.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(OccGridParams), vp,
+                                               C.POINTER(OccGridInfo), vp]
+    L.ndtgpu_occgrid_check.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32]
+    L.ndtgpu_occgrid_move.restype = None
+    L.ndtgpu_occgrid_move.argtypes = [dp, dp, dp]
     if hasattr(L, "ndtgpu_live_resources"):            # (NDTGPU_LIB may name a build from before this entry existed)
         L.ndtgpu_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
@@ -536,6 +547,37 @@ class MapSet:
     def set_cells(self, i, mean, cov):
         mean, cov = _f64(mean).reshape(-1, 3), _f64(cov).reshape(-1, 3, 3)
         _check(lib().ndtgpu_mapset_set_cells(self.h, int(i), _dp(mean), _dp(cov), mean.shape[0]))
+
+    def occupancy_grid(self, first, count, resolution, z=0.0, occupied_no_gaussian=100, out=None, stream=None):
+        """lslgeneric::toOccupancyGrid of maps [first, first + count) at pixel size `resolution` (ndtgpu_mapset_occupancy_grid):
+        returns (int8 array [count, height, width], info) -- info: one dict per map (width, height, resolution, origin and the
+        counts n_unknown / n_free / n_occupied).  out: a torch CUDA int8 tensor of count * height * width elements takes the
+        device form (ndtgpu_mapset_occupancy_grid_device, asynchronous on `stream`); it is returned, reshaped, instead of an
+        array, and the infos then carry width, height and resolution only (the origin: occupancy_grid_dims with the map's
+        centre)."""
+        p = occgrid_params(z=float(z), occupied_no_gaussian=int(occupied_no_gaussian))
+        first, count = int(first), int(count)
+        cpa = self.info()["cells_per_axis"]
+        w, h, _ = occupancy_grid_dims(self.res, cpa, [0.0, 0.0, 0.0], resolution)
+        _check(lib().ndtgpu_occgrid_check(self.n_maps, first, count, w, h))           # (before anything of that size is allocated)
+        infos = [dict(width=w, height=h, resolution=float(resolution)) for _ in range(count)]
+        if out is not None:
+            import torch
+            assert out.dtype == torch.int8 and out.is_cuda and out.is_contiguous() and out.numel() == count * h * w
+            if stream is None:
+                stream = torch.cuda.current_stream()
+            _check(lib().ndtgpu_mapset_occupancy_grid_device(self.h, first, count, float(resolution), C.byref(p), C.c_void_p(out.data_ptr()),
+                                                             _stream_ptr(stream)))
+            return out.view(count, h, w), infos
+        grid = np.empty((count, h, w), dtype=np.int8)
+        rec = (OccGridInfo * max(count, 1))()
+        buf = grid if grid.size else np.empty(1, dtype=np.int8)          # (never an empty buffer)
+        _check(lib().ndtgpu_mapset_occupancy_grid(self.h, first, count, float(resolution), C.byref(p), C.c_void_p(buf.ctypes.data), rec,
+                                                  _stream_ptr(stream)))
+        for k in range(count):
+            infos[k] = dict(width=rec[k].width, height=rec[k].height, resolution=rec[k].resolution, origin=list(rec[k].origin),
+                            n_unknown=rec[k].n_unknown, n_free=rec[k].n_free, n_occupied=rec[k].n_occupied)
+        return grid, infos
 
 
 def derivatives(target, tmap, src_mean, src_cov, n_neighbours=2, compute_hessian=True, lfd1=1.0, lfd2=0.05):
@@ -1130,6 +1172,46 @@ def assemble_world(dst, dst_first, src, node_lists, T16_lists, params=None, stre
     _check(lib().ndtgpu_world_assemble(dst.h, int(dst_first), count, src.h, off.ctypes.data_as(u32p), idx.ctypes.data_as(u32p), _dp(Tcm),
                                        None if p is None else C.byref(p), res, _stream_ptr(stream)))
     return [{k: getattr(res[w], k) for k, _ in WorldResult._fields_ if k != "pad_"} for w in range(count)]
+
+
+class OccGridParams(C.Structure):
+    _fields_ = [("z", C.c_double), ("occupied_no_gaussian", C.c_int32), ("reserved_", C.c_int32 * 5)]
+
+
+class OccGridInfo(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("resolution", C.c_double), ("origin", C.c_double * 3),
+                ("n_unknown", C.c_int64), ("n_free", C.c_int64), ("n_occupied", C.c_int64)]
+
+
+def occgrid_params(**fields):
+    """ndtgpu_default_occgrid_params with fields replaced"""
+    p = OccGridParams()
+    lib().ndtgpu_default_occgrid_params(C.byref(p))
+    for k, v in fields.items():
+        if not hasattr(p, k) or k == "reserved_":
+            raise TypeError("unknown occupancy-grid parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def occupancy_grid_dims(res, cells_per_axis, centre, resolution):
+    """ndtgpu_occgrid_dims: (width, height, origin[3]) of the occupancy grid of a map of cells_per_axis cells of `res` metres around
+    `centre`, at pixel size `resolution`.  Plain numbers: needs no map set and no device."""
+    cpa = (C.c_int32 * 3)(*[int(x) for x in cells_per_axis])
+    c = _f64(centre).reshape(3)
+    w, h = C.c_int32(), C.c_int32()
+    origin = np.zeros(3)
+    _check(lib().ndtgpu_occgrid_dims(float(res), cpa, _dp(c), float(resolution), C.byref(w), C.byref(h), _dp(origin)))
+    return int(w.value), int(h.value), [float(x) for x in origin]
+
+
+def occupancy_grid_move(T, origin_pose):
+    """ndtgpu_occgrid_move (moveOccupancyMap): T * origin_pose, both 4 x 4"""
+    a = np.ascontiguousarray(_f64(T).reshape(4, 4).T)                   # column-major
+    b = np.ascontiguousarray(_f64(origin_pose).reshape(4, 4).T)
+    m = np.zeros(16)
+    lib().ndtgpu_occgrid_move(_dp(a), _dp(b), _dp(m))
+    return m.reshape(4, 4).T.copy()
 
 
 class FeatMatchParams(C.Structure):
