@@ -1,9 +1,8 @@
 // ndtgpu_registrar.hip -- the registrar of the C-ABI (include/ndtgpu.h): scans in, poses out.
 #include "ndtgpu_host.h"
+#include "ndtgpu_split.h"
 
 #include <atomic>
-#include <chrono>
-#include <thread>
 
 extern "C" {
 
@@ -31,10 +30,38 @@ __global__ void ndt_reg_stats_kernel(const NdtMapCounters *ctr, unsigned n_maps,
     }
 }
 
+// the experiment switches of the submit path: read once, when the registrar is created
+struct RegKnobs {
+    bool verbose = false, trace = false, probe = true, no_helper = false;
+    int gap = 2;
+};
+
+// what a call of ndtgpu_register_batch_device / ndtgpu_register_batch_cov_device (cov_mode 0 / 1; < 0: no covariance) was given
+struct BatchCall {
+    const void *targets_dev, *sources_dev;
+    size_t n_points, stride_bytes, map_stride_bytes;
+    double range_limit;
+    const ndtgpu_cell_params *cell;
+    double *T16_dev;
+    size_t n_pairs;
+    const ndtgpu_match_params *prm;
+    ndtgpu_match_result *results_dev;
+    int cov_mode;
+    double *cov36_dev;
+    int32_t *cov_flags_dev;
+    ndtgpu_stream stream;
+    uint64_t *ticket;
+    NdtMatchParamsDev pdev;            // `prm` in its device form, checked (register_batch_core)
+    bool with_cov() const { return cov_mode >= 0; }
+    double *cov36(size_t off) const { return with_cov() ? cov36_dev + off * 36 : nullptr; }
+    int32_t *cov_flags(size_t off) const { return with_cov() ? cov_flags_dev + off : nullptr; }
+};
+
 struct ndtgpu_registrar {
     size_t per = 0;
     int depth = 0;
     ndtgpu_registrar_params prm{};     // as given to ndtgpu_registrar_create_ex (zeros resolved)
+    RegKnobs knobs;
     std::vector<MapsetOwner> sets;
     std::vector<Fence> built;
     // completion fences, one per sub-batch, in a ring of 4 x depth: sub-batch j records done[j % ring] -- an entry always
@@ -64,18 +91,12 @@ struct ndtgpu_registrar {
     // the split of the chip is measured on a sub-batch and re-measured when the maps change: per slot the map counters of
     // the last build travel to pinned host memory on a side stream; a later call looks at what has arrived (no waiting)
     int calibrations = 0;
-    double calib_cells = 0.0;          // mean Gaussian cells per map the split stands for: of the sub-batch it was first measured
-                                       // on; after a re-measurement, of the recent sub-batches that asked for it (a registrar
-                                       // that is fed two kinds of scenes in turn settles on their mean instead of measuring
-                                       // again at every change)
-    double recal_ref = 0.0;
-    size_t calib_at = 0;               // ... and its number
+    RecalWindow recal;                 // the cells per map the split stands for and those of the last sub-batches seen (ndtgpu_split.h)
     PinnedBuffer<unsigned long long> stat_host; // [depth][2]: {Gaussian cells of the slot's maps, sub-batch + 1} written by a
                                              // one-workgroup kernel behind the build (no copy engine, no event: a device-to-host
                                              // copy per sub-batch cost the pipeline a quarter of its rate, measured)
     std::vector<long long> stat_seq;   // sub-batch whose counters slot k was asked for (-1: none / consumed)
     std::vector<unsigned> stat_maps;
-    std::vector<double> recent_cells;  // mean cells per map of the last sub-batches seen (at most `depth`)
     // host clouds (ndtgpu_register_batch_host): per slot a device staging area for the scans of a sub-batch, one for the
     // poses / results of a call, a copy stream
     std::vector<DeviceBuffer<char>> hstage;
@@ -99,7 +120,30 @@ struct ndtgpu_registrar {
         masked.emplace_back(n_cus, std::move(st));
         return NDTGPU_OK;
     }
+    ndtgpu_status drain(bool ignore_errors = false);
+    ndtgpu_status new_mark(long long seq, ProfMark **out_mark);
+    ndtgpu_status build_pairs(const BatchCall &c, ndtgpu_mapset *set, size_t off, size_t p, hipStream_t st);
+    ndtgpu_status trace_record(size_t j, int end, hipStream_t st);
+    ndtgpu_status poll_map_stats(size_t j, int slot);
+    ndtgpu_status measure_clocks(const BatchCall &c, size_t off, size_t p, size_t j, int slot, hipStream_t st, SplitClocks &clk);
+    ndtgpu_status time_build(const BatchCall &c, size_t off, size_t p, int slot, unsigned groups, double *ms);
+    ndtgpu_status calibrate(const BatchCall &c, size_t off, size_t p, size_t j, int slot, hipStream_t st);
+    ndtgpu_status submit_stream_fed(const BatchCall &c);
+    ndtgpu_status submit_per_batch(const BatchCall &c);
+    ndtgpu_status print_trace();
 };
+
+// The streams of the stream-fed form, waited for by the host -- the ONLY place that lists them: an instance change at submit, a
+// re-measurement, ndtgpu_registrar_sync and (ignoring errors) ndtgpu_registrar_destroy.
+ndtgpu_status ndtgpu_registrar::drain(bool ignore_errors)
+{
+    for (Stream *st : {&bst, &bst2, &pst, &mst, &hst}) {
+        if (!st->get()) continue;
+        const hipError_t e = hipStreamSynchronize(st->get());
+        if (e != hipSuccess && !ignore_errors) return fail(NDTGPU_ERR_HIP, "registrar: hipStreamSynchronize", e);
+    }
+    return NDTGPU_OK;
+}
 
 
 ndtgpu_status ndtgpu_registrar_destroy(ndtgpu_registrar *r)
@@ -107,8 +151,10 @@ ndtgpu_status ndtgpu_registrar_destroy(ndtgpu_registrar *r)
     if (!r) return NDTGPU_OK;
     // every stream drained before the first one goes (a device-side wait on one of them ends with the matcher's progress on another)
     for (Stream &st : r->streams) (void)hipStreamSynchronize(st.get());
-    for (Stream *st : {&r->hcopy, &r->bst, &r->bst2, &r->pst, &r->hst, &r->mst})
-        if (st->get()) (void)hipStreamSynchronize(st->get());
+    if (r->hcopy.get()) (void)hipStreamSynchronize(r->hcopy.get());
+    // (the same streams as before drain() held the list, errors ignored; in drain()'s order, the matcher stream before the
+    //  drain helper's, as ndtgpu_registrar_sync has always waited -- everything is submitted, so the order of the host's waits is free)
+    (void)r->drain(true);
     delete r;
     return NDTGPU_OK;
 }
@@ -160,6 +206,11 @@ ndtgpu_status ndtgpu_registrar_create_ex(const ndtgpu_grid_params *grid, const n
     r->depth = depth;
     r->n_cu = device_cus();
     (void)hipGetDevice(&r->device);
+    r->knobs.verbose = getenv("NDTGPU_REG_VERBOSE") != nullptr;
+    r->knobs.trace = getenv("NDTGPU_REG_TRACE") != nullptr;
+    r->knobs.probe = env_int("NDTGPU_REG_PROBE", 1) != 0;
+    r->knobs.no_helper = getenv("NDTGPU_REG_NO_HELPER") != nullptr;
+    r->knobs.gap = env_int("NDTGPU_REG_GAP", 2);
     r->sets.resize(depth);
     r->streams.resize(depth);
     r->built.resize(depth);
@@ -252,7 +303,7 @@ ndtgpu_status ndtgpu_registrar_get_info(const ndtgpu_registrar *r, ndtgpu_regist
     info->build_streams = r->prm.build_streams;
     info->calibrations = r->calibrations;
     info->submitted = (uint64_t)r->submitted;
-    info->cells_per_map = r->calib_cells;
+    info->cells_per_map = r->recal.calib_cells;
     info->matcher_slots = r->queue.get() ? r->stream_slots : 2;
     info->resident_groups = 0;
     if (r->queue.get()) {                                         // (a 4-byte read on the null stream; the registrar's streams do not block it)
@@ -320,354 +371,293 @@ ndtgpu_status ndtgpu_registrar_kernel_ms(ndtgpu_registrar *r, float mean_ms[2], 
     return NDTGPU_OK;
 }
 
-// ndtgpu_register_batch_device (cov_mode < 0) and ndtgpu_register_batch_cov_device (cov_mode 0 / 1): one code path
-static ndtgpu_status register_batch_core(ndtgpu_registrar *r, const void *targets_dev, const void *sources_dev, size_t n_points,
-                                         size_t stride_bytes, size_t map_stride_bytes, double range_limit,
-                                         const ndtgpu_cell_params *cell, double *T16_dev, size_t n_pairs,
-                                         const ndtgpu_match_params *prm, ndtgpu_match_result *results_dev, ndtgpu_stream stream,
-                                         uint64_t *ticket, int cov_mode, double *cov36_dev, int32_t *cov_flags_dev)
+ndtgpu_status ndtgpu_registrar::new_mark(long long seq, ProfMark **out_mark)
 {
-    if (ticket) *ticket = r ? (uint64_t)r->submitted : 0;
-    if (!r || (n_pairs && (!T16_dev || !results_dev || (n_points && (!targets_dev || !sources_dev)))) || stride_bytes < 12 ||
-        (stride_bytes & 3) || n_points > 0xFFFFFFFFull)
-        return fail(NDTGPU_ERR_INVALID, "register_batch_device: bad argument");
-    const bool with_cov = cov_mode >= 0;
-    if (with_cov && n_pairs && (!cov36_dev || !cov_flags_dev))
-        return fail(NDTGPU_ERR_INVALID, "register_batch_cov_device: bad argument (cov36_dev / cov_flags_dev)");
-    if (n_pairs == 0) return NDTGPU_OK;
-    NdtMatchParamsDev pdev;
-    { ndtgpu_status prc = match_params_dev(prm, 0, pdev); if (prc != NDTGPU_OK) return prc; }
-    HIP_TRY(r->in_ev.record((hipStream_t)stream));
-    auto new_mark = [&](long long seq, ndtgpu_registrar::ProfMark **out_mark) -> ndtgpu_status {
-        ndtgpu_registrar::ProfMark m{};
-        m.seq = seq;
-        for (int k = 0; k < (seq >= 0 ? 2 : 4); k++) HIP_TRY(m.e[k].create(hipEventDefault));
-        r->marks.push_back(std::move(m));
-        *out_mark = &r->marks.back();
-        return NDTGPU_OK;
-    };
-    // one build launch when the sources follow the targets in memory, else two
-    auto build_pairs = [&](ndtgpu_mapset *set, size_t off, size_t p, hipStream_t st) -> ndtgpu_status {
-        const char *tg = (const char *)targets_dev + off * map_stride_bytes, *sc = (const char *)sources_dev + off * map_stride_bytes;
-        if (sc == tg + p * map_stride_bytes)
-            return ndtgpu_mapset_build(set, 0, 2 * p, tg, n_points, stride_bytes, map_stride_bytes, range_limit, nullptr, cell, st);
-        ndtgpu_status rc = ndtgpu_mapset_build(set, 0, p, tg, n_points, stride_bytes, map_stride_bytes, range_limit, nullptr, cell, st);
-        if (rc == NDTGPU_OK)
-            rc = ndtgpu_mapset_build(set, p, p, sc, n_points, stride_bytes, map_stride_bytes, range_limit, nullptr, cell, st);
-        return rc;
-    };
-    if (r->queue.get()) {
-        // ---- stream-fed form: builds on one stream, batches published to the running matcher instance -------------------
-        auto drain = [&]() -> ndtgpu_status {
-            HIP_TRY(hipStreamSynchronize(r->bst.get()));
-            if (r->bst2.get()) HIP_TRY(hipStreamSynchronize(r->bst2.get()));
-            HIP_TRY(hipStreamSynchronize(r->pst.get()));
-            HIP_TRY(hipStreamSynchronize(r->mst.get()));
-            if (r->hst.get()) HIP_TRY(hipStreamSynchronize(r->hst.get()));
-            return NDTGPU_OK;
-        };
-        // (an instance is compiled for one neighbourhood size, and with or without the covariance tail)
-        if (r->stream_nn != pdev.n_neighbours || r->stream_cov != (with_cov ? 1 : 0)) {
-            if (r->stream_nn >= 0) { ndtgpu_status drc = drain(); if (drc != NDTGPU_OK) return drc; }
-            r->stream_nn = pdev.n_neighbours;
-            r->stream_cov = with_cov ? 1 : 0;
-        }
-        for (size_t off = 0; off < n_pairs; off += r->per) {
-            const size_t p = std::min(r->per, n_pairs - off);
-            const size_t j = r->submitted;
-            const int slot = (int)(j % (size_t)r->depth);
-            ndtgpu_mapset *set = r->sets[slot].get();
-            hipStream_t st = (r->bst2.get() && (j & 1u)) ? r->bst2.get() : r->bst.get();
-            // ---- have the maps changed?  The counters of earlier builds that have arrived on the host say how many Gaussian
-            // cells a map holds now; when the mean over the last sub-batches has left the figure the split was measured at by
-            // more than recalibrate_pct, the pipeline is drained once and this sub-batch measures the split again (a
-            // registrar that moves from halls to clutter would otherwise keep 128 matcher CUs where 200 are right).
-            if (r->stat_host.get() && r->stream_groups != 0u) {
-                // (back-pressure: the host runs at most `depth` sub-batches ahead of the builds -- without it a caller that
-                //  never waits would have submitted everything before the first counters arrive)
-                if (j >= (size_t)r->depth) HIP_TRY(r->built[slot].sync());
-                for (int k = 0; k < r->depth; k++) {
-                    volatile unsigned long long *sh = r->stat_host.get() + 2 * k;
-                    if (r->stat_seq[k] < 0 || sh[1] != (unsigned long long)r->stat_seq[k] + 1ull) continue;
-                    std::atomic_thread_fence(std::memory_order_acquire);
-                    if (r->stat_maps[k]) {
-                        if (r->recent_cells.size() >= (size_t)r->depth) r->recent_cells.erase(r->recent_cells.begin());
-                        r->recent_cells.push_back((double)sh[0] / (double)r->stat_maps[k]);
-                    }
-                    r->stat_seq[k] = -1;
-                }
-                if (r->recent_cells.size() >= (size_t)std::min(r->depth, 4) && r->calib_cells > 0 && j >= r->calib_at + 2 * (size_t)r->depth) {
-                    double mean = 0;
-                    for (double v : r->recent_cells) mean += v;
-                    mean /= (double)r->recent_cells.size();
-                    if (std::fabs(mean / r->calib_cells - 1.0) * 100.0 > (double)r->prm.recalibrate_pct) {
-                        if (getenv("NDTGPU_REG_VERBOSE"))
-                            fprintf(stderr, "ndtgpu registrar: %.0f cells per map where the split was measured at %.0f: measuring again\n", mean, r->calib_cells);
-                        ndtgpu_status drc = drain();
-                        if (drc != NDTGPU_OK) return drc;
-                        r->stream_groups = 0u;
-                        r->recal_ref = mean;
-                    }
-                }
-            }
-            HIP_TRY(r->in_ev.order(st));
-            if (r->stream_groups == 0u) {
-                // ---- a sub-batch that measures the split of the chip (the first of a registrar's life; later ones after a
-                // drain, see above): its maps are built and its pairs registered with nothing else on the device (the whole
-                // chip each; the same bits), the host reads the kernels' own clocks -- CU-time of the builds B and of the
-                // registrations M -- and a matcher instance gets n_cu M / (M + B) CUs from then on: 128 of 256 on the bench's
-                // halls, 200 on a cluttered scene whose maps hold five times the cells.  Costs one synchronisation.
-                ndtgpu_registrar::ProfMark *mk0 = nullptr;
-                if (r->profiling) { ndtgpu_status mrc = new_mark(-1, &mk0); if (mrc != NDTGPU_OK) return mrc; HIP_TRY(mk0->e[0].record(st)); }
-                ndtgpu_status rc0 = build_pairs(set, off, p, st);
-                if (rc0 != NDTGPU_OK) return rc0;
-                if (mk0) { HIP_TRY(mk0->e[1].record(st)); HIP_TRY(mk0->e[2].record(st)); }
-                const unsigned saved_groups = set->match_groups;
-                set->match_groups = 0;                            // (the whole chip)
-                rc0 = match_batch_device_ex(set, r->iota.get(), set, r->iota.get() + p, T16_dev + off * 16, p, prm, results_dev + off, st, cov_mode,
-                                            with_cov ? cov36_dev + off * 36 : nullptr, with_cov ? cov_flags_dev + off : nullptr, nullptr);
-                set->match_groups = saved_groups;
-                if (rc0 != NDTGPU_OK) return rc0;
-                if (mk0) HIP_TRY(mk0->e[3].record(st));
-                hipError_t se = ndt_stream_skip(r->queue.get(), (unsigned)j, st);
-                if (se != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: calibration", se);
-                HIP_TRY(r->built[slot].record(st));
-                HIP_TRY(hipStreamSynchronize(st));
-                std::vector<NdtMapCounters> ctr(2 * p);
-                std::vector<ndtgpu_match_result> res(p);
-                HIP_TRY(hipMemcpy(ctr.data(), set->v.counters, 2 * p * sizeof(NdtMapCounters), hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(res.data(), results_dev + off, p * sizeof(ndtgpu_match_result), hipMemcpyDeviceToHost));
-                double B = 0, M = 0, cells = 0;
-                for (const NdtMapCounters &c : ctr) {
-                    B += (double)c.cyc[0] + (double)c.cyc[1] + (double)c.cyc[2] + (double)c.cyc[3];
-                    cells += (double)c.n_cells;
-                }
-                B /= 4.0;                                         // a build workgroup shares its CU with three others
-                // (a clock sum outside any plausible range -- seen once in six runs on the cluttered scene: 2^63 in one result -- is
-                //  left out: the split is a heuristic, one registration does not move it; NDTGPU_REG_VERBOSE reports it)
-                size_t m_bad = 0;
-                for (const ndtgpu_match_result &q : res) {
-                    const bool sane = q.cycles_eval >= 0 && q.cycles_eval < (1ll << 44) && q.cycles_solver >= 0 && q.cycles_solver < (1ll << 44);
-                    if (sane) M += (double)q.cycles_eval + (double)q.cycles_solver / 8.0;
-                    else {
-                        if (getenv("NDTGPU_REG_VERBOSE") && m_bad < 4)
-                            fprintf(stderr, "ndtgpu registrar: calibration result %zu: cycles_eval %lld cycles_solver %lld iterations %d exit %d\n",
-                                    (size_t)(&q - res.data()), (long long)q.cycles_eval, (long long)q.cycles_solver, (int)q.iterations, (int)q.exit_code);
-                        m_bad++;
-                    }
-                }
-                if (m_bad < res.size()) M *= (double)res.size() / (double)(res.size() - m_bad);
-                const double M_raw = M;                           // CU-clocks of the sub-batch's registrations
-                M *= 1.125;                                       // (measured optimum on the bench scene: 144 of 256 CUs where the raw clocks say 138)
-                const int n_cu = r->n_cu;
-                double share = (M + B) > 0 ? M / (M + B) : 0.5;
-                share = std::min(0.9, std::max(0.25, share));
-                r->stream_groups = std::max(8u, ((unsigned)(share * n_cu + 4.0) / 8u) * 8u);
-                // ... refined by what the build side really does with the CUs it is left: a build launch is one workgroup per
-                // map, four to a CU, so on F CUs it takes ceil(maps / 4F) ROUNDS of the mean workgroup time -- 2048 maps take
-                // four rounds on 128 CUs and five on 120, 112 or 104.  Of the splits around the proportional one, take the one
-                // whose slower side is fastest (the bench halls after the round's matcher savings: 136 by proportion, 573 k
-                // registrations/s; 128 by this rule, 624 k; 120: 585 k, 144: 544 k).
-                if (B > 0 && M > 0) {
-                    const double wg = 4.0 * B / (2.0 * (double)p);            // mean clocks of a build workgroup
-                    double best_t = 0;
-                    unsigned best_g = r->stream_groups;
-                    for (int g8 = (int)r->stream_groups - 32; g8 <= (int)r->stream_groups + 32; g8 += 8) {
-                        if (g8 < 16 || g8 > n_cu - 16) continue;
-                        const double slots = 4.0 * (n_cu - g8);
-                        const double t = std::max(M / g8, std::ceil(2.0 * (double)p / slots) * wg);
-                        const bool closer = std::abs(g8 - (int)r->stream_groups) < std::abs((int)best_g - (int)r->stream_groups);
-                        if (best_t == 0 || t < 0.99 * best_t || (t <= 1.01 * best_t && closer && t <= best_t)) { best_t = t; best_g = (unsigned)g8; }
-                    }
-                    r->stream_groups = best_g;
-                }
-                // ... and, since 0.6.5, MEASURED on the build side (round 6).  The clocks above are those of workgroups that had the
-                // whole chip: beside a matcher instance the builds of the bench halls run 20 % faster than that (half as many
-                // workgroups pull on the HBM), those of a cluttered scene 30 % slower (four workgroups to a CU where the lone launch
-                // had three), and a quarter more or less decides between two splits (halls 120 instead of 128 CUs on one box in
-                // three: -5 %; clutter 184 instead of 160: 103 against 127 k registrations/s).  A build launch takes whole rounds,
-                // so the only splits worth having are those that leave the builds just enough CUs for k rounds, k = 1, 2, ...:
-                // the sub-batch is built again on a stream that owns exactly those CUs (Stream::create_cu_mask: mask bits
-                // are dealt to the XCDs in turn, like the CUs a matcher instance leaves), timed with events, and the split whose
-                // slower side -- that time, or the registrations' CU-clocks over the matcher's CUs -- is fastest wins.  A few
-                // build launches, once per measurement; NDTGPU_REG_PROBE=0 keeps the model above.
-                if (B > 0 && M_raw > 0 && env_int("NDTGPU_REG_PROBE", 1) != 0) {
-                    int khz = 0;
-                    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeClockRate, r->device) != hipSuccess || khz <= 0) khz = 2400000;
-                    const double clk_per_ms = 0.85 * (double)khz;              // (the clock under these kernels: 1.93-2.1 of 2.4 GHz)
-                    const size_t maps = 2 * p;
-                    struct Cand { unsigned g; double build_ms, t_ms; };
-                    std::vector<Cand> cand;
-                    auto groups_of = [&](unsigned k) -> unsigned {             // the most matcher CUs that leave the builds k rounds
-                        const unsigned F = (unsigned)((maps + 4u * k - 1u) / (4u * k));
-                        const unsigned F8 = (F + 7u) / 8u * 8u;
-                        return ((unsigned)n_cu > F8 + 15u) ? (unsigned)n_cu - F8 : 0u;
-                    };
-                    auto probe = [&](unsigned g, double *ms) -> ndtgpu_status {
-                        hipStream_t ms_st = nullptr;
-                        ndtgpu_status prc = r->masked_stream((unsigned)n_cu - g, &ms_st);
-                        if (prc != NDTGPU_OK) return prc;
-                        HIP_TRY(r->probe_ev[0].create(hipEventDefault));
-                        HIP_TRY(r->probe_ev[1].create(hipEventDefault));
-                        float best = 0.f;
-                        for (int rep = 0; rep < 2; rep++) {                    // (the first launch on a new stream pays for the stream)
-                            HIP_TRY(r->probe_ev[0].record(ms_st));
-                            prc = build_pairs(set, off, p, ms_st);
-                            if (prc != NDTGPU_OK) return prc;
-                            HIP_TRY(r->probe_ev[1].record(ms_st));
-                            HIP_TRY(r->probe_ev[1].sync());
-                            float e = 0.f;
-                            HIP_TRY(hipEventElapsedTime(&e, r->probe_ev[0].get(), r->probe_ev[1].get()));
-                            if (rep == 0 || e < best) best = e;
-                        }
-                        *ms = (double)best;
-                        return NDTGPU_OK;
-                    };
-                    // the round count the model's split stands for, and its neighbours; further out while the edge keeps winning
-                    unsigned k0 = 1;
-                    for (unsigned k = 1; k <= 16; k++) { k0 = k; if (groups_of(k) >= r->stream_groups) break; }
-                    bool ok = true;
-                    auto have = [&](unsigned g) { for (const Cand &c : cand) if (c.g == g) return true; return false; };
-                    auto add = [&](unsigned k) {
-                        const unsigned g = k >= 1 && k <= 16 ? groups_of(k) : 0u;
-                        if (!ok || g < 16u || have(g)) return;
-                        Cand c{g, 0.0, 0.0};
-                        if (probe(g, &c.build_ms) != NDTGPU_OK) { ok = false; return; }
-                        c.t_ms = std::max(c.build_ms, M_raw / (double)g / clk_per_ms);
-                        cand.push_back(c);
-                    };
-                    auto best_of = [&]() { size_t b = 0; for (size_t i = 1; i < cand.size(); i++) if (cand[i].t_ms < cand[b].t_ms) b = i; return b; };
-                    add(k0); add(k0 > 1 ? k0 - 1 : k0 + 2); add(k0 + 1);
-                    for (int more = 0; ok && more < 3 && !cand.empty(); more++) {
-                        const Cand &b = cand[best_of()];
-                        unsigned kb = 0;
-                        for (unsigned k = 1; k <= 16; k++) if (groups_of(k) == b.g) { kb = k; break; }
-                        const size_t n_before = cand.size();
-                        if (kb > 1 && !have(groups_of(kb - 1))) add(kb - 1);
-                        if (kb && kb < 16 && !have(groups_of(kb + 1))) add(kb + 1);
-                        if (cand.size() == n_before) break;
-                    }
-                    if (ok && !cand.empty()) {
-                        const Cand &b = cand[best_of()];
-                        if (getenv("NDTGPU_REG_VERBOSE"))
-                            for (const Cand &c : cand)
-                                fprintf(stderr, "ndtgpu registrar: %u matcher CUs: builds %.3f ms on the other %u, registrations %.3f ms -> %.3f ms per sub-batch%s\n",
-                                        c.g, c.build_ms, (unsigned)n_cu - c.g, M_raw / (double)c.g / clk_per_ms, c.t_ms, c.g == b.g ? "  <-" : "");
-                        r->stream_groups = b.g;
-                    } else if (!ok) {
-                        (void)hipGetLastError();                               // (no masked streams on this device / runtime: the model's split stands)
-                        g_err.clear();
-                    }
-                    // (the probe streams go at once: each is a hardware queue of its own and of no use until the next measurement;
-                    //  creating them is most of what a measurement costs, ~50 ms with three or four candidates)
-                    r->masked.clear();
-                    HIP_TRY(r->built[slot].record(st));               // (the maps were rebuilt: same contents)
-                }
-                r->calibrations++;
-                // three registrations per workgroup (hit lists of 640 entries per share) where the maps are small -- up to 448 cells: the
-                // one-lane solver steps are a third of a registration there --, two with lists of 1024 entries otherwise (measured
-                // on the cluttered scene: three are slower)
-                if (r->prm.matcher_slots == 0) r->stream_slots = (cells / (double)(2 * p) <= 448.0) ? 3 : 2;
-                r->calib_cells = r->recal_ref > 0 ? r->recal_ref : cells / (double)(2 * p);
-                r->recal_ref = 0.0;
-                r->calib_at = j;
-                r->recent_cells.clear();
-                for (long long &q : r->stat_seq) q = -1;
-                if (getenv("NDTGPU_REG_VERBOSE")) fprintf(stderr, "ndtgpu registrar: build %.3g, registrations %.3g CU-clocks per sub-batch, %.0f cells per map -> matcher instances of %u workgroups\n", B, M, r->calib_cells, r->stream_groups);
-                r->submitted++;
-                if (ticket) *ticket = (uint64_t)r->submitted;
-                continue;
-            }
-            // This map set was last used by sub-batch j - depth: its registrations must be complete before it is rebuilt.
-            // (Depth: a batch is complete 3-5 ms after its publication; with 8 map sets the builds never wait for that, 4 cost
-            //  ~5 % on the bench -- include/ndtgpu.h.)
-            if (j >= (size_t)r->depth) {
-                hipError_t we = ndt_stream_wait(r->queue.get(), (unsigned)r->depth, (unsigned)(j - (size_t)r->depth), st);
-                if (we != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: wait launch", we);
-            }
-            ndtgpu_registrar::ProfMark *mk = nullptr;
-            if (r->profiling) { ndtgpu_status mrc = new_mark((long long)j, &mk); if (mrc != NDTGPU_OK) return mrc; HIP_TRY(mk->e[0].record(st)); }
-            const bool tracing = getenv("NDTGPU_REG_TRACE") != nullptr;
-            if (tracing) {
-                if (r->trace_ev.empty()) {
-                    std::vector<Fence> ev(128);
-                    for (Fence &e : ev) HIP_TRY(e.create(hipEventDefault));
-                    r->trace_ev = std::move(ev);                                      // (all 128 or none)
-                }
-                HIP_TRY(r->trace_ev[2 * (j % 64)].record(st));
-                if (r->trace_first == (size_t)-1) r->trace_first = j;
-            }
-            ndtgpu_status rc = build_pairs(set, off, p, st);
-            if (rc != NDTGPU_OK) return rc;
-            if (tracing) HIP_TRY(r->trace_ev[2 * (j % 64) + 1].record(st));
-            if (mk) HIP_TRY(mk->e[1].record(st));
-            if (r->stat_host.get() && r->stat_seq[slot] < 0 && j % 3u == 0u) {
-                // (how many Gaussian cells the maps of this build hold: one small kernel behind it writes the sum to the host.
-                //  Every third sub-batch: the launch costs the build stream a few microseconds -- 2 % of the bench's rate when
-                //  every sub-batch had one -- and an odd period does not lock onto callers that alternate between two scenes)
-                hipLaunchKernelGGL(ndt_reg_stats_kernel, dim3(1), dim3(256), 0, st, set->v.counters, (unsigned)(2 * p), (unsigned long long)j,
-                                   r->stat_host.get() + 2 * slot);
-                HIP_TRY(hipGetLastError());
-                r->stat_seq[slot] = (long long)j;
-                r->stat_maps[slot] = (unsigned)(2 * p);
-            }
-            HIP_TRY(r->built[slot].record(st));
-            HIP_TRY(r->built[slot].order(r->pst.get()));
-            hipError_t pe = ndt_stream_publish(r->queue.get(), set->v, T16_dev + off * 16, reinterpret_cast<NdtMatchResultDev *>(results_dev + off),
-                                               pdev, (unsigned)p, (unsigned)j, r->pst.get(), with_cov ? cov_mode : -1,
-                                               with_cov ? cov36_dev + off * 36 : nullptr, with_cov ? cov_flags_dev + off : nullptr);
-            if (pe != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: publish", pe);
-            HIP_TRY(r->pub_ev[slot].record(r->pst.get()));
-            // every published batch is followed by an instance launch: it starts when the running instance has ended (and
-            // then serves this batch and whatever is published while it runs), or finds the batch taken and leaves
-            HIP_TRY(r->pub_ev[slot].order(r->mst.get()));
-            pe = ndt_launch_match_stream(r->queue.get(), pdev.n_neighbours, r->stream_slots, r->stream_groups, r->mst.get(), r->stream_cov);
-            if (pe != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: matcher launch", pe);
-            r->submitted++;
-            if (ticket) *ticket = (uint64_t)r->submitted;
-        }
-        return NDTGPU_OK;
+    ProfMark m{};
+    m.seq = seq;
+    for (int k = 0; k < (seq >= 0 ? 2 : 4); k++) HIP_TRY(m.e[k].create(hipEventDefault));
+    marks.push_back(std::move(m));
+    *out_mark = &marks.back();
+    return NDTGPU_OK;
+}
+
+// the maps of the p pairs from `off` on: one build launch when the sources follow the targets in memory, else two
+ndtgpu_status ndtgpu_registrar::build_pairs(const BatchCall &c, ndtgpu_mapset *set, size_t off, size_t p, hipStream_t st)
+{
+    const char *tg = (const char *)c.targets_dev + off * c.map_stride_bytes, *sc = (const char *)c.sources_dev + off * c.map_stride_bytes;
+    if (sc == tg + p * c.map_stride_bytes)
+        return ndtgpu_mapset_build(set, 0, 2 * p, tg, c.n_points, c.stride_bytes, c.map_stride_bytes, c.range_limit, nullptr, c.cell, st);
+    ndtgpu_status rc = ndtgpu_mapset_build(set, 0, p, tg, c.n_points, c.stride_bytes, c.map_stride_bytes, c.range_limit, nullptr, c.cell, st);
+    if (rc == NDTGPU_OK)
+        rc = ndtgpu_mapset_build(set, p, p, sc, c.n_points, c.stride_bytes, c.map_stride_bytes, c.range_limit, nullptr, c.cell, st);
+    return rc;
+}
+
+// NDTGPU_REG_TRACE: the start (end = 0) or the end of sub-batch j's build; the events are made on first use
+ndtgpu_status ndtgpu_registrar::trace_record(size_t j, int end, hipStream_t st)
+{
+    if (trace_ev.empty()) {
+        std::vector<Fence> ev(128);
+        for (Fence &e : ev) HIP_TRY(e.create(hipEventDefault));
+        trace_ev = std::move(ev);                                         // (all 128 or none)
     }
-    if (with_cov && !r->cov_save.get()) {
+    HIP_TRY(trace_ev[2 * (j % 64) + (size_t)end].record(st));
+    if (!end && trace_first == (size_t)-1) trace_first = j;
+    return NDTGPU_OK;
+}
+
+// Have the maps changed?  The counters of earlier builds that have arrived on the host say how many Gaussian cells a map holds
+// now; when the mean over the last sub-batches has left the figure the split was measured at by more than recalibrate_pct
+// (RecalWindow, ndtgpu_split.h), the pipeline is drained once and sub-batch j measures the split again (a registrar that moves
+// from halls to clutter would otherwise keep 128 matcher CUs where 200 are right).
+ndtgpu_status ndtgpu_registrar::poll_map_stats(size_t j, int slot)
+{
+    if (!stat_host.get() || stream_groups == 0u) return NDTGPU_OK;
+    // (back-pressure: the host runs at most `depth` sub-batches ahead of the builds -- without it a caller that
+    //  never waits would have submitted everything before the first counters arrive)
+    if (j >= (size_t)depth) HIP_TRY(built[slot].sync());
+    for (int k = 0; k < depth; k++) {
+        volatile unsigned long long *sh = stat_host.get() + 2 * k;
+        if (stat_seq[k] < 0 || sh[1] != (unsigned long long)stat_seq[k] + 1ull) continue;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        if (stat_maps[k]) recal.sample((double)sh[0] / (double)stat_maps[k], depth);
+        stat_seq[k] = -1;
+    }
+    double mean = 0;
+    if (!recal.should_remeasure(j, depth, prm.recalibrate_pct, &mean)) return NDTGPU_OK;
+    if (knobs.verbose)
+        fprintf(stderr, "ndtgpu registrar: %.0f cells per map where the split was measured at %.0f: measuring again\n", mean, recal.calib_cells);
+    ndtgpu_status drc = drain();
+    if (drc != NDTGPU_OK) return drc;
+    stream_groups = 0u;
+    recal.recal_ref = mean;
+    return NDTGPU_OK;
+}
+
+// The first half of a measurement: sub-batch j's maps are built and its pairs registered on `st` with nothing else on the device
+// (the whole chip each; the same bits), its batch is marked as done in the queue, and the host reads the kernels' own clocks.
+// Costs one synchronisation.
+ndtgpu_status ndtgpu_registrar::measure_clocks(const BatchCall &c, size_t off, size_t p, size_t j, int slot, hipStream_t st, SplitClocks &clk)
+{
+    ndtgpu_mapset *set = sets[slot].get();
+    ProfMark *mk0 = nullptr;
+    if (profiling) { ndtgpu_status mrc = new_mark(-1, &mk0); if (mrc != NDTGPU_OK) return mrc; HIP_TRY(mk0->e[0].record(st)); }
+    ndtgpu_status rc0 = build_pairs(c, set, off, p, st);
+    if (rc0 != NDTGPU_OK) return rc0;
+    if (mk0) { HIP_TRY(mk0->e[1].record(st)); HIP_TRY(mk0->e[2].record(st)); }
+    const unsigned saved_groups = set->match_groups;
+    set->match_groups = 0;                            // (the whole chip)
+    rc0 = match_batch_device_ex(set, iota.get(), set, iota.get() + p, c.T16_dev + off * 16, p, c.prm, c.results_dev + off, st, c.cov_mode,
+                                c.cov36(off), c.cov_flags(off), nullptr);
+    set->match_groups = saved_groups;
+    if (rc0 != NDTGPU_OK) return rc0;
+    if (mk0) HIP_TRY(mk0->e[3].record(st));
+    hipError_t se = ndt_stream_skip(queue.get(), (unsigned)j, st);
+    if (se != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: calibration", se);
+    HIP_TRY(built[slot].record(st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<NdtMapCounters> ctr(2 * p);
+    std::vector<ndtgpu_match_result> res(p);
+    HIP_TRY(hipMemcpy(ctr.data(), set->v.counters, 2 * p * sizeof(NdtMapCounters), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(res.data(), c.results_dev + off, p * sizeof(ndtgpu_match_result), hipMemcpyDeviceToHost));
+    for (const NdtMapCounters &m : ctr) clk.add_map(m.cyc, m.n_cells);
+    for (const ndtgpu_match_result &q : res)
+        if (!clk.add_result((long long)q.cycles_eval, (long long)q.cycles_solver) && knobs.verbose && clk.n_bad <= 4)
+            fprintf(stderr, "ndtgpu registrar: calibration result %zu: cycles_eval %lld cycles_solver %lld iterations %d exit %d\n",
+                    (size_t)(&q - res.data()), (long long)q.cycles_eval, (long long)q.cycles_solver, (int)q.iterations, (int)q.exit_code);
+    clk.finish();
+    return NDTGPU_OK;
+}
+
+// What the builds of the sub-batch take beside `groups` matcher CUs: built again (same maps, same bits) on a stream that owns
+// exactly the other CUs (Stream::create_cu_mask: mask bits are dealt to the XCDs in turn, like the CUs a matcher instance
+// leaves), timed with events.
+ndtgpu_status ndtgpu_registrar::time_build(const BatchCall &c, size_t off, size_t p, int slot, unsigned groups, double *ms)
+{
+    hipStream_t ms_st = nullptr;
+    ndtgpu_status prc = masked_stream((unsigned)n_cu - groups, &ms_st);
+    if (prc != NDTGPU_OK) return prc;
+    HIP_TRY(probe_ev[0].create(hipEventDefault));
+    HIP_TRY(probe_ev[1].create(hipEventDefault));
+    float best = 0.f;
+    for (int rep = 0; rep < 2; rep++) {                    // (the first launch on a new stream pays for the stream)
+        HIP_TRY(probe_ev[0].record(ms_st));
+        prc = build_pairs(c, sets[slot].get(), off, p, ms_st);
+        if (prc != NDTGPU_OK) return prc;
+        HIP_TRY(probe_ev[1].record(ms_st));
+        HIP_TRY(probe_ev[1].sync());
+        float e = 0.f;
+        HIP_TRY(hipEventElapsedTime(&e, probe_ev[0].get(), probe_ev[1].get()));
+        if (rep == 0 || e < best) best = e;
+    }
+    *ms = (double)best;
+    return NDTGPU_OK;
+}
+
+// A sub-batch that measures the split of the chip (the first of a registrar's life; later ones after a drain, poll_map_stats):
+// from the clocks of its kernels -- CU-time of the builds B and of the registrations M -- a matcher instance gets n_cu M / (M + B)
+// CUs from then on, refined by whole build rounds and, since 0.6.5, by timing the builds on the CUs they would be left: 128 of
+// 256 on the bench's halls, 200 on a cluttered scene whose maps hold five times the cells.  Every decision is ndtgpu_split.h's;
+// here is the device work.  A few build launches, once per measurement; NDTGPU_REG_PROBE=0 keeps the model.
+ndtgpu_status ndtgpu_registrar::calibrate(const BatchCall &c, size_t off, size_t p, size_t j, int slot, hipStream_t st)
+{
+    SplitClocks clk;
+    ndtgpu_status rc = measure_clocks(c, off, p, j, slot, st, clk);
+    if (rc != NDTGPU_OK) return rc;
+    stream_groups = split_model(clk.B, clk.M_raw, p, n_cu);
+    if (clk.B > 0 && clk.M_raw > 0 && knobs.probe) {
+        int khz = 0;
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeClockRate, device) != hipSuccess) khz = 0;
+        const SplitSearch s = split_probe_search(stream_groups, 2 * p, n_cu, clk.M_raw, split_clk_per_ms(khz),
+                                                 [&](unsigned g, double *ms) { return time_build(c, off, p, slot, g, ms) == NDTGPU_OK; });
+        if (!s.ok) {
+            (void)hipGetLastError();                               // (no masked streams on this device / runtime: the model's split stands)
+            g_err.clear();
+        } else if (knobs.verbose) {
+            for (const SplitCand &q : s.cand)
+                fprintf(stderr, "ndtgpu registrar: %u matcher CUs: builds %.3f ms on the other %u, registrations %.3f ms -> %.3f ms per sub-batch%s\n",
+                        q.g, q.build_ms, (unsigned)n_cu - q.g, q.match_ms, q.t_ms, q.g == s.groups ? "  <-" : "");
+        }
+        stream_groups = s.groups;
+        // (the probe streams go at once: each is a hardware queue of its own and of no use until the next measurement;
+        //  creating them is most of what a measurement costs, ~50 ms with three or four candidates)
+        masked.clear();
+        HIP_TRY(built[slot].record(st));               // (the maps were rebuilt: same contents)
+    }
+    calibrations++;
+    const double cells_per_map = split_cells_per_map(clk.cells, p);
+    if (prm.matcher_slots == 0) stream_slots = split_slots(cells_per_map);
+    recal.measured(cells_per_map, j);
+    for (long long &q : stat_seq) q = -1;
+    if (knobs.verbose)
+        fprintf(stderr, "ndtgpu registrar: build %.3g, registrations %.3g CU-clocks per sub-batch, %.0f cells per map -> matcher instances of %u workgroups\n",
+                clk.B, split_matcher_clocks(clk.M_raw), recal.calib_cells, stream_groups);
+    return NDTGPU_OK;
+}
+
+// Stream-fed form: builds on two streams in turn, batches published in order to the running matcher instance.
+ndtgpu_status ndtgpu_registrar::submit_stream_fed(const BatchCall &c)
+{
+    // (an instance is compiled for one neighbourhood size, and with or without the covariance tail)
+    if (stream_nn != c.pdev.n_neighbours || stream_cov != (c.with_cov() ? 1 : 0)) {
+        if (stream_nn >= 0) { ndtgpu_status drc = drain(); if (drc != NDTGPU_OK) return drc; }
+        stream_nn = c.pdev.n_neighbours;
+        stream_cov = c.with_cov() ? 1 : 0;
+    }
+    for (size_t off = 0; off < c.n_pairs; off += per) {
+        const size_t p = std::min(per, c.n_pairs - off);
+        const size_t j = submitted;
+        const int slot = (int)(j % (size_t)depth);
+        ndtgpu_mapset *set = sets[slot].get();
+        hipStream_t st = (bst2.get() && (j & 1u)) ? bst2.get() : bst.get();
+        ndtgpu_status rc = poll_map_stats(j, slot);
+        if (rc != NDTGPU_OK) return rc;
+        HIP_TRY(in_ev.order(st));
+        if (stream_groups == 0u) {
+            rc = calibrate(c, off, p, j, slot, st);
+            if (rc != NDTGPU_OK) return rc;
+            submitted++;
+            if (c.ticket) *c.ticket = (uint64_t)submitted;
+            continue;
+        }
+        // This map set was last used by sub-batch j - depth: its registrations must be complete before it is rebuilt.
+        // (Depth: a batch is complete 3-5 ms after its publication; with 8 map sets the builds never wait for that, 4 cost
+        //  ~5 % on the bench -- include/ndtgpu.h.)
+        if (j >= (size_t)depth) {
+            hipError_t we = ndt_stream_wait(queue.get(), (unsigned)depth, (unsigned)(j - (size_t)depth), st);
+            if (we != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: wait launch", we);
+        }
+        ProfMark *mk = nullptr;
+        if (profiling) { ndtgpu_status mrc = new_mark((long long)j, &mk); if (mrc != NDTGPU_OK) return mrc; HIP_TRY(mk->e[0].record(st)); }
+        if (knobs.trace) { rc = trace_record(j, 0, st); if (rc != NDTGPU_OK) return rc; }
+        rc = build_pairs(c, set, off, p, st);
+        if (rc != NDTGPU_OK) return rc;
+        if (knobs.trace) { rc = trace_record(j, 1, st); if (rc != NDTGPU_OK) return rc; }
+        if (mk) HIP_TRY(mk->e[1].record(st));
+        if (stat_host.get() && stat_seq[slot] < 0 && j % 3u == 0u) {
+            // (how many Gaussian cells the maps of this build hold: one small kernel behind it writes the sum to the host.
+            //  Every third sub-batch: the launch costs the build stream a few microseconds -- 2 % of the bench's rate when
+            //  every sub-batch had one -- and an odd period does not lock onto callers that alternate between two scenes)
+            hipLaunchKernelGGL(ndt_reg_stats_kernel, dim3(1), dim3(256), 0, st, set->v.counters, (unsigned)(2 * p), (unsigned long long)j,
+                               stat_host.get() + 2 * slot);
+            HIP_TRY(hipGetLastError());
+            stat_seq[slot] = (long long)j;
+            stat_maps[slot] = (unsigned)(2 * p);
+        }
+        HIP_TRY(built[slot].record(st));
+        HIP_TRY(built[slot].order(pst.get()));
+        hipError_t pe = ndt_stream_publish(queue.get(), set->v, c.T16_dev + off * 16, reinterpret_cast<NdtMatchResultDev *>(c.results_dev + off),
+                                           c.pdev, (unsigned)p, (unsigned)j, pst.get(), c.with_cov() ? c.cov_mode : -1, c.cov36(off),
+                                           c.cov_flags(off));
+        if (pe != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: publish", pe);
+        HIP_TRY(pub_ev[slot].record(pst.get()));
+        // every published batch is followed by an instance launch: it starts when the running instance has ended (and
+        // then serves this batch and whatever is published while it runs), or finds the batch taken and leaves
+        HIP_TRY(pub_ev[slot].order(mst.get()));
+        pe = ndt_launch_match_stream(queue.get(), c.pdev.n_neighbours, stream_slots, stream_groups, mst.get(), stream_cov);
+        if (pe != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: matcher launch", pe);
+        submitted++;
+        if (c.ticket) *c.ticket = (uint64_t)submitted;
+    }
+    return NDTGPU_OK;
+}
+
+// One matcher launch per sub-batch, on the stream of the sub-batch's map set.
+ndtgpu_status ndtgpu_registrar::submit_per_batch(const BatchCall &c)
+{
+    if (c.with_cov() && !cov_save.get()) {
         // (only grid-barrier / pool sub-batches read it -- sets of large maps, at most half as many pairs as CUs.  Made once and
         //  never replaced: nothing to wait for)
-        const size_t n = std::min(r->per, (size_t)r->n_cu);
-        HIP_TRY(r->cov_save.reserve((size_t)r->depth * n * 16));
-        r->cov_save_pairs = n;
+        const size_t n = std::min(per, (size_t)n_cu);
+        HIP_TRY(cov_save.reserve((size_t)depth * n * 16));
+        cov_save_pairs = n;
     }
-    for (size_t off = 0; off < n_pairs; off += r->per) {
-        const size_t p = std::min(r->per, n_pairs - off);
-        const int slot = (int)(r->submitted % (size_t)r->depth);
-        hipStream_t st = r->streams[slot].get();
-        ndtgpu_mapset *set = r->sets[slot].get();
-        HIP_TRY(r->in_ev.order(st));
-        if (r->last_built >= 0 && r->last_built != slot) HIP_TRY(r->built[r->last_built].order(st));
-        ndtgpu_registrar::ProfMark *mk = nullptr;
-        if (r->profiling) { ndtgpu_status mrc = new_mark(-1, &mk); if (mrc != NDTGPU_OK) return mrc; HIP_TRY(mk->e[0].record(st)); }
-        ndtgpu_status rc = build_pairs(set, off, p, st);
+    for (size_t off = 0; off < c.n_pairs; off += per) {
+        const size_t p = std::min(per, c.n_pairs - off);
+        const int slot = (int)(submitted % (size_t)depth);
+        hipStream_t st = streams[slot].get();
+        ndtgpu_mapset *set = sets[slot].get();
+        HIP_TRY(in_ev.order(st));
+        if (last_built >= 0 && last_built != slot) HIP_TRY(built[last_built].order(st));
+        ProfMark *mk = nullptr;
+        if (profiling) { ndtgpu_status mrc = new_mark(-1, &mk); if (mrc != NDTGPU_OK) return mrc; HIP_TRY(mk->e[0].record(st)); }
+        ndtgpu_status rc = build_pairs(c, set, off, p, st);
         if (rc != NDTGPU_OK) return rc;
         if (mk) { HIP_TRY(mk->e[1].record(st)); HIP_TRY(mk->e[2].record(st)); }
-        HIP_TRY(r->built[slot].record(st));
-        r->last_built = slot;
+        HIP_TRY(built[slot].record(st));
+        last_built = slot;
         // `built` releases the next sub-batch's build AND, on this stream, this sub-batch's matcher.  The matcher's persistent
         // workgroups (one per CU, all registers and LDS of it) must not be placed first: the build would then only get the CUs
         // the matcher leaves, its end -- which releases the build after it -- moves out, and the pipeline loses a tenth of its
         // rate (measured: 430 k against 470 k registrations/s).  Two 4-byte fills keep this stream busy for the few
         // microseconds the next build's dispatch needs to get ahead (NDTGPU_REG_GAP: their number).
-        if (r->depth > 1) {
-            const int n_gap = env_int("NDTGPU_REG_GAP", 2);
-            for (int g = 0; g < n_gap; g++) HIP_TRY(hipMemsetAsync(r->iota.get() + 2 * r->per, 0, 4, st));
-        }
-        rc = match_batch_device_ex(set, r->iota.get(), set, r->iota.get() + p, T16_dev + off * 16, p, prm, results_dev + off, st, cov_mode,
-                                   with_cov ? cov36_dev + off * 36 : nullptr, with_cov ? cov_flags_dev + off : nullptr,
-                                   with_cov && p <= r->cov_save_pairs ? r->cov_save.get() + (size_t)slot * r->cov_save_pairs * 16 : nullptr);
+        if (depth > 1)
+            for (int g = 0; g < knobs.gap; g++) HIP_TRY(hipMemsetAsync(iota.get() + 2 * per, 0, 4, st));
+        rc = match_batch_device_ex(set, iota.get(), set, iota.get() + p, c.T16_dev + off * 16, p, c.prm, c.results_dev + off, st, c.cov_mode,
+                                   c.cov36(off), c.cov_flags(off),
+                                   c.with_cov() && p <= cov_save_pairs ? cov_save.get() + (size_t)slot * cov_save_pairs * 16 : nullptr);
         if (rc != NDTGPU_OK) return rc;
         if (mk) HIP_TRY(mk->e[3].record(st));
-        HIP_TRY(r->done[r->submitted % r->done.size()].record(st));
-        r->submitted++;
-        if (ticket) *ticket = (uint64_t)r->submitted;      // "every sub-batch before this count"
+        HIP_TRY(done[submitted % done.size()].record(st));
+        submitted++;
+        if (c.ticket) *c.ticket = (uint64_t)submitted;      // "every sub-batch before this count"
     }
     return NDTGPU_OK;
+}
+
+// ndtgpu_register_batch_device (cov_mode < 0) and ndtgpu_register_batch_cov_device (cov_mode 0 / 1): one code path
+static ndtgpu_status register_batch_core(ndtgpu_registrar *r, BatchCall &c)
+{
+    if (c.ticket) *c.ticket = r ? (uint64_t)r->submitted : 0;
+    if (!r || (c.n_pairs && (!c.T16_dev || !c.results_dev || (c.n_points && (!c.targets_dev || !c.sources_dev)))) || c.stride_bytes < 12 ||
+        (c.stride_bytes & 3) || c.n_points > 0xFFFFFFFFull)
+        return fail(NDTGPU_ERR_INVALID, "register_batch_device: bad argument");
+    if (c.with_cov() && c.n_pairs && (!c.cov36_dev || !c.cov_flags_dev))
+        return fail(NDTGPU_ERR_INVALID, "register_batch_cov_device: bad argument (cov36_dev / cov_flags_dev)");
+    if (c.n_pairs == 0) return NDTGPU_OK;
+    { ndtgpu_status prc = match_params_dev(c.prm, 0, c.pdev); if (prc != NDTGPU_OK) return prc; }
+    HIP_TRY(r->in_ev.record((hipStream_t)c.stream));
+    return r->queue.get() ? r->submit_stream_fed(c) : r->submit_per_batch(c);
 }
 
 ndtgpu_status ndtgpu_register_batch_device(ndtgpu_registrar *r, const void *targets_dev, const void *sources_dev, size_t n_points,
@@ -676,8 +666,9 @@ ndtgpu_status ndtgpu_register_batch_device(ndtgpu_registrar *r, const void *targ
                                            const ndtgpu_match_params *prm, ndtgpu_match_result *results_dev, ndtgpu_stream stream,
                                            uint64_t *ticket)
 {
-    return register_batch_core(r, targets_dev, sources_dev, n_points, stride_bytes, map_stride_bytes, range_limit, cell, T16_dev, n_pairs,
-                               prm, results_dev, stream, ticket, -1, nullptr, nullptr);
+    BatchCall c{targets_dev, sources_dev, n_points, stride_bytes, map_stride_bytes, range_limit, cell, T16_dev, n_pairs, prm, results_dev,
+                -1, nullptr, nullptr, stream, ticket, {}};
+    return register_batch_core(r, c);
 }
 
 ndtgpu_status ndtgpu_register_batch_cov_device(ndtgpu_registrar *r, const void *targets_dev, const void *sources_dev, size_t n_points,
@@ -690,8 +681,9 @@ ndtgpu_status ndtgpu_register_batch_cov_device(ndtgpu_registrar *r, const void *
         if (ticket) *ticket = r ? (uint64_t)r->submitted : 0;
         return fail(NDTGPU_ERR_INVALID, "register_batch_cov_device: covariance_mode must be 0 or 1");
     }
-    return register_batch_core(r, targets_dev, sources_dev, n_points, stride_bytes, map_stride_bytes, range_limit, cell, T16_dev, n_pairs,
-                               prm, results_dev, stream, ticket, covariance_mode, cov36_dev, cov_flags_dev);
+    BatchCall c{targets_dev, sources_dev, n_points, stride_bytes, map_stride_bytes, range_limit, cell, T16_dev, n_pairs, prm, results_dev,
+                covariance_mode, cov36_dev, cov_flags_dev, stream, ticket, {}};
+    return register_batch_core(r, c);
 }
 
 ndtgpu_status ndtgpu_registrar_wait_stream(ndtgpu_registrar *r, uint64_t ticket, ndtgpu_stream stream)
@@ -721,6 +713,31 @@ ndtgpu_status ndtgpu_registrar_wait_stream(ndtgpu_registrar *r, uint64_t ticket,
     return NDTGPU_OK;
 }
 
+// NDTGPU_REG_TRACE, at a sync: what the queue and the trace events saw of the last batches
+ndtgpu_status ndtgpu_registrar::print_trace()
+{
+    // (experiments: when the last batches were published -- their maps built -- and when their last registration finished,
+    //  in microseconds after the first of them)
+    const size_t nb = std::min<size_t>(submitted, ndt_stream_stamps());
+    unsigned long long t0 = 0;
+    for (size_t k = submitted - nb; k < submitted; k++) {
+        unsigned long long st[2] = {0, 0};
+        HIP_TRY(ndt_stream_read_stamps(queue.get(), (unsigned)k, st));
+        if (!t0) t0 = st[0];
+        float b0 = 0.f, b1 = 0.f;          // the build's start and end, against the end of the first listed build (~ its publication)
+        const size_t kref = std::max(submitted - nb, trace_first);
+        if (!trace_ev.empty() && k >= kref) {
+            (void)hipEventElapsedTime(&b0, trace_ev[2 * (kref % 64) + 1].get(), trace_ev[2 * (k % 64)].get());
+            (void)hipEventElapsedTime(&b1, trace_ev[2 * (kref % 64) + 1].get(), trace_ev[2 * (k % 64) + 1].get());
+            (void)hipGetLastError();
+        }
+        if (k == kref) t0 = st[0];
+        fprintf(stderr, "[ndtgpu trace] batch %zu build %+.1f .. %+.1f us, published %+.1f us, done %+.1f us\n", k, 1e3 * b0, 1e3 * b1,
+                ((double)st[0] - (double)t0) * 0.01, ((double)st[1] - (double)t0) * 0.01);
+    }
+    return NDTGPU_OK;
+}
+
 ndtgpu_status ndtgpu_registrar_sync(ndtgpu_registrar *r)
 {
     if (!r) return fail(NDTGPU_ERR_INVALID, "registrar_sync: null");
@@ -732,7 +749,7 @@ ndtgpu_status ndtgpu_registrar_sync(ndtgpu_registrar *r)
             hipError_t fe = ndt_stream_final(r->queue.get(), (unsigned)r->submitted, r->pst.get());
             if (fe != hipSuccess) return fail(NDTGPU_ERR_HIP, "registrar: final launch", fe);
         }
-        if (r->submitted > r->helped && r->stream_groups && r->stream_nn >= 0 && !getenv("NDTGPU_REG_NO_HELPER")) {
+        if (r->submitted > r->helped && r->stream_groups && r->stream_nn >= 0 && !r->knobs.no_helper) {
             const int n_cu = r->n_cu;
             if ((unsigned)n_cu > r->stream_groups + 8u) {
                 if (!r->hst.get()) HIP_TRY(r->hst.create(hipStreamNonBlocking));
@@ -743,32 +760,9 @@ ndtgpu_status ndtgpu_registrar_sync(ndtgpu_registrar *r)
             }
             r->helped = r->submitted;
         }
-        HIP_TRY(hipStreamSynchronize(r->bst.get()));
-        if (r->bst2.get()) HIP_TRY(hipStreamSynchronize(r->bst2.get()));
-        HIP_TRY(hipStreamSynchronize(r->pst.get()));
-        HIP_TRY(hipStreamSynchronize(r->mst.get()));
-        if (r->hst.get()) HIP_TRY(hipStreamSynchronize(r->hst.get()));
-        if (getenv("NDTGPU_REG_TRACE") && r->submitted) {
-            // (experiments: when the last batches were published -- their maps built -- and when their last registration finished,
-            //  in microseconds after the first of them)
-            const size_t nb = std::min<size_t>(r->submitted, ndt_stream_stamps());
-            unsigned long long t0 = 0;
-            for (size_t k = r->submitted - nb; k < r->submitted; k++) {
-                unsigned long long st[2] = {0, 0};
-                HIP_TRY(ndt_stream_read_stamps(r->queue.get(), (unsigned)k, st));
-                if (!t0) t0 = st[0];
-                float b0 = 0.f, b1 = 0.f;          // the build's start and end, against the end of the first listed build (~ its publication)
-                const size_t kref = std::max(r->submitted - nb, r->trace_first);
-                if (!r->trace_ev.empty() && k >= kref) {
-                    (void)hipEventElapsedTime(&b0, r->trace_ev[2 * (kref % 64) + 1].get(), r->trace_ev[2 * (k % 64)].get());
-                    (void)hipEventElapsedTime(&b1, r->trace_ev[2 * (kref % 64) + 1].get(), r->trace_ev[2 * (k % 64) + 1].get());
-                    (void)hipGetLastError();
-                }
-                if (k == kref) t0 = st[0];
-                fprintf(stderr, "[ndtgpu trace] batch %zu build %+.1f .. %+.1f us, published %+.1f us, done %+.1f us\n", k, 1e3 * b0, 1e3 * b1,
-                        ((double)st[0] - (double)t0) * 0.01, ((double)st[1] - (double)t0) * 0.01);
-            }
-        }
+        ndtgpu_status drc = r->drain();
+        if (drc != NDTGPU_OK) return drc;
+        if (r->knobs.trace && r->submitted) { drc = r->print_trace(); if (drc != NDTGPU_OK) return drc; }
         unsigned aborted = 0;
         HIP_TRY(hipMemcpy(&aborted, r->queue.get() + ndt_stream_abort_offset(), sizeof aborted, hipMemcpyDeviceToHost));
         if (aborted) {
@@ -838,9 +832,9 @@ static ndtgpu_status register_batch_host_core(ndtgpu_registrar *r, const void *t
             HIP_TRY(hipMemcpyAsync(sc, (const char *)sources_host + off * map_stride_bytes, half, hipMemcpyHostToDevice, r->hcopy.get()));
         }
         // (p <= pairs_per_batch: ONE sub-batch, in this slot, behind these copies)
-        ndtgpu_status rc = register_batch_core(r, tg, sc, n_points, stride_bytes, map_stride_bytes, range_limit, cell, T_dev + off * 16, p,
-                                               prm, R_dev + off, (ndtgpu_stream)r->hcopy.get(), nullptr, cov_mode,
-                                               with_cov ? C_dev + off * 36 : nullptr, with_cov ? F_dev + off : nullptr);
+        BatchCall c{tg, sc, n_points, stride_bytes, map_stride_bytes, range_limit, cell, T_dev + off * 16, p, prm, R_dev + off,
+                    cov_mode, with_cov ? C_dev + off * 36 : nullptr, with_cov ? F_dev + off : nullptr, (ndtgpu_stream)r->hcopy.get(), nullptr, {}};
+        ndtgpu_status rc = register_batch_core(r, c);
         if (rc != NDTGPU_OK) return rc;
     }
     ndtgpu_status rc = ndtgpu_registrar_sync(r);
