@@ -216,7 +216,7 @@ template <int STRIDE_DW, int MODE, bool NICE, bool SCAT>
 __global__ __launch_bounds__((MODE == 2 || MODE == 3) ? NDT_FIN_THREADS : NDT_BUILD_THREADS) NDT_BUILD_WPE void ndt_build_kernel(
     NdtSetView set, unsigned first, const char *__restrict__ xyz, unsigned n_points, unsigned stride_bytes,
     size_t map_stride_bytes, double range_limit, const double *__restrict__ range_origins, int n_min,
-    double eval_factor, int s1_shift, int s2_shift, int dbg, float z_max32)
+    double eval_factor, double floor_m2, int s1_shift, int s2_shift, int dbg, float z_max32)
 {
     constexpr int SD = STRIDE_DW ? STRIDE_DW : 3;
     constexpr int LANE_DW = NDT_PPL * SD + 1;          // +1: odd stride -> conflict-free per-lane walks
@@ -701,7 +701,7 @@ __global__ __launch_bounds__((MODE == 2 || MODE == 3) ? NDT_FIN_THREADS : NDT_BU
         const unsigned slot = n ? slot_of_id : 0u;
         const int iz = slot % g.size[2], iy = (slot / g.size[2]) % g.size[1], ix = slot / (g.size[2] * g.size[1]);
         const double centre[3] = {cx + (ix - hx) * res, cy + (iy - hy) * res, cz + (iz - hz) * res};
-        const NdtCell c = ndt_gaussian_from_moments(a, slot, centre, res, n_min, eval_factor, IS1, IS2);
+        const NdtCell c = ndt_gaussian_from_moments(a, slot, centre, res, n_min, eval_factor, IS1, IS2, floor_m2);
         *reinterpret_cast<NdtCell *>(tmp_base + id) = c;
         // a touched cell without a Gaussian leaves the occupancy bitmap here, so that phase C finds exactly the
         // Gaussian cells in it (n == 0: an id wasted by an allocation race, it has no slot)
@@ -1201,7 +1201,7 @@ hipError_t ndt_launch_build(const NdtSetView &set, size_t first, size_t count, c
 #define NDT_LAUNCH_BUILD_V(SDW, MODE, NICE_, SCAT_, GRID)                                                            \
     hipLaunchKernelGGL((ndt_build_kernel<SDW, MODE, NICE_, SCAT_>), GRID, dim3(NDT_BUILD_THREADS), 0, stream, set,   \
                        (unsigned)first, (const char *)xyz_dev, (unsigned)n_points, (unsigned)stride_bytes,           \
-                       map_stride_bytes, range_limit, range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, dbg, \
+                       map_stride_bytes, range_limit, range_origins_dev, n_min, eval_factor, ndt_first_gaussian_floor(set.grid.res, s1_shift, s2_shift), s1_shift, s2_shift, dbg, \
                        __builtin_inff())
 #define NDT_LAUNCH_BUILD(SDW, MODE, GRID)                                                                            \
     do {                                                                                                             \
@@ -1248,7 +1248,7 @@ hipError_t ndt_launch_build(const NdtSetView &set, size_t first, size_t count, c
         const int split_rank = (fin_parts > 1u && bm_words >= 16384u) ? 1 : 0;
         hipLaunchKernelGGL((ndt_build_kernel<0, 2, false, false>), dim3(fin_parts, (unsigned)count), dim3(NDT_FIN_THREADS), 0, stream,
                            set, (unsigned)first, (const char *)xyz_dev, (unsigned)n_points, (unsigned)stride_bytes,
-                           map_stride_bytes, range_limit, range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, split_rank,
+                           map_stride_bytes, range_limit, range_origins_dev, n_min, eval_factor, ndt_first_gaussian_floor(set.grid.res, s1_shift, s2_shift), s1_shift, s2_shift, split_rank,
                            __builtin_inff());
         // (the ranking and the placement launch may take other workgroup counts than the Gaussians: experiments)
         auto parts_of = [&](const char *name, unsigned dflt, unsigned cap) {
@@ -1261,7 +1261,7 @@ hipError_t ndt_launch_build(const NdtSetView &set, size_t first, size_t count, c
         if (split_rank)
             hipLaunchKernelGGL((ndt_build_kernel<0, 3, false, false>), dim3(rank_parts, (unsigned)count), dim3(NDT_FIN_THREADS), 0,
                                stream, set, (unsigned)first, (const char *)xyz_dev, (unsigned)n_points, (unsigned)stride_bytes,
-                               map_stride_bytes, range_limit, range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, 0,
+                               map_stride_bytes, range_limit, range_origins_dev, n_min, eval_factor, ndt_first_gaussian_floor(set.grid.res, s1_shift, s2_shift), s1_shift, s2_shift, 0,
                                __builtin_inff());
         if (split_rank)
             hipLaunchKernelGGL(ndt_place_cells_kernel, dim3(place_parts, (unsigned)count), dim3(NDT_FIN_THREADS), 0, stream, set,
@@ -1304,7 +1304,7 @@ hipError_t ndt_launch_accumulate(const NdtSetView &set, size_t first, size_t cou
 #define NDT_LAUNCH_ACC_V(SDW, NICE_, SCAT_)                                                                          \
     hipLaunchKernelGGL((ndt_build_kernel<SDW, 1, NICE_, SCAT_>), dim3(parts, (unsigned)count), dim3(NDT_BUILD_THREADS), 0, \
                        stream, set, (unsigned)first, (const char *)xyz_dev, (unsigned)n_points, (unsigned)stride_bytes, \
-                       map_stride_bytes, range_limit, range_origins_dev, 0, 0.0, s1_shift, s2_shift, 0, zf)
+                       map_stride_bytes, range_limit, range_origins_dev, 0, 0.0, 0.0, s1_shift, s2_shift, 0, zf)
 #define NDT_LAUNCH_ACC(SDW)                                                                                          \
     do {                                                                                                             \
         if (nice && scat) NDT_LAUNCH_ACC_V(SDW, true, true);                                                         \
@@ -1346,13 +1346,13 @@ hipError_t ndt_launch_finalise(const NdtSetView &set, size_t first, size_t count
     if (fin_parts < 1u) fin_parts = 1u;
     const int split_rank = (fin_parts > 1u && bm_words >= 16384u) ? 1 : 0;
     hipLaunchKernelGGL((ndt_build_kernel<0, 2, false, false>), dim3(fin_parts, (unsigned)count), dim3(NDT_FIN_THREADS), 0, stream, set,
-                       (unsigned)first, (const char *)nullptr, 0u, 12u, (size_t)0, 0.0, (const double *)nullptr, n_min, eval_factor,
+                       (unsigned)first, (const char *)nullptr, 0u, 12u, (size_t)0, 0.0, (const double *)nullptr, n_min, eval_factor, ndt_first_gaussian_floor(set.grid.res, s1_shift, s2_shift),
                        s1_shift, s2_shift, split_rank, __builtin_inff());
     if (split_rank) {
         unsigned parts = fin_parts;                       // (ndt_launch_build's defaults: as many as the Gaussians' launch)
         hipLaunchKernelGGL((ndt_build_kernel<0, 3, false, false>), dim3(std::min(parts, (unsigned)NDT_RANK_SEGS), (unsigned)count),
                            dim3(NDT_FIN_THREADS), 0, stream, set, (unsigned)first, (const char *)nullptr, 0u, 12u, (size_t)0, 0.0,
-                           (const double *)nullptr, n_min, eval_factor, s1_shift, s2_shift, 0, __builtin_inff());
+                           (const double *)nullptr, n_min, eval_factor, ndt_first_gaussian_floor(set.grid.res, s1_shift, s2_shift), s1_shift, s2_shift, 0, __builtin_inff());
         hipLaunchKernelGGL(ndt_place_cells_kernel, dim3(std::min(parts, 64u), (unsigned)count), dim3(NDT_FIN_THREADS), 0, stream, set,
                            (unsigned)first);
     }

@@ -129,7 +129,7 @@ NDT_D void flat_move_point(const double (&x)[12], float &px, float &py, float &p
 template <int SD, bool XF>
 __global__ __launch_bounds__(NDT_FLAT_THREADS) __attribute__((amdgpu_waves_per_eu(NDT_FLAT_WPE, NDT_FLAT_WPE))) void ndt_build_flat_kernel(
     NdtSetView set, unsigned first, const char *__restrict__ xyz, unsigned n_points, size_t map_stride_bytes,
-    double range_limit, const double *__restrict__ range_origins, int n_min, double eval_factor, int s1_shift, int s2_shift,
+    double range_limit, const double *__restrict__ range_origins, int n_min, double eval_factor, double floor_m2, int s1_shift, int s2_shift,
     unsigned hash_log2, const double *__restrict__ xf16, float *__restrict__ xf_out)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned s_dyn[];
@@ -534,7 +534,7 @@ __global__ __launch_bounds__(NDT_FLAT_THREADS) __attribute__((amdgpu_waves_per_e
         }
         const int iz = slot % g.size[2], iy = (slot / g.size[2]) % g.size[1], ix = slot / (g.size[2] * g.size[1]);
         const double centre[3] = {cx + (ix - hx) * res, cy + (iy - hy) * res, cz + (iz - hz) * res};
-        const NdtCell c = ndt_gaussian_from_moments(a, slot, centre, res, n_min, eval_factor, IS1, IS2);
+        const NdtCell c = ndt_gaussian_from_moments(a, slot, centre, res, n_min, eval_factor, IS1, IS2, floor_m2);
         if (c.n) atomicOr(&s_bits[slot >> 5], 1u << (slot & 31u));
         if (i < NDT_FLAT_THREADS) {
             mine = c;
@@ -659,18 +659,18 @@ hipError_t ndt_launch_build_flat(const NdtSetView &set, size_t first, size_t cou
         if (sdw == 3)
             hipLaunchKernelGGL((ndt_build_flat_kernel<3, true>), dim3((unsigned)count), dim3(NDT_FLAT_THREADS), dyn, stream, set,
                                (unsigned)first, (const char *)xyz_dev, (unsigned)n_points, map_stride_bytes, range_limit,
-                               range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, hash_log2, xf16_dev, xf_out_dev);
+                               range_origins_dev, n_min, eval_factor, ndt_first_gaussian_floor(set.grid.res, s1_shift, s2_shift), s1_shift, s2_shift, hash_log2, xf16_dev, xf_out_dev);
         else
             hipLaunchKernelGGL((ndt_build_flat_kernel<4, true>), dim3((unsigned)count), dim3(NDT_FLAT_THREADS), dyn, stream, set,
                                (unsigned)first, (const char *)xyz_dev, (unsigned)n_points, map_stride_bytes, range_limit,
-                               range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, hash_log2, xf16_dev, xf_out_dev);
+                               range_origins_dev, n_min, eval_factor, ndt_first_gaussian_floor(set.grid.res, s1_shift, s2_shift), s1_shift, s2_shift, hash_log2, xf16_dev, xf_out_dev);
     } else if (sdw == 3)
         hipLaunchKernelGGL((ndt_build_flat_kernel<3, false>), dim3((unsigned)count), dim3(NDT_FLAT_THREADS), dyn, stream, set,
                            (unsigned)first, (const char *)xyz_dev, (unsigned)n_points, map_stride_bytes, range_limit,
-                           range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, hash_log2, nullptr, nullptr);
+                           range_origins_dev, n_min, eval_factor, ndt_first_gaussian_floor(set.grid.res, s1_shift, s2_shift), s1_shift, s2_shift, hash_log2, nullptr, nullptr);
     else
         hipLaunchKernelGGL((ndt_build_flat_kernel<4, false>), dim3((unsigned)count), dim3(NDT_FLAT_THREADS), dyn, stream, set,
                            (unsigned)first, (const char *)xyz_dev, (unsigned)n_points, map_stride_bytes, range_limit,
-                           range_origins_dev, n_min, eval_factor, s1_shift, s2_shift, hash_log2, nullptr, nullptr);
+                           range_origins_dev, n_min, eval_factor, ndt_first_gaussian_floor(set.grid.res, s1_shift, s2_shift), s1_shift, s2_shift, hash_log2, nullptr, nullptr);
     return hipGetLastError();
 }

@@ -26,6 +26,7 @@
 // after beam, so a cell that loses its Gaussian half way through a cloud is treated as empty by the remaining beams,
 // and it accumulates in float.  Here every beam sees the cells as they were when the call started.
 #include "ndt_math.h"
+#include "ndt_binning.h"
 #include "ndt_wave.h"
 
 #define NDT_FUSE_THREADS 1024
@@ -254,8 +255,8 @@ extern "C" __global__ __launch_bounds__(256) void ndt_raytrace_kernel(
 
 // computeNDTCells of an incremental update: one workgroup per map.
 extern "C" __global__ __launch_bounds__(NDT_FIN2_THREADS) void ndt_fuse_finalize_kernel(
-    NdtSetView set, unsigned first, unsigned n_points, int n_min, double eval_factor, double maxnumpoints,
-    float occupancy_limit, int s1_shift, int s2_shift)
+    NdtSetView set, unsigned first, unsigned n_points, int n_min, double eval_factor, double floor_m2,
+    double maxnumpoints, float occupancy_limit, int s1_shift, int s2_shift)
 {
     __shared__ unsigned s_wave_cnt[NDT_FIN2_THREADS / 64];
     __shared__ unsigned s_binned;
@@ -397,7 +398,10 @@ extern "C" __global__ __launch_bounds__(NDT_FIN2_THREADS) void ndt_fuse_finalize
                 jacobi_static<3, true>(E, V);
                 double ev[3] = {E[0][0], E[1][1], E[2][2]};
                 const double mx = dmax3(ev[0], ev[1], ev[2]), mn = dmin3(ev[0], ev[1], ev[2]);
-                if (mx > 0 && mn > NDT_DEGENERATE_REL * mx) {
+                // a first Gaussian: the decision of the build's finaliser (the moments' noise floor); a Chan update keeps its own
+                const bool keep = had ? (mx > 0 && mn > NDT_DEGENERATE_REL * mx)
+                                      : !ndt_first_gaussian_rank_deficient(mx, mn, floor_m2);
+                if (keep) {
                     bool recalc = false;
 #pragma unroll
                     for (int k = 0; k < 3; k++)
@@ -731,7 +735,7 @@ hipError_t ndt_launch_fuse(const NdtSetView &set, size_t first, size_t count, co
                                          origins_dev, prm.maxz, nice, &s1, &s2, stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ndt_fuse_finalize_kernel, dim3((unsigned)count), dim3(NDT_FIN2_THREADS), 0, stream, set,
-                       (unsigned)first, (unsigned)n_points, prm.n_min, prm.eval_factor, prm.maxnumpoints,
+                       (unsigned)first, (unsigned)n_points, prm.n_min, prm.eval_factor, ndt_first_gaussian_floor(set.grid.res, s1, s2), prm.maxnumpoints,
                        (float)prm.occupancy_limit, s1, s2);
     return hipGetLastError();
 }

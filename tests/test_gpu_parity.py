@@ -1025,3 +1025,101 @@ def test_matcher_paths_on_a_grid_far_from_the_origin(N, O, monkeypatch):
             assert dt <= POSE_TOL_M and dr <= POSE_TOL_RAD, (name, k, dt, dr)
             assert r["iterations"][k] == ro["iterations"] and bool(r["converged"][k]) == ro["converged"], (name, k)
             assert dt < 1e-7, (name, k, dt)                  # (in fact: summation order only)
+
+
+def _rank_deficient_cloud(res=0.5, centre=(0.0, 0.0, 0.0)):
+    """About 2000 cells of 3 to 8 copies of one fp32 point at non-dyadic offsets, 500 cells of three exactly collinear points and
+    300 ordinary cells, in distinct cells of a 200 x 200 x 2 grid, within 30 m of the origin; shuffled.
+    Returns the cloud and the indices of the ordinary cells."""
+    g = np.random.default_rng(77)
+    cells = []
+    while len(cells) < 2800:
+        ix, iy = g.integers(30, 170, 2)
+        c = ((ix - 100) * res, (iy - 100) * res)
+        if np.hypot(*c) < 56.0 * res and (ix, iy) not in cells:
+            cells.append((int(ix), int(iy)))
+    ctr = np.array([[centre[0] + (ix - 100) * res, centre[1] + (iy - 100) * res, centre[2]] for ix, iy in cells])
+    pts = []
+    for k in range(2000):                                                  # copies of one point
+        p = (ctr[k] + g.uniform(-0.44, 0.44, 3) * res).astype(np.float32)
+        pts.append(np.repeat(p[None], int(g.integers(3, 9)), axis=0))
+    k = 2000
+    while k < 2500:                                                        # p, p + d, p + 2 d, all three fp32 numbers
+        p = (ctr[k] + g.uniform(-0.3, 0.3, 3) * res).astype(np.float32).astype(np.float64)
+        d = g.integers(-1023, 1024, 3) * 2.0 ** -17
+        line = np.stack([p, p + d, p + 2 * d])
+        if np.array_equal(line.astype(np.float32).astype(np.float64), line) and np.any(d != 0):
+            pts.append(line.astype(np.float32))
+            k += 1
+    for k in range(2500, 2800):                                            # ordinary cells
+        pts.append((ctr[k] + g.uniform(-0.4, 0.4, (int(g.integers(6, 11)), 3)) * res).astype(np.float32))
+    cloud = np.concatenate(pts)
+    cloud = cloud[g.permutation(len(cloud))]
+    ordinary = np.array([[ix, iy, 1] for ix, iy in cells[2500:]])
+    return cloud, ordinary
+
+
+def test_rank_deficient_cells_get_no_gaussian(N, O, monkeypatch):
+    """Cells of identical points and of exactly collinear points have a covariance of rank 0 and 1: the oracle's two-pass formula
+    gives them no Gaussian, and neither may the one-pass moments of the device, where the noise of S - n m m^T used to decide
+    (csrc/ndt_binning.h, ndt_first_gaussian_rank_deficient).  The general build kernel, the flat one and add_cloud into a set with
+    occupancy; the ordinary cells in between to the usual bars.  Before that decision had its noise floor an MI355X gave 0
+    spurious Gaussians on the grid with fp32 cell origins (the moments of fp32 points are exact there), and on the other 14 from
+    the general kernel and 3 from add_cloud."""
+    cloud, ordinary = _rank_deficient_cloud()
+    res, size = 0.5, [100, 100, 1]
+    cpu = oracle_map(O, cloud, res, size).export_cells()
+    want = {tuple(i) for i in cpu[2]}
+    assert want == {tuple(i) for i in ordinary}                            # (the oracle: the ordinary cells and no other)
+    got = {}
+    for name, flat in (("general", "0"), ("flat", "2")):
+        monkeypatch.setenv("NDTGPU_FLAT", flat)
+        ms = N.MapSet(res, [0, 0, 0], size, n_maps=2, max_cells=4096)
+        ms.build(np.stack([cloud, cloud]), range_limit=30.0)
+        got[name] = [ms.export_cells(m) for m in range(2)]
+    monkeypatch.delenv("NDTGPU_FLAT")
+    fs = N.MapSet(res, [0, 0, 0], size, n_maps=1, max_cells=4096)
+    fs.enable_occupancy()
+    fs.add_cloud(cloud[None], np.zeros((1, 3)), maxz=100.0, sensor_noise=0.1)
+    om = O.OracleMap(res, [0, 0, 0], size)
+    om.add_point_cloud(np.zeros(3), cloud, maxz=100.0, sensor_noise=0.1, occupancy_limit=255.0, order_free=True)
+    om.compute_cells_full(maxnumpoints=1e5, occupancy_limit=255.0)
+    fused_cpu = om.export_cells()
+    spurious = {name: len({tuple(i) for i in cells[0][2]} - want) for name, cells in got.items()}
+    spurious["add_cloud"] = len({tuple(i) for i in fs.export_cells(0)[2]} - {tuple(i) for i in fused_cpu[2]})
+    print("cells with a Gaussian that the oracle gives none:", spurious)
+    for name, cells in got.items():
+        for m in range(2):
+            assert {tuple(i) for i in cells[m][2]} == want, (name, m)
+            assert_cells_equal(cells[m], cpu, res)
+    assert {tuple(i) for i in fs.export_cells(0)[2]} == {tuple(i) for i in fused_cpu[2]}
+    assert len(fused_cpu[3]) >= 100                                        # (the beams took the occupancy of the others)
+    assert_cells_equal(fs.export_cells(0), fused_cpu, res)
+    # The grid above has fp32 cell origins: the offsets of fp32 points are exact there, and so are most of the moments.  On a
+    # grid whose cell origins are no fp32 numbers the offsets come out of fp64 arithmetic with all 53 bits and every run's
+    # moments do round (the general kernel; the flat one takes no such grid).
+    res2, centre2, size2 = 0.4, (0.13, -0.07, 0.02), [80, 80, 0.8]
+    cloud2, ordinary2 = _rank_deficient_cloud(res2, centre2)
+    cpu2 = oracle_map(O, cloud2, res2, size2, centre=centre2).export_cells()
+    want2 = {tuple(i) for i in cpu2[2]}
+    assert want2 == {tuple(i) for i in ordinary2}
+    ms2 = N.MapSet(res2, list(centre2), size2, n_maps=2, max_cells=4096)
+    ms2.build(np.stack([cloud2, cloud2]), range_limit=30.0)
+    cells2 = [ms2.export_cells(m) for m in range(2)]
+    print("... and on the grid without fp32 cell origins:", len({tuple(i) for i in cells2[0][2]} - want2))
+    # ... and add_cloud into a set with occupancy on this grid: the first-Gaussian branch of csrc/ndt_fuse.hip
+    fs2 = N.MapSet(res2, list(centre2), size2, n_maps=1, max_cells=4096)
+    fs2.enable_occupancy()
+    fs2.add_cloud(cloud2[None], np.zeros((1, 3)), maxz=100.0, sensor_noise=0.1)
+    om2 = O.OracleMap(res2, list(centre2), size2)
+    om2.add_point_cloud(np.zeros(3), cloud2, maxz=100.0, sensor_noise=0.1, occupancy_limit=255.0, order_free=True)
+    om2.compute_cells_full(maxnumpoints=1e5, occupancy_limit=255.0)
+    fused_cpu2 = om2.export_cells()
+    fused2 = fs2.export_cells(0)
+    print("... add_cloud there:", len({tuple(i) for i in fused2[2]} - {tuple(i) for i in fused_cpu2[2]}))
+    for m in range(2):
+        assert {tuple(i) for i in cells2[m][2]} == want2, m
+        assert_cells_equal(cells2[m], cpu2, res2)
+    assert {tuple(i) for i in fused2[2]} == {tuple(i) for i in fused_cpu2[2]}
+    assert len(fused_cpu2[3]) >= 100
+    assert_cells_equal(fused2, fused_cpu2, res2)
