@@ -1031,6 +1031,108 @@ ndtgpu_status ndtgpu_mapset_occupancy_grid(ndtgpu_mapset *set, size_t first, siz
 /* moveOccupancyMap: moved16 = T16 * origin_pose16 (4 x 4, column-major; moved16 may be origin_pose16) */
 void ndtgpu_occgrid_move(const double T16[16], const double origin_pose16[16], double moved16[16]);
 
+/* ---- link gating: which loop-closure links exist -- candidate pairs and getValidLinks -----------------------------------------
+ * The step of the chain scans -> feature sets -> seeded links -> registered links -> optimised poses -> world -> grid that decides
+ * which links there are.  Twice in the reference:
+ *   - computeAllPossibleLinks (ndt_feature_graph.cpp:395-405) enumerates every pair i < j of the nodes (i ascending, then j) and
+ *     calls computeLink for each.  ndtgpu_linkgate_candidates enumerates the same pairs in the same order and keeps those worth
+ *     matching: j - i >= min_idx_dist, and the nodes' own poses within max_dist / max_angle of each other
+ *     (distanceBetweenAffine3d(T_i, T_j)).  The survivors are written compacted as the arrays ndtgpu_featbank_match_device and
+ *     ndtgpu_match_batch_device take unchanged: uint32 ref = i, mov = j, and the initial guess T16 = T_i^-1 T_j.
+ *   - getValidLinks (ndt_feature_graph.cpp:527-556) filters the registered links before every optimisation, inside the offline
+ *     mapper's loop (ndt_feature_graph_opt.cpp:152-173): gate under the current node poses, optimise, gate again, until the number
+ *     of links stops changing.  ndtgpu_linkgate_valid is that filter, ndtgpu_linkgate_gather packs T16 / cov36 / flags / indices of
+ *     the links that stay behind the incremental links -- the contiguous arrays ndtgpu_pgo_set_links_device needs -- and only the
+ *     keep list (4 bytes per kept link) visits the host, for the index arrays of that call.  With one handle per threshold set this
+ *     is also how a ndtgpu_pgo bank gets "the same nodes under several getValidLinks thresholds".
+ * Semantics (restated).  Poses are column-major 4 x 4 doubles.
+ *   - distanceBetweenAffine3d(p1, p2) (utils.h:42-47):  dist = sqrt(dx^2 + dy^2 + dz^2) of t2 - t1;  r00 = col0(R1) . col0(R2);
+ *     ang = fabs(acos(r00)) -- getRobustYawFromAffine3d (utils.h:30-40): the angle of the rotated x axis in the xy plane, its sign
+ *     dropped by the fabs.  With clip_cosine r00 is clamped to [-1, 1] first.
+ *   - a pair i < j stays when  j - i >= min_idx_dist  &&  dist < max_dist  &&  ang < max_angle  for (T_i, T_j); max_score is not
+ *     read.  max_angle = +inf with clip_cosine = 1 switches the angle gate off.
+ *   - link k (ref, mov, T, score) stays when  score <= max_score (not tested where score_dev is NULL)  &&
+ *     |mov - ref| >= min_idx_dist  &&  dist < max_dist && ang < max_angle  for (T_mov, T_ref * T).  ref > mov is an ordinary link.
+ *   - THE NaN RULE, upstream's and the default: acos of a cosine a rounding above 1 is NaN, NaN < max_angle is false, the link is
+ *     rejected.  On a consistent graph (links exactly T_ref^-1 T_mov) that is about one link in six.  clip_cosine = 1 is the one
+ *     place to switch it off.
+ * PROVENANCE: restated from the reference files cited above; the defaults are ndt_feature_graph_opt.cpp:49-52.
+ * DEVIATIONS:
+ *   - the two of distanceBetweenAffine3d from upstream's p1.inverse() * p2 (both already in distributed.valid_links): the rigid
+ *     transpose instead of a general inverse, and no rotation of the difference vector (a rotation keeps its length).  T_ref * T
+ *     and T_i^-1 T_j are rigid products as well: the last row is written as 0 0 0 1.
+ *   - the operation order is fixed and NOT fused (csrc/ndt_linkgate.h states it; tests/linkgate_model.py follows it), the arc
+ *     cosine is the library's own (csrc/ndt_pgo.h ndt_pgo_acos), the same bits on host and device -- within an ulp or two of libm's.
+ *   - a NaN score is rejected (score <= max_score is false); upstream's "score > maxScore -> skip" would keep it.
+ *   - OURS: a link with an index >= n_nodes is rejected, on the device (upstream reads past its vector); a result larger than the
+ *     capacity given is truncated and reported (ndtgpu_linkgate_count), not an error status; max_rounds of the gated loop
+ *     (binding.optimize_gated, host/ndt_link_gate_gpu.h optimizeGraphGated): upstream's loop has no cap and can oscillate.
+ * Device form (csrc/ndt_linkgate.hip): an ordered selection in three plain launches, with no workgroup waiting on another (no
+ * look-back spin, no grid barrier, no atomics): a flag-and-count pass (one count per tile of 1024 consecutive items), a scan of
+ * the tile counts by one workgroup, an emit pass that evaluates the gate again and ranks within the tile (csrc/ndt_block.h
+ * ndt_block_rank).  Pairs run over a 64-bit linear index; its decoding to (i, j) proposes the row with a square root and settles it
+ * in integers.  The output is in input order and the same bits on any run; a link's fate does not depend on its batch.  The gather
+ * moves 4-byte words, one lane per word, and reads the count on the device.
+ * Calls on one handle are ordered on the device (each waits for the previous one, whatever stream that one named).
+ * Measured on MI355X (tools/linkgate_cost.py, HIP events, library 0.9.0): candidates of 5000 nodes (12 497 500 pairs, 119 651 kept, with
+ * T16) 0.31 ms, of 500 nodes 0.030 ms -- distributed.all_pairs + the NumPy gate + the initial guesses take 414 ms and 88 ms on the same
+ * box; valid of 44 486 links 0.026 ms, with the gathers of T16, cov36 and flags 0.045 ms (distributed.valid_links 9.5 ms + 1.1 ms of
+ * fancy indexing); valid of 12 497 500 links 0.49 ms, with the gathers of the 3.83 M links that stay 1.66 ms (3130 ms + 391 ms).
+ * Both sides decide the same links in all four cases. */
+typedef struct ndtgpu_linkgate ndtgpu_linkgate;
+typedef struct {
+    double  max_score;               /* a link's score at most (0.1) */
+    double  max_dist;                /* metres, strict (1.0) */
+    double  max_angle;               /* radians, strict (0.2) */
+    int32_t min_idx_dist;            /* node indices apart at least (2) */
+    int32_t clip_cosine;             /* 0: upstream's NaN rule; 1: the cosine is clamped to [-1, 1] before acos */
+} ndtgpu_linkgate_params;
+/* 0.1, 1.0, 0.2, 2 (ndt_feature_graph_opt.cpp:49-52) and clip_cosine = 0 */
+void ndtgpu_default_linkgate_params(ndtgpu_linkgate_params *p);
+/* the argument checks of the entries below on plain numbers (a handle's max_nodes / max_links; the call's n_nodes, n_links and
+ * row_bytes, 0 where the call has none): needs no handle and no device.  NDTGPU_ERR_INVALID: max_nodes 0 or > 65536, max_links
+ * > 2^27, row_bytes no multiple of 4 or > 4096;  NDTGPU_ERR_CAPACITY: n_nodes > max_nodes, n_links > max_links. */
+ndtgpu_status ndtgpu_linkgate_check(size_t max_nodes, size_t max_links, size_t n_nodes, size_t n_links, size_t row_bytes);
+/* room for max_nodes node poses (1 .. 65536), the tile counts of their pairs and of max_links links (<= 2^27), and a keep list of
+ * max_links entries */
+ndtgpu_status ndtgpu_linkgate_create(size_t max_nodes, size_t max_links, ndtgpu_linkgate **out);
+ndtgpu_status ndtgpu_linkgate_destroy(ndtgpu_linkgate *h);
+/* the node poses: T16 HOST n_nodes x 16 column-major -- what ndtgpu_pgo_poses returns as T16_out.  Synchronous. */
+ndtgpu_status ndtgpu_linkgate_set_nodes(ndtgpu_linkgate *h, size_t n_nodes, const double *T16);
+/* the same from DEVICE memory, asynchronous on `stream` */
+ndtgpu_status ndtgpu_linkgate_set_nodes_device(ndtgpu_linkgate *h, size_t n_nodes, const double *T16_dev, ndtgpu_stream stream);
+/* every pair i < j of the set nodes through the candidate gate; survivors compacted in enumeration order into ref_idx_dev /
+ * mov_idx_dev (uint32) and T16_dev (16 doubles each; may be NULL), DEVICE arrays of `capacity` entries.  prm NULL: the defaults.
+ * Asynchronous on `stream`. */
+ndtgpu_status ndtgpu_linkgate_candidates(ndtgpu_linkgate *h, const ndtgpu_linkgate_params *prm, uint32_t *ref_idx_dev,
+                                         uint32_t *mov_idx_dev, double *T16_dev, size_t capacity, ndtgpu_stream stream);
+/* getValidLinks of n_links registered links under the set nodes: ref_idx_dev / mov_idx_dev (uint32), T16_dev (n_links x 16) and
+ * score_dev (n_links doubles, or NULL: no score test) DEVICE.  The ascending indices of the links that stay go to the handle's
+ * keep list and, where keep_dev (DEVICE, `capacity` uint32) is not NULL, to it.  Asynchronous on `stream`. */
+ndtgpu_status ndtgpu_linkgate_valid(ndtgpu_linkgate *h, const ndtgpu_linkgate_params *prm, size_t n_links, const uint32_t *ref_idx_dev,
+                                    const uint32_t *mov_idx_dev, const double *T16_dev, const double *score_dev, uint32_t *keep_dev,
+                                    size_t capacity, ndtgpu_stream stream);
+/* the two selections with every array in HOST memory (the host mirror's form, host/ndt_link_gate_gpu.h): synchronous, on the
+ * handle's own stream; device temporaries are gone on return (ndtgpu_live_resources is unchanged by a call).  _candidates_host
+ * writes min(count, capacity) survivors (capacity 0 with NULL arrays: only the count, read with ndtgpu_linkgate_count);
+ * _valid_host leaves the keep list in the handle (ndtgpu_linkgate_count, ndtgpu_linkgate_keep). */
+ndtgpu_status ndtgpu_linkgate_candidates_host(ndtgpu_linkgate *h, const ndtgpu_linkgate_params *prm, uint32_t *ref_idx, uint32_t *mov_idx,
+                                              double *T16, size_t capacity);
+ndtgpu_status ndtgpu_linkgate_valid_host(ndtgpu_linkgate *h, const ndtgpu_linkgate_params *prm, size_t n_links, const uint32_t *ref_idx,
+                                         const uint32_t *mov_idx, const double *T16, const double *score);
+/* for the keep list of the last ndtgpu_linkgate_valid call: row keep[k] of src_dev becomes row dst_first_row + k of dst_dev, rows
+ * of row_bytes bytes (a multiple of 4, at most 4096: T16 128, cov36 288, flags and indices 4, result records), both 4-aligned.
+ * The count is read on the device: no host wait.  dst_dev has room for dst_first_row + (the links of that call) rows, or for what
+ * the caller knows the count to be; dst_first_row is where the caller has put the incremental links, in front.  Asynchronous on
+ * `stream`. */
+ndtgpu_status ndtgpu_linkgate_gather(ndtgpu_linkgate *h, const void *src_dev, size_t row_bytes, void *dst_dev, size_t dst_first_row,
+                                     ndtgpu_stream stream);
+/* how many pairs or links the handle's last candidates / valid call kept; waits for the handle.  A result larger than the call's
+ * capacity wrote nothing beyond it: *count is still the true count and *overflow (may be NULL) is 1.  Not an error status. */
+ndtgpu_status ndtgpu_linkgate_count(ndtgpu_linkgate *h, size_t *count, int32_t *overflow);
+/* entries [first, first + n) of the last valid call's keep list to HOST memory; waits for the handle */
+ndtgpu_status ndtgpu_linkgate_keep(ndtgpu_linkgate *h, size_t first, size_t n, uint32_t *keep);
+
 /* single pair convenience == graph.cpp:273 */
 ndtgpu_status ndtgpu_match_d2d(ndtgpu_mapset *target_set, size_t target_map, ndtgpu_mapset *source_set,
                                size_t source_map, double T16[16], const ndtgpu_match_params *prm,

@@ -12,7 +12,8 @@ _SO = os.path.join(_HERE, "libndtgpu.so")
 _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hip", "ndt_pack.hip", "ndt_fuser.hip", "ndtgpu_api.hip",
             "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip",
             "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
-            "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip", "ndt_occgrid.hip", "ndtgpu_occgrid.hip"]
+            "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip", "ndt_occgrid.hip", "ndtgpu_occgrid.hip", "ndt_linkgate.hip",
+            "ndtgpu_linkgate.hip"]
 
 STATUS = {0: "OK", -1: "ERR_INVALID", -2: "ERR_HIP", -3: "ERR_NO_DEVICE", -4: "ERR_CAPACITY", -5: "ERR_ALLOC"}
 
@@ -146,7 +147,11 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_featbank_extract_results", "ndtgpu_featbank_get",
            "ndtgpu_default_world_params", "ndtgpu_world_assemble", "ndtgpu_world_check",
            "ndtgpu_default_occgrid_params", "ndtgpu_occgrid_dims", "ndtgpu_mapset_occupancy_grid_device", "ndtgpu_mapset_occupancy_grid",
-           "ndtgpu_occgrid_move", "ndtgpu_occgrid_check"]
+           "ndtgpu_occgrid_move", "ndtgpu_occgrid_check",
+           "ndtgpu_default_linkgate_params", "ndtgpu_linkgate_check", "ndtgpu_linkgate_create", "ndtgpu_linkgate_destroy",
+           "ndtgpu_linkgate_set_nodes", "ndtgpu_linkgate_set_nodes_device", "ndtgpu_linkgate_candidates", "ndtgpu_linkgate_valid",
+           "ndtgpu_linkgate_gather", "ndtgpu_linkgate_count", "ndtgpu_linkgate_keep", "ndtgpu_linkgate_candidates_host",
+           "ndtgpu_linkgate_valid_host"]
 
 _lib = None
 
@@ -303,6 +308,20 @@ def lib():
     L.ndtgpu_occgrid_check.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32]
     L.ndtgpu_occgrid_move.restype = None
     L.ndtgpu_occgrid_move.argtypes = [dp, dp, dp]
+    L.ndtgpu_default_linkgate_params.restype = None
+    L.ndtgpu_default_linkgate_params.argtypes = [C.POINTER(LinkGateParams)]
+    L.ndtgpu_linkgate_check.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]
+    L.ndtgpu_linkgate_create.argtypes = [C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.ndtgpu_linkgate_destroy.argtypes = [vp]
+    L.ndtgpu_linkgate_set_nodes.argtypes = [vp, C.c_size_t, dp]
+    L.ndtgpu_linkgate_set_nodes_device.argtypes = [vp, C.c_size_t, vp, vp]
+    L.ndtgpu_linkgate_candidates.argtypes = [vp, C.POINTER(LinkGateParams), vp, vp, vp, C.c_size_t, vp]
+    L.ndtgpu_linkgate_valid.argtypes = [vp, C.POINTER(LinkGateParams), C.c_size_t, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.ndtgpu_linkgate_gather.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp]
+    L.ndtgpu_linkgate_candidates_host.argtypes = [vp, C.POINTER(LinkGateParams), u32p, u32p, dp, C.c_size_t]
+    L.ndtgpu_linkgate_valid_host.argtypes = [vp, C.POINTER(LinkGateParams), C.c_size_t, u32p, u32p, dp, dp]
+    L.ndtgpu_linkgate_count.argtypes = [vp, C.POINTER(C.c_size_t), i32p]
+    L.ndtgpu_linkgate_keep.argtypes = [vp, C.c_size_t, C.c_size_t, u32p]
     if hasattr(L, "ndtgpu_live_resources"):            # (NDTGPU_LIB may name a build from before this entry existed)
         L.ndtgpu_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
@@ -1212,6 +1231,190 @@ def occupancy_grid_move(T, origin_pose):
     m = np.zeros(16)
     lib().ndtgpu_occgrid_move(_dp(a), _dp(b), _dp(m))
     return m.reshape(4, 4).T.copy()
+
+
+class LinkGateParams(C.Structure):
+    _fields_ = [("max_score", C.c_double), ("max_dist", C.c_double), ("max_angle", C.c_double), ("min_idx_dist", C.c_int32),
+                ("clip_cosine", C.c_int32)]
+
+
+def linkgate_params(**fields):
+    """ndtgpu_default_linkgate_params (0.1, 1.0, 0.2, 2, clip_cosine 0) with fields replaced"""
+    p = LinkGateParams()
+    lib().ndtgpu_default_linkgate_params(C.byref(p))
+    for k, v in fields.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown link-gate parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _dev_ptr(t, dtype, numel, what):
+    """the address of a contiguous torch device tensor of `dtype` with at least `numel` elements (None stays None)"""
+    if t is None:
+        return None
+    if not (t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() >= numel):
+        raise ValueError("%s: a contiguous device tensor of %s with at least %d elements is required" % (what, dtype, numel))
+    return C.c_void_p(t.data_ptr())
+
+
+class LinkGate:
+    """ndtgpu_linkgate: which links exist (include/ndtgpu.h "link gating") -- the candidate pairs of computeAllPossibleLinks gated
+    by index distance and odometry, getValidLinks of the registered links, and the gather that packs what stays.  Works on torch
+    device tensors; uint32 index arrays are int32 tensors (torch has no uint32 arithmetic; the bits are the same).  Poses are
+    [n, 16] column-major on the device, [n, 4, 4] where a host array is taken."""
+
+    def __init__(self, max_nodes, max_links):
+        h = C.c_void_p()
+        _check(lib().ndtgpu_linkgate_create(int(max_nodes), int(max_links), C.byref(h)))
+        self.h, self.max_nodes, self.max_links, self.n_nodes = h, int(max_nodes), int(max_links), 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ndtgpu_linkgate_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_nodes(self, T, stream=None):
+        """the node poses: a host array [n, 4, 4] (synchronous), or a float64 device tensor [n, 16] column-major (on `stream`)"""
+        if hasattr(T, "is_cuda"):
+            n = T.numel() // 16
+            import torch
+            _check(lib().ndtgpu_linkgate_set_nodes_device(self.h, n, _dev_ptr(T, torch.float64, 16 * n, "LinkGate.set_nodes"), _stream_ptr(stream)))
+        else:
+            Tcm = np.ascontiguousarray(np.transpose(_f64(T).reshape(-1, 4, 4), (0, 2, 1)))
+            n = Tcm.shape[0]
+            _check(lib().ndtgpu_linkgate_set_nodes(self.h, n, _dp(Tcm) if n else None))
+        self.n_nodes = n
+
+    def candidates(self, capacity, with_T=True, stream=None, **params):
+        """every pair i < j through the candidate gate: (ref int32 [capacity], mov int32 [capacity], T16 float64 [capacity, 16] or
+        None) device tensors whose first count() entries are the survivors in computeAllPossibleLinks' order; asynchronous"""
+        import torch
+        cap = int(capacity)
+        ref = torch.empty(max(cap, 1), dtype=torch.int32, device="cuda")
+        mov = torch.empty(max(cap, 1), dtype=torch.int32, device="cuda")
+        T16 = torch.empty((max(cap, 1), 16), dtype=torch.float64, device="cuda") if with_T else None
+        self.candidates_into(ref, mov, T16, cap, stream=stream, **params)
+        return ref, mov, T16
+
+    def candidates_into(self, ref_dev, mov_dev, T16_dev, capacity, stream=None, **params):
+        """candidates() into the caller's tensors (T16_dev may be None); nothing is written behind `capacity` entries"""
+        import torch
+        cap = int(capacity)
+        p = linkgate_params(**params)
+        _check(lib().ndtgpu_linkgate_candidates(self.h, C.byref(p), _dev_ptr(ref_dev, torch.int32, cap, "LinkGate.candidates ref"),
+                                                _dev_ptr(mov_dev, torch.int32, cap, "LinkGate.candidates mov"),
+                                                _dev_ptr(T16_dev, torch.float64, 16 * cap, "LinkGate.candidates T16"), cap, _stream_ptr(stream)))
+
+    def valid(self, ref, mov, T16_dev, score_dev=None, keep_dev=None, capacity=None, stream=None, **params):
+        """getValidLinks of the links (ref, mov, T16_dev [m, 16] column-major, score_dev [m] or None) under the set nodes.  ref / mov:
+        int32 device tensors, or host arrays (uploaded, then the same entry).  The kept indices go to the handle's keep list and to
+        keep_dev (int32 device tensor of `capacity` entries) where given; asynchronous"""
+        import torch
+        if not hasattr(ref, "is_cuda"):
+            ref = torch.tensor(np.ascontiguousarray(ref, dtype=np.uint32).view(np.int32).reshape(-1), device="cuda")
+            mov = torch.tensor(np.ascontiguousarray(mov, dtype=np.uint32).view(np.int32).reshape(-1), device="cuda")
+        if not hasattr(T16_dev, "is_cuda"):
+            Tcm = np.transpose(_f64(T16_dev).reshape(-1, 4, 4), (0, 2, 1))
+            T16_dev = torch.tensor(np.ascontiguousarray(Tcm).reshape(Tcm.shape[0], 16), device="cuda")
+        if score_dev is not None and not hasattr(score_dev, "is_cuda"):
+            score_dev = torch.tensor(_f64(score_dev).reshape(-1), device="cuda")
+        m = ref.numel()
+        if mov.numel() != m:
+            raise ValueError("LinkGate.valid: one ref and one mov index per link")
+        cap = 0 if keep_dev is None else (keep_dev.numel() if capacity is None else int(capacity))
+        p = linkgate_params(**params)
+        self._inputs = (ref, mov, T16_dev, score_dev)       # (uploaded copies stay alive until the next call)
+        _check(lib().ndtgpu_linkgate_valid(self.h, C.byref(p), m, _dev_ptr(ref, torch.int32, m, "LinkGate.valid ref"),
+                                           _dev_ptr(mov, torch.int32, m, "LinkGate.valid mov"),
+                                           _dev_ptr(T16_dev, torch.float64, 16 * m, "LinkGate.valid T16") if m else None,
+                                           _dev_ptr(score_dev, torch.float64, m, "LinkGate.valid score"),
+                                           _dev_ptr(keep_dev, torch.int32, cap, "LinkGate.valid keep"), cap, _stream_ptr(stream)))
+
+    def gather(self, src_dev, dst_dev, dst_first_row=0, row_bytes=None, stream=None):
+        """row keep[k] of src_dev -> row dst_first_row + k of dst_dev for the last valid() call's keep list; rows are the tensors'
+        trailing dimensions (row_bytes: override); asynchronous, the count is read on the device"""
+        if row_bytes is None:
+            row_bytes = src_dev.element_size() * (src_dev.numel() // src_dev.shape[0] if src_dev.dim() > 1 else 1)
+        if not (src_dev.is_cuda and dst_dev.is_cuda and src_dev.is_contiguous() and dst_dev.is_contiguous()):
+            raise ValueError("LinkGate.gather: contiguous device tensors are required")
+        _check(lib().ndtgpu_linkgate_gather(self.h, C.c_void_p(src_dev.data_ptr()), int(row_bytes), C.c_void_p(dst_dev.data_ptr()),
+                                            int(dst_first_row), _stream_ptr(stream)))
+
+    def count(self):
+        """(count, overflow) of the last candidates() / valid() call; waits for the handle"""
+        n, o = C.c_size_t(), C.c_int32()
+        _check(lib().ndtgpu_linkgate_count(self.h, C.byref(n), C.byref(o)))
+        return int(n.value), bool(o.value)
+
+    def keep(self, first=0, n=None):
+        """the last valid() call's keep list [first, first + n) as a host int64 array (n None: to the end, where valid() was the
+        handle's last selection); waits for the handle"""
+        if n is None:
+            n = self.count()[0] - int(first)
+        out = np.zeros(max(int(n), 1), dtype=np.uint32)
+        _check(lib().ndtgpu_linkgate_keep(self.h, int(first), int(n), out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[:int(n)].astype(np.int64)
+
+
+def optimize_gated(pgo, g, gate, start_poses, incr_ref, incr_mov, incr_T16_dev, ref, mov, T16_dev, score_dev=None, cov36_dev=None,
+                   cov_flags_dev=None, max_rounds=10, pgo_fields=None, **params):
+    """The offline mapper's loop (ndt_feature_graph_opt.cpp:152-173) on the device: every round sets the gate's nodes to the current
+    poses, runs getValidLinks (gate.valid) over the matched links (ref, mov host arrays; T16_dev [m, 16], score_dev [m], cov36_dev
+    [m, 36], cov_flags_dev [m] device tensors), gathers T16 / cov36 / flags of the links that stay behind the incremental links
+    (incr_ref, incr_mov host arrays, incr_T16_dev [k, 16]; their covariance is the flagged stand-in 0.02 I where cov36_dev is
+    given), downloads ONLY the keep list, and optimises graph g of `pgo` from the current poses with incremental + kept links.
+    It stops when the kept count repeats, when nothing is kept, or after max_rounds rounds -- max_rounds is OURS: upstream's loop
+    has no cap and can oscillate between two link sets.  start_poses: [n, 3] (x, y, yaw).  **params: fields of
+    ndtgpu_linkgate_params; pgo_fields: a dict of ndtgpu_pgo_params fields.  Returns (kept index arrays per round, final poses
+    [n, 3])."""
+    import torch
+    poses = _f64(start_poses).reshape(-1, 3).copy()
+    n = poses.shape[0]
+    iref = np.ascontiguousarray(incr_ref, dtype=np.uint32).reshape(-1)
+    imov = np.ascontiguousarray(incr_mov, dtype=np.uint32).reshape(-1)
+    ref = np.ascontiguousarray(ref, dtype=np.uint32).reshape(-1)
+    mov = np.ascontiguousarray(mov, dtype=np.uint32).reshape(-1)
+    k, m = iref.shape[0], ref.shape[0]
+    ref_dev = torch.from_numpy(ref.view(np.int32)).cuda()
+    mov_dev = torch.from_numpy(mov.view(np.int32)).cuda()
+    T_all = torch.empty((k + m, 16), dtype=torch.float64, device="cuda")
+    if k:
+        T_all[:k] = incr_T16_dev.reshape(k, 16)
+    cov_all = flags_all = None
+    if cov36_dev is not None:
+        cov_all = torch.zeros((k + m, 36), dtype=torch.float64, device="cuda")
+        flags_all = torch.empty(k + m, dtype=torch.int32, device="cuda")
+        flags_all[:k] = 4                                # NDTGPU_COV_NOT_COMPUTED: the factor takes 0.02 I for an incremental link
+    rounds, prev = [], None
+    for _ in range(int(max_rounds)):
+        c, s = np.cos(poses[:, 2]), np.sin(poses[:, 2])
+        T = np.tile(np.eye(4), (n, 1, 1))
+        T[:, 0, 0], T[:, 0, 1], T[:, 1, 0], T[:, 1, 1], T[:, 0, 3], T[:, 1, 3] = c, -s, s, c, poses[:, 0], poses[:, 1]
+        gate.set_nodes(T)
+        gate.valid(ref_dev, mov_dev, T16_dev, score_dev, **params)
+        gate.gather(T16_dev, T_all, dst_first_row=k, row_bytes=128)
+        if cov_all is not None:
+            gate.gather(cov36_dev, cov_all, dst_first_row=k, row_bytes=288)
+            gate.gather(cov_flags_dev, flags_all, dst_first_row=k, row_bytes=4)
+        kept = gate.keep()
+        rounds.append(kept)
+        if kept.size == 0:
+            break
+        torch.cuda.synchronize()                         # (the gathers ran on torch's stream; set_links_device takes complete arrays)
+        pgo.set_links_device(g, poses, np.concatenate([iref, ref[kept]]), np.concatenate([imov, mov[kept]]), T_all, cov_all, flags_all)
+        pgo.optimize(g, 1, **(pgo_fields or {}))
+        poses = pgo.poses(g)[0][:n].copy()
+        if prev == kept.size:
+            break
+        prev = kept.size
+    return rounds, poses
 
 
 class FeatMatchParams(C.Structure):
