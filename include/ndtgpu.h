@@ -516,7 +516,9 @@ ndtgpu_status ndtgpu_registrar_mapset(ndtgpu_registrar *reg, int slot, ndtgpu_ma
  * the pose a registration yields goes into the fuse-in without visiting the host.  Results are bit for bit those of the calls
  * it replaces on the same inputs (tests/test_gpu_fuser_bank.py).
  * Covers the production configuration of the fuser -- globalTransf and loadCentroid (their defaults; the launch files never
- * change them), beHMT / visualisation / the FLIRT feature map outside the path. */
+ * change them), beHMT / visualisation outside the path.  The FLIRT feature term and the node feature maps
+ * (useFeat) are the *_feat entries at the end of this header ("the fuser bank's feature path"); the entries below run without them,
+ * also on a bank that has a feature bank attached, and leave its feature state untouched. */
 typedef struct ndtgpu_fuser_bank ndtgpu_fuser_bank;
 typedef struct {
     /* NDTFeatureFuserHMT::Params (ndt_feature_fuser_hmt.h:58-207): the fields the path reads, same names in snake case */
@@ -1370,6 +1372,132 @@ ndtgpu_status ndtgpu_featbank_extract_results(ndtgpu_featbank *h, size_t first, 
  * max_points x desc_len of room (either may be NULL), the first *n rows written, the descriptors row-major.  Waits for the
  * handle's last call. */
 ndtgpu_status ndtgpu_featbank_get(ndtgpu_featbank *h, size_t k, size_t *n, double *pos3, double *desc);
+
+/* ---- the fuser bank's feature path: the FLIRT feature term of the registration and the node feature maps ------------------------
+ * NDTFeatureFuserHMT::update (ndt_feature_fuser_hmt.cpp:108-512) with Params::useFeat (true in Params()): per scan it matches the
+ * scan's interest points against the previous scan's with the RANSAC set matcher (:251), gates the result against the odometry
+ * (:279-289), turns the correspondences into fixed-covariance NDT cell pairs (:299-300;
+ * convertCorrespondencesToCellvectorsFixedCovWithCorr, conversions.h:52-83), puts them IN FRONT of the 40 odometry cells of
+ * matchFusion (:304-357), and afterwards moves the points to the new pose and appends them to the fuser's NDTFeatureMap (:497-502;
+ * NDTFeatureMap::update, ndt_feature_map.h:62-68) -- the map that matchNodesUsingFeatureMap (ndt_feature_node.h:254-256) later
+ * matches between nodes.  With a feature bank attached the fuser bank does all of it on the caller's stream with no host visit:
+ * scan -> ndtgpu_featbank_extract_device -> ndtgpu_fuser_update_batch_feat -> the node's feature map -> ndtgpu_featbank_match*.
+ * PROVENANCE: restated from the cited lines of the reference; flirtlib itself is not vendored (see the RANSAC section above).
+ * Semantics (restated).  Per fuser slot three sets of the attached ndtgpu_featbank:
+ *   cur   the scan's interest points in the sensor frame: named per call, READ ONLY.
+ *   prev  ptsPrev: set prev_set_first + slot.
+ *   map   featuremap.map: set map_set_first + slot.
+ *   1. RANSAC (:251): ndt_featmatch_kernel unchanged on the pair (ref = prev, mov = cur) with prm.match -- ransac_'s constructor
+ *      arguments (ndt_feature_fuser_hmt.h:213), which are the defaults.  Skipped when use_feat == 0.
+ *   2. feature pose (:252-255): Tfeat = Tfeat_sensor * sensor_pose^-1, Tfeat_sensor the 4x4 built from (c, s, x, y) exactly as
+ *      ndtgpu_featbank_match_device's T16.
+ *   3. consistency gate (:279-289): the features are INCONSISTENT iff the RANSAC status is not OK or it has no inliers, or
+ *      check_consistency is set and, with diff = (Tnow * Tmotion)^-1 * Tfeat, |diff.translation| > max_translation_norm / 10 or
+ *      |eulerAngles(0,1,2)(diff)| > max_rotation_norm / 4 (the norms of the post-registration gate).
+ *   4. feature cells (:294-325): for correspondence (i, j) in the reported order (ascending i) the source cell has mean
+ *      (x_i, y_i, 0) of cur, the target cell mean (x_j, y_j, 0) of prev AS STORED, both covariance diag(feat_cov) ((2e-4, 2e-4,
+ *      1e-4), :249); both are pseudo-transformed by sensor_pose, then by Tnow (Tinit = Tnow under globalTransf, the only mode the
+ *      bank covers): mean' = T mean, cov' = R cov R^T, the loops of ndtgpu_fuser_prepare.  RESTATED AS WRITTEN, quirk included:
+ *      the stored prev points are already in the map frame when the previous call moved them, and both transforms are applied
+ *      again all the same.
+ *   5. cell order: the FLIRT cells first -- only if use_feat is set, the features are consistent and fusion2d is off (the bank
+ *      passes no cells in fusion2d) -- then the 40 odometry cells if use_odom (the last source cell un-rotated, as
+ *      ndtgpu_fuser_prepare hands them out).  A slot that ends with no cells is run by the rule ndtgpu_match_fusion_feat_batch
+ *      documents for registrations without correspondences; with neither odometry cells nor consistent features this is
+ *      upstream's use_odom_or_features = false (:341-347).
+ *   6. after the pose update (:497-502): prev <- cur.  With update_feature_map every point is moved by Tnow_new * sensor_pose --
+ *      P = the 4x4 of pose2d(x, y, theta), M = T * P, x' = M[12], y' = M[13], theta' = eulerAngles(0,1,2)(M)[2], descriptors
+ *      copied (moveInterestPointVec) -- and NDTFeatureMap::update runs: when the slot's call counter is a multiple of map_every
+ *      (4) the moved points are appended to map; the counter advances either way.  Without update_feature_map prev <- cur
+ *      unmoved and the counter stays.
+ *   7. initialize (:78-85): prev <- cur moved by initPose * sensor_pose, then the map update: the counter is 0, so it appends.
+ * DEVIATIONS:
+ *   - the (c, s) pose: upstream goes through the matcher's theta and a tf quaternion (convertOrientedPoint2DToEigen); here the
+ *     rotation is the (c, s) the matcher carries, no trigonometry.
+ *   - truncation: the matcher takes 64 correspondences per registration, so at most 64 - 40 * use_odom FLIRT cells are taken, the
+ *     FIRST ones; `truncated` reports any cut.  Upstream has no limit.
+ *   - prev_in_map_frame = 1 (default 0; an addition) uses a prev point that the previous call MOVED as it is, with the un-rotated
+ *     covariance, instead of restating the quirk of step 4.
+ *   - the points are moved without the quaternion detour of moveInterestPointVec: theta' comes from the product's rotation block.
+ *   - the caller's points are left alone: upstream's `ptsPrev = pts` aliases pointers and so also moves the caller's points;
+ *     cur is never written here.
+ *   - appending stops at the bank's max_points: the first points that fit are kept, map_overflow is set, nothing is written
+ *     outside the set.  ndtgpu_fuser_initialize_batch_feat empties the slot's map set first and resets its counter.
+ * Device form (csrc/ndt_fuserfeat.hip).  ndt_fuserfeat_offsets_kernel: one workgroup scans the slots' cell counts in slot order
+ * (ndt_block_scan, integers) into the offsets the matcher reads.  ndt_fuserfeat_cells_kernel: one wave per slot, one lane per cell
+ * pair (64 lanes = the matcher's 64 correspondences): gate, record, cells.  ndt_fuserfeat_commit_kernel: one workgroup of 256 per
+ * slot behind ndt_fuser_post_kernel: positions moved, descriptors copied coalesced, the append, the counts last by one lane.
+ * fp64, contraction off, no atomics, no workgroup waits for another; a slot's outputs depend on its own inputs only, so they
+ * are the same bits whichever batch the slot runs in.  Launches go on the caller's stream and are ordered against the feature
+ * bank's other calls through its fence, in both directions.
+ * Measured on MI355X (tools/fuser_feat_cost.py, library 0.10.0; HIP events around each call, median of 8 scan steps after a
+ * warm-up; 64 fusers x 100 k points): the plain update 3.30 ms, with cur sets of 24 points 3.79 ms (+0.49 ms), of 256 points
+ * 7.05 ms (+3.75 ms: the RANSAC's 64 workgroups run in front of the registration on the same stream). */
+typedef struct {
+    int32_t use_feat;                /* Params::useFeat (1) */
+    int32_t prev_in_map_frame;       /* see DEVIATIONS (0) */
+    int32_t map_every;               /* NDTFeatureMap::update appends on every map_every-th call (4) */
+    int32_t pad_;
+    double feat_cov[3];              /* the diagonal of the feature cells' covariance (2e-4, 2e-4, 1e-4; :249) */
+    ndtgpu_featmatch_params match;   /* ransac_ (ndt_feature_fuser_hmt.h:213): the defaults */
+} ndtgpu_fuser_feat_params;
+void ndtgpu_default_fuser_feat_params(ndtgpu_fuser_feat_params *p);
+typedef struct {
+    ndtgpu_featmatch_result ransac;  /* step 1 (zeroes when it was not run) */
+    double Tfeat[16];                /* step 2 (zeroes when RANSAC was not run) */
+    int32_t ransac_run, consistent;
+    int32_t n_feat_cells, n_odom_cells;   /* step 5: FLIRT cells taken, odometry cells */
+    int32_t truncated;               /* fewer FLIRT cells taken than there are correspondences */
+    int32_t n_prev, n_map;           /* points of the slot's prev and map sets after the call */
+    int32_t map_appended;            /* points this call appended to map */
+    int32_t map_overflow;            /* the append was cut at max_points */
+    int32_t pad_;
+} ndtgpu_fuser_feat_result;
+/* Pure host functions (no device), built on the functions the kernels call (csrc/ndt_fuserfeat.h).
+ * ndtgpu_fuser_feat_prepare: steps 2-5 for one slot (:252-334).  ransac: step 1's record (NULL: RANSAC not run); corr:
+ * ransac->n_inliers pairs (cur i, prev j); cur_pos3 / prev_pos3: n x (x, y, theta); prev_moved: the previous call moved prev
+ * (matters with prev_in_map_frame only).  rec: the record up to `truncated` (the rest zero); cells18: room for 64 records
+ * {source mean[3], cov[6] xx xy xz yy yz zz, target mean[3], cov[6]}, the odometry cells included; *n_cells of them written. */
+ndtgpu_status ndtgpu_fuser_feat_prepare(const ndtgpu_fuser_params *prm, const ndtgpu_fuser_feat_params *fprm, const double Tnow16[16],
+                                        const double Tmotion16[16], const ndtgpu_featmatch_result *ransac, const uint32_t *corr,
+                                        const double *cur_pos3, size_t n_cur, const double *prev_pos3, size_t n_prev, int prev_moved,
+                                        ndtgpu_fuser_feat_result *rec, double *cells18, uint32_t *n_cells);
+/* step 6's move of n points (x, y, theta) by T16 (:500, moveInterestPointVec) */
+ndtgpu_status ndtgpu_fuser_feat_move(const double T16[16], const double *pos3_in, size_t n, double *pos3_out);
+/* Attaches a feature bank (borrowed: it must outlive the fuser bank or the next attach): slot k's prev set is prev_set_first + k,
+ * its map set map_set_first + k.  The two ranges must lie inside the feature bank and must not overlap (NDTGPU_ERR_INVALID).
+ * prm NULL: the defaults.  ndtgpu_fuser_update_batch, ndtgpu_fuser_initialize_batch and their _host forms behave exactly as
+ * before on a bank with features attached: they leave the feature state (prev, map, the counters) UNTOUCHED. */
+ndtgpu_status ndtgpu_fuser_bank_attach_features(ndtgpu_fuser_bank *bank, ndtgpu_featbank *featbank, size_t prev_set_first,
+                                                size_t map_set_first, const ndtgpu_fuser_feat_params *prm);
+/* ndtgpu_fuser_initialize_batch / ndtgpu_fuser_update_batch with the feature path (:78-85; :245-334, 497-502): the plain entries'
+ * arguments plus cur_set_idx, HOST, count indices of the sets that hold the scans' interest points -- filled earlier, for
+ * instance by ndtgpu_featbank_extract_device on the same stream.  A cur index inside the prev / map ranges (or outside the
+ * feature bank) is refused.  Asynchronous on `stream`, as the plain entries are. */
+ndtgpu_status ndtgpu_fuser_initialize_batch_feat(ndtgpu_fuser_bank *bank, size_t first, size_t count, const double *initPose16,
+                                                 const void *xyz_dev, size_t n_points, size_t stride_bytes, size_t map_stride_bytes,
+                                                 const uint32_t *cur_set_idx, ndtgpu_stream stream);
+ndtgpu_status ndtgpu_fuser_update_batch_feat(ndtgpu_fuser_bank *bank, size_t first, size_t count, const double *Tmotion16,
+                                             const void *xyz_dev, size_t n_points, size_t stride_bytes, size_t map_stride_bytes,
+                                             const uint32_t *cur_set_idx, int update_feature_map, int update_ndt_map,
+                                             ndtgpu_stream stream);
+/* the same with the clouds in HOST memory, like ndtgpu_fuser_initialize_batch_host / ndtgpu_fuser_update_batch_host: on the
+ * bank's own stream (the cur sets were filled by a call that has returned, e.g. ndtgpu_featbank_set; the feature bank's fence
+ * orders the rest) */
+ndtgpu_status ndtgpu_fuser_initialize_batch_feat_host(ndtgpu_fuser_bank *bank, size_t first, size_t count, const double *initPose16,
+                                                      const void *xyz_host, size_t n_points, size_t stride_bytes, size_t map_stride_bytes,
+                                                      const uint32_t *cur_set_idx);
+ndtgpu_status ndtgpu_fuser_update_batch_feat_host(ndtgpu_fuser_bank *bank, size_t first, size_t count, const double *Tmotion16,
+                                                  const void *xyz_host, size_t n_points, size_t stride_bytes, size_t map_stride_bytes,
+                                                  const uint32_t *cur_set_idx, int update_feature_map, int update_ndt_map);
+/* the feature records of the LAST _feat call for the slots it covered (zeroes for the others); waits for the call in flight, as
+ * ndtgpu_fuser_poses does */
+ndtgpu_status ndtgpu_fuser_feat_results(ndtgpu_fuser_bank *bank, size_t first, size_t count, ndtgpu_fuser_feat_result *out);
+/* the cell records the LAST update call handed to the matcher, for slots [first, first + count) of it: offsets count + 1 (from
+ * 0), cells18 room for `capacity` records of 18 doubles (NDTGPU_ERR_CAPACITY when they do not fit).  For tests and for callers
+ * that drive ndtgpu_match_fusion_feat_batch themselves.  Waits for the call in flight. */
+ndtgpu_status ndtgpu_fuser_feat_cells(ndtgpu_fuser_bank *bank, size_t first, size_t count, uint32_t *offsets, double *cells18,
+                                      size_t capacity);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hi
             "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip",
             "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
             "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip", "ndt_occgrid.hip", "ndtgpu_occgrid.hip", "ndt_linkgate.hip",
-            "ndtgpu_linkgate.hip"]
+            "ndtgpu_linkgate.hip", "ndt_fuserfeat.hip"]
 
 STATUS = {0: "OK", -1: "ERR_INVALID", -2: "ERR_HIP", -3: "ERR_NO_DEVICE", -4: "ERR_CAPACITY", -5: "ERR_ALLOC"}
 
@@ -151,7 +151,10 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_default_linkgate_params", "ndtgpu_linkgate_check", "ndtgpu_linkgate_create", "ndtgpu_linkgate_destroy",
            "ndtgpu_linkgate_set_nodes", "ndtgpu_linkgate_set_nodes_device", "ndtgpu_linkgate_candidates", "ndtgpu_linkgate_valid",
            "ndtgpu_linkgate_gather", "ndtgpu_linkgate_count", "ndtgpu_linkgate_keep", "ndtgpu_linkgate_candidates_host",
-           "ndtgpu_linkgate_valid_host"]
+           "ndtgpu_linkgate_valid_host",
+           "ndtgpu_default_fuser_feat_params", "ndtgpu_fuser_feat_prepare", "ndtgpu_fuser_feat_move", "ndtgpu_fuser_bank_attach_features",
+           "ndtgpu_fuser_initialize_batch_feat", "ndtgpu_fuser_update_batch_feat", "ndtgpu_fuser_feat_results", "ndtgpu_fuser_feat_cells",
+           "ndtgpu_fuser_initialize_batch_feat_host", "ndtgpu_fuser_update_batch_feat_host"]
 
 _lib = None
 
@@ -322,6 +325,19 @@ def lib():
     L.ndtgpu_linkgate_valid_host.argtypes = [vp, C.POINTER(LinkGateParams), C.c_size_t, u32p, u32p, dp, dp]
     L.ndtgpu_linkgate_count.argtypes = [vp, C.POINTER(C.c_size_t), i32p]
     L.ndtgpu_linkgate_keep.argtypes = [vp, C.c_size_t, C.c_size_t, u32p]
+    L.ndtgpu_default_fuser_feat_params.restype = None
+    L.ndtgpu_default_fuser_feat_params.argtypes = [C.POINTER(FuserFeatParams)]
+    L.ndtgpu_fuser_feat_prepare.argtypes = [C.POINTER(FuserParams), C.POINTER(FuserFeatParams), dp, dp, C.POINTER(FeatMatchResult), u32p, dp,
+                                            C.c_size_t, dp, C.c_size_t, C.c_int, C.POINTER(FuserFeatResult), dp, u32p]
+    L.ndtgpu_fuser_feat_move.argtypes = [dp, dp, C.c_size_t, dp]
+    L.ndtgpu_fuser_bank_attach_features.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(FuserFeatParams)]
+    L.ndtgpu_fuser_initialize_batch_feat.argtypes = [vp, C.c_size_t, C.c_size_t, dp, vp, C.c_size_t, C.c_size_t, C.c_size_t, u32p, vp]
+    L.ndtgpu_fuser_update_batch_feat.argtypes = [vp, C.c_size_t, C.c_size_t, dp, vp, C.c_size_t, C.c_size_t, C.c_size_t, u32p, C.c_int, C.c_int, vp]
+    L.ndtgpu_fuser_initialize_batch_feat_host.argtypes = [vp, C.c_size_t, C.c_size_t, dp, vp, C.c_size_t, C.c_size_t, C.c_size_t, u32p]
+    L.ndtgpu_fuser_update_batch_feat_host.argtypes = [vp, C.c_size_t, C.c_size_t, dp, vp, C.c_size_t, C.c_size_t, C.c_size_t, u32p, C.c_int,
+                                                      C.c_int]
+    L.ndtgpu_fuser_feat_results.argtypes = [vp, C.c_size_t, C.c_size_t, vp]
+    L.ndtgpu_fuser_feat_cells.argtypes = [vp, C.c_size_t, C.c_size_t, u32p, dp, C.c_size_t]
     if hasattr(L, "ndtgpu_live_resources"):            # (NDTGPU_LIB may name a build from before this entry existed)
         L.ndtgpu_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
@@ -1611,6 +1627,72 @@ FUSER_RESULT_DTYPE = np.dtype([("Tnow", "<f8", (16,)), ("Tmotion_est", "<f8", (1
                                ("posecov_mean", "<f8", (3,)), ("posecov", "<f8", (9,))])
 
 
+class FuserFeatParams(C.Structure):
+    _fields_ = [("use_feat", C.c_int32), ("prev_in_map_frame", C.c_int32), ("map_every", C.c_int32), ("pad_", C.c_int32),
+                ("feat_cov", C.c_double * 3), ("match", FeatMatchParams)]
+
+
+class FuserFeatResult(C.Structure):
+    _fields_ = [("ransac", FeatMatchResult), ("Tfeat", C.c_double * 16), ("ransac_run", C.c_int32), ("consistent", C.c_int32),
+                ("n_feat_cells", C.c_int32), ("n_odom_cells", C.c_int32), ("truncated", C.c_int32), ("n_prev", C.c_int32),
+                ("n_map", C.c_int32), ("map_appended", C.c_int32), ("map_overflow", C.c_int32), ("pad_", C.c_int32)]
+
+
+FUSER_FEAT_RESULT_DTYPE = np.dtype([("ransac", FEATMATCH_RESULT_DTYPE), ("Tfeat", "<f8", (16,)), ("ransac_run", "<i4"), ("consistent", "<i4"),
+                                    ("n_feat_cells", "<i4"), ("n_odom_cells", "<i4"), ("truncated", "<i4"), ("n_prev", "<i4"),
+                                    ("n_map", "<i4"), ("map_appended", "<i4"), ("map_overflow", "<i4"), ("pad_", "<i4")])
+assert FUSER_FEAT_RESULT_DTYPE.itemsize == C.sizeof(FuserFeatResult)
+
+
+def fuser_feat_params(**fields):
+    """ndtgpu_default_fuser_feat_params with fields replaced; feat_cov: 3 numbers; match: a FeatMatchParams or a dict of its fields"""
+    p = FuserFeatParams()
+    lib().ndtgpu_default_fuser_feat_params(C.byref(p))
+    for k, v in fields.items():
+        if k == "feat_cov":
+            p.feat_cov[:] = [float(x) for x in v]
+        elif k == "match":
+            p.match = v if isinstance(v, FeatMatchParams) else featmatch_params(**v)
+        elif k not in dict(FuserFeatParams._fields_):
+            raise TypeError("fuser_feat_params: no field %r" % k)
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def fuser_feat_prepare(params, feat_params, Tnow, Tmotion, ransac, corr, cur_pos, prev_pos, prev_moved=False):
+    """ndtgpu_fuser_feat_prepare: the gate and the cell records of one slot, no device.  Tnow / Tmotion: 4x4 row-major NumPy;
+    ransac: a FEATMATCH_RESULT_DTYPE record (or None: RANSAC not run); corr [n_inliers, 2] (cur i, prev j); cur_pos / prev_pos [n, 3]
+    -> (record FUSER_FEAT_RESULT_DTYPE [1], cells [n_cells, 18])"""
+    tn = np.ascontiguousarray(np.asarray(Tnow, dtype=np.float64).T).reshape(16).copy()
+    tm = np.ascontiguousarray(np.asarray(Tmotion, dtype=np.float64).T).reshape(16).copy()
+    cp, pp = _f64(cur_pos).reshape(-1, 3), _f64(prev_pos).reshape(-1, 3)
+    rec = np.zeros(1, dtype=FUSER_FEAT_RESULT_DTYPE)
+    cells = np.zeros((64, 18))
+    n = C.c_uint32()
+    rp = None
+    if ransac is not None:
+        rr = np.zeros(1, dtype=FEATMATCH_RESULT_DTYPE)
+        rr[0] = ransac
+        rp = C.cast(C.c_void_p(rr.ctypes.data), C.POINTER(FeatMatchResult))
+    cr = np.ascontiguousarray(corr if corr is not None else np.zeros((0, 2)), dtype=np.uint32).reshape(-1, 2)
+    u32p = C.POINTER(C.c_uint32)
+    _check(lib().ndtgpu_fuser_feat_prepare(C.byref(params), C.byref(feat_params), _dp(tn), _dp(tm), rp, cr.ctypes.data_as(u32p) if cr.size else None,
+                                           _dp(cp) if cp.size else None, cp.shape[0], _dp(pp) if pp.size else None, pp.shape[0],
+                                           1 if prev_moved else 0, C.cast(C.c_void_p(rec.ctypes.data), C.POINTER(FuserFeatResult)), _dp(cells),
+                                           C.byref(n)))
+    return rec, cells[:n.value].copy()
+
+
+def fuser_feat_move(T, pos):
+    """ndtgpu_fuser_feat_move: points [n, 3] (x, y, theta) moved by the 4x4 row-major T (moveInterestPointVec)"""
+    t = np.ascontiguousarray(np.asarray(T, dtype=np.float64).T).reshape(16).copy()
+    ps = _f64(pos).reshape(-1, 3)
+    out = np.zeros_like(ps)
+    _check(lib().ndtgpu_fuser_feat_move(_dp(t), _dp(ps) if ps.size else None, ps.shape[0], _dp(out) if ps.size else None))
+    return out
+
+
 def fuser_params(**fields):
     """ndtgpu_default_fuser_params with fields overridden; sensor_pose: 4x4 (row-major NumPy) or 16 column-major numbers."""
     p = FuserParams()
@@ -1671,18 +1753,60 @@ class FuserBank:
         assert xyz.dtype == torch.float32 and xyz.is_cuda and xyz.stride(2) == 1 and xyz.stride(1) == xyz.shape[2]
         return C.c_void_p(xyz.data_ptr()), int(xyz.shape[1]), 4 * int(xyz.shape[2]), 4 * int(xyz.stride(0))
 
-    def initialize(self, init_poses, xyz, first=0, stream=None):
+    def attach_features(self, fm, prev_first, map_first, **params):
+        """ndtgpu_fuser_bank_attach_features: fm a FeatureMatcher (kept alive); slot k's prev / map sets are prev_first + k /
+        map_first + k; keyword arguments: fields of ndtgpu_fuser_feat_params (fuser_feat_params)"""
+        p = fuser_feat_params(**params)
+        _check(lib().ndtgpu_fuser_bank_attach_features(self.h, fm.h, int(prev_first), int(map_first), C.byref(p)))
+        self._features, self.feat_params = fm, p
+
+    @staticmethod
+    def _sets(cur_sets, n):
+        si = np.ascontiguousarray(cur_sets, dtype=np.uint32).reshape(-1)
+        if si.shape[0] != n:
+            raise ValueError("FuserBank: one cur set index per cloud")
+        return si
+
+    def initialize(self, init_poses, xyz, first=0, stream=None, cur_sets=None):
+        """cur_sets: the feature-bank sets that hold the scans' interest points (the feature path); None: the plain entry"""
         n = int(xyz.shape[0])
         T = self._poses16(init_poses, n)
         ptr, npts, stride, mstride = self._cloud_args(xyz)
-        _check(lib().ndtgpu_fuser_initialize_batch(self.h, int(first), n, _dp(T), ptr, npts, stride, mstride, _stream_ptr(stream)))
+        if cur_sets is None:
+            _check(lib().ndtgpu_fuser_initialize_batch(self.h, int(first), n, _dp(T), ptr, npts, stride, mstride, _stream_ptr(stream)))
+            return
+        si = self._sets(cur_sets, n)
+        _check(lib().ndtgpu_fuser_initialize_batch_feat(self.h, int(first), n, _dp(T), ptr, npts, stride, mstride,
+                                                        si.ctypes.data_as(C.POINTER(C.c_uint32)), _stream_ptr(stream)))
 
-    def update(self, Tmotion, xyz, first=0, update_ndt_map=True, stream=None):
+    def update(self, Tmotion, xyz, first=0, update_ndt_map=True, stream=None, cur_sets=None, update_feature_map=True):
+        """cur_sets / update_feature_map: the feature path (ndtgpu_fuser_update_batch_feat); cur_sets None: the plain entry"""
         n = int(xyz.shape[0])
         T = self._poses16(Tmotion, n)
         ptr, npts, stride, mstride = self._cloud_args(xyz)
-        _check(lib().ndtgpu_fuser_update_batch(self.h, int(first), n, _dp(T), ptr, npts, stride, mstride, 1 if update_ndt_map else 0,
-                                               _stream_ptr(stream)))
+        if cur_sets is None:
+            _check(lib().ndtgpu_fuser_update_batch(self.h, int(first), n, _dp(T), ptr, npts, stride, mstride, 1 if update_ndt_map else 0,
+                                                   _stream_ptr(stream)))
+            return
+        si = self._sets(cur_sets, n)
+        _check(lib().ndtgpu_fuser_update_batch_feat(self.h, int(first), n, _dp(T), ptr, npts, stride, mstride,
+                                                    si.ctypes.data_as(C.POINTER(C.c_uint32)), 1 if update_feature_map else 0,
+                                                    1 if update_ndt_map else 0, _stream_ptr(stream)))
+
+    def feat_results(self, first=0, count=None):
+        """the feature records of the last call with cur_sets: FUSER_FEAT_RESULT_DTYPE [n]; waits for the bank"""
+        n = self.n - first if count is None else int(count)
+        res = np.zeros(n, dtype=FUSER_FEAT_RESULT_DTYPE)
+        _check(lib().ndtgpu_fuser_feat_results(self.h, int(first), n, C.c_void_p(res.ctypes.data)))
+        return res
+
+    def feat_cells(self, first=0, count=None):
+        """the cell records the last update handed to the matcher -> list of n arrays [n_cells, 18]; waits for the bank"""
+        n = self.n - first if count is None else int(count)
+        off = np.zeros(n + 1, dtype=np.uint32)
+        cells = np.zeros((64 * max(n, 1), 18))
+        _check(lib().ndtgpu_fuser_feat_cells(self.h, int(first), n, off.ctypes.data_as(C.POINTER(C.c_uint32)), _dp(cells), cells.shape[0]))
+        return [cells[off[k]:off[k + 1]].copy() for k in range(n)]
 
     def poses(self, first=0, count=None):
         """-> (Tnow [n,4,4] row-major, results of the last update call: FUSER_RESULT_DTYPE [n]); waits for the bank"""

@@ -92,6 +92,26 @@ NDT_D unsigned ndt_block_count(unsigned c, NdtBlockCounts<WAVES> &cnt, int &par)
     return n;
 }
 
+// Ordered exclusive scan of c in thread order: the sum of c over the threads below this one; total: over all of them.  The wave
+// scan of ndt_block_count, the waves' totals through LDS.  Integer sums: the same result on every run.
+template <int WAVES>
+NDT_D unsigned ndt_block_scan(unsigned c, NdtBlockCounts<WAVES> &cnt, int &par, unsigned &total)
+{
+    const unsigned wave = threadIdx.x >> 6;
+    const unsigned incl = ndt_wave_incl_scan(c);
+    if ((threadIdx.x & 63) == 63) cnt.v[par][wave] = incl;
+    __syncthreads();
+    unsigned below = 0;
+    total = 0;
+    for (unsigned w = 0; w < (unsigned)WAVES; w++) {
+        const unsigned t = cnt.v[par][w];
+        below += w < wave ? t : 0u;
+        total += t;
+    }
+    par ^= 1;
+    return below + incl - c;
+}
+
 // Ordered compaction: where `keep`, the number of kept threads below this one (the kept threads get 0 .. total - 1 in thread
 // order); total: all of them.  A ballot and a population count per wave, the waves' counts through LDS.
 template <int WAVES>

@@ -4,35 +4,12 @@
 // launches; the matching runs in csrc/ndt_featmatch.hip.  The bank's sets are filled by ndtgpu_featbank_set or, from laser scans, by
 // ndtgpu_featbank_extract* (detector_->detect + descriptor_->describe, ndt_feature2d_fuser.cpp:766-779; the kernel is
 // csrc/ndt_featextract.hip).
-#include "ndtgpu_host.h"
-#include "ndt_featmatch.h"
+#include "ndtgpu_featbank.h"
 #include "ndt_featextract.h"
 
 #include <new>
 
-struct ndtgpu_featbank {
-    NdtFeatBankView v{};                   // what the kernel receives: filled from the owners below at create
-    DeviceBuffer<uint32_t> count;
-    DeviceBuffer<double> pos, desc;
-    // the last host-index match: its indices and outputs
-    size_t n_last = 0;
-    DeviceBuffer<uint32_t> idx, corr;      // idx: ref indices, then mov indices
-    DeviceBuffer<ndtgpu_featmatch_result> results;
-    DeviceBuffer<double> T16;
-    PinnedBuffer<uint32_t> idx_pin;
-    // the last host-range extraction: its inputs and outputs
-    size_t n_last_extract = 0;
-    DeviceBuffer<uint32_t> ex_idx, ex_beam;
-    DeviceBuffer<int32_t> ex_level;
-    DeviceBuffer<double> ex_ranges, ex_response;
-    DeviceBuffer<ndtgpu_featextract_result> ex_results;
-    PinnedBuffer<double> ex_ranges_pin;
-    PinnedBuffer<uint32_t> ex_idx_pin;
-    Fence used;                            // recorded after the last launch of a call
-    Stream hst;                            // set's copies (last: ndtgpu_resource.h)
-};
-
-static ndtgpu_status featmatch_params_dev(const char *what, const ndtgpu_featmatch_params *prm, NdtFeatMatchParamsDev &d)
+ndtgpu_status featmatch_params_dev(const char *what, const ndtgpu_featmatch_params *prm, NdtFeatMatchParamsDev &d)
 {
     ndtgpu_featmatch_params p;
     ndtgpu_default_featmatch_params(&p);

@@ -16,12 +16,19 @@
 //   * NDTFeatureGraph::updateLinksUsingNDTRegistration registers ALL links in one batched call each for the matcher, the
 //     covariance and the overlap score (three calls per batch instead of three per link), never blocks on stdin
 //     (graph.cpp:318-328) and reports non-convergence in NDTFeatureLink::converged.
-// Configurations the device path does not cover are rejected loudly (ndtgpu_host::Error), never silently ignored: the FLIRT
-// interest points (InterestPointVec is an empty placeholder: out of scope), globalTransf = false,
-// loadCentroid = false.  In a catkin build that needs those the reference's own ndt_feature_fuser_hmt.cpp runs against
+//   * the FLIRT feature path (useFeat): initialize / update overloads that take ndt_feature::InterestPointGPUVec
+//     (ndt_feature_map_gpu.h) stage the points into the bank's feature sets and run ndtgpu_fuser_*_batch_feat_host: RANSAC
+//     against the previous scan, the consistency gate, the FLIRT cells in front of the odometry cells, the points moved and
+//     appended to the node's feature map (ndt_feature_fuser_hmt.cpp:245-334, 497-502), all in the same device call.
+//     getFeatureMap() reads a node's map back; NDTFeatureGraph::matchNodesUsingFeatureMap (ndt_feature_node.h:254-256) matches
+//     two nodes' maps on the device.  computeLink itself is not rewired.  The overloads that take the empty placeholder
+//     InterestPointVec stay and run without features.
+// Configurations the device path does not cover are rejected loudly (ndtgpu_host::Error), never silently ignored:
+// globalTransf = false, loadCentroid = false.  In a catkin build that needs those the reference's own ndt_feature_fuser_hmt.cpp runs against
 // lslgeneric_gpu.h instead.
 #pragma once
 #include "lslgeneric_gpu.h"
+#include "ndt_feature_map_gpu.h"
 
 #include <cstdlib>
 #include <iostream>
@@ -219,7 +226,11 @@ public:
     {
         check(ndtgpu_fuser_bank_create(&p, pool_->size(), pool_->handle(), &bank_), "ndtgpu_fuser_bank_create");
     }
-    ~FuserBank() { ndtgpu_fuser_bank_destroy(bank_); }
+    ~FuserBank()
+    {
+        ndtgpu_fuser_bank_destroy(bank_);              // (waits for its last call, which may still use the feature bank)
+        if (feat_) ndtgpu_featbank_destroy(feat_);
+    }
     FuserBank(const FuserBank &) = delete;
     FuserBank &operator=(const FuserBank &) = delete;
     const ndtgpu_fuser_params &params() const { return prm_; }
@@ -253,7 +264,90 @@ public:
         return T;
     }
 
+    // ---- the feature path (include/ndtgpu.h "the fuser bank's feature path"): a feature bank of the bank's own with three sets
+    // per slot -- [0, n) the scans' points (cur), [n, 2n) ptsPrev, [2n, 3n) the feature maps
+    void attachFeatures(size_t max_points = 256, size_t desc_len = 48, const ndtgpu_fuser_feat_params *prm = nullptr)
+    {
+        if (feat_) throw Error(NDTGPU_ERR_INVALID, "FuserBank::attachFeatures: already attached");
+        const size_t n = pool_->size();
+        check(ndtgpu_featbank_create(3 * n, max_points, desc_len, &feat_), "ndtgpu_featbank_create");
+        feat_max_points_ = max_points;
+        feat_desc_len_ = desc_len;
+        check(ndtgpu_fuser_bank_attach_features(bank_, feat_, n, 2 * n, prm), "ndtgpu_fuser_bank_attach_features");
+    }
+    ndtgpu_featbank *features() const { return feat_; }
+    size_t featMaxPoints() const { return feat_max_points_; }
+    size_t curSet(size_t slot) const { return slot; }
+    size_t prevSet(size_t slot) const { return pool_->size() + slot; }
+    size_t mapSet(size_t slot) const { return 2 * pool_->size() + slot; }
+    // initialize / update with the scans' interest points: staged into the cur sets with ndtgpu_featbank_set, then ONE call
+    void initialize(size_t first, const std::vector<Eigen::Affine3d> &initPos, const std::vector<const pcl::PointCloud<pcl::PointXYZ> *> &clouds,
+                    const std::vector<const ndt_feature::InterestPointGPUVec *> &pts)
+    {
+        const std::vector<uint32_t> cur = stage(first, clouds.size(), pts);
+        pack(clouds);
+        std::vector<double> T = flat(initPos);
+        check(ndtgpu_fuser_initialize_batch_feat_host(bank_, first, clouds.size(), T.data(), pts_.data(), np_, 16, np_ * 16, cur.data()),
+              "ndtgpu_fuser_initialize_batch_feat_host");
+    }
+    std::vector<ndtgpu_fuser_result> update(size_t first, const std::vector<Eigen::Affine3d> &Tmotion,
+                                            const std::vector<const pcl::PointCloud<pcl::PointXYZ> *> &clouds,
+                                            const std::vector<const ndt_feature::InterestPointGPUVec *> &pts, bool updateFeatureMap = true,
+                                            bool updateNDTMap = true)
+    {
+        if (Tmotion.size() != clouds.size()) throw Error(NDTGPU_ERR_INVALID, "FuserBank::update: one odometry increment per cloud");
+        const std::vector<uint32_t> cur = stage(first, clouds.size(), pts);
+        pack(clouds);
+        std::vector<double> T = flat(Tmotion);
+        check(ndtgpu_fuser_update_batch_feat_host(bank_, first, clouds.size(), T.data(), pts_.data(), np_, 16, np_ * 16, cur.data(),
+                                                  updateFeatureMap ? 1 : 0, updateNDTMap ? 1 : 0),
+              "ndtgpu_fuser_update_batch_feat_host");
+        std::vector<ndtgpu_fuser_result> res(clouds.size());
+        std::vector<double> now(16 * clouds.size());
+        check(ndtgpu_fuser_poses(bank_, first, clouds.size(), now.data(), res.data()), "ndtgpu_fuser_poses");
+        return res;
+    }
+    std::vector<ndtgpu_fuser_feat_result> featResults(size_t first, size_t count)
+    {
+        std::vector<ndtgpu_fuser_feat_result> res(count);
+        check(ndtgpu_fuser_feat_results(bank_, first, count, res.data()), "ndtgpu_fuser_feat_results");
+        return res;
+    }
+    // a set of the feature bank read back (a slot's feature map: mapSet(slot))
+    ndt_feature::InterestPointGPUVec readSet(size_t set)
+    {
+        if (!feat_) throw Error(NDTGPU_ERR_INVALID, "FuserBank::readSet: no feature bank attached");
+        std::vector<double> pos(3 * feat_max_points_), desc(feat_max_points_ * feat_desc_len_);
+        size_t m = 0;
+        check(ndtgpu_featbank_get(feat_, set, &m, pos.data(), desc.data()), "ndtgpu_featbank_get");
+        ndt_feature::InterestPointGPUVec out(m);
+        for (size_t i = 0; i < m; i++) {
+            out[i].x = pos[3 * i]; out[i].y = pos[3 * i + 1]; out[i].theta = pos[3 * i + 2];
+            out[i].descriptor.assign(desc.begin() + i * feat_desc_len_, desc.begin() + (i + 1) * feat_desc_len_);
+        }
+        return out;
+    }
+
 private:
+    std::vector<uint32_t> stage(size_t first, size_t count, const std::vector<const ndt_feature::InterestPointGPUVec *> &pts)
+    {
+        if (!feat_) throw Error(NDTGPU_ERR_INVALID, "FuserBank: call attachFeatures first");
+        if (pts.size() != count) throw Error(NDTGPU_ERR_INVALID, "FuserBank: one set of interest points per cloud");
+        std::vector<uint32_t> cur(count);
+        std::vector<double> pos, desc;
+        for (size_t k = 0; k < count; k++) {
+            pos.clear();
+            desc.clear();
+            for (const ndt_feature::InterestPointGPU &p : *pts[k]) {
+                if (p.descriptor.size() != feat_desc_len_) throw Error(NDTGPU_ERR_INVALID, "FuserBank: a descriptor of another length than the bank's");
+                pos.push_back(p.x); pos.push_back(p.y); pos.push_back(p.theta);
+                desc.insert(desc.end(), p.descriptor.begin(), p.descriptor.end());
+            }
+            cur[k] = (uint32_t)curSet(first + k);
+            check(ndtgpu_featbank_set(feat_, cur[k], pts[k]->size(), pos.data(), desc.data()), "ndtgpu_featbank_set");
+        }
+        return cur;
+    }
     static std::vector<double> flat(const std::vector<Eigen::Affine3d> &T)
     {
         std::vector<double> o(16 * T.size());
@@ -278,6 +372,8 @@ private:
     std::shared_ptr<MapPool> pool_;
     ndtgpu_fuser_params prm_;
     ndtgpu_fuser_bank *bank_ = nullptr;
+    ndtgpu_featbank *feat_ = nullptr;
+    size_t feat_max_points_ = 0, feat_desc_len_ = 0;
     std::vector<float> pts_;
     size_t np_ = 0;
 };
@@ -419,6 +515,47 @@ public:
         absorb(bank_->update(slot_, {Tmotion}, {&cloudOrig}, updateNDTMap)[0], Tmotion);
         return Tnow;
     }
+    // ---- with the scans' interest points (ndt_feature_map_gpu.h: InterestPointGPUVec): the feature path of the device call --
+    // RANSAC against the previous scan's points, the consistency gate, the FLIRT cells in front of the odometry cells
+    // (ndt_feature_fuser_hmt.cpp:245-334), the points moved and appended to the feature map (:497-502).  The bank gets a feature
+    // bank on first use (max 256 points per set, descriptors of the first point's length).
+    void initialize(Eigen::Affine3d initPos, const pcl::PointCloud<pcl::PointXYZ> &cloudOrig, const InterestPointGPUVec &pts, bool /*preLoad*/ = false)
+    {
+        if (!bank_) {
+            const double c[3] = {0, 0, 0}, sz[3] = {params_.map_size_x, params_.map_size_y, params_.map_size_z};
+            auto pool = std::make_shared<ndtgpu_host::MapPool>(params_.resolution, c, sz, 1);
+            bank_ = std::make_shared<ndtgpu_host::FuserBank>(bankParams(params_, motion_params_, sensor_pose), pool);
+            slot_ = 0;
+        }
+        ensureFeatures(pts);
+        if (map != NULL) delete map;
+        map = new lslgeneric::NDTMap(bank_->pool(), slot_);
+        map->initialize(initPos.translation()(0), initPos.translation()(1), 0., params_.map_size_x, params_.map_size_y, params_.map_size_z);
+        bank_->initialize(slot_, {initPos}, {&cloudOrig}, {&pts});
+        last_feat = bank_->featResults(slot_, 1)[0];
+        Tnow = Tlast_fuse = Todom = initPos;
+        isInit = true;
+    }
+    Eigen::Affine3d update(Eigen::Affine3d Tmotion, const pcl::PointCloud<pcl::PointXYZ> &cloudOrig, const InterestPointGPUVec &pts,
+                           bool updateFeatureMap = true, bool updateNDTMap = true)
+    {
+        if (!isInit) {
+            fprintf(stderr, "NDT-FuserHMT: Call Initialize first!!\n");
+            return Tnow;
+        }
+        ensureFeatures(pts);
+        absorb(bank_->update(slot_, {Tmotion}, {&cloudOrig}, {&pts}, updateFeatureMap, updateNDTMap)[0], Tmotion);
+        last_feat = bank_->featResults(slot_, 1)[0];
+        return Tnow;
+    }
+    // featuremap (ndt_feature_fuser_hmt.h): the slot's map set read back
+    NDTFeatureMapGPU getFeatureMap()
+    {
+        NDTFeatureMapGPU m;
+        if (bank_ && bank_->features()) m.map = bank_->readSet(bank_->mapSet(slot_));
+        return m;
+    }
+    ndtgpu_fuser_feat_result last_feat{};    // (added) the feature record of the last call with interest points
     // (added) what a batched caller does after FuserBank::update on this fuser's slot
     void absorb(const ndtgpu_fuser_result &r, const Eigen::Affine3d &Tmotion)
     {
@@ -433,6 +570,14 @@ public:
     size_t slot() const { return slot_; }
 
 private:
+    void ensureFeatures(const InterestPointGPUVec &pts)
+    {
+        if (bank_->features()) return;
+        ndtgpu_fuser_feat_params fp;
+        ndtgpu_default_fuser_feat_params(&fp);
+        fp.use_feat = params_.useFeat ? 1 : 0;
+        bank_->attachFeatures(256, pts.empty() ? 48 : pts[0].descriptor.size(), &fp);
+    }
     bool isInit;
     Eigen::Affine3d sensor_pose;
     Pose2dCov current_posecov;
@@ -616,11 +761,49 @@ public:
         open_node(initPose, cloud, pts, preLoad);
         Tnow = initPose;
     }
+    // ... and update with the scans' interest points: they go through to the node's fuser (its feature path)
+    void initialize(Eigen::Affine3d initPose, pcl::PointCloud<pcl::PointXYZ> &cloud, const InterestPointGPUVec &pts, bool preLoad = false)
+    {
+        open_node(initPose, cloud, pts, preLoad);
+        Tnow = initPose;
+    }
+    Eigen::Affine3d update(Eigen::Affine3d Tmotion, pcl::PointCloud<pcl::PointXYZ> &cloud, const InterestPointGPUVec &pts)
+    {
+        return update_with(Tmotion, cloud, pts);
+    }
+    // matchNodesUsingFeatureMap(ref, mov, matches, T) (ndt_feature_node.h:254-256): the RANSAC of two nodes' feature maps where
+    // they are, in the bank's device sets, without reading them back.  Returns matchFeatureMap's score (ndt_feature_map.h:104-122).
+    double matchNodesUsingFeatureMap(size_t idx_ref, size_t idx_mov, CorrespondencesGPU &matches, Eigen::Affine3d &T,
+                                     const ndtgpu_featmatch_params *params = nullptr)
+    {
+        if (!bank_ || !bank_->features()) throw ndtgpu_host::Error(NDTGPU_ERR_INVALID, "matchNodesUsingFeatureMap: the nodes have no feature maps");
+        const uint32_t ref = (uint32_t)bank_->mapSet(nodes_[idx_ref].map->slot()), mov = (uint32_t)bank_->mapSet(nodes_[idx_mov].map->slot());
+        const ndtgpu_fuser_feat_result r = nodes_[idx_ref].map->last_feat, m = nodes_[idx_mov].map->last_feat;
+        if (r.n_map == 0 || m.n_map == 0) return std::numeric_limits<double>::max();
+        ndtgpu_featbank *h = bank_->features();
+        ndtgpu_host::check(ndtgpu_featbank_match(h, &ref, &mov, 1, params, nullptr), "ndtgpu_featbank_match");
+        ndtgpu_featmatch_result res;
+        double T16[16];
+        std::vector<uint32_t> corr(2 * bank_->featMaxPoints());
+        ndtgpu_host::check(ndtgpu_featbank_results(h, 0, 1, &res, T16, corr.data()), "ndtgpu_featbank_results");
+        matches.clear();
+        for (int k = 0; k < res.n_inliers; k++) matches.emplace_back(corr[2 * k], corr[2 * k + 1]);
+        if (res.status == NDTGPU_FEATMATCH_NO_HYPOTHESIS) return std::numeric_limits<double>::max();
+        for (int e = 0; e < 16; e++) T.data()[e] = T16[e];
+        return res.score;
+    }
 
     // update(Tmotion, cloud, pts) -- ndt_feature_graph.cpp:60-144: the scan goes to the current node's fuser; once the robot
     // has moved newNodeTranslDist inside a node, the scan is only LOCALISED there (no fuse-in) and becomes the first scan of
     // a new node at the pose that localisation gave.  Returns the pose in world coordinates.
     Eigen::Affine3d update(Eigen::Affine3d Tmotion, pcl::PointCloud<pcl::PointXYZ> &cloud, const InterestPointVec &pts)
+    {
+        return update_with(Tmotion, cloud, pts);
+    }
+
+private:
+    template <class Pts>
+    Eigen::Affine3d update_with(Eigen::Affine3d Tmotion, pcl::PointCloud<pcl::PointXYZ> &cloud, const Pts &pts)
     {
         distance_moved_in_last_node_ += Tmotion.translation().norm();
         const bool leave = distance_moved_in_last_node_ > params_.newNodeTranslDist;
@@ -646,6 +829,8 @@ public:
         cur.nbUpdates++;
         return Tnow;
     }
+
+public:
 
     // computeLink (graph.cpp:162-177) without the FLIRT feature match that seeds link.T upstream (out of scope): the
     // relative pose of the node estimates, scored by the occupancy overlap like the reference
@@ -767,7 +952,8 @@ protected:
         return new NDTFeatureFuserHMT(fuser_params_, bank_, pool_->allocate());
     }
     // a new node at world pose `at`, its map started from `cloud`
-    void open_node(const Eigen::Affine3d &at, pcl::PointCloud<pcl::PointXYZ> &cloud, const InterestPointVec &pts, bool preLoad)
+    template <class Pts>
+    void open_node(const Eigen::Affine3d &at, pcl::PointCloud<pcl::PointXYZ> &cloud, const Pts &pts, bool preLoad)
     {
         NDTFeatureNode node;
         node.T = at;

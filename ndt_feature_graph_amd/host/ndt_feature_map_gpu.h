@@ -15,8 +15,12 @@
 //                                                 deviates from flirtlib's CurvatureDetector and BetaGridGenerator)
 // A caller may also fill InterestPointGPU from flirtlib's own points (position, BetaGrid histogram flattened row by row:
 // flirtlib_utils.h:32-42 gives bin_rho 4 x bin_phi 12).
-// NOT WIRED: NDTFeatureGraph::computeLink and the fuser's InterestPointVec (host/ndt_feature_graph_gpu.h, still an empty
-// placeholder) do not call this header; a caller chains detectAndDescribe -> NDTFeatureMapGPU::update -> matchFeatureMap itself.
+// WIRED: host/ndt_feature_graph_gpu.h takes InterestPointGPUVec in NDTFeatureFuserHMT / NDTFeatureGraph initialize and update (the
+// fuser bank's feature path: the feature term of the registration and the node feature maps, on the device), reads a node's
+// feature map back as an NDTFeatureMapGPU (getFeatureMap) and matches two nodes' maps where they are
+// (matchNodesUsingFeatureMap).  Its InterestPointVec overloads remain an empty placeholder without features.
+// NOT WIRED: NDTFeatureGraph::computeLink still seeds link.T from the node poses; a caller that wants the RANSAC seed calls
+// matchNodesUsingFeatureMap (or computeAllPossibleFeatureLinks on maps it read back) itself.
 // There is no CPU fallback: a failed C-ABI call throws ndtgpu_host::Error.
 #pragma once
 #include "lslgeneric_gpu.h"
