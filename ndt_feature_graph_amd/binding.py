@@ -13,7 +13,7 @@ _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hi
             "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip",
             "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
             "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip", "ndt_occgrid.hip", "ndtgpu_occgrid.hip", "ndt_linkgate.hip",
-            "ndtgpu_linkgate.hip", "ndt_fuserfeat.hip"]
+            "ndtgpu_linkgate.hip", "ndt_fuserfeat.hip", "ndt_scanproject.hip", "ndtgpu_scanproject.hip"]
 
 STATUS = {0: "OK", -1: "ERR_INVALID", -2: "ERR_HIP", -3: "ERR_NO_DEVICE", -4: "ERR_CAPACITY", -5: "ERR_ALLOC"}
 
@@ -154,7 +154,9 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_linkgate_valid_host",
            "ndtgpu_default_fuser_feat_params", "ndtgpu_fuser_feat_prepare", "ndtgpu_fuser_feat_move", "ndtgpu_fuser_bank_attach_features",
            "ndtgpu_fuser_initialize_batch_feat", "ndtgpu_fuser_update_batch_feat", "ndtgpu_fuser_feat_results", "ndtgpu_fuser_feat_cells",
-           "ndtgpu_fuser_initialize_batch_feat_host", "ndtgpu_fuser_update_batch_feat_host"]
+           "ndtgpu_fuser_initialize_batch_feat_host", "ndtgpu_fuser_update_batch_feat_host",
+           "ndtgpu_default_scanproject_params", "ndtgpu_scanproj_tile", "ndtgpu_scanproj_check", "ndtgpu_scanproj_beam",
+           "ndtgpu_scanproj_create", "ndtgpu_scanproj_destroy", "ndtgpu_scanproj_project_device", "ndtgpu_scanproj_project"]
 
 _lib = None
 
@@ -338,6 +340,19 @@ def lib():
                                                       C.c_int]
     L.ndtgpu_fuser_feat_results.argtypes = [vp, C.c_size_t, C.c_size_t, vp]
     L.ndtgpu_fuser_feat_cells.argtypes = [vp, C.c_size_t, C.c_size_t, u32p, dp, C.c_size_t]
+    L.ndtgpu_default_scanproject_params.restype = None
+    L.ndtgpu_default_scanproject_params.argtypes = [C.POINTER(ScanProjectParams)]
+    L.ndtgpu_scanproj_tile.restype = C.c_uint32
+    L.ndtgpu_scanproj_tile.argtypes = []
+    L.ndtgpu_scanproj_check.argtypes = [C.c_size_t, C.c_size_t, C.c_double, C.c_double, C.c_size_t, C.c_size_t, C.POINTER(ScanProjectParams)]
+    L.ndtgpu_scanproj_beam.argtypes = [C.POINTER(ScanProjectParams), C.c_double, C.c_double, C.c_uint64, C.c_uint32, C.c_double,
+                                       C.POINTER(C.c_float)]
+    L.ndtgpu_scanproj_create.argtypes = [C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.ndtgpu_scanproj_destroy.argtypes = [vp]
+    L.ndtgpu_scanproj_project_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_double, C.c_double, C.POINTER(ScanProjectParams),
+                                                 vp, C.c_size_t, C.c_size_t, vp, vp]
+    L.ndtgpu_scanproj_project.argtypes = [vp, dp, C.POINTER(C.c_uint64), C.c_size_t, C.c_size_t, C.c_double, C.c_double,
+                                          C.POINTER(ScanProjectParams), vp, C.c_size_t, C.c_size_t, u32p]
     if hasattr(L, "ndtgpu_live_resources"):            # (NDTGPU_LIB may name a build from before this entry existed)
         L.ndtgpu_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
@@ -1815,6 +1830,97 @@ class FuserBank:
         res = np.zeros(n, dtype=FUSER_RESULT_DTYPE)
         _check(lib().ndtgpu_fuser_poses(self.h, int(first), n, _dp(T), C.c_void_p(res.ctypes.data)))
         return np.transpose(T.reshape(n, 4, 4), (0, 2, 1)).copy(), res
+
+
+class ScanProjectParams(C.Structure):
+    _fields_ = [("r_min", C.c_double), ("r_max", C.c_double), ("varz", C.c_double), ("seed", C.c_uint64)]
+
+
+SCANPROJECT_TILE = 1024      # ndtgpu_scanproj_tile(): the beams of a tile
+
+
+def scanproject_params(**fields):
+    """ndtgpu_default_scanproject_params (r_min 0.5, r_max 30.0, varz 0.02, seed 0) with fields replaced"""
+    p = ScanProjectParams()
+    lib().ndtgpu_default_scanproject_params(C.byref(p))
+    for k, v in fields.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown scan-projection parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def scan_project_beam(angle_min, angle_increment, scan_id, i, r, **params):
+    """ndtgpu_scanproj_beam on the host: (x, y, z) as float32 [3] of beam i with range r of scan scan_id, or None where the beam
+    is dropped"""
+    p = scanproject_params(**params)
+    xyz = (C.c_float * 3)()
+    kept = lib().ndtgpu_scanproj_beam(C.byref(p), float(angle_min), float(angle_increment), int(scan_id), int(i), float(r), xyz)
+    return np.array(xyz[:], dtype=np.float32) if kept else None
+
+
+class ScanProjector:
+    """ndtgpu_scanproj: a batch of laser scans (ranges, beam i at angle_min + i * angle_increment) to the clouds in the sensor frame
+    that the fuser bank and the registrar take (include/ndtgpu.h "laser-scan projection"): the kept points in beam order, NaN rows
+    behind them."""
+
+    def __init__(self, max_scans, max_beams):
+        h = C.c_void_p()
+        _check(lib().ndtgpu_scanproj_create(int(max_scans), int(max_beams), C.byref(h)))
+        self.h, self.max_scans, self.max_beams = h, int(max_scans), int(max_beams)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ndtgpu_scanproj_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def project(self, ranges, angle_min, angle_increment, scan_ids=None, stride=12, **params):
+        """HOST ranges [n, n_beams] -> (xyz float32 [n, n_beams, stride / 4] -- floats behind the fourth are zero --, n_kept uint32
+        [n]); scan_ids: n ids (None: 0 .. n - 1); keyword arguments: fields of ndtgpu_scanproject_params.  Synchronous."""
+        rr = np.ascontiguousarray(ranges, dtype=np.float64)
+        if rr.ndim != 2 or stride % 4 != 0:
+            raise ValueError("ScanProjector.project: ranges must be [n_scans, n_beams] and stride a multiple of 4")
+        n, nb = rr.shape
+        ids = None if scan_ids is None else np.ascontiguousarray(scan_ids, dtype=np.uint64).reshape(-1)
+        if ids is not None and ids.shape[0] != n:
+            raise ValueError("ScanProjector.project: one scan id per scan")
+        xyz = np.zeros((n, nb, stride // 4), dtype=np.float32)
+        kept = np.zeros(n, dtype=np.uint32)
+        p = scanproject_params(**params)
+        _check(lib().ndtgpu_scanproj_project(self.h, _dp(rr), None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_uint64)), n, nb,
+                                             float(angle_min), float(angle_increment), C.byref(p), C.c_void_p(xyz.ctypes.data), int(stride),
+                                             nb * int(stride), kept.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return xyz, kept
+
+    def project_device(self, ranges_t, xyz_t, angle_min, angle_increment, scan_ids_t=None, n_kept_t=None, stream=None, **params):
+        """the same on torch device tensors, asynchronous on `stream`: ranges_t float64 [n, n_beams] contiguous; xyz_t float32
+        [n, n_beams, w >= 3], possibly a view of a larger tensor -- its strides give stride_bytes (rows) and map_stride_bytes
+        (scans), and a row stride of 4 floats or more gets the fourth float written; scan_ids_t int64 / uint64 [n] (None: 0 .. n - 1);
+        n_kept_t int32 [n] (read as uint32; may be None)"""
+        import torch
+        if not (ranges_t.is_cuda and ranges_t.is_contiguous() and ranges_t.dtype == torch.float64 and ranges_t.dim() == 2):
+            raise ValueError("ScanProjector.project_device: ranges_t must be a contiguous float64 device tensor [n_scans, n_beams]")
+        n, nb = int(ranges_t.shape[0]), int(ranges_t.shape[1])
+        if not (xyz_t.is_cuda and xyz_t.dtype == torch.float32 and xyz_t.dim() == 3 and xyz_t.shape[0] == n and xyz_t.shape[1] == nb and
+                xyz_t.shape[2] >= 3 and (xyz_t.stride(2) == 1)):
+            raise ValueError("ScanProjector.project_device: xyz_t must be a float32 device tensor [n_scans, n_beams, >= 3] with unit "
+                             "stride along its last axis")
+        if scan_ids_t is not None and not (scan_ids_t.is_cuda and scan_ids_t.is_contiguous() and scan_ids_t.element_size() == 8 and
+                                           scan_ids_t.numel() == n):
+            raise ValueError("ScanProjector.project_device: scan_ids_t must be a contiguous 64-bit integer device tensor [n_scans]")
+        p = scanproject_params(**params)
+        _check(lib().ndtgpu_scanproj_project_device(self.h, C.c_void_p(ranges_t.data_ptr()),
+                                                    None if scan_ids_t is None else C.c_void_p(scan_ids_t.data_ptr()), n, nb,
+                                                    float(angle_min), float(angle_increment), C.byref(p), C.c_void_p(xyz_t.data_ptr()),
+                                                    4 * int(xyz_t.stride(1)), 4 * int(xyz_t.stride(0)) if n > 1 else 4 * nb * int(xyz_t.stride(1)),
+                                                    _dev_ptr(n_kept_t, torch.int32, n, "ScanProjector.project_device n_kept_t"),
+                                                    _stream_ptr(stream)))
 
 
 def match_d2d(target_set, tmap, source_set, smap, T, **params):

@@ -13,6 +13,9 @@
 //                                                 batch of scans in ONE device call (include/ndtgpu.h, "laser-scan feature
 //                                                 extraction": the detector and descriptor are restated there, with what
 //                                                 deviates from flirtlib's CurvatureDetector and BetaGridGenerator)
+//   ndt_feature::projectLaserGPU                  projector_.projectLaser, the range gate and the z jitter of every consumer of a
+//                                                 scan (ndt_feature2d_fuser.cpp:747-765) for a batch of scans in ONE device call:
+//                                                 the pcl_cloud of every scan (include/ndtgpu.h, "laser-scan projection")
 // A caller may also fill InterestPointGPU from flirtlib's own points (position, BetaGrid histogram flattened row by row:
 // flirtlib_utils.h:32-42 gives bin_rho 4 x bin_phi 12).
 // WIRED: host/ndt_feature_graph_gpu.h takes InterestPointGPUVec in NDTFeatureFuserHMT / NDTFeatureGraph initialize and update (the
@@ -202,6 +205,43 @@ inline std::vector<InterestPointGPUVec> detectAndDescribe(const std::vector<Lase
     ndtgpu_featbank_destroy(h);
     if (rc != NDTGPU_OK) throw ndtgpu_host::Error(rc, "detectAndDescribe: " + err);
     if (records) *records = res;
+    return out;
+}
+
+// projector_.projectLaser(*msg_in, cloud), the range gate and the z jitter (ndt_feature2d_fuser.cpp:747-765, publish_graph_message.cpp:
+// 1356-1381 and the other call sites include/ndtgpu.h "laser-scan projection" lists) for a batch of scans in one device call: scan
+// b's pcl_cloud, the kept points in beam order, cut to its n_kept points.  Every scan must have the first scan's angle_min,
+// angle_increment and number of beams.  `params` is an addition (NULL: gustav_laser_tf.launch:20-23); `scan_ids` names the z
+// draws of every scan (empty: scan b has id b).
+inline std::vector<pcl::PointCloud<pcl::PointXYZ>> projectLaserGPU(const std::vector<LaserScanGPU> &scans,
+                                                                   const ndtgpu_scanproject_params *params = nullptr,
+                                                                   const std::vector<uint64_t> &scan_ids = {})
+{
+    std::vector<pcl::PointCloud<pcl::PointXYZ>> out(scans.size());
+    if (scans.empty()) return out;
+    const size_t n = scans.size(), n_beams = scans[0].ranges.size();
+    if (!scan_ids.empty() && scan_ids.size() != n) throw ndtgpu_host::Error(NDTGPU_ERR_INVALID, "projectLaserGPU: one scan id per scan");
+    std::vector<double> ranges;
+    for (size_t b = 0; b < n; b++) {
+        if (scans[b].ranges.size() != n_beams || scans[b].angle_min != scans[0].angle_min || scans[b].angle_increment != scans[0].angle_increment)
+            throw ndtgpu_host::Error(NDTGPU_ERR_INVALID, "projectLaserGPU: every scan must have the same angles and number of beams");
+        ranges.insert(ranges.end(), scans[b].ranges.begin(), scans[b].ranges.end());
+    }
+    // (the checks first: a scan without beams is refused with the library's message, not by the handle's capacity)
+    ndtgpu_host::check(ndtgpu_scanproj_check(n, n_beams, scans[0].angle_min, scans[0].angle_increment, sizeof(pcl::PointXYZ),
+                                             n_beams * sizeof(pcl::PointXYZ), params), "ndtgpu_scanproj_check");
+    ndtgpu_scanproj *h = nullptr;
+    ndtgpu_host::check(ndtgpu_scanproj_create(n, n_beams, &h), "ndtgpu_scanproj_create");
+    std::vector<pcl::PointXYZ> rows(n * n_beams);
+    std::vector<uint32_t> n_kept(n);
+    const ndtgpu_status rc = ndtgpu_scanproj_project(h, ranges.data(), scan_ids.empty() ? nullptr : scan_ids.data(), n, n_beams,
+                                                     scans[0].angle_min, scans[0].angle_increment, params, rows.data(), sizeof(pcl::PointXYZ),
+                                                     n_beams * sizeof(pcl::PointXYZ), n_kept.data());
+    const std::string err = rc == NDTGPU_OK ? std::string() : std::string(ndtgpu_last_error());
+    ndtgpu_scanproj_destroy(h);
+    if (rc != NDTGPU_OK) throw ndtgpu_host::Error(rc, "projectLaserGPU: " + err);
+    for (size_t b = 0; b < n; b++)
+        for (size_t k = 0; k < n_kept[b]; k++) out[b].push_back(rows[b * n_beams + k]);
     return out;
 }
 
