@@ -791,8 +791,8 @@ ndtgpu_status ndtgpu_mcl_mean(ndtgpu_mcl *h, size_t first, size_t count, double 
  * Device form (csrc/ndt_pgo.hip, ndt_pgo_kernel): one workgroup of 1024 threads optimises one graph from start to finish, `count`
  * graphs are `count` workgroups of one launch.  Nothing but the workgroup barrier orders its passes: no grid barrier, no queue,
  * no spin on memory, no atomics; every sum has one fixed order, so a graph's poses and result are the same bits whichever
- * batch it runs in, whatever first / count are.  A multi-workgroup form for ONE large graph is not written (the
- * untried lead).
+ * batch it runs in, whatever first / count are.  The multi-workgroup form for ONE large graph is ndtgpu_pgo_optimize_wide
+ * (the section below).
  * Measured on MI355X (tools/pgo_cost.py; grid-world graphs of 0.5 m cells, start 0.2 m / 0.1 rad off, defaults): 500 nodes and
  * 1886 links: 5 updates, 1082 inner iterations, 13.8 ms; 256 such graphs in one launch: 25.8 ms (0.10 ms per graph; 5-6 updates,
  * at most 1306 inner iterations); the replay's size, 5000 nodes and 43.5 k links: 5 updates, 2506 inner iterations, 740 ms,
@@ -855,6 +855,63 @@ ndtgpu_status ndtgpu_pgo_optimize(ndtgpu_pgo *h, size_t first, size_t count, con
 /* graph g's poses: pose3_out HOST n_nodes x (x, y, yaw); T16_out HOST n_nodes x 16 column-major or NULL; result may be NULL.
  * Waits for the handle. */
 ndtgpu_status ndtgpu_pgo_poses(ndtgpu_pgo *h, size_t g, double *pose3_out, double *T16_out, ndtgpu_pgo_result *result);
+
+/* ---- the chip-wide form of the optimiser: ONE large graph spread over the device ---------------------------------------------
+ * ndtgpu_pgo_optimize gives a graph to one workgroup, which is right for a bank of small graphs and leaves the rest of the chip
+ * idle for the one large graph the offline mapper's loop (ndt_feature_graph_opt.cpp:152-173) optimises once per round.
+ * ndtgpu_pgo_optimize_wide optimises graph g of a bank alone with the same algorithm, operation for operation -- linearisation per
+ * link, gather and 3x3 block inverse per node, block-Jacobi preconditioned conjugate gradients from zero with the same break
+ * rules, the wrapped pose update with the roll-back to the last finite iterate, the same stop rule and exit codes -- so
+ * ndtgpu_pgo_poses and ndtgpu_pgo_result mean the same, field for field; linear_iterations counts the inner iterations TAKEN,
+ * never the launches enqueued.
+ * Launch structure (csrc/ndt_pgo_wide.hip): a lane per link or per node over a grid of ceil(n / 256) workgroups, ONE PLAIN LAUNCH
+ * PER PASS on `stream`; the boundary between two launches is the only synchronisation: no grid barrier, no cooperative launch, no
+ * workgroup that waits for another, no spin on memory, no atomics, no captured graph.  Per Gauss-Newton update: one launch that
+ * gathers and starts the solve; THREE launches per inner iteration (a link pass that forms p = z + beta p of its two end nodes
+ * on the fly, a node pass that stores it and gathers A p, a node pass for alpha, x, r and z); then the pose update, the
+ * linearisation and the cost assessment.  The run's scalars travel in a control block in device memory, two copies of which a
+ * launch reads one and writes the other, so no word is written by a launch in which a workgroup reads it; every launch begins by
+ * reading it and does nothing where its phase is over.
+ * The host steers the phases: it enqueues check_every inner iterations at a time, then copies the control block to pinned
+ * memory and waits for it (also after every cost assessment).  That is why the call is SYNCHRONOUS TOWARDS THE HOST: it returns
+ * when the graph is done -- only the host can decide how many more launches to enqueue.  Launches enqueued past a stop do nothing.
+ * Summation rule: items are cut into tiles of 256 consecutive items (ndtgpu_pgo_wide_plan), a tile's sum is taken by its
+ * workgroup in the order of csrc/ndt_block.h and stored per tile; every workgroup that needs the graph's sum adds the per-tile
+ * sums in one fixed order (thread t takes t, t + 256, ... ascending, then the workgroup sum).  A node's incident links are summed
+ * in ascending link order by one lane.  The tiling follows the graph's n_nodes and n_edges alone: a graph's poses and result are
+ * the same bits for every check_every, whatever the bank's capacity, whatever the other graphs of the bank hold, and from run
+ * to run.  They are NOT the bits of ndtgpu_pgo_optimize, which adds in another order (a thread's strided items, 1024 threads):
+ * the two forms agree to rounding (tests/test_gpu_pgo_wide.py: both within ten times the model's own floor of the NumPy model).
+ * Two more device buffers (the per-tile sums and the control blocks, with a pinned mirror) are allocated by a handle's first
+ * wide call and released by ndtgpu_pgo_destroy.
+ * Measured on MI355X (tools/pgo_cost.py --wide; the graphs and defaults of the section above; one-workgroup form by device
+ * events, wide form by host wall time round the synchronous call, median of the repeats after a warm-up):
+ *   nodes / links   updates / inner iterations   one workgroup          wide, check_every 8 / 32 / 128        wide per inner iteration
+ *   500 / 1886      5 / 1082                    13.5 ms (12.5 us each)  18.6 / 17.0 / 17.7 ms  (0.80 x)       15.7 us
+ *   1500 / 8575     6 / 1965                    93.9 ms (47.8 us each)  40.9 / 37.8 / 36.2 ms  (2.5 x)        19.2 us
+ *   5000 / 43 509   5 / 2506                    740 ms  (295 us each)   64.1 / 59.2 / 58.0 ms  (12.5 x)       23.6 us
+ * (ratios at the default check_every, 32; every run converged, both forms took the same updates and inner iterations).  The
+ * forms cross between 500 and 1500 nodes: BELOW SOME 600 NODES (2.5 k links) ndtgpu_pgo_optimize IS THE ONE TO CALL -- and always
+ * for a bank of graphs, which it fills the chip with -- above it the wide form.  At the replay's size the device, not the host,
+ * sets the pace: the three launches of an inner iteration run 5.0 + 14.0 + 4.9 us (link, node, step: rocprofv3 --kernel-trace);
+ * the node pass gathers some 17 links per lane from 20 workgroups.  Kernels (tools/kernel_resources.py pgo_wide): 18 to 74
+ * VGPRs, no spills, no scratch, 128 B of LDS each. */
+typedef struct {
+    int32_t check_every;             /* inner iterations enqueued between two looks at the control block (ours: 32; >= 1) */
+    int32_t pad_;
+} ndtgpu_pgo_wide_params;
+void ndtgpu_default_pgo_wide_params(ndtgpu_pgo_wide_params *p);
+/* pure host: the tile (256), the node and link tiles of a graph of this size and the extra device bytes the wide form needs for
+ * it (a handle allocates them for its capacity).  NDTGPU_ERR_INVALID beyond ndtgpu_pgo_create's limits (n_nodes 1 .. 2^24,
+ * n_edges <= 2^27).  Any out pointer may be NULL. */
+ndtgpu_status ndtgpu_pgo_wide_plan(size_t n_nodes, size_t n_edges, uint32_t *tile, size_t *node_tiles, size_t *edge_tiles,
+                                   size_t *extra_bytes);
+/* graph g alone, spread over the device; launches on `stream`; RETURNS WHEN THE GRAPH IS DONE (the host steers the phases).
+ * prm / wide NULL: the defaults.  The parameter checks of ndtgpu_pgo_optimize and check_every >= 1, made before the handle is
+ * read and the device is looked for.  Calls on one handle stay ordered, whichever form and stream they name.  A graph that ends
+ * with NDTGPU_PGO_NOT_FINITE does not fail the call. */
+ndtgpu_status ndtgpu_pgo_optimize_wide(ndtgpu_pgo *h, size_t g, const ndtgpu_pgo_params *prm, const ndtgpu_pgo_wide_params *wide,
+                                       ndtgpu_stream stream);
 
 /* ---- world-map assembly: the node maps of a graph, under its poses, merged into one map -------------------------------------
  * The chain scans -> feature sets -> seeded links -> registered links -> optimised poses ends in node poses; the product the

@@ -11,7 +11,7 @@ _ROOT = os.path.dirname(_HERE)
 _SO = os.path.join(_HERE, "libndtgpu.so")
 _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hip", "ndt_pack.hip", "ndt_fuser.hip", "ndtgpu_api.hip",
             "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip",
-            "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
+            "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndt_pgo_wide.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
             "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip", "ndt_occgrid.hip", "ndtgpu_occgrid.hip", "ndt_linkgate.hip",
             "ndtgpu_linkgate.hip", "ndt_fuserfeat.hip", "ndt_scanproject.hip", "ndtgpu_scanproject.hip"]
 
@@ -141,6 +141,7 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_mcl_set_particles", "ndtgpu_mcl_update", "ndtgpu_mcl_update_host", "ndtgpu_mcl_particles", "ndtgpu_mcl_mean",
            "ndtgpu_default_pgo_params", "ndtgpu_pgo_create", "ndtgpu_pgo_destroy", "ndtgpu_pgo_set_graph", "ndtgpu_pgo_set_links_device",
            "ndtgpu_pgo_optimize", "ndtgpu_pgo_poses", "ndtgpu_live_resources",
+           "ndtgpu_default_pgo_wide_params", "ndtgpu_pgo_wide_plan", "ndtgpu_pgo_optimize_wide",
            "ndtgpu_default_featmatch_params", "ndtgpu_featbank_create", "ndtgpu_featbank_destroy", "ndtgpu_featbank_set",
            "ndtgpu_featbank_match", "ndtgpu_featbank_match_device", "ndtgpu_featbank_results",
            "ndtgpu_default_featextract_params", "ndtgpu_featbank_extract", "ndtgpu_featbank_extract_device",
@@ -285,6 +286,11 @@ def lib():
     L.ndtgpu_pgo_set_links_device.argtypes = [vp, C.c_size_t, C.c_size_t, dp, C.c_size_t, u32p, u32p, vp, vp, vp]
     L.ndtgpu_pgo_optimize.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(PgoParams), vp]
     L.ndtgpu_pgo_poses.argtypes = [vp, C.c_size_t, dp, dp, C.POINTER(PgoResult)]
+    L.ndtgpu_default_pgo_wide_params.restype = None
+    L.ndtgpu_default_pgo_wide_params.argtypes = [C.POINTER(PgoWideParams)]
+    L.ndtgpu_pgo_wide_plan.argtypes = [C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                       C.POINTER(C.c_size_t)]
+    L.ndtgpu_pgo_optimize_wide.argtypes = [vp, C.c_size_t, C.POINTER(PgoParams), C.POINTER(PgoWideParams), vp]
     L.ndtgpu_default_featmatch_params.restype = None
     L.ndtgpu_default_featmatch_params.argtypes = [C.POINTER(FeatMatchParams)]
     L.ndtgpu_featbank_create.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp)]
@@ -1081,6 +1087,10 @@ class PgoResult(C.Structure):
                 ("n_edges", C.c_int32)]
 
 
+class PgoWideParams(C.Structure):
+    _fields_ = [("check_every", C.c_int32), ("pad_", C.c_int32)]
+
+
 # ndtgpu_pgo_result.exit_code (include/ndtgpu.h NDTGPU_PGO_*)
 PGO_CONVERGED, PGO_MAX_ITERATIONS, PGO_LINEAR_CAP, PGO_NOT_FINITE = 0, 1, 2, 3
 
@@ -1097,6 +1107,22 @@ def pgo_params(**fields):
         else:
             setattr(p, k, v)
     return p
+
+
+def pgo_wide_params(check_every=None):
+    """ndtgpu_default_pgo_wide_params, check_every replaced where given"""
+    p = PgoWideParams()
+    lib().ndtgpu_default_pgo_wide_params(C.byref(p))
+    if check_every is not None:
+        p.check_every = int(check_every)
+    return p
+
+
+def pgo_wide_plan(n_nodes, n_edges):
+    """ndtgpu_pgo_wide_plan -> (tile, node tiles, link tiles, extra device bytes) of a graph of this size"""
+    tile, nt, et, extra = C.c_uint32(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+    _check(lib().ndtgpu_pgo_wide_plan(int(n_nodes), int(n_edges), C.byref(tile), C.byref(nt), C.byref(et), C.byref(extra)))
+    return tile.value, nt.value, et.value, extra.value
 
 
 class PGO:
@@ -1159,6 +1185,12 @@ class PGO:
         count = self.n_graphs - first if count is None else int(count)
         p = pgo_params(**params)
         _check(lib().ndtgpu_pgo_optimize(self.h, int(first), count, C.byref(p), _stream_ptr(stream)))
+
+    def optimize_wide(self, g, stream=None, check_every=None, **params):
+        """graph g alone, spread over the device (ndtgpu_pgo_optimize_wide): returns when the graph is done; check_every: inner
+        iterations enqueued between two looks at the control block (None: the default); keyword arguments: fields of ndtgpu_pgo_params"""
+        p, w = pgo_params(**params), pgo_wide_params(check_every)
+        _check(lib().ndtgpu_pgo_optimize_wide(self.h, int(g), C.byref(p), C.byref(w), _stream_ptr(stream)))
 
     def poses(self, g, with_T=False):
         """(poses [n, 3], result dict) of graph g, with_T: (poses, T [n, 4, 4], result); waits for the handle"""
@@ -1395,7 +1427,7 @@ class LinkGate:
 
 
 def optimize_gated(pgo, g, gate, start_poses, incr_ref, incr_mov, incr_T16_dev, ref, mov, T16_dev, score_dev=None, cov36_dev=None,
-                   cov_flags_dev=None, max_rounds=10, pgo_fields=None, **params):
+                   cov_flags_dev=None, max_rounds=10, pgo_fields=None, wide=False, **params):
     """The offline mapper's loop (ndt_feature_graph_opt.cpp:152-173) on the device: every round sets the gate's nodes to the current
     poses, runs getValidLinks (gate.valid) over the matched links (ref, mov host arrays; T16_dev [m, 16], score_dev [m], cov36_dev
     [m, 36], cov_flags_dev [m] device tensors), gathers T16 / cov36 / flags of the links that stay behind the incremental links
@@ -1403,7 +1435,8 @@ def optimize_gated(pgo, g, gate, start_poses, incr_ref, incr_mov, incr_T16_dev, 
     given), downloads ONLY the keep list, and optimises graph g of `pgo` from the current poses with incremental + kept links.
     It stops when the kept count repeats, when nothing is kept, or after max_rounds rounds -- max_rounds is OURS: upstream's loop
     has no cap and can oscillate between two link sets.  start_poses: [n, 3] (x, y, yaw).  **params: fields of
-    ndtgpu_linkgate_params; pgo_fields: a dict of ndtgpu_pgo_params fields.  Returns (kept index arrays per round, final poses
+    ndtgpu_linkgate_params; pgo_fields: a dict of ndtgpu_pgo_params fields; wide: optimise with the chip-wide form
+    (PGO.optimize_wide), the one for a large graph.  Returns (kept index arrays per round, final poses
     [n, 3])."""
     import torch
     poses = _f64(start_poses).reshape(-1, 3).copy()
@@ -1440,7 +1473,10 @@ def optimize_gated(pgo, g, gate, start_poses, incr_ref, incr_mov, incr_T16_dev, 
             break
         torch.cuda.synchronize()                         # (the gathers ran on torch's stream; set_links_device takes complete arrays)
         pgo.set_links_device(g, poses, np.concatenate([iref, ref[kept]]), np.concatenate([imov, mov[kept]]), T_all, cov_all, flags_all)
-        pgo.optimize(g, 1, **(pgo_fields or {}))
+        if wide:
+            pgo.optimize_wide(g, **(pgo_fields or {}))
+        else:
+            pgo.optimize(g, 1, **(pgo_fields or {}))
         poses = pgo.poses(g)[0][:n].copy()
         if prev == kept.size:
             break

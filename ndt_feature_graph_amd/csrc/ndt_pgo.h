@@ -1,7 +1,9 @@
-// ndt_pgo.h -- what the SE(2) pose-graph kernels (csrc/ndt_pgo.hip) and their C-ABI (csrc/ndtgpu_pgo.hip) share: the device view
-// of a bank of graphs, the angle wrap, and the conversion of a registered link (T16, cov36, flags) into the factor's
-// measurement and information.  tests/pgo_model.py restates the conversion operation for operation (its results are compared
-// bit for bit), which is why it is written with +, -, *, / and sqrt alone -- the arc cosine included -- and without contraction.
+// ndt_pgo.h -- what the SE(2) pose-graph kernels (csrc/ndt_pgo.hip: one workgroup per graph; csrc/ndt_pgo_wide.hip: one graph over
+// the whole device) and their C-ABI (csrc/ndtgpu_pgo.hip) share: the device view of a bank of graphs, the angle wrap, the
+// conversion of a registered link (T16, cov36, flags) into the factor's measurement and information, and the per-link and
+// per-node bodies of the optimisation, which both kernel forms call so that they differ in the order of their sums alone.
+// tests/pgo_model.py restates the conversion operation for operation (its results are compared bit for bit), which is why it is
+// written with +, -, *, / and sqrt alone -- the arc cosine included -- and without contraction.
 #pragma once
 #include "../../include/ndtgpu.h"
 #include "ndt_math.h"
@@ -139,6 +141,177 @@ NDT_HD void ndt_pgo_link_from_registration(const double *T16, const double *cov3
                                      0.5 * (cov36[11] + cov36[31]), cov36[35], W6))
         return;
     (void)ndt_pgo_inv_sym3(0.02, 0.0, 0.0, 0.02, 0.0, 0.02, W6);
+}
+
+// ---- what the one-workgroup form (csrc/ndt_pgo.hip) and the chip-wide form (csrc/ndt_pgo_wide.hip) do per link and per node ----
+
+// y = W x, W symmetric as 6 numbers
+NDT_D void pgo_symv(const double *W, double x0, double x1, double x2, double &y0, double &y1, double &y2)
+{
+    y0 = W[0] * x0 + W[1] * x1 + W[2] * x2;
+    y1 = W[1] * x0 + W[3] * x1 + W[4] * x2;
+    y2 = W[2] * x0 + W[4] * x1 + W[5] * x2;
+}
+
+// The factor's error is e = (p_mov ominus p_ref) - z.  With c, s of t_ref and (lx, ly) = p_mov ominus p_ref's translation:
+//   J_ref = [[-c, -s, ly], [s, -c, -lx], [0, 0, -1]]      J_mov = [[c, s, 0], [-s, c, 0], [0, 0, 1]]
+// J^T w for the side of the edge the node is on
+NDT_D void pgo_jt(int side, double c, double s, double lx, double ly, double w0, double w1, double w2, double &g0, double &g1, double &g2)
+{
+    if (side == 0) {
+        g0 = -c * w0 + s * w1;
+        g1 = -s * w0 - c * w1;
+        g2 = ly * w0 - lx * w1 - w2;
+    } else {
+        g0 = c * w0 - s * w1;
+        g1 = s * w0 + c * w1;
+        g2 = w2;
+    }
+}
+
+// one graph of a bank: its arrays and its part of the scratch
+struct PgoGraph {
+    unsigned N, E;
+    double *pose;
+    const double *origin;
+    const int32_t *ref, *mov;
+    const double *meas, *info;
+    const uint32_t *adj_off, *adj;
+    double *jac, *te;
+    double *prev, *b, *x, *r, *z, *p, *ap, *dinv;
+};
+
+// graph g of the bank, with n_nodes nodes and n_edges links
+NDT_HD PgoGraph ndt_pgo_graph(const NdtPgoView &v, size_t g, unsigned n_nodes, unsigned n_edges)
+{
+    PgoGraph G;
+    G.N = n_nodes;
+    G.E = n_edges;
+    G.pose = v.pose + g * 3 * v.max_nodes;
+    G.origin = v.origin + g * 3;
+    G.ref = v.ref + g * v.max_edges;
+    G.mov = v.mov + g * v.max_edges;
+    G.meas = v.meas + g * 3 * v.max_edges;
+    G.info = v.info + g * 6 * v.max_edges;
+    G.adj_off = v.adj_off + g * (v.max_nodes + 1);
+    G.adj = v.adj + g * 2 * v.max_edges;
+    G.jac = v.jac + g * 4 * v.max_edges;
+    G.te = v.te + g * 3 * v.max_edges;
+    double *nb = v.node + g * NDT_PGO_NODE_DOUBLES * v.max_nodes;
+    G.prev = nb;
+    G.b = nb + 3 * v.max_nodes;
+    G.x = nb + 6 * v.max_nodes;
+    G.r = nb + 9 * v.max_nodes;
+    G.z = nb + 12 * v.max_nodes;
+    G.p = nb + 15 * v.max_nodes;
+    G.ap = nb + 18 * v.max_nodes;
+    G.dinv = nb + 21 * v.max_nodes;
+    return G;
+}
+
+// the prior's error on node 0
+NDT_D void pgo_prior_error(const PgoGraph &G, double &e0, double &e1, double &e2)
+{
+    e0 = G.pose[0] - G.origin[0];
+    e1 = G.pose[1] - G.origin[1];
+    e2 = ndt_pgo_wrap(G.pose[2] - G.origin[2]);
+}
+
+// the prior's term of the cost
+NDT_D double pgo_prior_cost(const PgoGraph &G, const NdtPgoParamsDev &prm)
+{
+    double e0, e1, e2, w0, w1, w2;
+    pgo_prior_error(G, e0, e1, e2);
+    pgo_symv(prm.prior, e0, e1, e2, w0, w1, w2);
+    return e0 * w0 + e1 * w1 + e2 * w2;
+}
+
+// link e at the current poses: error, the Jacobian numbers c, s, lx, ly into jac, W e into te; returns e^T W e
+NDT_D double pgo_linearise_link(const PgoGraph &G, unsigned e)
+{
+    const double *pi = G.pose + 3 * (size_t)G.ref[e], *pj = G.pose + 3 * (size_t)G.mov[e];
+    double s, c;
+    sincos(pi[2], &s, &c);
+    const double dx = pj[0] - pi[0], dy = pj[1] - pi[1];
+    const double lx = c * dx + s * dy, ly = -s * dx + c * dy;
+    const double *zm = G.meas + 3 * (size_t)e;
+    const double e0 = lx - zm[0], e1 = ly - zm[1], e2 = ndt_pgo_wrap(ndt_pgo_wrap(pj[2] - pi[2]) - zm[2]);
+    double w0, w1, w2;
+    pgo_symv(G.info + 6 * (size_t)e, e0, e1, e2, w0, w1, w2);
+    double *j = G.jac + 4 * (size_t)e, *t = G.te + 3 * (size_t)e;
+    j[0] = c; j[1] = s; j[2] = lx; j[3] = ly;
+    t[0] = w0; t[1] = w1; t[2] = w2;
+    return e0 * w0 + e1 * w1 + e2 * w2;
+}
+
+// node i: b = -gradient and the inverse of the 3x3 diagonal block of J^T W J, over the node's incident edges in ascending order
+NDT_D void pgo_gather_node(const PgoGraph &G, const NdtPgoParamsDev &prm, unsigned i)
+{
+    double g0 = 0.0, g1 = 0.0, g2 = 0.0, D[6] = {0, 0, 0, 0, 0, 0};
+    for (unsigned k = G.adj_off[i]; k < G.adj_off[i + 1]; k++) {
+        const unsigned a = G.adj[k], e = a >> 1;
+        const int side = (int)(a & 1u);
+        const double *j = G.jac + 4 * (size_t)e, *t = G.te + 3 * (size_t)e, *W = G.info + 6 * (size_t)e;
+        double h0, h1, h2;
+        pgo_jt(side, j[0], j[1], j[2], j[3], t[0], t[1], t[2], h0, h1, h2);
+        g0 += h0; g1 += h1; g2 += h2;
+        // J^T W J: column q of W J, then J^T of it
+        const double c = j[0], s = j[1], lx = j[2], ly = j[3];
+        const double Jc[3][3] = {{side ? c : -c, side ? -s : s, 0.0}, {side ? s : -s, side ? c : -c, 0.0},
+                                 {side ? 0.0 : ly, side ? 0.0 : -lx, side ? 1.0 : -1.0}};   // Jc[q] = column q of J
+        double M[3][3];
+        for (int q = 0; q < 3; q++) {
+            double u0, u1, u2;
+            pgo_symv(W, Jc[q][0], Jc[q][1], Jc[q][2], u0, u1, u2);
+            pgo_jt(side, c, s, lx, ly, u0, u1, u2, M[0][q], M[1][q], M[2][q]);
+        }
+        D[0] += M[0][0]; D[1] += M[0][1]; D[2] += M[0][2]; D[3] += M[1][1]; D[4] += M[1][2]; D[5] += M[2][2];
+    }
+    if (i == 0) {
+        double e0, e1, e2, w0, w1, w2;
+        pgo_prior_error(G, e0, e1, e2);
+        pgo_symv(prm.prior, e0, e1, e2, w0, w1, w2);
+        g0 += w0; g1 += w1; g2 += w2;
+        for (int k = 0; k < 6; k++) D[k] += prm.prior[k];
+    }
+    double *b = G.b + 3 * (size_t)i, *di = G.dinv + 6 * (size_t)i;
+    b[0] = -g0; b[1] = -g1; b[2] = -g2;
+    if (!ndt_pgo_inv_sym3(D[0], D[1], D[2], D[3], D[4], D[5], di)) {      // (an information matrix that is not positive definite)
+        di[0] = di[3] = di[5] = 1.0;
+        di[1] = di[2] = di[4] = 0.0;
+    }
+}
+
+// link e of the matrix-vector product: t_e = W (J_ref p_ref + J_mov p_mov) from the two end nodes' search directions
+NDT_D void pgo_link_product(const PgoGraph &G, unsigned e, const double *pi, const double *pj)
+{
+    const double *j = G.jac + 4 * (size_t)e;
+    const double c = j[0], s = j[1], lx = j[2], ly = j[3];
+    const double u0 = -c * pi[0] - s * pi[1] + ly * pi[2] + c * pj[0] + s * pj[1];
+    const double u1 = s * pi[0] - c * pi[1] - lx * pi[2] - s * pj[0] + c * pj[1];
+    const double u2 = pj[2] - pi[2];
+    double *t = G.te + 3 * (size_t)e;
+    pgo_symv(G.info + 6 * (size_t)e, u0, u1, u2, t[0], t[1], t[2]);
+}
+
+// node i of the matrix-vector product: (A p)_i = sum J^T t_e over the node's incident edges in ascending order, the prior's
+// block on node 0; p0..p2 is the node's search direction
+NDT_D void pgo_node_product(const PgoGraph &G, const NdtPgoParamsDev &prm, unsigned i, double p0, double p1, double p2, double &a0,
+                            double &a1, double &a2)
+{
+    a0 = 0.0; a1 = 0.0; a2 = 0.0;
+    for (unsigned q = G.adj_off[i]; q < G.adj_off[i + 1]; q++) {
+        const unsigned a = G.adj[q], e = a >> 1;
+        const double *j = G.jac + 4 * (size_t)e, *t = G.te + 3 * (size_t)e;
+        double h0, h1, h2;
+        pgo_jt((int)(a & 1u), j[0], j[1], j[2], j[3], t[0], t[1], t[2], h0, h1, h2);
+        a0 += h0; a1 += h1; a2 += h2;
+    }
+    if (i == 0) {
+        double w0, w1, w2;
+        pgo_symv(prm.prior, p0, p1, p2, w0, w1, w2);
+        a0 += w0; a1 += w1; a2 += w2;
+    }
 }
 
 // host launchers (csrc/ndt_pgo.hip)

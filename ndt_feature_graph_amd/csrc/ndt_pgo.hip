@@ -13,122 +13,26 @@
 //   matrix-vector product: a per-edge pass t_e = W (J_ref p_ref + J_mov p_mov), then a per-node gather sum J^T t_e.
 // A node is always handled by the same thread, so the vector updates between the passes need no barrier.  The vectors live in a
 // per-graph scratch area in device memory (27 doubles per node, 7 per edge), LDS holds the reductions' partial sums.
+// The per-link and per-node bodies are inlines of ndt_pgo.h, shared with the chip-wide form for one large graph (ndt_pgo_wide.hip).
 #include "ndt_pgo.h"
 #include "ndt_block.h"
 
 typedef NdtBlockSums<NDT_PGO_WAVES, 2> PgoRed;
-
-// y = W x, W symmetric as 6 numbers
-__device__ __forceinline__ void pgo_symv(const double *W, double x0, double x1, double x2, double &y0, double &y1, double &y2)
-{
-    y0 = W[0] * x0 + W[1] * x1 + W[2] * x2;
-    y1 = W[1] * x0 + W[3] * x1 + W[4] * x2;
-    y2 = W[2] * x0 + W[4] * x1 + W[5] * x2;
-}
-
-// The factor's error is e = (p_mov ominus p_ref) - z.  With c, s of t_ref and (lx, ly) = p_mov ominus p_ref's translation:
-//   J_ref = [[-c, -s, ly], [s, -c, -lx], [0, 0, -1]]      J_mov = [[c, s, 0], [-s, c, 0], [0, 0, 1]]
-// J^T w for the side of the edge the node is on
-__device__ __forceinline__ void pgo_jt(int side, double c, double s, double lx, double ly, double w0, double w1, double w2, double &g0,
-                                       double &g1, double &g2)
-{
-    if (side == 0) {
-        g0 = -c * w0 + s * w1;
-        g1 = -s * w0 - c * w1;
-        g2 = ly * w0 - lx * w1 - w2;
-    } else {
-        g0 = c * w0 - s * w1;
-        g1 = s * w0 + c * w1;
-        g2 = w2;
-    }
-}
-
-struct PgoGraph {
-    unsigned N, E;
-    double *pose;
-    const double *origin;
-    const int32_t *ref, *mov;
-    const double *meas, *info;
-    const uint32_t *adj_off, *adj;
-    double *jac, *te;
-    double *prev, *b, *x, *r, *z, *p, *ap, *dinv;
-};
-
-// the prior's error on node 0
-__device__ __forceinline__ void pgo_prior_error(const PgoGraph &G, double &e0, double &e1, double &e2)
-{
-    e0 = G.pose[0] - G.origin[0];
-    e1 = G.pose[1] - G.origin[1];
-    e2 = ndt_pgo_wrap(G.pose[2] - G.origin[2]);
-}
 
 // per edge: error, Jacobian numbers, W e.  Returns the graph's cost sum e^T W e (prior included) in every thread; its barrier
 // is the one that makes jac / te visible to the gather.
 __device__ double pgo_linearise(const PgoGraph &G, const NdtPgoParamsDev &prm, PgoRed &red, int &par)
 {
     double cost = 0.0;
-    if (threadIdx.x == 0) {
-        double e0, e1, e2, w0, w1, w2;
-        pgo_prior_error(G, e0, e1, e2);
-        pgo_symv(prm.prior, e0, e1, e2, w0, w1, w2);
-        cost = e0 * w0 + e1 * w1 + e2 * w2;
-    }
-    for (unsigned e = threadIdx.x; e < G.E; e += NDT_PGO_THREADS) {
-        const double *pi = G.pose + 3 * (size_t)G.ref[e], *pj = G.pose + 3 * (size_t)G.mov[e];
-        double s, c;
-        sincos(pi[2], &s, &c);
-        const double dx = pj[0] - pi[0], dy = pj[1] - pi[1];
-        const double lx = c * dx + s * dy, ly = -s * dx + c * dy;
-        const double *zm = G.meas + 3 * (size_t)e;
-        const double e0 = lx - zm[0], e1 = ly - zm[1], e2 = ndt_pgo_wrap(ndt_pgo_wrap(pj[2] - pi[2]) - zm[2]);
-        double w0, w1, w2;
-        pgo_symv(G.info + 6 * (size_t)e, e0, e1, e2, w0, w1, w2);
-        double *j = G.jac + 4 * (size_t)e, *t = G.te + 3 * (size_t)e;
-        j[0] = c; j[1] = s; j[2] = lx; j[3] = ly;
-        t[0] = w0; t[1] = w1; t[2] = w2;
-        cost += e0 * w0 + e1 * w1 + e2 * w2;
-    }
+    if (threadIdx.x == 0) cost = pgo_prior_cost(G, prm);
+    for (unsigned e = threadIdx.x; e < G.E; e += NDT_PGO_THREADS) cost += pgo_linearise_link(G, e);
     return ndt_block_sum(cost, red, par);
 }
 
 // per node: b = -gradient and the inverse of the 3x3 diagonal block of J^T W J, over the node's incident edges
 __device__ void pgo_gather(const PgoGraph &G, const NdtPgoParamsDev &prm)
 {
-    for (unsigned i = threadIdx.x; i < G.N; i += NDT_PGO_THREADS) {
-        double g0 = 0.0, g1 = 0.0, g2 = 0.0, D[6] = {0, 0, 0, 0, 0, 0};
-        for (unsigned k = G.adj_off[i]; k < G.adj_off[i + 1]; k++) {
-            const unsigned a = G.adj[k], e = a >> 1;
-            const int side = (int)(a & 1u);
-            const double *j = G.jac + 4 * (size_t)e, *t = G.te + 3 * (size_t)e, *W = G.info + 6 * (size_t)e;
-            double h0, h1, h2;
-            pgo_jt(side, j[0], j[1], j[2], j[3], t[0], t[1], t[2], h0, h1, h2);
-            g0 += h0; g1 += h1; g2 += h2;
-            // J^T W J: column q of W J, then J^T of it
-            const double c = j[0], s = j[1], lx = j[2], ly = j[3];
-            const double Jc[3][3] = {{side ? c : -c, side ? -s : s, 0.0}, {side ? s : -s, side ? c : -c, 0.0},
-                                     {side ? 0.0 : ly, side ? 0.0 : -lx, side ? 1.0 : -1.0}};   // Jc[q] = column q of J
-            double M[3][3];
-            for (int q = 0; q < 3; q++) {
-                double u0, u1, u2;
-                pgo_symv(W, Jc[q][0], Jc[q][1], Jc[q][2], u0, u1, u2);
-                pgo_jt(side, c, s, lx, ly, u0, u1, u2, M[0][q], M[1][q], M[2][q]);
-            }
-            D[0] += M[0][0]; D[1] += M[0][1]; D[2] += M[0][2]; D[3] += M[1][1]; D[4] += M[1][2]; D[5] += M[2][2];
-        }
-        if (i == 0) {
-            double e0, e1, e2, w0, w1, w2;
-            pgo_prior_error(G, e0, e1, e2);
-            pgo_symv(prm.prior, e0, e1, e2, w0, w1, w2);
-            g0 += w0; g1 += w1; g2 += w2;
-            for (int k = 0; k < 6; k++) D[k] += prm.prior[k];
-        }
-        double *b = G.b + 3 * (size_t)i, *di = G.dinv + 6 * (size_t)i;
-        b[0] = -g0; b[1] = -g1; b[2] = -g2;
-        if (!ndt_pgo_inv_sym3(D[0], D[1], D[2], D[3], D[4], D[5], di)) {      // (an information matrix that is not positive definite)
-            di[0] = di[3] = di[5] = 1.0;
-            di[1] = di[2] = di[4] = 0.0;
-        }
-    }
+    for (unsigned i = threadIdx.x; i < G.N; i += NDT_PGO_THREADS) pgo_gather_node(G, prm, i);
 }
 
 // Solves (J^T W J) x = b by preconditioned conjugate gradients from x = 0; returns the iterations taken, `capped` where it
@@ -157,33 +61,15 @@ __device__ int pgo_solve(const PgoGraph &G, const NdtPgoParamsDev &prm, PgoRed &
             capped = true;
             break;
         }
-        for (unsigned e = threadIdx.x; e < G.E; e += NDT_PGO_THREADS) {
-            const double *pi = G.p + 3 * (size_t)G.ref[e], *pj = G.p + 3 * (size_t)G.mov[e], *j = G.jac + 4 * (size_t)e;
-            const double c = j[0], s = j[1], lx = j[2], ly = j[3];
-            const double u0 = -c * pi[0] - s * pi[1] + ly * pi[2] + c * pj[0] + s * pj[1];
-            const double u1 = s * pi[0] - c * pi[1] - lx * pi[2] - s * pj[0] + c * pj[1];
-            const double u2 = pj[2] - pi[2];
-            double *t = G.te + 3 * (size_t)e;
-            pgo_symv(G.info + 6 * (size_t)e, u0, u1, u2, t[0], t[1], t[2]);
-        }
+        for (unsigned e = threadIdx.x; e < G.E; e += NDT_PGO_THREADS)
+            pgo_link_product(G, e, G.p + 3 * (size_t)G.ref[e], G.p + 3 * (size_t)G.mov[e]);
         __syncthreads();
         double pap = 0.0;
         for (unsigned i = threadIdx.x; i < G.N; i += NDT_PGO_THREADS) {
             const size_t o = 3 * (size_t)i;
-            double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-            for (unsigned q = G.adj_off[i]; q < G.adj_off[i + 1]; q++) {
-                const unsigned a = G.adj[q], e = a >> 1;
-                const double *j = G.jac + 4 * (size_t)e, *t = G.te + 3 * (size_t)e;
-                double h0, h1, h2;
-                pgo_jt((int)(a & 1u), j[0], j[1], j[2], j[3], t[0], t[1], t[2], h0, h1, h2);
-                a0 += h0; a1 += h1; a2 += h2;
-            }
             const double p0 = G.p[o], p1 = G.p[o + 1], p2 = G.p[o + 2];
-            if (i == 0) {
-                double w0, w1, w2;
-                pgo_symv(prm.prior, p0, p1, p2, w0, w1, w2);
-                a0 += w0; a1 += w1; a2 += w2;
-            }
+            double a0, a1, a2;
+            pgo_node_product(G, prm, i, p0, p1, p2, a0, a1, a2);
             G.ap[o] = a0; G.ap[o + 1] = a1; G.ap[o + 2] = a2;
             pap += p0 * a0 + p1 * a1 + p2 * a2;
         }
@@ -223,28 +109,7 @@ __global__ __launch_bounds__(NDT_PGO_THREADS) void ndt_pgo_kernel(NdtPgoView v, 
     int par = 0;
     const size_t g = first + blockIdx.x;
     ndtgpu_pgo_result *out = v.state + g;
-    PgoGraph G;
-    G.N = (unsigned)out->n_nodes;
-    G.E = (unsigned)out->n_edges;
-    G.pose = v.pose + g * 3 * v.max_nodes;
-    G.origin = v.origin + g * 3;
-    G.ref = v.ref + g * v.max_edges;
-    G.mov = v.mov + g * v.max_edges;
-    G.meas = v.meas + g * 3 * v.max_edges;
-    G.info = v.info + g * 6 * v.max_edges;
-    G.adj_off = v.adj_off + g * (v.max_nodes + 1);
-    G.adj = v.adj + g * 2 * v.max_edges;
-    G.jac = v.jac + g * 4 * v.max_edges;
-    G.te = v.te + g * 3 * v.max_edges;
-    double *nb = v.node + g * NDT_PGO_NODE_DOUBLES * v.max_nodes;
-    G.prev = nb;
-    G.b = nb + 3 * v.max_nodes;
-    G.x = nb + 6 * v.max_nodes;
-    G.r = nb + 9 * v.max_nodes;
-    G.z = nb + 12 * v.max_nodes;
-    G.p = nb + 15 * v.max_nodes;
-    G.ap = nb + 18 * v.max_nodes;
-    G.dinv = nb + 21 * v.max_nodes;
+    const PgoGraph G = ndt_pgo_graph(v, g, (unsigned)out->n_nodes, (unsigned)out->n_edges);
 
     int exit_code = NDTGPU_PGO_CONVERGED, iterations = 0, linear = 0;
     bool any_capped = false;

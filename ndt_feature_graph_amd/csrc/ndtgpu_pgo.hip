@@ -1,9 +1,11 @@
 // ndtgpu_pgo.hip -- C-ABI (include/ndtgpu.h) of the SE(2) pose-graph optimiser: optimizeGraphUsingISAM
 // (ndt_feature/include/ndt_feature/ndt_offline_mapper.h:40-107; call site ndt_feature/src/ndt_feature_graph_opt.cpp:152-164) for
 // a bank of independent graphs.  Host side only: the handle, the checks of a graph (index range, self links, connectivity by
-// union-find), the node-to-edge adjacency and the order of the launches; the optimisation runs in csrc/ndt_pgo.hip.
+// union-find), the node-to-edge adjacency and the order of the launches; the optimisation runs in csrc/ndt_pgo.hip and, for one
+// large graph spread over the device with the host steering the phases (ndtgpu_pgo_optimize_wide), in csrc/ndt_pgo_wide.hip.
 #include "ndtgpu_host.h"
 #include "ndt_pgo.h"
+#include "ndt_pgo_wide.h"
 
 #include <new>
 #include <numeric>
@@ -16,6 +18,12 @@ struct ndtgpu_pgo {
     DeviceBuffer<int32_t> ref, mov;
     DeviceBuffer<uint32_t> adj_off, adj;
     std::vector<uint32_t> n_nodes;         // per graph, 0: not set
+    std::vector<uint32_t> n_edges;         // per graph
+    // the chip-wide form's own (ndtgpu_pgo_optimize_wide), allocated by the handle's first wide call for the handle's capacity:
+    // per-tile partial sums, the two control blocks and their pinned mirror
+    DeviceBuffer<double> wide_part;
+    DeviceBuffer<NdtPgoWideCtl> wide_ctl;
+    PinnedBuffer<NdtPgoWideCtl> wide_mirror;
     Fence used;                            // recorded after the last launch of a call
     Stream hst;                            // the synchronous entries' stream (last: ndtgpu_resource.h)
 };
@@ -54,6 +62,22 @@ static ndtgpu_status pgo_check_graph(const char *what, size_t n_nodes, const dou
     return NDTGPU_OK;
 }
 
+// the device form of a call's parameters (NULL: the defaults); false where one is out of range
+static bool pgo_params_dev(const ndtgpu_pgo_params *prm, NdtPgoParamsDev &d)
+{
+    ndtgpu_pgo_params p;
+    ndtgpu_default_pgo_params(&p);
+    if (prm) p = *prm;
+    bool ok = p.max_iterations >= 0 && p.max_linear_iterations >= 0 && p.eps_step >= 0.0 && p.eps_linear >= 0.0;   // (NaN fails)
+    for (double w : p.prior_information) ok = ok && std::isfinite(w);
+    d.max_iterations = p.max_iterations;
+    d.max_linear_iterations = p.max_linear_iterations;
+    d.eps_step = p.eps_step;
+    d.eps_linear = p.eps_linear;
+    sym6(p.prior_information, d.prior);
+    return ok;
+}
+
 extern "C" {
 
 void ndtgpu_default_pgo_params(ndtgpu_pgo_params *p)
@@ -87,6 +111,7 @@ ndtgpu_status ndtgpu_pgo_create(size_t n_graphs, size_t max_nodes, size_t max_ed
     if (!h) return fail(NDTGPU_ERR_ALLOC, "pgo_create: host alloc");
     h->G = n_graphs;
     h->n_nodes.assign(n_graphs, 0);
+    h->n_edges.assign(n_graphs, 0);
     NdtPgoView &v = h->v;
     v.max_nodes = max_nodes;
     v.max_edges = max_edges;
@@ -140,6 +165,7 @@ static ndtgpu_status pgo_install(ndtgpu_pgo *h, const char *what, size_t g, size
     st.n_edges = (int32_t)n_edges;
     const NdtPgoView &v = h->v;
     h->n_nodes[g] = 0;
+    h->n_edges[g] = (uint32_t)n_edges;
     HIP_TRY(h->used.order(h->hst.get()));
     HIP_TRY(hipMemcpyAsync(v.pose + g * 3 * v.max_nodes, pose3, 3 * n_nodes * sizeof(double), hipMemcpyHostToDevice, h->hst.get()));
     HIP_TRY(hipMemcpyAsync(v.origin + g * 3, pose3, 3 * sizeof(double), hipMemcpyHostToDevice, h->hst.get()));
@@ -202,20 +228,10 @@ ndtgpu_status ndtgpu_pgo_optimize(ndtgpu_pgo *h, size_t first, size_t count, con
     if (!h) return fail(NDTGPU_ERR_INVALID, "pgo_optimize: null handle");
     if (count == 0 || first >= h->G || count > h->G - first)
         return fail(NDTGPU_ERR_INVALID, "pgo_optimize: graphs [first, first + count) out of range");
-    ndtgpu_pgo_params p;
-    ndtgpu_default_pgo_params(&p);
-    if (prm) p = *prm;
-    bool ok = p.max_iterations >= 0 && p.max_linear_iterations >= 0 && p.eps_step >= 0.0 && p.eps_linear >= 0.0;   // (NaN fails)
-    for (double w : p.prior_information) ok = ok && std::isfinite(w);
-    if (!ok) return fail(NDTGPU_ERR_INVALID, "pgo_optimize: bad parameter (caps and tolerances >= 0, a finite prior)");
+    NdtPgoParamsDev d;
+    if (!pgo_params_dev(prm, d)) return fail(NDTGPU_ERR_INVALID, "pgo_optimize: bad parameter (caps and tolerances >= 0, a finite prior)");
     for (size_t g = first; g < first + count; g++)
         if (!h->n_nodes[g]) return fail(NDTGPU_ERR_INVALID, "pgo_optimize: a graph of the range has not been set");
-    NdtPgoParamsDev d;
-    d.max_iterations = p.max_iterations;
-    d.max_linear_iterations = p.max_linear_iterations;
-    d.eps_step = p.eps_step;
-    d.eps_linear = p.eps_linear;
-    sym6(p.prior_information, d.prior);
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(h->used.order(st));   // (the previous call may have run on another stream)
     hipError_t e = ndt_pgo_launch(h->v, first, count, d, st);
@@ -242,6 +258,95 @@ ndtgpu_status ndtgpu_pgo_poses(ndtgpu_pgo *h, size_t g, double *pose3_out, doubl
             T[12] = p[3 * i]; T[13] = p[3 * i + 1]; T[15] = 1.0;
         }
     if (result) HIP_TRY(hipMemcpy(result, h->v.state + g, sizeof *result, hipMemcpyDeviceToHost));
+    return NDTGPU_OK;
+}
+
+void ndtgpu_default_pgo_wide_params(ndtgpu_pgo_wide_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->check_every = 32;
+}
+
+ndtgpu_status ndtgpu_pgo_wide_plan(size_t n_nodes, size_t n_edges, uint32_t *tile, size_t *node_tiles, size_t *edge_tiles, size_t *extra_bytes)
+{
+    if (n_nodes == 0 || n_nodes > (1u << 24) || n_edges > (1u << 27))
+        return fail(NDTGPU_ERR_INVALID, "pgo_wide_plan: n_nodes must be 1 .. 2^24, n_edges <= 2^27");
+    if (tile) *tile = NDT_PGO_WIDE_TILE;
+    if (node_tiles) *node_tiles = ndt_pgo_wide_tiles(n_nodes);
+    if (edge_tiles) *edge_tiles = ndt_pgo_wide_tiles(n_edges);
+    if (extra_bytes) *extra_bytes = ndt_pgo_wide_partials(n_nodes, n_edges) * sizeof(double) + 2 * sizeof(NdtPgoWideCtl);
+    return NDTGPU_OK;
+}
+
+// The host steers the phases: it enqueues the passes of ndt_pgo_wide.hip on `stream` one launch each, and after every chunk of
+// check_every inner iterations -- and after every cost assessment -- copies the control block to pinned memory and waits for it.
+// Launches enqueued past a stop do nothing, so the result does not depend on check_every.
+ndtgpu_status ndtgpu_pgo_optimize_wide(ndtgpu_pgo *h, size_t g, const ndtgpu_pgo_params *prm, const ndtgpu_pgo_wide_params *wide,
+                                       ndtgpu_stream stream)
+{
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo_optimize_wide: null handle");
+    ndtgpu_pgo_wide_params wp;
+    ndtgpu_default_pgo_wide_params(&wp);
+    if (wide) wp = *wide;
+    NdtPgoWide W{};
+    if (!pgo_params_dev(prm, W.prm))
+        return fail(NDTGPU_ERR_INVALID, "pgo_optimize_wide: bad parameter (caps and tolerances >= 0, a finite prior)");
+    if (wp.check_every < 1) return fail(NDTGPU_ERR_INVALID, "pgo_optimize_wide: check_every must be >= 1");
+    if (g >= h->G || !h->n_nodes[g]) return fail(NDTGPU_ERR_INVALID, "pgo_optimize_wide: no such graph, or it has not been set");
+    const NdtPgoView &v = h->v;
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->wide_ctl.get()) {
+        HIP_TRY(h->wide_part.alloc(ndt_pgo_wide_partials(v.max_nodes, v.max_edges)));
+        HIP_TRY(h->wide_mirror.alloc(1));
+        HIP_TRY(h->wide_ctl.alloc(2));
+    }
+    const size_t N = h->n_nodes[g], E = h->n_edges[g];
+    W.G = ndt_pgo_graph(v, g, (unsigned)N, (unsigned)E);
+    W.node_tiles = (unsigned)ndt_pgo_wide_tiles(N);
+    W.edge_tiles = (unsigned)ndt_pgo_wide_tiles(E);
+    W.part_dot = h->wide_part.get();
+    W.part_pap = W.part_dot + 2 * (size_t)W.node_tiles;
+    W.part_step = W.part_pap + W.node_tiles;
+    W.part_cost = W.part_step + W.node_tiles;
+    W.out = v.state + g;
+    NdtPgoWideCtl *ctl = h->wide_ctl.get(), *mirror = h->wide_mirror.get();
+    int cur = 0;                           // which of the two control blocks holds the state
+    // a link pass reads the control block the node pass behind it reads; a node pass writes the other one
+    auto pass = [&](NdtPgoWidePass what) -> hipError_t {
+        const bool link = ndt_pgo_wide_is_link_pass(what);
+        if (link && !E) return hipSuccess;                   // (a launch with a grid of no workgroups is an error)
+        W.src = ctl + cur;
+        W.dst = ctl + (cur ^ 1);
+        const hipError_t e = ndt_pgo_wide_launch(what, W, st);
+        if (!link) cur ^= 1;
+        return e;
+    };
+    auto look = [&]() -> hipError_t {
+        const hipError_t e = hipMemcpyAsync(mirror, ctl + cur, sizeof *mirror, hipMemcpyDeviceToHost, st);
+        return e != hipSuccess ? e : hipStreamSynchronize(st);
+    };
+    HIP_TRY(h->used.order(st));            // (the previous call may have run on another stream)
+    HIP_TRY(hipMemsetAsync(ctl, 0, 2 * sizeof *ctl, st));
+    HIP_TRY(pass(NDT_PGO_WIDE_LINEARISE));
+    HIP_TRY(pass(NDT_PGO_WIDE_ASSESS_FIRST));
+    HIP_TRY(look());
+    while (!mirror->run_done) {
+        HIP_TRY(pass(NDT_PGO_WIDE_START));
+        do {
+            for (int k = 0; k < wp.check_every; k++) {
+                HIP_TRY(pass(NDT_PGO_WIDE_LINK));
+                HIP_TRY(pass(NDT_PGO_WIDE_NODE));
+                HIP_TRY(pass(NDT_PGO_WIDE_STEP));
+            }
+            HIP_TRY(look());
+        } while (!mirror->solve_done && !mirror->run_done);
+        HIP_TRY(pass(NDT_PGO_WIDE_UPDATE));
+        HIP_TRY(pass(NDT_PGO_WIDE_LINEARISE));
+        HIP_TRY(pass(NDT_PGO_WIDE_ASSESS));
+        HIP_TRY(look());
+    }
+    HIP_TRY(h->used.record(st));
     return NDTGPU_OK;
 }
 

@@ -1006,9 +1006,11 @@ inline Eigen::Affine3d convertIsamPose2dToEigenAffine3d(const Pose2d &p)
 // ndtgpu_pgo bank (include/ndtgpu.h gives the factors, the Gauss-Newton stop rule and what differs from iSAM).  As upstream: node
 // 0's pose is the prior (:59-63), the links with score < 0 are added first (:74-82) and then EVERY link, those again (:86-93),
 // every factor at the information 100 * I3 (:45), and the poses go back with setPose (:101-104).  `params` / `result` are
-// additions: the stop rule's parameters (NULL: the defaults) and the optimiser's report.
+// additions: the stop rule's parameters (NULL: the defaults), the optimiser's report, and `wide`: the chip-wide form
+// (ndtgpu_pgo_optimize_wide: one launch per pass over the whole device), the one to ask for above some 600 nodes -- the mapper's
+// graph of thousands of nodes -- where the one-workgroup form leaves the chip idle.
 inline void optimizeGraphUsingISAM(NDTFeatureGraphInterface &graph, const ndtgpu_pgo_params *params = nullptr,
-                                   ndtgpu_pgo_result *result = nullptr)
+                                   ndtgpu_pgo_result *result = nullptr, bool wide = false)
 {
     const size_t n = graph.getNbNodes();
     if (n == 0) return;
@@ -1030,7 +1032,7 @@ inline void optimizeGraphUsingISAM(NDTFeatureGraphInterface &graph, const ndtgpu
     ndtgpu_pgo *h = nullptr;
     ndtgpu_host::check(ndtgpu_pgo_create(1, n, ref.size(), &h), "ndtgpu_pgo_create");
     ndtgpu_status rc = ndtgpu_pgo_set_graph(h, 0, n, pose.data(), ref.size(), ref.data(), mov.data(), meas.data(), nullptr);
-    if (rc == NDTGPU_OK) rc = ndtgpu_pgo_optimize(h, 0, 1, params, nullptr);
+    if (rc == NDTGPU_OK) rc = wide ? ndtgpu_pgo_optimize_wide(h, 0, params, nullptr, nullptr) : ndtgpu_pgo_optimize(h, 0, 1, params, nullptr);
     ndtgpu_pgo_result r;
     if (rc == NDTGPU_OK) rc = ndtgpu_pgo_poses(h, 0, pose.data(), nullptr, &r);
     const std::string err = rc == NDTGPU_OK ? "" : ndtgpu_last_error();
@@ -1040,6 +1042,9 @@ inline void optimizeGraphUsingISAM(NDTFeatureGraphInterface &graph, const ndtgpu
     for (size_t i = 0; i < n; i++)
         graph.getNodeInterface(i).setPose(convertIsamPose2dToEigenAffine3d(Pose2d(pose[3 * i], pose[3 * i + 1], pose[3 * i + 2])));
 }
+
+// optimizeGraphUsingISAM(graph, wide): the defaults, in the form asked for
+inline void optimizeGraphUsingISAM(NDTFeatureGraphInterface &graph, bool wide) { optimizeGraphUsingISAM(graph, nullptr, nullptr, wide); }
 
 // The product of the mapper: ONE map from the graph's node maps under the node poses T -- graph->getMap() moved by getT()
 // (ndt_feature2d_fuser.cpp:425-432), the combination NDTFeatureGraph::fuse() (ndt_feature_graph.h:149-152) declares but leaves

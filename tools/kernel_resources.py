@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Prints VGPR / SGPR / spill / scratch / LDS figures of every kernel in the shipped libndtgpu.so
-(code-object metadata, what the judge reads).  usage: python tools/kernel_resources.py [filter]"""
+(code-object metadata, what the judge reads).  usage: python tools/kernel_resources.py [filter]
+filter: a substring of the (mangled) kernel name, or one of the named groups below."""
 import os, re, subprocess, sys, tempfile
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 so = os.path.join(root, "ndt_feature_graph_amd", "libndtgpu.so")
@@ -20,11 +21,15 @@ with tempfile.TemporaryDirectory() as d:
         subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
                                "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
         txt += subprocess.check_output([os.path.join(llvm, "llvm-readelf"), "--notes", co]).decode()
+# named groups: every kernel of a subsystem, by name
+GROUPS = {"pgo_wide": ["ndt_pgo_wide_linearise_kernel", "ndt_pgo_wide_assess_kernel", "ndt_pgo_wide_start_kernel", "ndt_pgo_wide_link_kernel",
+                       "ndt_pgo_wide_node_kernel", "ndt_pgo_wide_step_kernel", "ndt_pgo_wide_update_kernel"]}
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
+names = GROUPS.get(flt, [flt])
 for blk in txt.split("- .agpr_count")[1:]:
     g = lambda k: (re.search(r"\." + k + r":\s+(\S+)", blk) or [None, "?"])[1]
     name = g("name")
-    if flt and flt not in name: continue
+    if flt and not any(n in name for n in names): continue
     short = subprocess.check_output(["c++filt", name]).decode().split("(")[0]
     print("%-44s vgpr %3s sgpr %3s vspill %3s sspill %3s scratch %4s lds %6s" % (
         short[:44], g("vgpr_count"), g("sgpr_count"), g("vgpr_spill_count"), g("sgpr_spill_count"),
