@@ -1645,6 +1645,117 @@ ndtgpu_status ndtgpu_scanproj_project(ndtgpu_scanproj *h, const double *ranges, 
                                       double angle_min, double angle_increment, const ndtgpu_scanproject_params *prm, void *xyz,
                                       size_t stride_bytes, size_t map_stride_bytes, uint32_t *n_kept);
 
+/* ---- extrinsic calibration: the laser's pose on the base, by brute-force search over sensor offsets ------------------------------
+ * Every entry that turns a scan into a pose takes a sensor_pose; the reference ships the tool that produces it,
+ * ndt_feature/src/laser2d_extrinsic_calibration.cpp (automower_laser2d_calib.launch, cth_laser2d_calib.launch,
+ * coop_laser2d_calib.launch): bruteForceOptimization (:176-204) walks a lattice of (x, y, yaw) candidates, errorFunction (:146-152)
+ * sums ScanPair::scoreICP (:85-122) over the collected pairs, and the callback (:250-353) collects the pairs.  ndtgpu_calib_search*
+ * is that search on the device, over clouds in the layout ndtgpu_scanproj_project_device writes.
+ * PROVENANCE: restated from the reference's program text cited above; its kd-tree (PCL / FLANN) is not vendored and is replaced by
+ * an exact nearest neighbour, which has one right answer.  No program text of the reference is copied.
+ * Semantics (restated).  A pair is (cloud1, pose1, cloud2, pose2), the poses those of the base in a world frame; a candidate is the
+ * sensor offset Ts = (x, y, yaw).  The reference moves cloud1 by pose1 Ts and cloud2 by pose2 Ts into the world frame; for every
+ * point of cloud2 it takes d2, the squared 3-D distance to its nearest neighbour in cloud1, and adds d2 > th2 ? th2 : d2 with
+ * th2 = 0.1 * 0.1; the sum over the points and then over the pairs is the candidate's score.  The winner is the candidate with the
+ * smallest score under a strict <, so among equals the first in loop order -- x outer, y middle, yaw inner.  The lattice is
+ * for (double x = ix - x_s; x < ix + x_s; x += t_r), repeated addition in doubles, and likewise for y (t_r) and yaw (yaw_r).
+ * The form computed here.  |p1 a - p2 b| = |a - M b| with M = Ts^-1 D Ts and D = pose1^-1 pose2; rotations of the plane commute, so
+ * M's rotation is D's and only its translation depends on the candidate: t = R(-yaw) (t_D + (R_D - I) t_s).  cloud1 never moves,
+ * cloud2 is rotated once per pair, a candidate is a 2-D translation.  The search sees yaw only through R(-yaw) acting on a
+ * non-zero bracket, which is why the callback insists on 25 degrees between the scans of a pair.  The order of every operation --
+ * fp64, not contracted, on the float32 coordinates widened to double -- is written out in csrc/ndt_calib.h and is part of the
+ * contract: tests/calib_model.py restates it and the device's scores equal the model's bit for bit.
+ *   rows     rows at or beyond n_kept[scan] are ignored; a row in front of it with a non-finite coordinate is skipped and counted
+ *            (n_skipped: per pair, the skipped rows of its cloud1 and of its cloud2); a pair whose cloud1 has no usable row
+ *            contributes 0.0, and so does an empty cloud2.
+ *   winner   the smallest score, ties to the lowest linear index (ix * ny + iy) * nyaw + iyaw.
+ *   flags    NDTGPU_CALIB_NO_RESULT where the winner's score is >= 1e6; NDTGPU_CALIB_BAD_PAIR where a pair of the device form names
+ *            a scan >= n_scans (that pair contributes 0.0; the host form refuses such a call).
+ *   pairs    ndtgpu_calib_select_pairs: Tmotion = Told^-1 Tgt; a translation above max_translation (1.0 m) resets the anchor with no
+ *            pair; |yaw| < min_yaw (25 degrees) keeps waiting; otherwise (anchor, current) is a pair and current the new anchor.
+ * DEVIATIONS:
+ *   - sensor-frame form: |a - M b| instead of two float clouds in the world frame.  The same value in exact arithmetic; the
+ *     rounding is better conditioned (no world coordinates are rounded to float).
+ *   - fp64 on the float32 points instead of PCL's float kd-tree and float distances.
+ *   - no 1e6 cap: the reference starts from min_score = 1e6 and reports nothing above it; the flag reports the condition instead.
+ *   - z offset: clouds from ndtgpu_scanproj_project_device carry the z jitter but not the callback's constant 0.1; only differences
+ *     of z enter the distance.  The callback's own gate (r >= range_min && r < range_max && r > 0.3 && r < 20) is the caller's r_min
+ *     / r_max of the projection.
+ *   - the candidates' cosines and sines come from host tables (ndtgpu_calib_lattice): the device evaluates neither.
+ *   - an empty cloud contributes 0 (the reference prints a complaint and queries an empty tree).
+ *   - the pair gate uses the robust yaw, acos of the clamped cosine (getRobustYawFromAffine3d's form), not eulerAngles(0,1,2)[2].
+ * Limits: 1 .. 2^16 rows per scan, 1 .. 1024 pairs, 1 .. 2^20 scans in the bank, 1 .. 2^24 candidates.  The (pair, candidate) sums
+ * live in the handle's scratch, at most 2^22 doubles (32 MiB): a handle made for max_pairs pairs works through the lattice in
+ * chunks of floor(2^22 / max_pairs / 256) * 256 candidates (at least 256), two launches per chunk; 16 pairs: 262 144 candidates a chunk.
+ * Device form (csrc/ndt_calib.hip): plain launches on the caller's stream, no atomics, no workgroup waits on another.  prepare, a
+ * workgroup per pair: usable rows widened, cloud2 rotated, both compacted in row order; score, (candidate tiles of 256) x (pairs)
+ * workgroups, a lane per candidate, the cloud rows uniform across the wave; finish, a lane per candidate: the pairs added in
+ * order, the volume, the tile's ordered arg-min; winner, one workgroup over the tile winners.  The walk is not pruned.
+ * Measured on MI355X (tools/calib_cost.py, library 0.13.0; HIP events around the call, median of 7 after a warm-up; 16 pairs of
+ * 720-beam synthetic hall scans, 600 kept points a scan on average): the launch files' lattice, 100 x 100 x 20 = 200 000 candidates or
+ * 1.15e12 point pairs, 305.6 ms (304.6 .. 305.9; 3.8e12 point pairs a second); the program's default lattice, 10 x 10 x 80 = 8000
+ * candidates, 25.6 ms (512 workgroups: the chip is not full).  The literal form with SciPy's cKDTree on one core of the same box takes
+ * 3.07 / 3.02 ms a candidate over 48 sampled candidates; SCALED to the lattices (an extrapolation) that is 613 s and 24 s: ratios of
+ * 2000 and 940.  Kernels (tools/kernel_resources.py calib): prepare 32, score 28, finish 13, winner 36 VGPRs, no spills, no scratch,
+ * LDS 32 / 0 / 48 / 80 B.  Pruning the walk to the neighbours within reach of the lattice's translations was not built or measured. */
+typedef struct ndtgpu_calib ndtgpu_calib;
+typedef struct {
+    double max_dist;                 /* th: a nearest neighbour farther than this counts as th * th (0.1: scoreICP's error_th) */
+} ndtgpu_calib_params;
+#define NDTGPU_CALIB_NO_RESULT 1u
+#define NDTGPU_CALIB_BAD_PAIR 2u
+typedef struct {
+    double score;                    /* the winner's */
+    uint32_t index;                  /* (ix * ny + iy) * nyaw + iyaw */
+    uint32_t flags;                  /* NDTGPU_CALIB_* */
+    uint32_t n_skipped;              /* rows in front of n_kept with a non-finite coordinate, summed over the pairs' clouds */
+    uint32_t reserved;
+} ndtgpu_calib_result;
+/* laser2d_extrinsic_calibration.cpp:106 */
+void ndtgpu_default_calib_params(ndtgpu_calib_params *p);
+/* the candidates of a workgroup */
+uint32_t ndtgpu_calib_tile(void);
+/* Pure host functions (no device), built on what the kernels call (csrc/ndt_calib.h).
+ * ndtgpu_calib_lattice: the three loops of bruteForceOptimization by repeated addition.  counts3 = (nx, ny, nyaw) is always written;
+ * xs, ys, yaws, cs = cos(yaws), sn = sin(yaws) are written where not NULL, each with room for `room` doubles (NDTGPU_ERR_CAPACITY
+ * where an axis has more nodes than room and an array was given).  NDTGPU_ERR_INVALID for a non-finite argument, a span or step
+ * that is not > 0, or more than 2^24 nodes on an axis. */
+ndtgpu_status ndtgpu_calib_lattice(double ix, double iy, double iyaw, double x_s, double y_s, double yaw_s, double t_r, double yaw_r,
+                                   size_t counts3[3], double *xs, double *ys, double *yaws, double *cs, double *sn, size_t room);
+/* D = pose1^-1 pose2 as (dx, dy, cd, sd) of two poses (x, y, c, s) */
+ndtgpu_status ndtgpu_calib_pair_motion(const double pose1[4], const double pose2[4], double D[4]);
+/* the callback's anchor and gate walk over n poses (x, y, c, s): the first `room` pairs (anchor, current) into pairs2 (may be NULL),
+ * their count into n_pairs */
+ndtgpu_status ndtgpu_calib_select_pairs(const double *poses4, size_t n, double max_translation, double min_yaw, uint32_t *pairs2,
+                                        size_t room, size_t *n_pairs);
+/* the checks of a search's arguments and parameters (prm NULL: the defaults): NDTGPU_ERR_INVALID with a message that names the
+ * argument */
+ndtgpu_status ndtgpu_calib_check(size_t n_scans, size_t n_points, size_t stride_bytes, size_t map_stride_bytes, size_t n_pairs, size_t nx,
+                                 size_t ny, size_t nyaw, const ndtgpu_calib_params *prm);
+/* a calibrator for searches of up to max_pairs pairs (1 .. 1024) of scans of up to max_points rows (1 .. 2^16) over up to
+ * max_candidates candidates (1 .. 2^24): it owns the compacted clouds, the (pair, candidate) sums, the tile winners and, from its
+ * first use, the staging */
+ndtgpu_status ndtgpu_calib_create(size_t max_pairs, size_t max_points, size_t max_candidates, ndtgpu_calib **out);
+ndtgpu_status ndtgpu_calib_destroy(ndtgpu_calib *h);
+/* The search.  DEVICE: xyz_dev, a bank of n_scans clouds of n_points rows (stride_bytes / map_stride_bytes as in
+ * ndtgpu_scanproj_project_device), n_kept_dev [n_scans], poses_dev [n_scans][4] = (x, y, c, s) of the base, pairs_dev [n_pairs][2] =
+ * (scan of cloud1, scan of cloud2), result_dev, volume_dev (NULL, or nx * ny * nyaw doubles: every candidate's score).  HOST: the
+ * lattice tables xs [nx], ys [ny], cs / sn [nyaw] of ndtgpu_calib_lattice, copied before the call returns.  prm NULL: the defaults.
+ * Asynchronous on `stream`; calls on one handle are ordered on the device whatever stream each names, and a call waits on the host
+ * for the previous call's table upload.  The arguments and parameters are checked before the handle is read and the device is
+ * looked for; NDTGPU_ERR_CAPACITY beyond what the handle was created for. */
+ndtgpu_status ndtgpu_calib_search_device(ndtgpu_calib *h, const void *xyz_dev, size_t n_scans, size_t n_points, size_t stride_bytes,
+                                         size_t map_stride_bytes, const uint32_t *n_kept_dev, const double *poses_dev,
+                                         const uint32_t *pairs_dev, size_t n_pairs, const double *xs, size_t nx, const double *ys, size_t ny,
+                                         const double *cs, const double *sn, size_t nyaw, const ndtgpu_calib_params *prm,
+                                         ndtgpu_calib_result *result_dev, double *volume_dev, ndtgpu_stream stream);
+/* the same on HOST arrays through the handle's pinned staging, synchronous: result and volume (may be NULL) are written when it
+ * returns.  A pair that names a scan >= n_scans is refused (NDTGPU_ERR_INVALID). */
+ndtgpu_status ndtgpu_calib_search(ndtgpu_calib *h, const void *xyz, size_t n_scans, size_t n_points, size_t stride_bytes,
+                                  size_t map_stride_bytes, const uint32_t *n_kept, const double *poses, const uint32_t *pairs, size_t n_pairs,
+                                  const double *xs, size_t nx, const double *ys, size_t ny, const double *cs, const double *sn, size_t nyaw,
+                                  const ndtgpu_calib_params *prm, ndtgpu_calib_result *result, double *volume);
+
 #ifdef __cplusplus
 }
 #endif

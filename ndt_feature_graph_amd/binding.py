@@ -13,7 +13,8 @@ _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hi
             "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip",
             "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndt_pgo_wide.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
             "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip", "ndt_occgrid.hip", "ndtgpu_occgrid.hip", "ndt_linkgate.hip",
-            "ndtgpu_linkgate.hip", "ndt_fuserfeat.hip", "ndt_scanproject.hip", "ndtgpu_scanproject.hip"]
+            "ndtgpu_linkgate.hip", "ndt_fuserfeat.hip", "ndt_scanproject.hip", "ndtgpu_scanproject.hip",
+            "ndt_calib.hip", "ndtgpu_calib.hip"]
 
 STATUS = {0: "OK", -1: "ERR_INVALID", -2: "ERR_HIP", -3: "ERR_NO_DEVICE", -4: "ERR_CAPACITY", -5: "ERR_ALLOC"}
 
@@ -110,6 +111,17 @@ class MatchResult(C.Structure):
                 ("pair_terms_g", C.c_int64), ("pair_terms_h", C.c_int64)]
 
 
+class CalibParams(C.Structure):
+    _fields_ = [("max_dist", C.c_double)]
+
+
+class CalibResult(C.Structure):
+    _fields_ = [("score", C.c_double), ("index", C.c_uint32), ("flags", C.c_uint32), ("n_skipped", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+CALIB_RESULT_DTYPE = np.dtype([("score", "<f8"), ("index", "<u4"), ("flags", "<u4"), ("n_skipped", "<u4"), ("reserved", "<u4")])
+assert CALIB_RESULT_DTYPE.itemsize == C.sizeof(CalibResult) == 24
+
 RESULT_DTYPE = np.dtype([("converged", "<i4"), ("iterations", "<i4"), ("fevals", "<i4"), ("exit_code", "<i4"),
                          ("score", "<f8"), ("n_source", "<i4"), ("n_target", "<i4"), ("cycles_eval", "<i8"),
                          ("cycles_solver", "<i8"), ("pair_terms_g", "<i8"), ("pair_terms_h", "<i8")])
@@ -157,7 +169,9 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_fuser_initialize_batch_feat", "ndtgpu_fuser_update_batch_feat", "ndtgpu_fuser_feat_results", "ndtgpu_fuser_feat_cells",
            "ndtgpu_fuser_initialize_batch_feat_host", "ndtgpu_fuser_update_batch_feat_host",
            "ndtgpu_default_scanproject_params", "ndtgpu_scanproj_tile", "ndtgpu_scanproj_check", "ndtgpu_scanproj_beam",
-           "ndtgpu_scanproj_create", "ndtgpu_scanproj_destroy", "ndtgpu_scanproj_project_device", "ndtgpu_scanproj_project"]
+           "ndtgpu_scanproj_create", "ndtgpu_scanproj_destroy", "ndtgpu_scanproj_project_device", "ndtgpu_scanproj_project",
+           "ndtgpu_default_calib_params", "ndtgpu_calib_tile", "ndtgpu_calib_lattice", "ndtgpu_calib_pair_motion", "ndtgpu_calib_select_pairs",
+           "ndtgpu_calib_check", "ndtgpu_calib_create", "ndtgpu_calib_destroy", "ndtgpu_calib_search_device", "ndtgpu_calib_search"]
 
 _lib = None
 
@@ -359,6 +373,20 @@ def lib():
                                                  vp, C.c_size_t, C.c_size_t, vp, vp]
     L.ndtgpu_scanproj_project.argtypes = [vp, dp, C.POINTER(C.c_uint64), C.c_size_t, C.c_size_t, C.c_double, C.c_double,
                                           C.POINTER(ScanProjectParams), vp, C.c_size_t, C.c_size_t, u32p]
+    L.ndtgpu_default_calib_params.restype = None
+    L.ndtgpu_default_calib_params.argtypes = [C.POINTER(CalibParams)]
+    L.ndtgpu_calib_tile.restype = C.c_uint32
+    L.ndtgpu_calib_tile.argtypes = []
+    L.ndtgpu_calib_lattice.argtypes = [C.c_double] * 8 + [C.POINTER(C.c_size_t), dp, dp, dp, dp, dp, C.c_size_t]
+    L.ndtgpu_calib_pair_motion.argtypes = [dp, dp, dp]
+    L.ndtgpu_calib_select_pairs.argtypes = [dp, C.c_size_t, C.c_double, C.c_double, u32p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.ndtgpu_calib_check.argtypes = [C.c_size_t] * 8 + [C.POINTER(CalibParams)]
+    L.ndtgpu_calib_create.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.ndtgpu_calib_destroy.argtypes = [vp]
+    L.ndtgpu_calib_search_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, vp, C.c_size_t, dp, C.c_size_t, dp,
+                                             C.c_size_t, dp, dp, C.c_size_t, C.POINTER(CalibParams), vp, vp, vp]
+    L.ndtgpu_calib_search.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, u32p, dp, u32p, C.c_size_t, dp, C.c_size_t, dp,
+                                      C.c_size_t, dp, dp, C.c_size_t, C.POINTER(CalibParams), C.POINTER(CalibResult), dp]
     if hasattr(L, "ndtgpu_live_resources"):            # (NDTGPU_LIB may name a build from before this entry existed)
         L.ndtgpu_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
@@ -1957,6 +1985,139 @@ class ScanProjector:
                                                     4 * int(xyz_t.stride(1)), 4 * int(xyz_t.stride(0)) if n > 1 else 4 * nb * int(xyz_t.stride(1)),
                                                     _dev_ptr(n_kept_t, torch.int32, n, "ScanProjector.project_device n_kept_t"),
                                                     _stream_ptr(stream)))
+
+
+CALIB_TILE = 256             # ndtgpu_calib_tile(): the candidates of a workgroup
+CALIB_NO_RESULT, CALIB_BAD_PAIR = 1, 2
+
+
+def calib_params(**fields):
+    """ndtgpu_default_calib_params (max_dist 0.1) with fields replaced"""
+    p = CalibParams()
+    lib().ndtgpu_default_calib_params(C.byref(p))
+    for k, v in fields.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown calibration parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def calib_lattice(ix, iy, iyaw, x_s, y_s, yaw_s, t_r, yaw_r):
+    """ndtgpu_calib_lattice: the candidates of bruteForceOptimization -> dict(xs [nx], ys [ny], yaws [nyaw], cs, sn [nyaw])"""
+    a = [float(v) for v in (ix, iy, iyaw, x_s, y_s, yaw_s, t_r, yaw_r)]
+    cnt = (C.c_size_t * 3)()
+    _check(lib().ndtgpu_calib_lattice(*a, cnt, None, None, None, None, None, 0))
+    room = max(cnt[:])
+    xs, ys, yaws, cs, sn = (np.zeros(room) for _ in range(5))
+    _check(lib().ndtgpu_calib_lattice(*a, cnt, _dp(xs), _dp(ys), _dp(yaws), _dp(cs), _dp(sn), room))
+    nx, ny, nyaw = cnt[:]
+    return dict(xs=xs[:nx].copy(), ys=ys[:ny].copy(), yaws=yaws[:nyaw].copy(), cs=cs[:nyaw].copy(), sn=sn[:nyaw].copy())
+
+
+def calib_pair_motion(pose1, pose2):
+    """ndtgpu_calib_pair_motion: D = pose1^-1 pose2 as (dx, dy, cd, sd) of two poses (x, y, c, s)"""
+    p1, p2, D = _f64(pose1).reshape(4), _f64(pose2).reshape(4), np.zeros(4)
+    _check(lib().ndtgpu_calib_pair_motion(_dp(p1), _dp(p2), _dp(D)))
+    return D
+
+
+def calib_select_pairs(poses4, max_translation=1.0, min_yaw=25.0 * np.pi / 180.0):
+    """ndtgpu_calib_select_pairs: the callback's anchor and gate walk over poses (x, y, c, s) [n, 4] -> pairs uint32 [m, 2]"""
+    pp = _f64(poses4).reshape(-1, 4)
+    n = pp.shape[0]
+    pairs = np.zeros((max(n, 1), 2), dtype=np.uint32)
+    m = C.c_size_t()
+    _check(lib().ndtgpu_calib_select_pairs(_dp(pp), n, float(max_translation), float(min_yaw), pairs.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                           pairs.shape[0], C.byref(m)))
+    return pairs[:m.value].copy()
+
+
+class Calibrator:
+    """ndtgpu_calib: the laser's pose on the base by brute-force search over sensor offsets (include/ndtgpu.h "extrinsic
+    calibration").  Clouds are a bank in the layout ScanProjector writes; poses are (x, y, cos yaw, sin yaw) of the base; pairs are
+    (scan of cloud1, scan of cloud2); the lattice is what calib_lattice returns."""
+
+    def __init__(self, max_pairs, max_points, max_candidates):
+        h = C.c_void_p()
+        _check(lib().ndtgpu_calib_create(int(max_pairs), int(max_points), int(max_candidates), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ndtgpu_calib_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _tables(lattice):
+        t = [_f64(lattice[k]).reshape(-1) for k in ("xs", "ys", "cs", "sn")]
+        if t[2].shape != t[3].shape:
+            raise ValueError("Calibrator: cs and sn must have one entry per yaw")
+        return t
+
+    def search(self, xyz, n_kept, poses4, pairs, lattice, want_volume=False, **params):
+        """HOST xyz float32 [n_scans, n_points, w >= 3], n_kept [n_scans], poses4 [n_scans, 4], pairs [n_pairs, 2] ->
+        dict(index, ix, iy, iyaw, score, flags, n_skipped, volume [nx, ny, nyaw] or None).  Synchronous."""
+        pts = np.ascontiguousarray(xyz, dtype=np.float32)
+        if pts.ndim != 3 or pts.shape[2] < 3:
+            raise ValueError("Calibrator.search: xyz must be [n_scans, n_points, >= 3]")
+        n, npts, w = pts.shape
+        kept = np.ascontiguousarray(n_kept, dtype=np.uint32).reshape(-1)
+        pp = _f64(poses4).reshape(-1, 4)
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        if kept.shape[0] != n or pp.shape[0] != n:
+            raise ValueError("Calibrator.search: one n_kept and one pose per scan")
+        xs, ys, cs, sn = self._tables(lattice)
+        vol = np.zeros(xs.shape[0] * ys.shape[0] * cs.shape[0]) if want_volume else None
+        res = CalibResult()
+        p = calib_params(**params)
+        u32 = C.POINTER(C.c_uint32)
+        _check(lib().ndtgpu_calib_search(self.h, C.c_void_p(pts.ctypes.data), n, npts, 4 * w, 4 * w * npts, kept.ctypes.data_as(u32), _dp(pp),
+                                         pr.ctypes.data_as(u32), pr.shape[0], _dp(xs), xs.shape[0], _dp(ys), ys.shape[0], _dp(cs), _dp(sn),
+                                         cs.shape[0], C.byref(p), C.byref(res), None if vol is None else _dp(vol)))
+        return self._result(res.score, res.index, res.flags, res.n_skipped, vol, xs.shape[0], ys.shape[0], cs.shape[0])
+
+    @staticmethod
+    def _result(score, index, flags, n_skipped, vol, nx, ny, nyaw):
+        index = int(index)
+        return dict(index=index, ix=index // (ny * nyaw), iy=(index // nyaw) % ny, iyaw=index % nyaw, score=float(score), flags=int(flags),
+                    n_skipped=int(n_skipped), volume=None if vol is None else vol.reshape(nx, ny, nyaw))
+
+    def search_device(self, xyz_t, n_kept_t, poses_t, pairs_t, lattice, result_t, volume_t=None, stream=None, **params):
+        """the same on torch device tensors, asynchronous on `stream`: xyz_t float32 [n_scans, n_points, w >= 3], possibly a view (its
+        strides give stride_bytes and map_stride_bytes); n_kept_t int32 [n_scans] (read as uint32); poses_t float64 [n_scans, 4];
+        pairs_t int32 [n_pairs, 2]; result_t: 24 bytes of device memory (CALIB_RESULT_DTYPE; a uint8 [24] or int32 [6] tensor);
+        volume_t float64 [nx * ny * nyaw] or None.  read_result(result_t) decodes the record once the stream has run."""
+        import torch
+        if not (xyz_t.is_cuda and xyz_t.dtype == torch.float32 and xyz_t.dim() == 3 and xyz_t.shape[2] >= 3 and xyz_t.stride(2) == 1):
+            raise ValueError("Calibrator.search_device: xyz_t must be a float32 device tensor [n_scans, n_points, >= 3] with unit stride "
+                             "along its last axis")
+        n, npts = int(xyz_t.shape[0]), int(xyz_t.shape[1])
+        if not (pairs_t.is_cuda and pairs_t.is_contiguous() and pairs_t.dtype == torch.int32 and pairs_t.dim() == 2 and pairs_t.shape[1] == 2):
+            raise ValueError("Calibrator.search_device: pairs_t must be a contiguous int32 device tensor [n_pairs, 2]")
+        if not (result_t.is_cuda and result_t.is_contiguous() and result_t.numel() * result_t.element_size() >= 24):
+            raise ValueError("Calibrator.search_device: result_t must be a contiguous device tensor of at least 24 bytes")
+        xs, ys, cs, sn = self._tables(lattice)
+        nc = xs.shape[0] * ys.shape[0] * cs.shape[0]
+        p = calib_params(**params)
+        _check(lib().ndtgpu_calib_search_device(self.h, C.c_void_p(xyz_t.data_ptr()), n, npts, 4 * int(xyz_t.stride(1)),
+                                                4 * int(xyz_t.stride(0)) if n > 1 else 4 * npts * int(xyz_t.stride(1)),
+                                                _dev_ptr(n_kept_t, torch.int32, n, "Calibrator.search_device n_kept_t"),
+                                                _dev_ptr(poses_t, torch.float64, 4 * n, "Calibrator.search_device poses_t"),
+                                                C.c_void_p(pairs_t.data_ptr()), int(pairs_t.shape[0]), _dp(xs), xs.shape[0], _dp(ys), ys.shape[0],
+                                                _dp(cs), _dp(sn), cs.shape[0], C.byref(p), C.c_void_p(result_t.data_ptr()),
+                                                _dev_ptr(volume_t, torch.float64, nc, "Calibrator.search_device volume_t"), _stream_ptr(stream)))
+
+    @staticmethod
+    def read_result(result_t):
+        """the record search_device wrote (synchronises through the copy to the host): CALIB_RESULT_DTYPE scalar"""
+        import torch
+        return np.frombuffer(result_t.view(torch.uint8).cpu().numpy().tobytes()[:24], dtype=CALIB_RESULT_DTYPE)[0]
 
 
 def match_d2d(target_set, tmap, source_set, smap, T, **params):

@@ -63,7 +63,7 @@ ndtgpu_status pack_cells(const NdtGrid &g, const double *centre, const double *m
 extern "C" {
 
 // (bumped whenever a kernel changes: bench.py only quotes PMC figures taken with the same version)
-const char *ndtgpu_version(void) { return "ndtgpu 0.12.0 (gfx950)"; }
+const char *ndtgpu_version(void) { return "ndtgpu 0.13.0 (gfx950)"; }
 const char *ndtgpu_last_error(void) { return g_err.c_str(); }
 
 ndtgpu_status ndtgpu_live_resources(uint64_t counts[4])
