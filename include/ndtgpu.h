@@ -1756,6 +1756,190 @@ ndtgpu_status ndtgpu_calib_search(ndtgpu_calib *h, const void *xyz, size_t n_sca
                                   const double *xs, size_t nx, const double *ys, size_t ny, const double *cs, const double *sn, size_t nyaw,
                                   const ndtgpu_calib_params *prm, ndtgpu_calib_result *result, double *volume);
 
+/* ---- localisation monitor: distance field of an occupancy grid, scan-pose badness, pose adjustment, relocalisation pick ------------
+ * The chain ends in occupancy grids (ndtgpu_mapset_occupancy_grid_device); this section consumes them and tells a caller whether a
+ * robot's pose in such a grid is still right.  The reference ships that piece in flirtlib_ros: ScanPoseEvaluator
+ * (flirtlib_ros/src/localization_monitor.cpp:41-120, include/flirtlib_ros/localization_monitor.h:41-63) builds a distance field of
+ * the grid; the badness of a (scan, pose) is the median distance from the scan's endpoints to the nearest obstacle; adjustPose
+ * (:61-65) is a brute-force lattice search over (x, y, theta) for the smallest badness.  localization_monitor_node.cpp uses it on
+ * every scan (scanCB :498-537) to decide "well localised" at badness_threshold_ 0.25 (:214, :324, :529); when not localised,
+ * updateUnlocalized (:331-413) matches the scan's features against a bank of reference scans, takes the one with the most matches
+ * above min_num_matches (8, :209), composes the pose (common.cpp:56-66) and accepts it only if its badness is below the threshold.
+ * startup_loc.cpp:262-329 is the same relocalisation at start-up.
+ * PROVENANCE: restated from the reference's program text cited above.  occupancy_grid_utils (distanceField, pointCell,
+ * withinBounds) is not vendored by the reference, only its call sites are; its semantics are restated here from those call sites
+ * and its public documentation: pointCell is the floor of (point - origin) / resolution per axis, withinBounds is 0 <= cell <
+ * (width, height), distanceField is the distance of every cell to the nearest occupied cell, not computed beyond max_dist.  No
+ * program text of the reference is copied.
+ * Semantics (restated; the order of every fp64 operation -- not contracted -- is written out in csrc/ndt_locmon.h and is part of the
+ * contract: tests/locmon_model.py restates it and the device's outputs equal the model's bit for bit).
+ *   field    input: n_grids int8 grids of width x height, row-major, back to back, as ndtgpu_mapset_occupancy_grid_device writes
+ *            them; resolution; origin[2] per grid.  A pixel is an obstacle iff its value is >= occupied_min.  R = (int)floor(max_dist
+ *            / resolution), 1 <= R <= 254.  The field's value at a pixel is k = min(dx^2 + dy^2) over the obstacle pixels of the same
+ *            grid with k <= R^2, a uint16; 0xFFFF ("far") where there is none.  Pixels outside the grid are not obstacles.  All
+ *            arithmetic is integer.  The handle owns the fields and origins, as the evaluator owns geom_ and distances_.
+ *   query    (scan, grid, x, y, c, s): poses are carried as (x, y, cos, sin), as in the calibration entries.  Beam i has the table
+ *            entry (cb_i, sb_i) = (cos a_i, sin a_i), a_i = angle_min + (double)i * angle_increment, made on the host once per
+ *            scanner geometry (ndtgpu_locmon_set_beams).  Beam i is kept iff its range r is finite and r_min < r < r_max.  For a kept
+ *            beam ex = c * cb - s * sb, ey = s * cb + c * sb, px = x + ex * r, py = y + ey * r, fi = floor((px - ox) / resolution),
+ *            fj likewise; in bounds iff 0 <= fi < width and 0 <= fj < height, compared as doubles (a NaN is off the map).  The
+ *            beam's key is the field's value k, 0x10000 for far, 0x10001 off the map.  The result key is the element at index
+ *            n_kept / 2 of the ascending keys: the reference's distances[size / 2], the upper median.
+ *   badness  resolution * sqrt((double)k) metres; far: max_dist; off the map: 1e9.
+ *   flags    NDTGPU_LOCMON_NO_BEAMS: n_kept == 0 (key off-map, badness 1e9); NDTGPU_LOCMON_BAD_INDEX: scan >= n_scans or grid >=
+ *            n_grids (the same); NDTGPU_LOCMON_NO_QUERY: scan == 0xFFFFFFFF, no work is done (the same).
+ *   adjust   the three loops of :61-65 are ndtgpu_calib_lattice(x0, y0, theta0, pos_range, pos_range, 3.14, dpos, dtheta, ...): its
+ *            xs, ys, cs, sn tables are the candidates.  The smallest key wins, ties to the lowest linear index
+ *            (ix * ny + iy) * nyaw + iyaw: the reference's strict < in loop order.  NDTGPU_LOCMON_NO_RESULT where the winner's
+ *            badness is >= 1e8 (the reference's ROS_ASSERT(best < 1e8)).
+ *   pick     over n_pairs records of ndtgpu_featbank_match_device, pair p = (reference set p, the current scan's set): the pair
+ *            with the most n_inliers among those with status OK and n_inliers > min_num_matches, strict >, so the first of equals
+ *            wins.  The picked pose is ref_pose o (x, y, c, s of the match) o (post_x, post_y); post is the reference's hard-coded
+ *            laser offset (-0.275, 0) of common.cpp:58, a parameter here.  No pair qualifies: the written query's scan is
+ *            0xFFFFFFFF and the evaluation that follows on the same stream reports NDTGPU_LOCMON_NO_QUERY.
+ * DEVIATIONS:
+ *   - occupied_min: an obstacle is a pixel >= occupied_min (55, the smallest value the rasteriser of this library gives an occupied
+ *     pixel); upstream seeds on its own OCCUPIED constant (100).
+ *   - exact Euclidean transform in squared pixel units; upstream propagates a wavefront from the seeds, which is exact only up to
+ *     its neighbourhood's metric.
+ *   - the angle-addition form replaces cos(theta0 + a_i) and sin(theta0 + a_i): the device evaluates no trigonometry.
+ *   - the range gate: a NaN, an infinite or a gated beam is dropped; the reference pushes every beam, NaN included, into its sort.
+ *   - off the map is the key 0x10001 and far the key 0x10000 in place of 1e9 and max_dist among doubles: the same order.
+ *   - the badness is a double (the reference returns a float).
+ *   - no 1e8 assertion: the flag reports the condition.
+ *   - the pick requires n_inliers > min_num_matches for every pair; the reference's second test (best < min_num_matches, :371) can
+ *     then never fire and is not restated.
+ *   - left out: the scan database, the one-day expiry, the navigation counter, odometry compensation (:415-428).
+ * Limits: n_beams 1 .. 8192; R 1 .. 254; width, height 1 .. 2^15; 1 .. 1024 grids, 2^31 pixels a handle; 2^24 scans, queries and
+ * candidates; 2^20 pairs.  A search works through the lattice in chunks of floor(2^23 / max_beams / 256) * 256 candidates (at least
+ * 256) through the handle's scratch, two launches per chunk.
+ * Device form (csrc/ndt_locmon.hip): plain launches on the caller's stream, no atomics, no workgroup waits on another, no
+ * environment switches.  Field: two launches over (tiles of 256 pixels) x (grids) -- the row pass writes the nearest obstacle
+ * distance along the row, capped at R with 255 for none, one byte per pixel into the handle's scratch; the column pass computes
+ * min over |dy| <= R of dy^2 + g^2.  Badness: one workgroup of 256 lanes per query, lanes over beams, the keys in LDS (4 bytes a
+ * beam), n_kept by a block count and the n_kept / 2-th key by a 17-round most-significant-bit-first radix select of block counts
+ * (csrc/ndt_block.h).  Adjust: the badness kernel over the candidates, a tile arg-min and one workgroup over the tile winners.
+ * Pick: one workgroup.  The workgroup-per-query form shipped; a wave-per-query variant was not built.
+ * Measured on MI355X (tools/locmon_cost.py, library 0.13.0; HIP events around the call, median of 7 after a warm-up, min .. max): the
+ * field of the replay's world at 0.05 m (13600 x 12000 = 163.2 M pixels, 2.4 M obstacle pixels, R = 7) 3.29 ms (3.28 .. 3.33; 50 G
+ * pixels a second); evaluate, 1024 queries of 1440 beams, 0.033 ms (0.032 .. 0.039; 0.03 us a query); adjust, pos_range 0.5 by 0.05 and
+ * +- 3.14 by 0.02 -- 21 x 21 x 314 = 138 474 candidates by repeated addition, where the issue's arithmetic says 20 x 20 x 315 -- 1.83 ms
+ * (1.77 .. 1.90; 0.013 us a candidate); 64 queries in front of the fuser bank's plain update (64 fusers x 1440 beams) on one stream: 2.31
+ * ms against 2.32 ms for the update alone (-0.01 ms, inside the spread 2.16 .. 2.42 of either run), the same poses.  On one core of the
+ * same box: SciPy's distance_transform_edt on a crop of 3000 x 3000 pixels 256 ms, SCALED to the grid by the pixel count (an
+ * extrapolation) 4.6 s, 1400 times the device (the device's field of the crop's interior equals SciPy's); the NumPy evaluator of
+ * tests/locmon_model.py 0.138 ms a query (32 queries, the same records as the device), SCALED 141 ms and 5.3 s: 4300 and 2900 times.
+ * Kernels (tools/kernel_resources.py locmon): row 11, column 11, badness 32, finish 9, winner 14, pick 16 VGPRs, no spills, no scratch;
+ * LDS 0 / 0 / 32 B + 4 B a beam / 32 / 32 / 32 B. */
+typedef struct ndtgpu_locmon ndtgpu_locmon;
+typedef struct {
+    double max_dist;                 /* the field's reach, metres (0.375 = badness_threshold 0.25 * 1.5, :324); read by set_grids* */
+    double r_min;                    /* a kept range is above this (0.0); read by evaluate* and adjust* */
+    double r_max;                    /* ... and below this; +inf: no upper gate (+inf) */
+    double post_x, post_y;           /* the translation behind the match in a picked pose (-0.275, 0: common.cpp:58); read by pick */
+    int32_t occupied_min;            /* a pixel >= this is an obstacle (55); read by set_grids* */
+    int32_t min_num_matches;         /* a pair qualifies with n_inliers above this (8, :209); read by pick */
+} ndtgpu_locmon_params;
+#define NDTGPU_LOCMON_NO_BEAMS 1u
+#define NDTGPU_LOCMON_BAD_INDEX 2u
+#define NDTGPU_LOCMON_NO_QUERY 4u
+#define NDTGPU_LOCMON_NO_RESULT 8u
+#define NDTGPU_LOCMON_NO_PICK 16u
+typedef struct {
+    double x, y, c, s;               /* the scanner's pose in the grid's frame */
+    uint32_t scan;                   /* row of ranges; 0xFFFFFFFF: no query */
+    uint32_t grid;                   /* of the installed grids */
+} ndtgpu_locmon_query;
+typedef struct {
+    double badness;                  /* metres; max_dist for far; 1e9 off the map or where a flag is set */
+    uint32_t key;                    /* the median key: dx^2 + dy^2 in pixels, 0x10000 far, 0x10001 off the map */
+    uint32_t n_kept;                 /* beams that passed the range gate */
+    uint32_t n_offmap;               /* ... whose endpoint is off the map */
+    uint32_t flags;                  /* NDTGPU_LOCMON_NO_BEAMS | _BAD_INDEX | _NO_QUERY */
+} ndtgpu_locmon_result;
+typedef struct {
+    double badness;                  /* the winner's */
+    uint32_t key;
+    uint32_t index;                  /* (ix * ny + iy) * nyaw + iyaw */
+    uint32_t flags;                  /* NDTGPU_LOCMON_NO_RESULT */
+    uint32_t reserved;
+} ndtgpu_locmon_adjust_result;
+typedef struct {
+    int32_t pair;                    /* the picked pair, -1 where none qualifies */
+    int32_t n_inliers;               /* its n_inliers (0) */
+    uint32_t flags;                  /* NDTGPU_LOCMON_NO_PICK */
+    uint32_t reserved;
+} ndtgpu_locmon_pick;
+/* localization_monitor_node.cpp:209, :214, :324; common.cpp:58 */
+void ndtgpu_default_locmon_params(ndtgpu_locmon_params *p);
+/* the lanes of a badness workgroup, the candidates of an arg-min tile, the pixels of a field tile */
+uint32_t ndtgpu_locmon_tile(void);
+/* Pure host functions (no device), built on what the kernels call (csrc/ndt_locmon.h).
+ * ndtgpu_locmon_check: the checks of the arguments of set_grids* (n_grids, width, height, resolution, prm), set_beams (n_beams,
+ * angle_min, angle_increment) and evaluate* (n_scans, n_queries) at once; prm NULL: the defaults.  NDTGPU_ERR_INVALID with a message
+ * that names the argument. */
+ndtgpu_status ndtgpu_locmon_check(size_t n_grids, size_t width, size_t height, double resolution, size_t n_beams, double angle_min,
+                                  double angle_increment, size_t n_scans, size_t n_queries, const ndtgpu_locmon_params *prm);
+/* R = (int)floor(max_dist / resolution); NDTGPU_ERR_INVALID (and *R = 0) unless both are finite and > 0 and R is 1 .. 254 */
+ndtgpu_status ndtgpu_locmon_radius(double max_dist, double resolution, int32_t *R);
+/* cb[i] = cos(a_i), sb[i] = sin(a_i), a_i = angle_min + (double)i * angle_increment, i < n_beams: the table set_beams installs */
+ndtgpu_status ndtgpu_locmon_beam_table(size_t n_beams, double angle_min, double angle_increment, double *cb, double *sb);
+/* the pixel of the endpoint of a beam with table entry (cb, sb) and range r from pose4 = (x, y, c, s) in a grid of width x height at
+ * origin2: *in_bounds = 1 and cell2 = (fi, fj), or *in_bounds = 0 (cell2 untouched) */
+ndtgpu_status ndtgpu_locmon_pixel(const double pose4[4], double cb, double sb, double r, const double origin2[2], double resolution,
+                                  uint32_t width, uint32_t height, int32_t cell2[2], int32_t *in_bounds);
+/* the badness of a key */
+ndtgpu_status ndtgpu_locmon_metres(uint32_t key, double resolution, double max_dist, double *badness);
+/* out4 = ref_pose4 o match4 o (post2 as a translation), poses as (x, y, c, s) */
+ndtgpu_status ndtgpu_locmon_compose(const double ref_pose4[4], const double match4[4], const double post2[2], double out4[4]);
+/* a monitor for up to max_grids grids (1 .. 1024) of max_pixels pixels in all (1 .. 2^31), scans of up to max_beams beams (1 ..
+ * 8192) and searches of up to max_candidates candidates (1 .. 2^24): it owns the fields, the origins, the beam table, the row pass's
+ * scratch, the candidates' keys, the tile winners and, from its first use, the staging of the host forms */
+ndtgpu_status ndtgpu_locmon_create(size_t max_grids, size_t max_pixels, size_t max_beams, size_t max_candidates, ndtgpu_locmon **out);
+ndtgpu_status ndtgpu_locmon_destroy(ndtgpu_locmon *h);
+/* installs the beam table of a scanner geometry (made on the host, uploaded on `stream`): every later evaluate*, adjust* reads
+ * ranges of n_beams beams a scan.  Waits on the host for the handle's previous call. */
+ndtgpu_status ndtgpu_locmon_set_beams(ndtgpu_locmon *h, size_t n_beams, double angle_min, double angle_increment, ndtgpu_stream stream);
+/* builds the distance fields of n_grids grids: DEVICE grids_dev, n_grids x height x width int8; HOST origins2, n_grids x 2, copied
+ * before the call returns.  prm NULL: the defaults (max_dist, occupied_min are read).  Asynchronous on `stream`.  The arguments are
+ * checked before the handle is read and the device is looked for; NDTGPU_ERR_CAPACITY beyond max_grids / max_pixels.  Calls on one
+ * handle are ordered on the device whatever stream each names. */
+ndtgpu_status ndtgpu_locmon_set_grids_device(ndtgpu_locmon *h, const int8_t *grids_dev, size_t n_grids, size_t width, size_t height,
+                                             double resolution, const double *origins2, const ndtgpu_locmon_params *prm,
+                                             ndtgpu_stream stream);
+/* the same on a HOST array of grids, synchronous */
+ndtgpu_status ndtgpu_locmon_set_grids(ndtgpu_locmon *h, const int8_t *grids, size_t n_grids, size_t width, size_t height, double resolution,
+                                      const double *origins2, const ndtgpu_locmon_params *prm);
+/* copies the field of one installed grid back: HOST field, width x height uint16.  Synchronous. */
+ndtgpu_status ndtgpu_locmon_field_get(ndtgpu_locmon *h, size_t grid, uint16_t *field);
+/* The badness of n_queries queries.  DEVICE: ranges_dev n_scans x n_beams doubles (the buffer ndtgpu_featbank_extract_device and
+ * ndtgpu_scanproj_project_device read), queries_dev, results_dev.  prm NULL: the defaults (r_min, r_max are read).  Asynchronous on
+ * `stream`; n_queries == 0 is a successful no-op; NDTGPU_ERR_INVALID where no grids or no beams are installed. */
+ndtgpu_status ndtgpu_locmon_evaluate_device(ndtgpu_locmon *h, const double *ranges_dev, size_t n_scans, const ndtgpu_locmon_query *queries_dev,
+                                            size_t n_queries, const ndtgpu_locmon_params *prm, ndtgpu_locmon_result *results_dev,
+                                            ndtgpu_stream stream);
+/* the same on HOST arrays through the handle's pinned staging, synchronous */
+ndtgpu_status ndtgpu_locmon_evaluate(ndtgpu_locmon *h, const double *ranges, size_t n_scans, const ndtgpu_locmon_query *queries,
+                                     size_t n_queries, const ndtgpu_locmon_params *prm, ndtgpu_locmon_result *results);
+/* adjustPose: the candidate of least badness of scan `scan` in grid `grid` over the lattice tables xs [nx], ys [ny], cs / sn [nyaw]
+ * (HOST, of ndtgpu_calib_lattice, copied before the call returns).  DEVICE: ranges_dev, result_dev, volume_dev (NULL, or nx * ny *
+ * nyaw uint32: every candidate's key).  Asynchronous on `stream`; NDTGPU_ERR_CAPACITY beyond max_candidates. */
+ndtgpu_status ndtgpu_locmon_adjust_device(ndtgpu_locmon *h, const double *ranges_dev, size_t n_scans, uint32_t scan, uint32_t grid,
+                                          const double *xs, size_t nx, const double *ys, size_t ny, const double *cs, const double *sn,
+                                          size_t nyaw, const ndtgpu_locmon_params *prm, ndtgpu_locmon_adjust_result *result_dev,
+                                          uint32_t *volume_dev, ndtgpu_stream stream);
+/* the same on a HOST array of ranges, synchronous: result and volume (may be NULL) are written when it returns */
+ndtgpu_status ndtgpu_locmon_adjust(ndtgpu_locmon *h, const double *ranges, size_t n_scans, uint32_t scan, uint32_t grid, const double *xs,
+                                   size_t nx, const double *ys, size_t ny, const double *cs, const double *sn, size_t nyaw,
+                                   const ndtgpu_locmon_params *prm, ndtgpu_locmon_adjust_result *result, uint32_t *volume);
+/* The pick.  DEVICE: matches_dev n_pairs records of ndtgpu_featbank_match_device, ref_poses_dev n_pairs x 4, query_dev one query
+ * (written: the picked pose with `scan` and `grid`, or scan 0xFFFFFFFF), pick_dev one record.  prm NULL: the defaults
+ * (min_num_matches, post_x, post_y are read).  n_pairs 0 .. 2^20.  Asynchronous on `stream`: extract -> match -> pick -> evaluate ->
+ * verdict stays on the device. */
+ndtgpu_status ndtgpu_locmon_pick_device(ndtgpu_locmon *h, const ndtgpu_featmatch_result *matches_dev, const double *ref_poses_dev,
+                                        size_t n_pairs, uint32_t scan, uint32_t grid, const ndtgpu_locmon_params *prm,
+                                        ndtgpu_locmon_query *query_dev, ndtgpu_locmon_pick *pick_dev, ndtgpu_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hi
             "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndt_pgo_wide.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
             "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip", "ndt_occgrid.hip", "ndtgpu_occgrid.hip", "ndt_linkgate.hip",
             "ndtgpu_linkgate.hip", "ndt_fuserfeat.hip", "ndt_scanproject.hip", "ndtgpu_scanproject.hip",
-            "ndt_calib.hip", "ndtgpu_calib.hip"]
+            "ndt_calib.hip", "ndtgpu_calib.hip", "ndt_locmon.hip", "ndtgpu_locmon.hip"]
 
 STATUS = {0: "OK", -1: "ERR_INVALID", -2: "ERR_HIP", -3: "ERR_NO_DEVICE", -4: "ERR_CAPACITY", -5: "ERR_ALLOC"}
 
@@ -119,6 +119,34 @@ class CalibResult(C.Structure):
     _fields_ = [("score", C.c_double), ("index", C.c_uint32), ("flags", C.c_uint32), ("n_skipped", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class LocmonParams(C.Structure):
+    _fields_ = [("max_dist", C.c_double), ("r_min", C.c_double), ("r_max", C.c_double), ("post_x", C.c_double), ("post_y", C.c_double),
+                ("occupied_min", C.c_int32), ("min_num_matches", C.c_int32)]
+
+
+class LocmonQuery(C.Structure):
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("c", C.c_double), ("s", C.c_double), ("scan", C.c_uint32), ("grid", C.c_uint32)]
+
+
+class LocmonResult(C.Structure):
+    _fields_ = [("badness", C.c_double), ("key", C.c_uint32), ("n_kept", C.c_uint32), ("n_offmap", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LocmonAdjustResult(C.Structure):
+    _fields_ = [("badness", C.c_double), ("key", C.c_uint32), ("index", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LocmonPick(C.Structure):
+    _fields_ = [("pair", C.c_int32), ("n_inliers", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+LOCMON_QUERY_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("c", "<f8"), ("s", "<f8"), ("scan", "<u4"), ("grid", "<u4")])
+LOCMON_RESULT_DTYPE = np.dtype([("badness", "<f8"), ("key", "<u4"), ("n_kept", "<u4"), ("n_offmap", "<u4"), ("flags", "<u4")])
+LOCMON_ADJUST_DTYPE = np.dtype([("badness", "<f8"), ("key", "<u4"), ("index", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+LOCMON_PICK_DTYPE = np.dtype([("pair", "<i4"), ("n_inliers", "<i4"), ("flags", "<u4"), ("reserved", "<u4")])
+assert LOCMON_QUERY_DTYPE.itemsize == C.sizeof(LocmonQuery) == 40 and LOCMON_RESULT_DTYPE.itemsize == C.sizeof(LocmonResult) == 24
+assert LOCMON_ADJUST_DTYPE.itemsize == C.sizeof(LocmonAdjustResult) == 24 and LOCMON_PICK_DTYPE.itemsize == C.sizeof(LocmonPick) == 16
+
 CALIB_RESULT_DTYPE = np.dtype([("score", "<f8"), ("index", "<u4"), ("flags", "<u4"), ("n_skipped", "<u4"), ("reserved", "<u4")])
 assert CALIB_RESULT_DTYPE.itemsize == C.sizeof(CalibResult) == 24
 
@@ -171,7 +199,12 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_default_scanproject_params", "ndtgpu_scanproj_tile", "ndtgpu_scanproj_check", "ndtgpu_scanproj_beam",
            "ndtgpu_scanproj_create", "ndtgpu_scanproj_destroy", "ndtgpu_scanproj_project_device", "ndtgpu_scanproj_project",
            "ndtgpu_default_calib_params", "ndtgpu_calib_tile", "ndtgpu_calib_lattice", "ndtgpu_calib_pair_motion", "ndtgpu_calib_select_pairs",
-           "ndtgpu_calib_check", "ndtgpu_calib_create", "ndtgpu_calib_destroy", "ndtgpu_calib_search_device", "ndtgpu_calib_search"]
+           "ndtgpu_calib_check", "ndtgpu_calib_create", "ndtgpu_calib_destroy", "ndtgpu_calib_search_device", "ndtgpu_calib_search",
+           "ndtgpu_default_locmon_params", "ndtgpu_locmon_tile", "ndtgpu_locmon_check", "ndtgpu_locmon_radius", "ndtgpu_locmon_beam_table",
+           "ndtgpu_locmon_pixel", "ndtgpu_locmon_metres", "ndtgpu_locmon_compose", "ndtgpu_locmon_create", "ndtgpu_locmon_destroy",
+           "ndtgpu_locmon_set_beams", "ndtgpu_locmon_set_grids_device", "ndtgpu_locmon_set_grids", "ndtgpu_locmon_field_get",
+           "ndtgpu_locmon_evaluate_device", "ndtgpu_locmon_evaluate", "ndtgpu_locmon_adjust_device", "ndtgpu_locmon_adjust",
+           "ndtgpu_locmon_pick_device"]
 
 _lib = None
 
@@ -387,6 +420,29 @@ def lib():
                                              C.c_size_t, dp, dp, C.c_size_t, C.POINTER(CalibParams), vp, vp, vp]
     L.ndtgpu_calib_search.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, u32p, dp, u32p, C.c_size_t, dp, C.c_size_t, dp,
                                       C.c_size_t, dp, dp, C.c_size_t, C.POINTER(CalibParams), C.POINTER(CalibResult), dp]
+    sz, i32, u32 = C.c_size_t, C.c_int32, C.c_uint32
+    lp = C.POINTER(LocmonParams)
+    L.ndtgpu_default_locmon_params.restype = None
+    L.ndtgpu_default_locmon_params.argtypes = [lp]
+    L.ndtgpu_locmon_tile.restype = u32
+    L.ndtgpu_locmon_tile.argtypes = []
+    L.ndtgpu_locmon_check.argtypes = [sz, sz, sz, C.c_double, sz, C.c_double, C.c_double, sz, sz, lp]
+    L.ndtgpu_locmon_radius.argtypes = [C.c_double, C.c_double, i32p]
+    L.ndtgpu_locmon_beam_table.argtypes = [sz, C.c_double, C.c_double, dp, dp]
+    L.ndtgpu_locmon_pixel.argtypes = [dp, C.c_double, C.c_double, C.c_double, dp, C.c_double, u32, u32, i32p, i32p]
+    L.ndtgpu_locmon_metres.argtypes = [u32, C.c_double, C.c_double, dp]
+    L.ndtgpu_locmon_compose.argtypes = [dp, dp, dp, dp]
+    L.ndtgpu_locmon_create.argtypes = [sz, sz, sz, sz, C.POINTER(vp)]
+    L.ndtgpu_locmon_destroy.argtypes = [vp]
+    L.ndtgpu_locmon_set_beams.argtypes = [vp, sz, C.c_double, C.c_double, vp]
+    L.ndtgpu_locmon_set_grids_device.argtypes = [vp, vp, sz, sz, sz, C.c_double, dp, lp, vp]
+    L.ndtgpu_locmon_set_grids.argtypes = [vp, vp, sz, sz, sz, C.c_double, dp, lp]
+    L.ndtgpu_locmon_field_get.argtypes = [vp, sz, vp]
+    L.ndtgpu_locmon_evaluate_device.argtypes = [vp, vp, sz, vp, sz, lp, vp, vp]
+    L.ndtgpu_locmon_evaluate.argtypes = [vp, dp, sz, vp, sz, lp, vp]
+    L.ndtgpu_locmon_adjust_device.argtypes = [vp, vp, sz, u32, u32, dp, sz, dp, sz, dp, dp, sz, lp, vp, vp, vp]
+    L.ndtgpu_locmon_adjust.argtypes = [vp, dp, sz, u32, u32, dp, sz, dp, sz, dp, dp, sz, lp, C.POINTER(LocmonAdjustResult), u32p]
+    L.ndtgpu_locmon_pick_device.argtypes = [vp, vp, vp, sz, u32, u32, lp, vp, vp, vp]
     if hasattr(L, "ndtgpu_live_resources"):            # (NDTGPU_LIB may name a build from before this entry existed)
         L.ndtgpu_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
@@ -2118,6 +2174,227 @@ class Calibrator:
         """the record search_device wrote (synchronises through the copy to the host): CALIB_RESULT_DTYPE scalar"""
         import torch
         return np.frombuffer(result_t.view(torch.uint8).cpu().numpy().tobytes()[:24], dtype=CALIB_RESULT_DTYPE)[0]
+
+
+LOCMON_TILE = 256            # ndtgpu_locmon_tile()
+LOCMON_NO_BEAMS, LOCMON_BAD_INDEX, LOCMON_NO_QUERY, LOCMON_NO_RESULT, LOCMON_NO_PICK = 1, 2, 4, 8, 16
+LOCMON_KEY_FAR, LOCMON_KEY_OFFMAP, LOCMON_NO_SCAN = 0x10000, 0x10001, 0xFFFFFFFF
+
+
+def locmon_params(**fields):
+    """ndtgpu_default_locmon_params (max_dist 0.375, r_min 0, r_max inf, post (-0.275, 0), occupied_min 55, min_num_matches 8) with
+    fields replaced"""
+    p = LocmonParams()
+    lib().ndtgpu_default_locmon_params(C.byref(p))
+    for k, v in fields.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown localisation-monitor parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def locmon_radius(max_dist, resolution):
+    """ndtgpu_locmon_radius: R = (int)floor(max_dist / resolution), 1 .. 254"""
+    R = C.c_int32()
+    _check(lib().ndtgpu_locmon_radius(float(max_dist), float(resolution), C.byref(R)))
+    return R.value
+
+
+def locmon_beam_table(n_beams, angle_min, angle_increment):
+    """ndtgpu_locmon_beam_table -> (cb [n_beams], sb [n_beams])"""
+    cb, sb = np.zeros(int(n_beams)), np.zeros(int(n_beams))
+    _check(lib().ndtgpu_locmon_beam_table(int(n_beams), float(angle_min), float(angle_increment), _dp(cb), _dp(sb)))
+    return cb, sb
+
+
+def locmon_pixel(pose4, cb, sb, r, origin2, resolution, width, height):
+    """ndtgpu_locmon_pixel -> (fi, fj), or None where the endpoint is off the map"""
+    p, o = _f64(pose4).reshape(4), _f64(origin2).reshape(2)
+    cell, inb = (C.c_int32 * 2)(), C.c_int32()
+    _check(lib().ndtgpu_locmon_pixel(_dp(p), float(cb), float(sb), float(r), _dp(o), float(resolution), int(width), int(height), cell,
+                                     C.byref(inb)))
+    return (cell[0], cell[1]) if inb.value else None
+
+
+def locmon_metres(key, resolution, max_dist):
+    """ndtgpu_locmon_metres: the badness of a key"""
+    out = np.zeros(1)
+    _check(lib().ndtgpu_locmon_metres(int(key), float(resolution), float(max_dist), _dp(out)))
+    return float(out[0])
+
+
+def locmon_compose(ref_pose4, match4, post2=(-0.275, 0.0)):
+    """ndtgpu_locmon_compose: ref_pose o match o post as (x, y, c, s)"""
+    a, b, c, out = _f64(ref_pose4).reshape(4), _f64(match4).reshape(4), _f64(post2).reshape(2), np.zeros(4)
+    _check(lib().ndtgpu_locmon_compose(_dp(a), _dp(b), _dp(c), _dp(out)))
+    return out
+
+
+class LocalizationMonitor:
+    """ndtgpu_locmon: the scan-pose evaluator of flirtlib_ros over occupancy grids (include/ndtgpu.h "localisation monitor"): the
+    distance field of the installed grids, the badness of (scan, grid, x, y, cos, sin) queries, adjustPose over a lattice of
+    calib_lattice, and the pick of the best-matching reference scan from FeatureMatcher's device results."""
+
+    def __init__(self, max_grids, max_pixels, max_beams, max_candidates=1):
+        h = C.c_void_p()
+        _check(lib().ndtgpu_locmon_create(int(max_grids), int(max_pixels), int(max_beams), int(max_candidates), C.byref(h)))
+        self.h = h
+        self.shape = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ndtgpu_locmon_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_beams(self, n_beams, angle_min, angle_increment, stream=None):
+        _check(lib().ndtgpu_locmon_set_beams(self.h, int(n_beams), float(angle_min), float(angle_increment), _stream_ptr(stream)))
+        self.n_beams = int(n_beams)
+
+    def set_grids(self, grids, resolution, origins, **params):
+        """HOST grids int8 [n_grids, height, width], origins [n_grids, 2]; keyword arguments: fields of ndtgpu_locmon_params.
+        Synchronous."""
+        g = np.ascontiguousarray(grids, dtype=np.int8)
+        if g.ndim != 3:
+            raise ValueError("LocalizationMonitor.set_grids: grids must be [n_grids, height, width]")
+        o = _f64(origins).reshape(-1, 2)
+        if o.shape[0] != g.shape[0]:
+            raise ValueError("LocalizationMonitor.set_grids: one origin per grid")
+        p = locmon_params(**params)
+        _check(lib().ndtgpu_locmon_set_grids(self.h, C.c_void_p(g.ctypes.data), g.shape[0], g.shape[2], g.shape[1], float(resolution), _dp(o),
+                                             C.byref(p)))
+        self.shape = g.shape
+
+    def set_grids_device(self, grids_t, resolution, origins, stream=None, **params):
+        """the same on a contiguous int8 device tensor [n_grids, height, width] (what MapSet.occupancy_grid_device writes),
+        asynchronous on `stream`"""
+        import torch
+        if not (grids_t.is_cuda and grids_t.is_contiguous() and grids_t.dtype == torch.int8 and grids_t.dim() == 3):
+            raise ValueError("LocalizationMonitor.set_grids_device: grids_t must be a contiguous int8 device tensor [n_grids, height, width]")
+        o = _f64(origins).reshape(-1, 2)
+        if o.shape[0] != grids_t.shape[0]:
+            raise ValueError("LocalizationMonitor.set_grids_device: one origin per grid")
+        p = locmon_params(**params)
+        n, hgt, wid = (int(v) for v in grids_t.shape)
+        _check(lib().ndtgpu_locmon_set_grids_device(self.h, C.c_void_p(grids_t.data_ptr()), n, wid, hgt, float(resolution), _dp(o), C.byref(p),
+                                                    _stream_ptr(stream)))
+        self.shape = (n, hgt, wid)
+
+    def field(self, grid=0):
+        """ndtgpu_locmon_field_get: uint16 [height, width]; 0xFFFF: no obstacle within the radius"""
+        if self.shape is None:
+            raise ValueError("LocalizationMonitor.field: no grids are installed")
+        out = np.zeros(self.shape[1:], dtype=np.uint16)
+        _check(lib().ndtgpu_locmon_field_get(self.h, int(grid), C.c_void_p(out.ctypes.data)))
+        return out
+
+    @staticmethod
+    def queries(scan, grid, x, y, c, s):
+        """a LOCMON_QUERY_DTYPE array from broadcastable columns"""
+        cols = np.broadcast_arrays(scan, grid, x, y, c, s)
+        q = np.zeros(cols[0].shape, dtype=LOCMON_QUERY_DTYPE).reshape(-1)
+        for name, col in zip(("scan", "grid", "x", "y", "c", "s"), cols):
+            q[name] = np.asarray(col).reshape(-1)
+        return q
+
+    def evaluate(self, ranges, queries, **params):
+        """HOST ranges [n_scans, n_beams], queries LOCMON_QUERY_DTYPE [n] -> LOCMON_RESULT_DTYPE [n].  Synchronous."""
+        rr = _f64(ranges)
+        q = np.ascontiguousarray(queries, dtype=LOCMON_QUERY_DTYPE).reshape(-1)
+        if rr.ndim != 2 or rr.shape[1] != getattr(self, "n_beams", -1):
+            raise ValueError("LocalizationMonitor.evaluate: ranges must be [n_scans, n_beams of set_beams]")
+        res = np.zeros(q.shape[0], dtype=LOCMON_RESULT_DTYPE)
+        p = locmon_params(**params)
+        _check(lib().ndtgpu_locmon_evaluate(self.h, _dp(rr), rr.shape[0], C.c_void_p(q.ctypes.data), q.shape[0], C.byref(p),
+                                            C.c_void_p(res.ctypes.data)))
+        return res
+
+    def evaluate_device(self, ranges_t, queries_t, results_t, n_queries=None, stream=None, **params):
+        """the same on torch device tensors, asynchronous on `stream`: ranges_t float64 [n_scans, n_beams] contiguous; queries_t and
+        results_t contiguous device tensors of 40 and 24 bytes a record (uint8 [n, 40] / [n, 24])"""
+        import torch
+        if not (ranges_t.is_cuda and ranges_t.is_contiguous() and ranges_t.dtype == torch.float64 and ranges_t.dim() == 2 and
+                ranges_t.shape[1] == getattr(self, "n_beams", -1)):
+            raise ValueError("LocalizationMonitor.evaluate_device: ranges_t must be a contiguous float64 device tensor [n_scans, n_beams]")
+        qb = queries_t.numel() * queries_t.element_size()
+        n = qb // 40 if n_queries is None else int(n_queries)
+        if not (queries_t.is_cuda and queries_t.is_contiguous() and qb >= 40 * n and results_t.is_cuda and results_t.is_contiguous() and
+                results_t.numel() * results_t.element_size() >= 24 * n):
+            raise ValueError("LocalizationMonitor.evaluate_device: queries_t / results_t must be contiguous device tensors of 40 / 24 bytes "
+                             "a record")
+        p = locmon_params(**params)
+        _check(lib().ndtgpu_locmon_evaluate_device(self.h, C.c_void_p(ranges_t.data_ptr()), int(ranges_t.shape[0]),
+                                                   C.c_void_p(queries_t.data_ptr()), n, C.byref(p), C.c_void_p(results_t.data_ptr()),
+                                                   _stream_ptr(stream)))
+
+    @staticmethod
+    def _tables(lattice):
+        t = [_f64(lattice[k]).reshape(-1) for k in ("xs", "ys", "cs", "sn")]
+        if t[2].shape != t[3].shape:
+            raise ValueError("LocalizationMonitor: cs and sn must have one entry per yaw")
+        return t
+
+    def adjust(self, ranges, scan, grid, lattice, want_volume=False, **params):
+        """adjustPose on HOST ranges [n_scans, n_beams]: lattice is what calib_lattice(x0, y0, theta0, pos_range, pos_range, 3.14, dpos,
+        dtheta) returns -> dict(index, ix, iy, iyaw, key, badness, flags, volume uint32 [nx, ny, nyaw] or None).  Synchronous."""
+        rr = _f64(ranges)
+        if rr.ndim != 2 or rr.shape[1] != getattr(self, "n_beams", -1):
+            raise ValueError("LocalizationMonitor.adjust: ranges must be [n_scans, n_beams of set_beams]")
+        xs, ys, cs, sn = self._tables(lattice)
+        nx, ny, nyaw = xs.shape[0], ys.shape[0], cs.shape[0]
+        vol = np.zeros(nx * ny * nyaw, dtype=np.uint32) if want_volume else None
+        res = LocmonAdjustResult()
+        p = locmon_params(**params)
+        _check(lib().ndtgpu_locmon_adjust(self.h, _dp(rr), rr.shape[0], int(scan), int(grid), _dp(xs), nx, _dp(ys), ny, _dp(cs), _dp(sn), nyaw,
+                                          C.byref(p), C.byref(res), None if vol is None else vol.ctypes.data_as(C.POINTER(C.c_uint32))))
+        i = int(res.index)
+        return dict(index=i, ix=i // (ny * nyaw), iy=(i // nyaw) % ny, iyaw=i % nyaw, key=int(res.key), badness=float(res.badness),
+                    flags=int(res.flags), volume=None if vol is None else vol.reshape(nx, ny, nyaw))
+
+    def adjust_device(self, ranges_t, scan, grid, lattice, result_t, volume_t=None, stream=None, **params):
+        """the same on torch device tensors, asynchronous on `stream`: result_t 24 bytes (LOCMON_ADJUST_DTYPE), volume_t int32
+        [nx * ny * nyaw] (read as uint32) or None"""
+        import torch
+        if not (ranges_t.is_cuda and ranges_t.is_contiguous() and ranges_t.dtype == torch.float64 and ranges_t.dim() == 2 and
+                ranges_t.shape[1] == getattr(self, "n_beams", -1)):
+            raise ValueError("LocalizationMonitor.adjust_device: ranges_t must be a contiguous float64 device tensor [n_scans, n_beams]")
+        if not (result_t.is_cuda and result_t.is_contiguous() and result_t.numel() * result_t.element_size() >= 24):
+            raise ValueError("LocalizationMonitor.adjust_device: result_t must be a contiguous device tensor of at least 24 bytes")
+        xs, ys, cs, sn = self._tables(lattice)
+        nc = xs.shape[0] * ys.shape[0] * cs.shape[0]
+        p = locmon_params(**params)
+        _check(lib().ndtgpu_locmon_adjust_device(self.h, C.c_void_p(ranges_t.data_ptr()), int(ranges_t.shape[0]), int(scan), int(grid), _dp(xs),
+                                                 xs.shape[0], _dp(ys), ys.shape[0], _dp(cs), _dp(sn), cs.shape[0], C.byref(p),
+                                                 C.c_void_p(result_t.data_ptr()),
+                                                 _dev_ptr(volume_t, torch.int32, nc, "LocalizationMonitor.adjust_device volume_t"),
+                                                 _stream_ptr(stream)))
+
+    def pick_device(self, matches_t, ref_poses_t, n_pairs, scan, grid, query_t, pick_t, stream=None, **params):
+        """ndtgpu_locmon_pick_device: matches_t the results_dev of FeatureMatcher's device match (72 bytes a record), ref_poses_t float64
+        [n_pairs, 4]; writes one query (40 bytes) into query_t and one LOCMON_PICK_DTYPE record (16 bytes) into pick_t"""
+        import torch
+        n = int(n_pairs)
+        if n and not (matches_t.is_cuda and matches_t.is_contiguous() and matches_t.numel() * matches_t.element_size() >= 72 * n):
+            raise ValueError("LocalizationMonitor.pick_device: matches_t must be a contiguous device tensor of 72 bytes a pair")
+        if not (query_t.is_cuda and query_t.is_contiguous() and query_t.numel() * query_t.element_size() >= 40 and pick_t.is_cuda and
+                pick_t.is_contiguous() and pick_t.numel() * pick_t.element_size() >= 16):
+            raise ValueError("LocalizationMonitor.pick_device: query_t / pick_t must be contiguous device tensors of 40 / 16 bytes")
+        p = locmon_params(**params)
+        _check(lib().ndtgpu_locmon_pick_device(self.h, C.c_void_p(matches_t.data_ptr()) if n else None,
+                                               _dev_ptr(ref_poses_t, torch.float64, 4 * n, "LocalizationMonitor.pick_device ref_poses_t") if n
+                                               else None, n, int(scan), int(grid), C.byref(p), C.c_void_p(query_t.data_ptr()),
+                                               C.c_void_p(pick_t.data_ptr()), _stream_ptr(stream)))
+
+    @staticmethod
+    def read(t, dtype, n=1):
+        """n records of `dtype` from a device tensor (synchronises through the copy to the host)"""
+        import torch
+        return np.frombuffer(t.view(torch.uint8).cpu().numpy().tobytes()[:dtype.itemsize * n], dtype=dtype).copy()
 
 
 def match_d2d(target_set, tmap, source_set, smap, T, **params):
