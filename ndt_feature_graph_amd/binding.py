@@ -473,14 +473,39 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
-def match_params(**kw):
-    p = MatchParams()
-    lib().ndtgpu_default_match_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise TypeError("unknown match parameter %r" % k)
-        setattr(p, k, v)
+def _params(struct_type, default_fn, label, fields, hidden=()):
+    """the library's defaults (default_fn names the ndtgpu_default_* function) with `fields` replaced; a field that is an array takes
+    a sequence of numbers"""
+    p = struct_type()
+    getattr(lib(), default_fn)(C.byref(p))
+    for k, v in fields.items():
+        if not hasattr(p, k) or k in hidden:
+            raise TypeError("unknown %s parameter %r" % (label, k))
+        if isinstance(getattr(p, k), C.Array):
+            getattr(p, k)[:] = [float(x) for x in np.asarray(v, dtype=np.float64).ravel()]
+        else:
+            setattr(p, k, v)
     return p
+
+
+class _Handle:
+    """close / __del__ of a class that keeps a handle of the library in self.h; _destroy names the function that destroys it"""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(lib(), self._destroy)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def match_params(**kw):
+    return _params(MatchParams, "ndtgpu_default_match_params", "match", kw)
 
 
 def _stream_ptr(stream):
@@ -491,8 +516,9 @@ def _stream_ptr(stream):
     return C.c_void_p(int(stream))
 
 
-class MapSet:
+class MapSet(_Handle):
     """B x lslgeneric::NDTMap(new LazyGrid(res)) with one grid geometry, resident in HBM."""
+    _destroy = "ndtgpu_mapset_destroy"
 
     def __init__(self, res, centre, size_m, n_maps=1, max_cells=0):
         L = lib()
@@ -506,17 +532,6 @@ class MapSet:
         self.h = h
         self.n_maps = int(n_maps)
         self.res = float(res)
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().ndtgpu_mapset_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def info(self):
         n = C.c_size_t()
@@ -838,10 +853,11 @@ MATCHER_AUTO, MATCHER_PER_BATCH, MATCHER_STREAM_FED = 0, 1, 2
 COV_SINGULAR, COV_POSE_UNCHANGED, COV_NOT_COMPUTED = 1, 2, 4
 
 
-class Registrar:
+class Registrar(_Handle):
     """ndtgpu_registrar: scans in, poses out -- grid builds + D2D matcher of batches of scan pairs as ONE asynchronous call,
     pipelined over the library's own streams (include/ndtgpu.h).  Keyword arguments beyond pairs_per_batch / depth are the
     fields of ndtgpu_registrar_params (matcher_form, matcher_groups, build_streams, linger_us, recalibrate_pct)."""
+    _destroy = "ndtgpu_registrar_destroy"
 
     def __init__(self, res, centre, size_m, pairs_per_batch=1024, depth=8, max_cells=0, **fields):
         gp = GridParams()
@@ -868,17 +884,6 @@ class Registrar:
         i = RegistrarInfo()
         _check(lib().ndtgpu_registrar_get_info(self.h, C.byref(i)))
         return {k: getattr(i, k) for k, _ in RegistrarInfo._fields_}
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().ndtgpu_registrar_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def submit(self, targets, sources, T16_dev, results_dev, range_limit=-1.0, n_min=3, eval_factor=1000.0, stream=None,
                covariance_mode=None, cov36_dev=None, cov_flags_dev=None, **params):
@@ -965,11 +970,12 @@ def default_resolutions():
     return tuple(r[:n.value])
 
 
-class MultiRes:
+class MultiRes(_Handle):
     """ndtgpu_multires: NDTMatcherD2D(irregular, useDefaultGridResolutions, resolutions).match(target_pc, source_pc, T,
     useInitialGuess) -- coarse-to-fine D2D registration of raw scan pairs, sub-batch after sub-batch of pairs_per_batch
     (include/ndtgpu.h).  Every level's maps sit on the grid (centre, size_m) at the level's cell size; resolutions=None: the
     default list.  The levels run from the last entry of the list to the first."""
+    _destroy = "ndtgpu_multires_destroy"
 
     def __init__(self, centre, size_m, resolutions=None, pairs_per_batch=1024, max_cells=0):
         gp = GridParams()
@@ -993,17 +999,6 @@ class MultiRes:
         i = MultiResInfo()
         _check(lib().ndtgpu_multires_get_info(self.h, C.byref(i)))
         return {k: getattr(i, k) for k, _ in MultiResInfo._fields_}
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().ndtgpu_multires_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def register_device(self, targets, sources, T16_dev, results_dev, use_initial_guess=True, range_limit=-1.0, n_min=3,
                         eval_factor=1000.0, stream=None, **params):
@@ -1058,21 +1053,13 @@ assert MCL_RESULT_DTYPE.itemsize == C.sizeof(MclResult)
 
 def mcl_params(**fields):
     """ndtgpu_default_mcl_params with fields replaced (motion_model: 36 values row-major, scan_size / motion_model_offset: 3 / 6)"""
-    p = MclParams()
-    lib().ndtgpu_default_mcl_params(C.byref(p))
-    for k, v in fields.items():
-        if not hasattr(p, k):
-            raise TypeError("unknown MCL parameter %r" % k)
-        if k in ("scan_size", "motion_model", "motion_model_offset"):
-            getattr(p, k)[:] = [float(x) for x in np.asarray(v, dtype=np.float64).ravel()]
-        else:
-            setattr(p, k, v)
-    return p
+    return _params(MclParams, "ndtgpu_default_mcl_params", "MCL", fields)
 
 
-class MCL:
+class MCL(_Handle):
     """ndtgpu_mcl: a bank of n_filters NDTMCL3D particle filters of n_particles particles; filter k localises in map map_idx[k]
     of the borrowed MapSet map_set (include/ndtgpu.h).  Poses are 4x4 (math convention) in and out."""
+    _destroy = "ndtgpu_mcl_destroy"
 
     def __init__(self, map_set, map_idx, n_particles, **params):
         idx = np.ascontiguousarray(np.atleast_1d(map_idx), dtype=np.uint32)
@@ -1081,17 +1068,6 @@ class MCL:
         _check(lib().ndtgpu_mcl_create(map_set.h, idx.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(p), idx.shape[0], int(n_particles),
                                        C.byref(h)))
         self.h, self.map_set, self.n_filters, self.n_particles = h, map_set, int(idx.shape[0]), int(n_particles)
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().ndtgpu_mcl_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _cm(T, n):
@@ -1181,16 +1157,7 @@ PGO_CONVERGED, PGO_MAX_ITERATIONS, PGO_LINEAR_CAP, PGO_NOT_FINITE = 0, 1, 2, 3
 
 def pgo_params(**fields):
     """ndtgpu_default_pgo_params with fields replaced (prior_information: 9 values row-major)"""
-    p = PgoParams()
-    lib().ndtgpu_default_pgo_params(C.byref(p))
-    for k, v in fields.items():
-        if not hasattr(p, k):
-            raise TypeError("unknown PGO parameter %r" % k)
-        if k == "prior_information":
-            p.prior_information[:] = [float(x) for x in np.asarray(v, dtype=np.float64).ravel()]
-        else:
-            setattr(p, k, v)
-    return p
+    return _params(PgoParams, "ndtgpu_default_pgo_params", "PGO", fields)
 
 
 def pgo_wide_params(check_every=None):
@@ -1209,26 +1176,16 @@ def pgo_wide_plan(n_nodes, n_edges):
     return tile.value, nt.value, et.value, extra.value
 
 
-class PGO:
+class PGO(_Handle):
     """ndtgpu_pgo: a bank of n_graphs SE(2) pose graphs of up to max_nodes nodes and max_edges links, optimised one workgroup per
     graph (include/ndtgpu.h: optimizeGraphUsingISAM).  Poses are (x, y, yaw) rows."""
+    _destroy = "ndtgpu_pgo_destroy"
 
     def __init__(self, n_graphs, max_nodes, max_edges):
         h = C.c_void_p()
         _check(lib().ndtgpu_pgo_create(int(n_graphs), int(max_nodes), int(max_edges), C.byref(h)))
         self.h, self.n_graphs = h, int(n_graphs)
         self._n_nodes = [0] * int(n_graphs)
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().ndtgpu_pgo_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _graph(poses, ref, mov):
@@ -1301,13 +1258,7 @@ class WorldResult(C.Structure):
 
 def world_params(**fields):
     """ndtgpu_default_world_params with fields replaced"""
-    p = WorldParams()
-    lib().ndtgpu_default_world_params(C.byref(p))
-    for k, v in fields.items():
-        if not hasattr(p, k) or k == "reserved_":
-            raise TypeError("unknown world parameter %r" % k)
-        setattr(p, k, v)
-    return p
+    return _params(WorldParams, "ndtgpu_default_world_params", "world", fields, hidden=("reserved_",))
 
 
 def assemble_world(dst, dst_first, src, node_lists, T16_lists, params=None, stream=None):
@@ -1351,13 +1302,7 @@ class OccGridInfo(C.Structure):
 
 def occgrid_params(**fields):
     """ndtgpu_default_occgrid_params with fields replaced"""
-    p = OccGridParams()
-    lib().ndtgpu_default_occgrid_params(C.byref(p))
-    for k, v in fields.items():
-        if not hasattr(p, k) or k == "reserved_":
-            raise TypeError("unknown occupancy-grid parameter %r" % k)
-        setattr(p, k, v)
-    return p
+    return _params(OccGridParams, "ndtgpu_default_occgrid_params", "occupancy-grid", fields, hidden=("reserved_",))
 
 
 def occupancy_grid_dims(res, cells_per_axis, centre, resolution):
@@ -1387,13 +1332,7 @@ class LinkGateParams(C.Structure):
 
 def linkgate_params(**fields):
     """ndtgpu_default_linkgate_params (0.1, 1.0, 0.2, 2, clip_cosine 0) with fields replaced"""
-    p = LinkGateParams()
-    lib().ndtgpu_default_linkgate_params(C.byref(p))
-    for k, v in fields.items():
-        if not hasattr(p, k):
-            raise TypeError("unknown link-gate parameter %r" % k)
-        setattr(p, k, v)
-    return p
+    return _params(LinkGateParams, "ndtgpu_default_linkgate_params", "link-gate", fields)
 
 
 def _dev_ptr(t, dtype, numel, what):
@@ -1405,27 +1344,17 @@ def _dev_ptr(t, dtype, numel, what):
     return C.c_void_p(t.data_ptr())
 
 
-class LinkGate:
+class LinkGate(_Handle):
     """ndtgpu_linkgate: which links exist (include/ndtgpu.h "link gating") -- the candidate pairs of computeAllPossibleLinks gated
     by index distance and odometry, getValidLinks of the registered links, and the gather that packs what stays.  Works on torch
     device tensors; uint32 index arrays are int32 tensors (torch has no uint32 arithmetic; the bits are the same).  Poses are
     [n, 16] column-major on the device, [n, 4, 4] where a host array is taken."""
+    _destroy = "ndtgpu_linkgate_destroy"
 
     def __init__(self, max_nodes, max_links):
         h = C.c_void_p()
         _check(lib().ndtgpu_linkgate_create(int(max_nodes), int(max_links), C.byref(h)))
         self.h, self.max_nodes, self.max_links, self.n_nodes = h, int(max_nodes), int(max_links), 0
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().ndtgpu_linkgate_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_nodes(self, T, stream=None):
         """the node poses: a host array [n, 4, 4] (synchronous), or a float64 device tensor [n, 16] column-major (on `stream`)"""
@@ -1607,45 +1536,23 @@ FEATEXTRACT_OK, FEATEXTRACT_TOO_FEW_POINTS, FEATEXTRACT_OVERFLOW, FEATEXTRACT_BA
 
 def featextract_params(**fields):
     """ndtgpu_default_featextract_params with fields replaced"""
-    p = FeatExtractParams()
-    lib().ndtgpu_default_featextract_params(C.byref(p))
-    for k, v in fields.items():
-        if not hasattr(p, k):
-            raise TypeError("unknown feature-extraction parameter %r" % k)
-        setattr(p, k, v)
-    return p
+    return _params(FeatExtractParams, "ndtgpu_default_featextract_params", "feature-extraction", fields)
 
 
 def featmatch_params(**fields):
     """ndtgpu_default_featmatch_params with fields replaced"""
-    p = FeatMatchParams()
-    lib().ndtgpu_default_featmatch_params(C.byref(p))
-    for k, v in fields.items():
-        if not hasattr(p, k):
-            raise TypeError("unknown feature-match parameter %r" % k)
-        setattr(p, k, v)
-    return p
+    return _params(FeatMatchParams, "ndtgpu_default_featmatch_params", "feature-match", fields)
 
 
-class FeatureMatcher:
+class FeatureMatcher(_Handle):
     """ndtgpu_featbank: n_sets feature sets of up to max_points points (position (x, y, theta) + descriptor of desc_len doubles) in
     device memory, and the RANSAC matching of pairs of them, one workgroup per pair (include/ndtgpu.h: matchFeatureMap)."""
+    _destroy = "ndtgpu_featbank_destroy"
 
     def __init__(self, n_sets, max_points, desc_len=48):
         h = C.c_void_p()
         _check(lib().ndtgpu_featbank_create(int(n_sets), int(max_points), int(desc_len), C.byref(h)))
         self.h, self.n_sets, self.max_points, self.desc_len = h, int(n_sets), int(max_points), int(desc_len)
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().ndtgpu_featbank_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set(self, k, pos, desc):
         """set k: pos [n, 3] (x, y, theta), desc [n, desc_len]; n = 0 empties it"""
@@ -1853,26 +1760,16 @@ def fuser_prepare(params, Tnow, Tmotion, node_centre):
     return {k: np.array(getattr(out, k)) for k, _ in FuserPrepared._fields_}
 
 
-class FuserBank:
+class FuserBank(_Handle):
     """ndtgpu_fuser_bank: NDTFeatureFuserHMT::initialize / update for a batch of independent fusers, one asynchronous call
     each (include/ndtgpu.h).  Poses are 4x4 row-major NumPy arrays on this side."""
+    _destroy = "ndtgpu_fuser_bank_destroy"
 
     def __init__(self, params, n_fusers, node_maps=None):
         h = C.c_void_p()
         _check(lib().ndtgpu_fuser_bank_create(C.byref(params), int(n_fusers), node_maps.h if node_maps is not None else None, C.byref(h)))
         self.h, self.n, self.params = h, int(n_fusers), params
         self._node_maps = node_maps       # (kept alive)
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().ndtgpu_fuser_bank_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def mapsets(self):
         a, b = C.c_void_p(), C.c_void_p()
@@ -1961,13 +1858,7 @@ SCANPROJECT_TILE = 1024      # ndtgpu_scanproj_tile(): the beams of a tile
 
 def scanproject_params(**fields):
     """ndtgpu_default_scanproject_params (r_min 0.5, r_max 30.0, varz 0.02, seed 0) with fields replaced"""
-    p = ScanProjectParams()
-    lib().ndtgpu_default_scanproject_params(C.byref(p))
-    for k, v in fields.items():
-        if not hasattr(p, k):
-            raise TypeError("unknown scan-projection parameter %r" % k)
-        setattr(p, k, v)
-    return p
+    return _params(ScanProjectParams, "ndtgpu_default_scanproject_params", "scan-projection", fields)
 
 
 def scan_project_beam(angle_min, angle_increment, scan_id, i, r, **params):
@@ -1979,26 +1870,16 @@ def scan_project_beam(angle_min, angle_increment, scan_id, i, r, **params):
     return np.array(xyz[:], dtype=np.float32) if kept else None
 
 
-class ScanProjector:
+class ScanProjector(_Handle):
     """ndtgpu_scanproj: a batch of laser scans (ranges, beam i at angle_min + i * angle_increment) to the clouds in the sensor frame
     that the fuser bank and the registrar take (include/ndtgpu.h "laser-scan projection"): the kept points in beam order, NaN rows
     behind them."""
+    _destroy = "ndtgpu_scanproj_destroy"
 
     def __init__(self, max_scans, max_beams):
         h = C.c_void_p()
         _check(lib().ndtgpu_scanproj_create(int(max_scans), int(max_beams), C.byref(h)))
         self.h, self.max_scans, self.max_beams = h, int(max_scans), int(max_beams)
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().ndtgpu_scanproj_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def project(self, ranges, angle_min, angle_increment, scan_ids=None, stride=12, **params):
         """HOST ranges [n, n_beams] -> (xyz float32 [n, n_beams, stride / 4] -- floats behind the fourth are zero --, n_kept uint32
@@ -2049,13 +1930,7 @@ CALIB_NO_RESULT, CALIB_BAD_PAIR = 1, 2
 
 def calib_params(**fields):
     """ndtgpu_default_calib_params (max_dist 0.1) with fields replaced"""
-    p = CalibParams()
-    lib().ndtgpu_default_calib_params(C.byref(p))
-    for k, v in fields.items():
-        if not hasattr(p, k):
-            raise TypeError("unknown calibration parameter %r" % k)
-        setattr(p, k, v)
-    return p
+    return _params(CalibParams, "ndtgpu_default_calib_params", "calibration", fields)
 
 
 def calib_lattice(ix, iy, iyaw, x_s, y_s, yaw_s, t_r, yaw_r):
@@ -2088,33 +1963,24 @@ def calib_select_pairs(poses4, max_translation=1.0, min_yaw=25.0 * np.pi / 180.0
     return pairs[:m.value].copy()
 
 
-class Calibrator:
+def _lattice_tables(lattice, who):
+    """the tables xs, ys, cs, sn of a lattice (what calib_lattice returns) as flat float64 arrays"""
+    t = [_f64(lattice[k]).reshape(-1) for k in ("xs", "ys", "cs", "sn")]
+    if t[2].shape != t[3].shape:
+        raise ValueError("%s: cs and sn must have one entry per yaw" % who)
+    return t
+
+
+class Calibrator(_Handle):
     """ndtgpu_calib: the laser's pose on the base by brute-force search over sensor offsets (include/ndtgpu.h "extrinsic
     calibration").  Clouds are a bank in the layout ScanProjector writes; poses are (x, y, cos yaw, sin yaw) of the base; pairs are
     (scan of cloud1, scan of cloud2); the lattice is what calib_lattice returns."""
+    _destroy = "ndtgpu_calib_destroy"
 
     def __init__(self, max_pairs, max_points, max_candidates):
         h = C.c_void_p()
         _check(lib().ndtgpu_calib_create(int(max_pairs), int(max_points), int(max_candidates), C.byref(h)))
         self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().ndtgpu_calib_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @staticmethod
-    def _tables(lattice):
-        t = [_f64(lattice[k]).reshape(-1) for k in ("xs", "ys", "cs", "sn")]
-        if t[2].shape != t[3].shape:
-            raise ValueError("Calibrator: cs and sn must have one entry per yaw")
-        return t
 
     def search(self, xyz, n_kept, poses4, pairs, lattice, want_volume=False, **params):
         """HOST xyz float32 [n_scans, n_points, w >= 3], n_kept [n_scans], poses4 [n_scans, 4], pairs [n_pairs, 2] ->
@@ -2128,7 +1994,7 @@ class Calibrator:
         pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
         if kept.shape[0] != n or pp.shape[0] != n:
             raise ValueError("Calibrator.search: one n_kept and one pose per scan")
-        xs, ys, cs, sn = self._tables(lattice)
+        xs, ys, cs, sn = _lattice_tables(lattice, "Calibrator")
         vol = np.zeros(xs.shape[0] * ys.shape[0] * cs.shape[0]) if want_volume else None
         res = CalibResult()
         p = calib_params(**params)
@@ -2158,7 +2024,7 @@ class Calibrator:
             raise ValueError("Calibrator.search_device: pairs_t must be a contiguous int32 device tensor [n_pairs, 2]")
         if not (result_t.is_cuda and result_t.is_contiguous() and result_t.numel() * result_t.element_size() >= 24):
             raise ValueError("Calibrator.search_device: result_t must be a contiguous device tensor of at least 24 bytes")
-        xs, ys, cs, sn = self._tables(lattice)
+        xs, ys, cs, sn = _lattice_tables(lattice, "Calibrator")
         nc = xs.shape[0] * ys.shape[0] * cs.shape[0]
         p = calib_params(**params)
         _check(lib().ndtgpu_calib_search_device(self.h, C.c_void_p(xyz_t.data_ptr()), n, npts, 4 * int(xyz_t.stride(1)),
@@ -2184,13 +2050,7 @@ LOCMON_KEY_FAR, LOCMON_KEY_OFFMAP, LOCMON_NO_SCAN = 0x10000, 0x10001, 0xFFFFFFFF
 def locmon_params(**fields):
     """ndtgpu_default_locmon_params (max_dist 0.375, r_min 0, r_max inf, post (-0.275, 0), occupied_min 55, min_num_matches 8) with
     fields replaced"""
-    p = LocmonParams()
-    lib().ndtgpu_default_locmon_params(C.byref(p))
-    for k, v in fields.items():
-        if not hasattr(p, k):
-            raise TypeError("unknown localisation-monitor parameter %r" % k)
-        setattr(p, k, v)
-    return p
+    return _params(LocmonParams, "ndtgpu_default_locmon_params", "localisation-monitor", fields)
 
 
 def locmon_radius(max_dist, resolution):
@@ -2230,27 +2090,17 @@ def locmon_compose(ref_pose4, match4, post2=(-0.275, 0.0)):
     return out
 
 
-class LocalizationMonitor:
+class LocalizationMonitor(_Handle):
     """ndtgpu_locmon: the scan-pose evaluator of flirtlib_ros over occupancy grids (include/ndtgpu.h "localisation monitor"): the
     distance field of the installed grids, the badness of (scan, grid, x, y, cos, sin) queries, adjustPose over a lattice of
     calib_lattice, and the pick of the best-matching reference scan from FeatureMatcher's device results."""
+    _destroy = "ndtgpu_locmon_destroy"
 
     def __init__(self, max_grids, max_pixels, max_beams, max_candidates=1):
         h = C.c_void_p()
         _check(lib().ndtgpu_locmon_create(int(max_grids), int(max_pixels), int(max_beams), int(max_candidates), C.byref(h)))
         self.h = h
         self.shape = None
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().ndtgpu_locmon_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_beams(self, n_beams, angle_min, angle_increment, stream=None):
         _check(lib().ndtgpu_locmon_set_beams(self.h, int(n_beams), float(angle_min), float(angle_increment), _stream_ptr(stream)))
@@ -2332,20 +2182,13 @@ class LocalizationMonitor:
                                                    C.c_void_p(queries_t.data_ptr()), n, C.byref(p), C.c_void_p(results_t.data_ptr()),
                                                    _stream_ptr(stream)))
 
-    @staticmethod
-    def _tables(lattice):
-        t = [_f64(lattice[k]).reshape(-1) for k in ("xs", "ys", "cs", "sn")]
-        if t[2].shape != t[3].shape:
-            raise ValueError("LocalizationMonitor: cs and sn must have one entry per yaw")
-        return t
-
     def adjust(self, ranges, scan, grid, lattice, want_volume=False, **params):
         """adjustPose on HOST ranges [n_scans, n_beams]: lattice is what calib_lattice(x0, y0, theta0, pos_range, pos_range, 3.14, dpos,
         dtheta) returns -> dict(index, ix, iy, iyaw, key, badness, flags, volume uint32 [nx, ny, nyaw] or None).  Synchronous."""
         rr = _f64(ranges)
         if rr.ndim != 2 or rr.shape[1] != getattr(self, "n_beams", -1):
             raise ValueError("LocalizationMonitor.adjust: ranges must be [n_scans, n_beams of set_beams]")
-        xs, ys, cs, sn = self._tables(lattice)
+        xs, ys, cs, sn = _lattice_tables(lattice, "LocalizationMonitor")
         nx, ny, nyaw = xs.shape[0], ys.shape[0], cs.shape[0]
         vol = np.zeros(nx * ny * nyaw, dtype=np.uint32) if want_volume else None
         res = LocmonAdjustResult()
@@ -2365,7 +2208,7 @@ class LocalizationMonitor:
             raise ValueError("LocalizationMonitor.adjust_device: ranges_t must be a contiguous float64 device tensor [n_scans, n_beams]")
         if not (result_t.is_cuda and result_t.is_contiguous() and result_t.numel() * result_t.element_size() >= 24):
             raise ValueError("LocalizationMonitor.adjust_device: result_t must be a contiguous device tensor of at least 24 bytes")
-        xs, ys, cs, sn = self._tables(lattice)
+        xs, ys, cs, sn = _lattice_tables(lattice, "LocalizationMonitor")
         nc = xs.shape[0] * ys.shape[0] * cs.shape[0]
         p = locmon_params(**params)
         _check(lib().ndtgpu_locmon_adjust_device(self.h, C.c_void_p(ranges_t.data_ptr()), int(ranges_t.shape[0]), int(scan), int(grid), _dp(xs),

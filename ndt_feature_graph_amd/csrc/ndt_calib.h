@@ -193,17 +193,7 @@ inline const char *ndt_calib_check_params(const ndtgpu_calib_params &p)
     if (!(p.max_dist > 0.0 && p.max_dist < 1e150)) return "max_dist must be finite and > 0";
     return nullptr;
 }
-// the lattice tables of a call: finite, and c * c + s * s within 1e-6 of 1
-inline const char *ndt_calib_check_tables(const double *xs, size_t nx, const double *ys, size_t ny, const double *cs, const double *sn, size_t nyaw)
-{
-    for (size_t k = 0; k < nx; k++)
-        if (!(std::fabs(xs[k]) < 1e150)) return "xs must be finite";
-    for (size_t k = 0; k < ny; k++)
-        if (!(std::fabs(ys[k]) < 1e150)) return "ys must be finite";
-    for (size_t k = 0; k < nyaw; k++)
-        if (!(std::fabs(cs[k] * cs[k] + sn[k] * sn[k] - 1.0) < 1e-6)) return "cs / sn must be the cosine and sine of an angle";
-    return nullptr;
-}
+// (the lattice tables of a call: csrc/ndt_lattice.h)
 inline const char *ndt_calib_check_capacity(size_t max_pairs, size_t max_points, size_t max_candidates)
 {
     if (max_pairs == 0 || max_pairs > NDT_CALIB_MAX_PAIRS) return "max_pairs must be 1 .. 1024";

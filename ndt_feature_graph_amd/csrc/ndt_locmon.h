@@ -203,17 +203,7 @@ inline const char *ndt_locmon_check_lattice(size_t nx, size_t ny, size_t nyaw)
     if (nx * ny > NDT_LOCMON_MAX_CANDIDATES || nx * ny * nyaw > NDT_LOCMON_MAX_CANDIDATES) return "nx * ny * nyaw: more than 2^24 candidates";
     return nullptr;
 }
-// the lattice tables of a search: finite, and c * c + s * s within 1e-6 of 1
-inline const char *ndt_locmon_check_tables(const double *xs, size_t nx, const double *ys, size_t ny, const double *cs, const double *sn, size_t nyaw)
-{
-    for (size_t k = 0; k < nx; k++)
-        if (!(std::fabs(xs[k]) < 1e150)) return "xs must be finite";
-    for (size_t k = 0; k < ny; k++)
-        if (!(std::fabs(ys[k]) < 1e150)) return "ys must be finite";
-    for (size_t k = 0; k < nyaw; k++)
-        if (!(std::fabs(cs[k] * cs[k] + sn[k] * sn[k] - 1.0) < 1e-6)) return "cs / sn must be the cosine and sine of an angle";
-    return nullptr;
-}
+// (the lattice tables of a call: csrc/ndt_lattice.h)
 inline const char *ndt_locmon_check_capacity(size_t max_grids, size_t max_pixels, size_t max_beams, size_t max_candidates)
 {
     if (max_grids == 0 || max_grids > NDT_LOCMON_MAX_GRIDS) return "max_grids must be 1 .. 1024";

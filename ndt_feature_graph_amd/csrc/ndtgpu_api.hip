@@ -19,9 +19,7 @@ ndtgpu_status mapset_build_core(ndtgpu_mapset *s, size_t first, size_t count, co
     if (!s || first + count > s->n_maps || (!xyz_dev && n_points) || stride_bytes < 12 || (stride_bytes & 3) ||
         n_points > 0xFFFFFFFFull)
         return fail(NDTGPU_ERR_INVALID, "mapset_build: bad argument");
-    ndtgpu_cell_params cp;
-    ndtgpu_default_cell_params(&cp);
-    if (cell) cp = *cell;
+    const ndtgpu_cell_params cp = params_or_default(cell, ndtgpu_default_cell_params);
     if (s->v.occ && count)   // a rebuilt map starts from cells without readings
         HIP_TRY(hipMemsetAsync(s->v.occ + first * (size_t)s->v.grid.slots, 0, count * (size_t)s->v.grid.slots * sizeof(float), st));
     if (s->profiling && !s->profile_span) HIP_TRY(s->ev[0].record(st));
@@ -518,9 +516,7 @@ ndtgpu_status ndtgpu_mapset_add_cloud(ndtgpu_mapset *s, size_t first, size_t cou
         return fail(NDTGPU_ERR_INVALID, "add_cloud: bad argument");
     if (!s->v.occ) return fail(NDTGPU_ERR_INVALID, "add_cloud: call ndtgpu_mapset_enable_occupancy first (NDTMap::initialize)");
     if (count == 0) return NDTGPU_OK;
-    ndtgpu_fuse_params fp;
-    ndtgpu_default_fuse_params(&fp);
-    if (prm) fp = *prm;
+    const ndtgpu_fuse_params fp = params_or_default(prm, ndtgpu_default_fuse_params);
     if (!(fp.occupancy_limit > 0)) return fail(NDTGPU_ERR_INVALID, "add_cloud: occupancy_limit must be positive");
     hipStream_t st = (hipStream_t)stream;
     {

@@ -5,29 +5,17 @@
 #include "ndtgpu_host.h"
 #include "ndt_calib.h"
 
-#include <new>
-
 struct ndtgpu_calib {
     size_t max_pairs = 0, max_points = 0, max_candidates = 0, chunk = 0;
     DeviceBuffer<double> a3, b3, motion, partial, tile_score;
     DeviceBuffer<uint32_t> counts, tile_index;
-    // the lattice tables of a call: xs | ys | cs | sn, made by the first call and grown by later ones
-    DeviceBuffer<double> tables;
-    PinnedBuffer<double> tables_pin;
-    // the host form's staging (clouds | counts | poses | pairs in, result | volume out)
-    DeviceBuffer<char> stage;
-    PinnedBuffer<char> pin;
+    LatticeTables lattice;                 // the lattice tables of a call
+    HostStage host;                        // the host form's staging (clouds | counts | poses | pairs in, result | volume out)
     Fence used;                            // recorded after the last launch of a call
     Stream hst;                            // the host form's stream (last: ndtgpu_resource.h)
 };
 
-static ndtgpu_calib_params calib_params(const ndtgpu_calib_params *prm)
-{
-    ndtgpu_calib_params p;
-    ndtgpu_default_calib_params(&p);
-    if (prm) p = *prm;
-    return p;
-}
+static ndtgpu_calib_params calib_params(const ndtgpu_calib_params *prm) { return params_or_default(prm, ndtgpu_default_calib_params); }
 
 // the checks every entry makes before it reads the handle
 static ndtgpu_status calib_check(const char *who, size_t n_scans, size_t n_points, size_t stride_bytes, size_t map_stride_bytes, size_t n_pairs,
@@ -35,25 +23,14 @@ static ndtgpu_status calib_check(const char *who, size_t n_scans, size_t n_point
 {
     const char *bad = ndt_calib_check_args(n_scans, n_points, stride_bytes, map_stride_bytes, n_pairs, nx, ny, nyaw);
     if (!bad) bad = ndt_calib_check_params(p);
-    if (!bad) return NDTGPU_OK;
-    return fail(NDTGPU_ERR_INVALID, (std::string(who) + ": " + bad).c_str());
-}
-
-static ndtgpu_status calib_check_tables(const char *who, const double *xs, size_t nx, const double *ys, size_t ny, const double *cs,
-                                        const double *sn, size_t nyaw)
-{
-    if (!xs || !ys || !cs || !sn) return fail(NDTGPU_ERR_INVALID, (std::string(who) + ": null xs, ys, cs or sn").c_str());
-    if (const char *bad = ndt_calib_check_tables(xs, nx, ys, ny, cs, sn, nyaw))
-        return fail(NDTGPU_ERR_INVALID, (std::string(who) + ": " + bad).c_str());
-    return NDTGPU_OK;
+    return bad ? fail_in(NDTGPU_ERR_INVALID, who, bad) : NDTGPU_OK;
 }
 
 static ndtgpu_status calib_fits(const char *who, const ndtgpu_calib *h, size_t n_points, size_t n_pairs, size_t n_candidates)
 {
-    if (n_pairs > h->max_pairs) return fail(NDTGPU_ERR_CAPACITY, (std::string(who) + ": more pairs than the handle was created for").c_str());
-    if (n_points > h->max_points) return fail(NDTGPU_ERR_CAPACITY, (std::string(who) + ": more points than the handle was created for").c_str());
-    if (n_candidates > h->max_candidates)
-        return fail(NDTGPU_ERR_CAPACITY, (std::string(who) + ": more candidates than the handle was created for").c_str());
+    if (n_pairs > h->max_pairs) return fail_in(NDTGPU_ERR_CAPACITY, who, "more pairs than the handle was created for");
+    if (n_points > h->max_points) return fail_in(NDTGPU_ERR_CAPACITY, who, "more points than the handle was created for");
+    if (n_candidates > h->max_candidates) return fail_in(NDTGPU_ERR_CAPACITY, who, "more candidates than the handle was created for");
     return NDTGPU_OK;
 }
 
@@ -74,7 +51,7 @@ ndtgpu_status ndtgpu_calib_lattice(double ix, double iy, double iyaw, double x_s
     if (!counts3) return fail(NDTGPU_ERR_INVALID, "calib_lattice: counts3 is NULL");
     counts3[0] = counts3[1] = counts3[2] = 0;
     if (const char *bad = ndt_calib_check_lattice(ix, iy, iyaw, x_s, y_s, yaw_s, t_r, yaw_r))
-        return fail(NDTGPU_ERR_INVALID, (std::string("calib_lattice: ") + bad).c_str());
+        return fail_in(NDTGPU_ERR_INVALID, "calib_lattice", bad);
     const size_t cap = NDT_CALIB_MAX_CANDIDATES;
     const size_t nx = ndt_calib_axis(ix, x_s, t_r, xs, room, cap);
     const size_t ny = ndt_calib_axis(iy, y_s, t_r, ys, room, cap);
@@ -125,11 +102,10 @@ ndtgpu_status ndtgpu_calib_create(size_t max_pairs, size_t max_points, size_t ma
 {
     if (!out) return fail(NDTGPU_ERR_INVALID, "calib_create: out is NULL");
     *out = nullptr;
-    if (const char *bad = ndt_calib_check_capacity(max_pairs, max_points, max_candidates))
-        return fail(NDTGPU_ERR_INVALID, (std::string("calib_create: ") + bad).c_str());
-    if (!have_device()) return fail(NDTGPU_ERR_NO_DEVICE, "calib_create: no HIP device");
-    ndtgpu_calib *h = new (std::nothrow) ndtgpu_calib();
-    if (!h) return fail(NDTGPU_ERR_ALLOC, "calib_create: host alloc");
+    if (const char *bad = ndt_calib_check_capacity(max_pairs, max_points, max_candidates)) return fail_in(NDTGPU_ERR_INVALID, "calib_create", bad);
+    ndtgpu_calib *h;
+    const ndtgpu_status rc = handle_new("calib_create", h);
+    if (rc != NDTGPU_OK) return rc;
     h->max_pairs = max_pairs;
     h->max_points = max_points;
     h->max_candidates = max_candidates;
@@ -149,13 +125,7 @@ ndtgpu_status ndtgpu_calib_create(size_t max_pairs, size_t max_points, size_t ma
     return NDTGPU_OK;
 }
 
-ndtgpu_status ndtgpu_calib_destroy(ndtgpu_calib *h)
-{
-    if (!h) return fail(NDTGPU_ERR_INVALID, "calib_destroy: null");
-    (void)h->used.sync();                  // (the last call may have run on a stream of the caller's)
-    delete h;
-    return NDTGPU_OK;
-}
+ndtgpu_status ndtgpu_calib_destroy(ndtgpu_calib *h) { return handle_destroy(h, "calib_destroy"); }
 
 ndtgpu_status ndtgpu_calib_search_device(ndtgpu_calib *h, const void *xyz_dev, size_t n_scans, size_t n_points, size_t stride_bytes,
                                          size_t map_stride_bytes, const uint32_t *n_kept_dev, const double *poses_dev,
@@ -169,31 +139,22 @@ ndtgpu_status ndtgpu_calib_search_device(ndtgpu_calib *h, const void *xyz_dev, s
     if (rc != NDTGPU_OK) return rc;
     if (!xyz_dev || !n_kept_dev || !poses_dev || !pairs_dev || !result_dev)
         return fail(NDTGPU_ERR_INVALID, "calib_search_device: null xyz_dev, n_kept_dev, poses_dev, pairs_dev or result_dev");
-    if ((rc = calib_check_tables(who, xs, nx, ys, ny, cs, sn, nyaw)) != NDTGPU_OK) return rc;
+    if ((rc = LatticeTables::check(who, xs, nx, ys, ny, cs, sn, nyaw)) != NDTGPU_OK) return rc;
     if (!h) return fail(NDTGPU_ERR_INVALID, "calib_search_device: null handle");
     const size_t n_candidates = nx * ny * nyaw;
     if ((rc = calib_fits(who, h, n_points, n_pairs, n_candidates)) != NDTGPU_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    // the tables: the pinned copy is overwritten, so the previous call's upload must have ended (and the blocks may be replaced)
-    const size_t n_tab = nx + ny + 2 * nyaw;
-    HIP_TRY(h->used.sync());
-    if (h->tables.reserve(n_tab) != hipSuccess || h->tables_pin.reserve(n_tab) != hipSuccess)
-        return fail(NDTGPU_ERR_ALLOC, "calib_search_device: lattice tables");
-    double *tp = h->tables_pin.get(), *td = h->tables.get();
-    memcpy(tp, xs, nx * sizeof(double));
-    memcpy(tp + nx, ys, ny * sizeof(double));
-    memcpy(tp + nx + ny, cs, nyaw * sizeof(double));
-    memcpy(tp + nx + ny + nyaw, sn, nyaw * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(td, tp, n_tab * sizeof(double), hipMemcpyHostToDevice, st));
+    LatticeTables::Dev t;
+    if ((rc = h->lattice.upload(h, who, xs, nx, ys, ny, cs, sn, nyaw, st, t)) != NDTGPU_OK) return rc;
     NdtCalibArgs a{};
     a.xyz = (const uint32_t *)xyz_dev;
     a.n_kept = n_kept_dev;
     a.poses = poses_dev;
     a.pairs = pairs_dev;
-    a.xs = td;
-    a.ys = td + nx;
-    a.cs = td + nx + ny;
-    a.sn = td + nx + ny + nyaw;
+    a.xs = t.xs;
+    a.ys = t.ys;
+    a.cs = t.cs;
+    a.sn = t.sn;
     a.stride_words = stride_bytes / 4;
     a.map_stride_words = map_stride_bytes / 4;
     a.n_scans = (uint32_t)n_scans;
@@ -230,7 +191,7 @@ ndtgpu_status ndtgpu_calib_search(ndtgpu_calib *h, const void *xyz, size_t n_sca
     ndtgpu_status rc = calib_check(who, n_scans, n_points, stride_bytes, map_stride_bytes, n_pairs, nx, ny, nyaw, p);
     if (rc != NDTGPU_OK) return rc;
     if (!xyz || !n_kept || !poses || !pairs || !result) return fail(NDTGPU_ERR_INVALID, "calib_search: null xyz, n_kept, poses, pairs or result");
-    if ((rc = calib_check_tables(who, xs, nx, ys, ny, cs, sn, nyaw)) != NDTGPU_OK) return rc;
+    if ((rc = LatticeTables::check(who, xs, nx, ys, ny, cs, sn, nyaw)) != NDTGPU_OK) return rc;
     for (size_t k = 0; k < 2 * n_pairs; k++)
         if (pairs[k] >= n_scans) return fail(NDTGPU_ERR_INVALID, "calib_search: pairs names a scan >= n_scans");
     if (!h) return fail(NDTGPU_ERR_INVALID, "calib_search: null handle");
@@ -242,32 +203,27 @@ ndtgpu_status ndtgpu_calib_search(ndtgpu_calib *h, const void *xyz, size_t n_sca
     const size_t o_rows = in.take(n_used * n_points * row), o_kept = in.take(n_used * sizeof(uint32_t)),
                  o_poses = in.take(n_used * 4 * sizeof(double)), o_pairs = in.take(n_used * sizeof(uint32_t));
     const size_t o_res = outl.take(sizeof(ndtgpu_calib_result)), o_vol = outl.take(volume ? n_candidates * sizeof(double) : 0);
-    const size_t bytes = in.at + outl.at;
     hipStream_t st = h->hst.get();
-    HIP_TRY(h->used.sync());               // (the staging blocks may be replaced below, and are overwritten)
-    if (h->stage.reserve(bytes) != hipSuccess || h->pin.reserve(bytes) != hipSuccess) return fail(NDTGPU_ERR_ALLOC, "calib_search: staging buffers");
-    char *pin = h->pin.get(), *dev = h->stage.get();
+    HostStage &hs = h->host;
+    if ((rc = hs.open(h, who, in, outl)) != NDTGPU_OK) return rc;
     for (size_t k = 0; k < n_used; k++) {
         const size_t s = pairs[k];
         const char *src = (const char *)xyz + s * map_stride_bytes;
-        char *dst = pin + o_rows + k * n_points * row;
+        char *dst = hs.in_host(o_rows) + k * n_points * row;
         for (size_t i = 0; i < n_points; i++) memcpy(dst + i * row, src + i * stride_bytes, row);
-        ((uint32_t *)(pin + o_kept))[k] = n_kept[s];
-        memcpy(pin + o_poses + k * 4 * sizeof(double), poses + 4 * s, 4 * sizeof(double));
-        ((uint32_t *)(pin + o_pairs))[k] = (uint32_t)k;
+        ((uint32_t *)hs.in_host(o_kept))[k] = n_kept[s];
+        memcpy(hs.in_host(o_poses) + k * 4 * sizeof(double), poses + 4 * s, 4 * sizeof(double));
+        ((uint32_t *)hs.in_host(o_pairs))[k] = (uint32_t)k;
     }
-    HIP_TRY(hipMemcpyAsync(dev, pin, in.at, hipMemcpyHostToDevice, st));
-    char *dev_out = dev + in.at, *pin_out = pin + in.at;
-    rc = ndtgpu_calib_search_device(h, dev + o_rows, n_used, n_points, row, n_points * row, (const uint32_t *)(dev + o_kept),
-                                    (const double *)(dev + o_poses), (const uint32_t *)(dev + o_pairs), n_pairs, xs, nx, ys, ny, cs, sn, nyaw,
-                                    &p, (ndtgpu_calib_result *)(dev_out + o_res), volume ? (double *)(dev_out + o_vol) : nullptr,
+    if ((rc = hs.upload(st)) != NDTGPU_OK) return rc;
+    rc = ndtgpu_calib_search_device(h, hs.in_dev(o_rows), n_used, n_points, row, n_points * row, (const uint32_t *)hs.in_dev(o_kept),
+                                    (const double *)hs.in_dev(o_poses), (const uint32_t *)hs.in_dev(o_pairs), n_pairs, xs, nx, ys, ny, cs, sn,
+                                    nyaw, &p, (ndtgpu_calib_result *)hs.out_dev(o_res), volume ? (double *)hs.out_dev(o_vol) : nullptr,
                                     (ndtgpu_stream)st);
     if (rc != NDTGPU_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(pin_out, dev_out, outl.at, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h->used.record(st));
-    HIP_TRY(hipStreamSynchronize(st));
-    memcpy(result, pin_out + o_res, sizeof *result);
-    if (volume) memcpy(volume, pin_out + o_vol, n_candidates * sizeof(double));
+    if ((rc = hs.finish(h, st)) != NDTGPU_OK) return rc;
+    memcpy(result, hs.out_host(o_res), sizeof *result);
+    if (volume) memcpy(volume, hs.out_host(o_vol), n_candidates * sizeof(double));
     return NDTGPU_OK;
 }
 

@@ -7,14 +7,10 @@
 #include "ndtgpu_featbank.h"
 #include "ndt_featextract.h"
 
-#include <new>
-
 ndtgpu_status featmatch_params_dev(const char *what, const ndtgpu_featmatch_params *prm, NdtFeatMatchParamsDev &d)
 {
-    ndtgpu_featmatch_params p;
-    ndtgpu_default_featmatch_params(&p);
-    if (prm) p = *prm;
-    if (const char *msg = ndt_featmatch_check_params(p)) return fail(NDTGPU_ERR_INVALID, (std::string(what) + ": " + msg).c_str());
+    const ndtgpu_featmatch_params p = params_or_default(prm, ndtgpu_default_featmatch_params);
+    if (const char *msg = ndt_featmatch_check_params(p)) return fail_in(NDTGPU_ERR_INVALID, what, msg);
     d.acceptance_threshold = p.acceptance_threshold;
     d.inlier_probability = p.inlier_probability;
     d.distance_threshold = p.distance_threshold;
@@ -28,15 +24,13 @@ ndtgpu_status featmatch_params_dev(const char *what, const ndtgpu_featmatch_para
 static ndtgpu_status featextract_params_dev(const char *what, const ndtgpu_featbank *h, size_t n_scans, size_t n_beams, double angle_min,
                                             double angle_increment, const ndtgpu_featextract_params *prm, NdtFeatExtractParamsDev &d)
 {
-    ndtgpu_featextract_params p;
-    ndtgpu_default_featextract_params(&p);
-    if (prm) p = *prm;
+    const ndtgpu_featextract_params p = params_or_default(prm, ndtgpu_default_featextract_params);
     const char *msg = ndt_featextract_check_args(n_scans, n_beams, angle_min, angle_increment);
     if (!msg) msg = ndt_featextract_check_params(p);
-    if (msg) return fail(NDTGPU_ERR_INVALID, (std::string(what) + ": " + msg).c_str());
-    if (!h) return fail(NDTGPU_ERR_INVALID, (std::string(what) + ": null handle").c_str());
+    if (msg) return fail_in(NDTGPU_ERR_INVALID, what, msg);
+    if (!h) return fail_in(NDTGPU_ERR_INVALID, what, "null handle");
     if ((size_t)p.bin_rho * (size_t)p.bin_phi != h->v.desc_len)
-        return fail(NDTGPU_ERR_INVALID, (std::string(what) + ": the bank's desc_len must equal bin_rho * bin_phi").c_str());
+        return fail_in(NDTGPU_ERR_INVALID, what, "the bank's desc_len must equal bin_rho * bin_phi");
     d = ndt_featextract_params_dev(p);
     return NDTGPU_OK;
 }
@@ -76,23 +70,16 @@ void ndtgpu_default_featmatch_params(ndtgpu_featmatch_params *p)
     p->rigidity_threshold = 0.0499;
 }
 
-ndtgpu_status ndtgpu_featbank_destroy(ndtgpu_featbank *h)
-{
-    if (!h) return fail(NDTGPU_ERR_INVALID, "featbank_destroy: null");
-    (void)h->used.sync();                  // (the last call may have run on a stream of the caller's)
-    delete h;
-    return NDTGPU_OK;
-}
+ndtgpu_status ndtgpu_featbank_destroy(ndtgpu_featbank *h) { return handle_destroy(h, "featbank_destroy"); }
 
 ndtgpu_status ndtgpu_featbank_create(size_t n_sets, size_t max_points, size_t desc_len, ndtgpu_featbank **out)
 {
     if (!out) return fail(NDTGPU_ERR_INVALID, "featbank_create: out is NULL");
     *out = nullptr;
-    if (const char *msg = ndt_featmatch_check_shape(n_sets, max_points, desc_len))
-        return fail(NDTGPU_ERR_INVALID, (std::string("featbank_create: ") + msg).c_str());
-    if (!have_device()) return fail(NDTGPU_ERR_NO_DEVICE, "featbank_create: no HIP device");
-    ndtgpu_featbank *h = new (std::nothrow) ndtgpu_featbank();
-    if (!h) return fail(NDTGPU_ERR_ALLOC, "featbank_create: host alloc");
+    if (const char *msg = ndt_featmatch_check_shape(n_sets, max_points, desc_len)) return fail_in(NDTGPU_ERR_INVALID, "featbank_create", msg);
+    ndtgpu_featbank *h;
+    const ndtgpu_status rc = handle_new("featbank_create", h);
+    if (rc != NDTGPU_OK) return rc;
     NdtFeatBankView &v = h->v;
     v.n_sets = (unsigned)n_sets;
     v.max_points = (unsigned)max_points;

@@ -286,12 +286,12 @@ static ndtgpu_status fuser_stage(ndtgpu_fuser_bank *b, size_t bytes, size_t coun
 // bank outside the prev / map ranges
 static ndtgpu_status fuser_feat_check(const char *what, const ndtgpu_fuser_bank *b, size_t count, const uint32_t *cur_set_idx)
 {
-    if (!b->fb) return fail(NDTGPU_ERR_INVALID, (std::string(what) + ": no feature bank attached (ndtgpu_fuser_bank_attach_features)").c_str());
-    if (count && !cur_set_idx) return fail(NDTGPU_ERR_INVALID, (std::string(what) + ": cur_set_idx is NULL").c_str());
+    if (!b->fb) return fail_in(NDTGPU_ERR_INVALID, what, "no feature bank attached (ndtgpu_fuser_bank_attach_features)");
+    if (count && !cur_set_idx) return fail_in(NDTGPU_ERR_INVALID, what, "cur_set_idx is NULL");
     for (size_t k = 0; k < count; k++) {
         const size_t c = cur_set_idx[k];
         if (c >= b->fb->v.n_sets || (c >= b->prev_first && c < b->prev_first + b->n) || (c >= b->map_first && c < b->map_first + b->n))
-            return fail(NDTGPU_ERR_INVALID, (std::string(what) + ": a cur set index is outside the feature bank or inside the prev / map ranges").c_str());
+            return fail_in(NDTGPU_ERR_INVALID, what, "a cur set index is outside the feature bank or inside the prev / map ranges");
     }
     return NDTGPU_OK;
 }
@@ -694,9 +694,7 @@ ndtgpu_status ndtgpu_fuser_bank_attach_features(ndtgpu_fuser_bank *b, ndtgpu_fea
                                                 const ndtgpu_fuser_feat_params *prm)
 {
     if (!b || !fb) return fail(NDTGPU_ERR_INVALID, "fuser_bank_attach_features: null handle");
-    ndtgpu_fuser_feat_params p;
-    ndtgpu_default_fuser_feat_params(&p);
-    if (prm) p = *prm;
+    const ndtgpu_fuser_feat_params p = params_or_default(prm, ndtgpu_default_fuser_feat_params);
     if (p.map_every < 1 || !(p.feat_cov[0] > 0) || !(p.feat_cov[1] > 0) || !(p.feat_cov[2] > 0))
         return fail(NDTGPU_ERR_INVALID, "fuser_bank_attach_features: map_every must be >= 1, feat_cov positive");
     NdtFeatMatchParamsDev d;

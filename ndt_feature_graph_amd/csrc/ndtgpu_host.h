@@ -1,12 +1,14 @@
 // ndtgpu_host.h -- what the C-ABI sources share (ndtgpu_api.hip: map sets; ndtgpu_matcher.hip; ndtgpu_registrar.hip;
-// ndtgpu_fuser_bank.hip): error reporting, the map set handle and the helpers one of them defines for the others.  Host
-// side only and internal: not installed, and nothing declared here is exported from libndtgpu.so.
+// ndtgpu_fuser_bank.hip; every ndtgpu_<subsystem>.hip): error reporting, the skeleton of a handle's create and destroy, the
+// staging of a synchronous host form, the upload of a search's lattice tables, the map set handle and the helpers one of them
+// defines for the others.  Host side only and internal: not installed, and nothing declared here is exported from libndtgpu.so.
 #pragma once
 #include "../../include/ndtgpu.h"
 #include "ndtgpu_resource.h"
 #include "ndt_math.h"
 #include "ndt_solver.h"
 #include "ndt_pose.h"
+#include "ndt_lattice.h"
 
 #include <algorithm>
 #include <cmath>
@@ -14,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -28,6 +31,25 @@ inline ndtgpu_status fail(ndtgpu_status s, const char *what, hipError_t e = hipS
     else snprintf(buf, sizeof buf, "%s", what);
     g_err = buf;
     return s;
+}
+
+// ... with the message "<who>: <what>": who is the entry's name
+inline ndtgpu_status fail_in(ndtgpu_status s, const char *who, const char *what)
+{
+    char buf[512];
+    snprintf(buf, sizeof buf, "%s: %s", who, what);
+    g_err = buf;
+    return s;
+}
+
+// the caller's parameters, or the defaults where it passed NULL
+template <class P>
+inline P params_or_default(const P *prm, void (*defaults)(P *))
+{
+    P p;
+    defaults(&p);
+    if (prm) p = *prm;
+    return p;
 }
 
 #define HIP_TRY(expr)                                                       \
@@ -208,6 +230,27 @@ inline ndtgpu_status mapset_create_owned(const ndtgpu_grid_params *grid, size_t 
         if (_e != hipSuccess) { delete (handle); return fail((status), (what), _e); } \
     } while (0)
 
+// The tail of every create, behind the entry's own argument checks: a handle of type H, or why there is none.  The caller fills
+// it (TRY / CREATE_TRY over its own buffers, then used.create() and hst.create() last) and hands it out.
+template <class H>
+inline ndtgpu_status handle_new(const char *who, H *&h)
+{
+    h = nullptr;
+    if (!have_device()) return fail_in(NDTGPU_ERR_NO_DEVICE, who, "no HIP device");
+    h = new (std::nothrow) H();
+    return h ? NDTGPU_OK : fail_in(NDTGPU_ERR_ALLOC, who, "host alloc");
+}
+
+// ... and every destroy, of a handle whose calls record `used` behind their last launch
+template <class H>
+inline ndtgpu_status handle_destroy(H *h, const char *who)
+{
+    if (!h) return fail_in(NDTGPU_ERR_INVALID, who, "null");
+    (void)h->used.sync();                  // (the last call may have run on a stream of the caller's)
+    delete h;
+    return NDTGPU_OK;
+}
+
 // Consecutive regions of one staging block, each on a 256-byte boundary: take(bytes) returns where the region starts; `at` is
 // where the next one would.
 struct StageLayout {
@@ -220,11 +263,89 @@ struct StageLayout {
     }
 };
 
+// The staging of a synchronous host form: one device block and its pinned mirror, the `in` regions (host -> device in one copy
+// before the work) in front of the `outl` regions (device -> host in one copy behind it).  It owns neither the stream nor the
+// fence: those are the handle's `hst` and `used`, declared behind this (ndtgpu_resource.h: the stream goes first).  A host form
+//   lays out its regions in two StageLayouts, open()s with them, fills in_host(), upload()s, calls its _device form on h->hst
+//   with in_dev() / out_dev() pointers, finish()es and reads out_host().
+// HIP_TRY reports the text of its expression: the names below are the ones those messages carry.
+struct HostStage {
+    DeviceBuffer<char> stage;
+    PinnedBuffer<char> pin;
+    StageLayout in, outl;                  // of the call in progress
+
+    // room for the call's regions, once the previous call's work has ended (the blocks may be replaced, and are overwritten)
+    template <class H>
+    ndtgpu_status open(H *h, const char *who, const StageLayout &in_regions, const StageLayout &out_regions)
+    {
+        in = in_regions;
+        outl = out_regions;
+        HIP_TRY(h->used.sync());
+        const size_t bytes = in.at + outl.at;
+        if (stage.reserve(bytes) != hipSuccess || pin.reserve(bytes) != hipSuccess) return fail_in(NDTGPU_ERR_ALLOC, who, "staging buffers");
+        return NDTGPU_OK;
+    }
+    char *in_host(size_t o) const { return pin.get() + o; }
+    char *in_dev(size_t o) const { return stage.get() + o; }
+    char *out_host(size_t o) const { return pin.get() + in.at + o; }
+    char *out_dev(size_t o) const { return stage.get() + in.at + o; }
+    ndtgpu_status upload(hipStream_t st)
+    {
+        char *pin = this->pin.get(), *dev = stage.get();
+        HIP_TRY(hipMemcpyAsync(dev, pin, in.at, hipMemcpyHostToDevice, st));
+        return NDTGPU_OK;
+    }
+    // the results back, the fence behind them, and the wait: out_host() is valid on return
+    template <class H>
+    ndtgpu_status finish(H *h, hipStream_t st)
+    {
+        char *pin_out = out_host(0), *dev_out = out_dev(0);
+        HIP_TRY(hipMemcpyAsync(pin_out, dev_out, outl.at, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h->used.record(st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return NDTGPU_OK;
+    }
+};
+
+// The lattice tables of a search on the device, xs | ys | cs | sn in one block, and their pinned mirror: made by a handle's first
+// search and grown by later ones (csrc/ndt_lattice.h checks what goes in).
+struct LatticeTables {
+    DeviceBuffer<double> tables;
+    PinnedBuffer<double> tables_pin;
+    struct Dev { const double *xs, *ys, *cs, *sn; };
+
+    // what every entry that takes the tables checks before it reads its handle
+    static ndtgpu_status check(const char *who, const double *xs, size_t nx, const double *ys, size_t ny, const double *cs, const double *sn,
+                               size_t nyaw)
+    {
+        if (!xs || !ys || !cs || !sn) return fail_in(NDTGPU_ERR_INVALID, who, "null xs, ys, cs or sn");
+        const char *bad = ndt_lattice_check_tables(xs, nx, ys, ny, cs, sn, nyaw);
+        return bad ? fail_in(NDTGPU_ERR_INVALID, who, bad) : NDTGPU_OK;
+    }
+
+    // onto the device on `st`.  The pinned copy is overwritten, so the previous call's upload must have ended (and the blocks may
+    // be replaced): the host waits for h->used first
+    template <class H>
+    ndtgpu_status upload(H *h, const char *who, const double *xs, size_t nx, const double *ys, size_t ny, const double *cs,
+                         const double *sn, size_t nyaw, hipStream_t st, Dev &out)
+    {
+        const size_t n_tab = nx + ny + 2 * nyaw;
+        HIP_TRY(h->used.sync());
+        if (tables.reserve(n_tab) != hipSuccess || tables_pin.reserve(n_tab) != hipSuccess) return fail_in(NDTGPU_ERR_ALLOC, who, "lattice tables");
+        double *tp = tables_pin.get(), *td = tables.get();
+        memcpy(tp, xs, nx * sizeof(double));
+        memcpy(tp + nx, ys, ny * sizeof(double));
+        memcpy(tp + nx + ny, cs, nyaw * sizeof(double));
+        memcpy(tp + nx + ny + nyaw, sn, nyaw * sizeof(double));
+        HIP_TRY(hipMemcpyAsync(td, tp, n_tab * sizeof(double), hipMemcpyHostToDevice, st));
+        out = Dev{td, td + nx, td + nx + ny, td + nx + ny + nyaw};
+        return NDTGPU_OK;
+    }
+};
+
 inline NdtMatchParamsDev to_dev(const ndtgpu_match_params *p)
 {
-    ndtgpu_match_params d;
-    ndtgpu_default_match_params(&d);
-    if (p) d = *p;
+    const ndtgpu_match_params d = params_or_default(p, ndtgpu_default_match_params);
     NdtMatchParamsDev o;
     o.n_neighbours = d.n_neighbours;
     o.itr_max = d.itr_max;

@@ -6,8 +6,6 @@
 #include "ndtgpu_host.h"
 #include "ndt_linkgate.h"
 
-#include <new>
-
 struct ndtgpu_linkgate {
     size_t max_nodes = 0, max_links = 0;
     NdtLinkGateView v{};                   // what the kernels receive: filled from the owners below at create
@@ -23,9 +21,7 @@ struct ndtgpu_linkgate {
 
 static NdtLinkGateParamsDev linkgate_params_dev(const ndtgpu_linkgate_params *prm)
 {
-    ndtgpu_linkgate_params p;
-    ndtgpu_default_linkgate_params(&p);
-    if (prm) p = *prm;
+    const ndtgpu_linkgate_params p = params_or_default(prm, ndtgpu_default_linkgate_params);
     NdtLinkGateParamsDev d;
     d.max_score = p.max_score;
     d.max_dist = p.max_dist;
@@ -63,11 +59,10 @@ ndtgpu_status ndtgpu_linkgate_create(size_t max_nodes, size_t max_links, ndtgpu_
 {
     if (!out) return fail(NDTGPU_ERR_INVALID, "linkgate_create: out is NULL");
     *out = nullptr;
-    const ndtgpu_status rc = ndtgpu_linkgate_check(max_nodes, max_links, 0, 0, 0);
+    ndtgpu_status rc = ndtgpu_linkgate_check(max_nodes, max_links, 0, 0, 0);
     if (rc != NDTGPU_OK) return rc;
-    if (!have_device()) return fail(NDTGPU_ERR_NO_DEVICE, "linkgate_create: no HIP device");
-    ndtgpu_linkgate *h = new (std::nothrow) ndtgpu_linkgate();
-    if (!h) return fail(NDTGPU_ERR_ALLOC, "linkgate_create: host alloc");
+    ndtgpu_linkgate *h;
+    if ((rc = handle_new("linkgate_create", h)) != NDTGPU_OK) return rc;
     h->max_nodes = max_nodes;
     h->max_links = max_links;
     const size_t pairs = max_nodes * (max_nodes - 1) / 2;
@@ -89,13 +84,7 @@ ndtgpu_status ndtgpu_linkgate_create(size_t max_nodes, size_t max_links, ndtgpu_
     return NDTGPU_OK;
 }
 
-ndtgpu_status ndtgpu_linkgate_destroy(ndtgpu_linkgate *h)
-{
-    if (!h) return fail(NDTGPU_ERR_INVALID, "linkgate_destroy: null");
-    (void)h->used.sync();                  // (the last call may have run on a stream of the caller's)
-    delete h;
-    return NDTGPU_OK;
-}
+ndtgpu_status ndtgpu_linkgate_destroy(ndtgpu_linkgate *h) { return handle_destroy(h, "linkgate_destroy"); }
 
 ndtgpu_status ndtgpu_linkgate_set_nodes(ndtgpu_linkgate *h, size_t n_nodes, const double *T16)
 {

@@ -6,7 +6,6 @@
 #include "ndt_locmon.h"
 
 #include <limits>
-#include <new>
 
 struct ndtgpu_locmon {
     size_t max_grids = 0, max_pixels = 0, max_beams = 0, max_candidates = 0, chunk = 0;
@@ -20,28 +19,13 @@ struct ndtgpu_locmon {
     DeviceBuffer<uint32_t> cand_key;       // [chunk]
     DeviceBuffer<unsigned long long> tile_word;
     PinnedBuffer<double> origin_pin, beams_pin;
-    // the lattice tables of a search: xs | ys | cs | sn
-    DeviceBuffer<double> tables;
-    PinnedBuffer<double> tables_pin;
-    // the host forms' staging
-    DeviceBuffer<char> stage;
-    PinnedBuffer<char> pin;
+    LatticeTables lattice;                 // the lattice tables of a search
+    HostStage host;                        // the host forms' staging
     Fence used;                            // recorded after the last launch of a call
     Stream hst;                            // the host forms' stream (last: ndtgpu_resource.h)
 };
 
-static ndtgpu_locmon_params locmon_params(const ndtgpu_locmon_params *prm)
-{
-    ndtgpu_locmon_params p;
-    ndtgpu_default_locmon_params(&p);
-    if (prm) p = *prm;
-    return p;
-}
-
-static ndtgpu_status locmon_bad(const char *who, const char *bad, ndtgpu_status s = NDTGPU_ERR_INVALID)
-{
-    return fail(s, (std::string(who) + ": " + bad).c_str());
-}
+static ndtgpu_locmon_params locmon_params(const ndtgpu_locmon_params *prm) { return params_or_default(prm, ndtgpu_default_locmon_params); }
 
 static NdtLocmonMap locmon_map(const ndtgpu_locmon *h)
 {
@@ -60,8 +44,8 @@ static NdtLocmonMap locmon_map(const ndtgpu_locmon *h)
 
 static ndtgpu_status locmon_installed(const char *who, const ndtgpu_locmon *h)
 {
-    if (h->n_grids == 0) return locmon_bad(who, "no grids are installed (set_grids)");
-    if (h->n_beams == 0) return locmon_bad(who, "no beam table is installed (set_beams)");
+    if (h->n_grids == 0) return fail_in(NDTGPU_ERR_INVALID, who, "no grids are installed (set_grids)");
+    if (h->n_beams == 0) return fail_in(NDTGPU_ERR_INVALID, who, "no beam table is installed (set_beams)");
     return NDTGPU_OK;
 }
 
@@ -88,7 +72,7 @@ ndtgpu_status ndtgpu_locmon_check(size_t n_grids, size_t width, size_t height, d
     const char *bad = ndt_locmon_check_grids(n_grids, width, height, resolution, locmon_params(prm));
     if (!bad) bad = ndt_locmon_check_beams(n_beams, angle_min, angle_increment);
     if (!bad) bad = ndt_locmon_check_counts(n_scans, n_queries);
-    return bad ? locmon_bad("locmon_check", bad) : NDTGPU_OK;
+    return bad ? fail_in(NDTGPU_ERR_INVALID, "locmon_check", bad) : NDTGPU_OK;
 }
 
 ndtgpu_status ndtgpu_locmon_radius(double max_dist, double resolution, int32_t *R)
@@ -104,7 +88,7 @@ ndtgpu_status ndtgpu_locmon_radius(double max_dist, double resolution, int32_t *
 
 ndtgpu_status ndtgpu_locmon_beam_table(size_t n_beams, double angle_min, double angle_increment, double *cb, double *sb)
 {
-    if (const char *bad = ndt_locmon_check_beams(n_beams, angle_min, angle_increment)) return locmon_bad("locmon_beam_table", bad);
+    if (const char *bad = ndt_locmon_check_beams(n_beams, angle_min, angle_increment)) return fail_in(NDTGPU_ERR_INVALID, "locmon_beam_table", bad);
     if (!cb || !sb) return fail(NDTGPU_ERR_INVALID, "locmon_beam_table: null cb or sb");
     for (size_t i = 0; i < n_beams; i++) {
         const double a = angle_min + (double)i * angle_increment;
@@ -151,10 +135,11 @@ ndtgpu_status ndtgpu_locmon_create(size_t max_grids, size_t max_pixels, size_t m
 {
     if (!out) return fail(NDTGPU_ERR_INVALID, "locmon_create: out is NULL");
     *out = nullptr;
-    if (const char *bad = ndt_locmon_check_capacity(max_grids, max_pixels, max_beams, max_candidates)) return locmon_bad("locmon_create", bad);
-    if (!have_device()) return fail(NDTGPU_ERR_NO_DEVICE, "locmon_create: no HIP device");
-    ndtgpu_locmon *h = new (std::nothrow) ndtgpu_locmon();
-    if (!h) return fail(NDTGPU_ERR_ALLOC, "locmon_create: host alloc");
+    if (const char *bad = ndt_locmon_check_capacity(max_grids, max_pixels, max_beams, max_candidates))
+        return fail_in(NDTGPU_ERR_INVALID, "locmon_create", bad);
+    ndtgpu_locmon *h;
+    const ndtgpu_status rc = handle_new("locmon_create", h);
+    if (rc != NDTGPU_OK) return rc;
     h->max_grids = max_grids;
     h->max_pixels = max_pixels;
     h->max_beams = max_beams;
@@ -176,17 +161,11 @@ ndtgpu_status ndtgpu_locmon_create(size_t max_grids, size_t max_pixels, size_t m
     return NDTGPU_OK;
 }
 
-ndtgpu_status ndtgpu_locmon_destroy(ndtgpu_locmon *h)
-{
-    if (!h) return fail(NDTGPU_ERR_INVALID, "locmon_destroy: null");
-    (void)h->used.sync();                  // (the last call may have run on a stream of the caller's)
-    delete h;
-    return NDTGPU_OK;
-}
+ndtgpu_status ndtgpu_locmon_destroy(ndtgpu_locmon *h) { return handle_destroy(h, "locmon_destroy"); }
 
 ndtgpu_status ndtgpu_locmon_set_beams(ndtgpu_locmon *h, size_t n_beams, double angle_min, double angle_increment, ndtgpu_stream stream)
 {
-    if (const char *bad = ndt_locmon_check_beams(n_beams, angle_min, angle_increment)) return locmon_bad("locmon_set_beams", bad);
+    if (const char *bad = ndt_locmon_check_beams(n_beams, angle_min, angle_increment)) return fail_in(NDTGPU_ERR_INVALID, "locmon_set_beams", bad);
     if (!h) return fail(NDTGPU_ERR_INVALID, "locmon_set_beams: null handle");
     if (n_beams > h->max_beams) return fail(NDTGPU_ERR_CAPACITY, "locmon_set_beams: more beams than the handle was created for");
     hipStream_t st = (hipStream_t)stream;
@@ -209,13 +188,13 @@ ndtgpu_status ndtgpu_locmon_set_grids_device(ndtgpu_locmon *h, const int8_t *gri
 {
     const char *who = "locmon_set_grids_device";
     const ndtgpu_locmon_params p = locmon_params(prm);
-    if (const char *bad = ndt_locmon_check_grids(n_grids, width, height, resolution, p)) return locmon_bad(who, bad);
+    if (const char *bad = ndt_locmon_check_grids(n_grids, width, height, resolution, p)) return fail_in(NDTGPU_ERR_INVALID, who, bad);
     if (!grids_dev || !origins2) return fail(NDTGPU_ERR_INVALID, "locmon_set_grids_device: null grids_dev or origins2");
     for (size_t k = 0; k < 2 * n_grids; k++)
-        if (!(std::fabs(origins2[k]) < 1e150)) return locmon_bad(who, "origins2 must be finite");
+        if (!(std::fabs(origins2[k]) < 1e150)) return fail_in(NDTGPU_ERR_INVALID, who, "origins2 must be finite");
     if (!h) return fail(NDTGPU_ERR_INVALID, "locmon_set_grids_device: null handle");
-    if (n_grids > h->max_grids) return locmon_bad(who, "more grids than the handle was created for", NDTGPU_ERR_CAPACITY);
-    if (n_grids * width * height > h->max_pixels) return locmon_bad(who, "more pixels than the handle was created for", NDTGPU_ERR_CAPACITY);
+    if (n_grids > h->max_grids) return fail_in(NDTGPU_ERR_CAPACITY, who, "more grids than the handle was created for");
+    if (n_grids * width * height > h->max_pixels) return fail_in(NDTGPU_ERR_CAPACITY, who, "more pixels than the handle was created for");
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(h->used.sync());               // (the pinned origins and the fields are overwritten: the previous call's work must have ended)
     memcpy(h->origin_pin.get(), origins2, 2 * n_grids * sizeof(double));
@@ -238,18 +217,21 @@ ndtgpu_status ndtgpu_locmon_set_grids(ndtgpu_locmon *h, const int8_t *grids, siz
 {
     const char *who = "locmon_set_grids";
     const ndtgpu_locmon_params p = locmon_params(prm);
-    if (const char *bad = ndt_locmon_check_grids(n_grids, width, height, resolution, p)) return locmon_bad(who, bad);
+    if (const char *bad = ndt_locmon_check_grids(n_grids, width, height, resolution, p)) return fail_in(NDTGPU_ERR_INVALID, who, bad);
     if (!grids || !origins2) return fail(NDTGPU_ERR_INVALID, "locmon_set_grids: null grids or origins2");
     if (!h) return fail(NDTGPU_ERR_INVALID, "locmon_set_grids: null handle");
     const size_t bytes = n_grids * width * height;
-    if (n_grids > h->max_grids) return locmon_bad(who, "more grids than the handle was created for", NDTGPU_ERR_CAPACITY);
-    if (bytes > h->max_pixels) return locmon_bad(who, "more pixels than the handle was created for", NDTGPU_ERR_CAPACITY);
+    if (n_grids > h->max_grids) return fail_in(NDTGPU_ERR_CAPACITY, who, "more grids than the handle was created for");
+    if (bytes > h->max_pixels) return fail_in(NDTGPU_ERR_CAPACITY, who, "more pixels than the handle was created for");
     hipStream_t st = h->hst.get();
+    // only the device block of the staging: the grids travel from the caller's pageable memory
+    DeviceBuffer<char> &stage = h->host.stage;
     HIP_TRY(h->used.sync());               // (the staging block may be replaced below)
-    if (h->stage.reserve(bytes) != hipSuccess) return fail(NDTGPU_ERR_ALLOC, "locmon_set_grids: staging buffer");
-    HIP_TRY(hipMemcpyAsync(h->stage.get(), grids, bytes, hipMemcpyHostToDevice, st));
+    if (stage.reserve(bytes) != hipSuccess) return fail(NDTGPU_ERR_ALLOC, "locmon_set_grids: staging buffer");
+    const hipError_t e = hipMemcpyAsync(stage.get(), grids, bytes, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "hipMemcpyAsync(h->stage.get(), grids, bytes, hipMemcpyHostToDevice, st)", e);
     HIP_TRY(hipStreamSynchronize(st));     // (the copy read pageable memory of the caller's)
-    const ndtgpu_status rc = ndtgpu_locmon_set_grids_device(h, (const int8_t *)h->stage.get(), n_grids, width, height, resolution, origins2, &p,
+    const ndtgpu_status rc = ndtgpu_locmon_set_grids_device(h, (const int8_t *)stage.get(), n_grids, width, height, resolution, origins2, &p,
                                                             (ndtgpu_stream)st);
     if (rc != NDTGPU_OK) return rc;
     HIP_TRY(hipStreamSynchronize(st));
@@ -276,7 +258,7 @@ ndtgpu_status ndtgpu_locmon_evaluate_device(ndtgpu_locmon *h, const double *rang
     const ndtgpu_locmon_params p = locmon_params(prm);
     const char *bad = ndt_locmon_check_counts(n_scans, n_queries);
     if (!bad) bad = ndt_locmon_check_params(p);
-    if (bad) return locmon_bad(who, bad);
+    if (bad) return fail_in(NDTGPU_ERR_INVALID, who, bad);
     if (!ranges_dev || (n_queries && (!queries_dev || !results_dev)))
         return fail(NDTGPU_ERR_INVALID, "locmon_evaluate_device: null ranges_dev, queries_dev or results_dev");
     if (!h) return fail(NDTGPU_ERR_INVALID, "locmon_evaluate_device: null handle");
@@ -299,7 +281,7 @@ ndtgpu_status ndtgpu_locmon_evaluate(ndtgpu_locmon *h, const double *ranges, siz
     const ndtgpu_locmon_params p = locmon_params(prm);
     const char *bad = ndt_locmon_check_counts(n_scans, n_queries);
     if (!bad) bad = ndt_locmon_check_params(p);
-    if (bad) return locmon_bad(who, bad);
+    if (bad) return fail_in(NDTGPU_ERR_INVALID, who, bad);
     if (!ranges || (n_queries && (!queries || !results))) return fail(NDTGPU_ERR_INVALID, "locmon_evaluate: null ranges, queries or results");
     if (!h) return fail(NDTGPU_ERR_INVALID, "locmon_evaluate: null handle");
     ndtgpu_status rc = locmon_installed(who, h);
@@ -308,22 +290,17 @@ ndtgpu_status ndtgpu_locmon_evaluate(ndtgpu_locmon *h, const double *ranges, siz
     StageLayout in, outl;
     const size_t o_ranges = in.take(n_scans * h->n_beams * sizeof(double)), o_q = in.take(n_queries * sizeof(ndtgpu_locmon_query));
     const size_t o_res = outl.take(n_queries * sizeof(ndtgpu_locmon_result));
-    const size_t bytes = in.at + outl.at;
     hipStream_t st = h->hst.get();
-    HIP_TRY(h->used.sync());               // (the staging blocks may be replaced below, and are overwritten)
-    if (h->stage.reserve(bytes) != hipSuccess || h->pin.reserve(bytes) != hipSuccess) return fail(NDTGPU_ERR_ALLOC, "locmon_evaluate: staging buffers");
-    char *pin = h->pin.get(), *dev = h->stage.get();
-    memcpy(pin + o_ranges, ranges, n_scans * h->n_beams * sizeof(double));
-    memcpy(pin + o_q, queries, n_queries * sizeof(ndtgpu_locmon_query));
-    HIP_TRY(hipMemcpyAsync(dev, pin, in.at, hipMemcpyHostToDevice, st));
-    char *dev_out = dev + in.at, *pin_out = pin + in.at;
-    rc = ndtgpu_locmon_evaluate_device(h, (const double *)(dev + o_ranges), n_scans, (const ndtgpu_locmon_query *)(dev + o_q), n_queries, &p,
-                                       (ndtgpu_locmon_result *)(dev_out + o_res), (ndtgpu_stream)st);
+    HostStage &hs = h->host;
+    if ((rc = hs.open(h, who, in, outl)) != NDTGPU_OK) return rc;
+    memcpy(hs.in_host(o_ranges), ranges, n_scans * h->n_beams * sizeof(double));
+    memcpy(hs.in_host(o_q), queries, n_queries * sizeof(ndtgpu_locmon_query));
+    if ((rc = hs.upload(st)) != NDTGPU_OK) return rc;
+    rc = ndtgpu_locmon_evaluate_device(h, (const double *)hs.in_dev(o_ranges), n_scans, (const ndtgpu_locmon_query *)hs.in_dev(o_q), n_queries, &p,
+                                       (ndtgpu_locmon_result *)hs.out_dev(o_res), (ndtgpu_stream)st);
     if (rc != NDTGPU_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(pin_out, dev_out, outl.at, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h->used.record(st));
-    HIP_TRY(hipStreamSynchronize(st));
-    memcpy(results, pin_out + o_res, n_queries * sizeof(ndtgpu_locmon_result));
+    if ((rc = hs.finish(h, st)) != NDTGPU_OK) return rc;
+    memcpy(results, hs.out_host(o_res), n_queries * sizeof(ndtgpu_locmon_result));
     return NDTGPU_OK;
 }
 
@@ -337,32 +314,22 @@ ndtgpu_status ndtgpu_locmon_adjust_device(ndtgpu_locmon *h, const double *ranges
     const char *bad = ndt_locmon_check_counts(n_scans, 0);
     if (!bad) bad = ndt_locmon_check_lattice(nx, ny, nyaw);
     if (!bad) bad = ndt_locmon_check_params(p);
-    if (bad) return locmon_bad(who, bad);
+    if (bad) return fail_in(NDTGPU_ERR_INVALID, who, bad);
     if (!ranges_dev || !result_dev) return fail(NDTGPU_ERR_INVALID, "locmon_adjust_device: null ranges_dev or result_dev");
-    if (!xs || !ys || !cs || !sn) return fail(NDTGPU_ERR_INVALID, "locmon_adjust_device: null xs, ys, cs or sn");
-    if ((bad = ndt_locmon_check_tables(xs, nx, ys, ny, cs, sn, nyaw))) return locmon_bad(who, bad);
+    ndtgpu_status rc = LatticeTables::check(who, xs, nx, ys, ny, cs, sn, nyaw);
+    if (rc != NDTGPU_OK) return rc;
     if (!h) return fail(NDTGPU_ERR_INVALID, "locmon_adjust_device: null handle");
     const size_t n_candidates = nx * ny * nyaw;
-    if (n_candidates > h->max_candidates) return locmon_bad(who, "more candidates than the handle was created for", NDTGPU_ERR_CAPACITY);
-    ndtgpu_status rc = locmon_installed(who, h);
-    if (rc != NDTGPU_OK) return rc;
+    if (n_candidates > h->max_candidates) return fail_in(NDTGPU_ERR_CAPACITY, who, "more candidates than the handle was created for");
+    if ((rc = locmon_installed(who, h)) != NDTGPU_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    // the tables: the pinned copy is overwritten, so the previous call's upload must have ended (and the blocks may be replaced)
-    const size_t n_tab = nx + ny + 2 * nyaw;
-    HIP_TRY(h->used.sync());
-    if (h->tables.reserve(n_tab) != hipSuccess || h->tables_pin.reserve(n_tab) != hipSuccess)
-        return fail(NDTGPU_ERR_ALLOC, "locmon_adjust_device: lattice tables");
-    double *tp = h->tables_pin.get(), *td = h->tables.get();
-    memcpy(tp, xs, nx * sizeof(double));
-    memcpy(tp + nx, ys, ny * sizeof(double));
-    memcpy(tp + nx + ny, cs, nyaw * sizeof(double));
-    memcpy(tp + nx + ny + nyaw, sn, nyaw * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(td, tp, n_tab * sizeof(double), hipMemcpyHostToDevice, st));
+    LatticeTables::Dev t;
+    if ((rc = h->lattice.upload(h, who, xs, nx, ys, ny, cs, sn, nyaw, st, t)) != NDTGPU_OK) return rc;
     NdtLocmonSearch s{};
-    s.xs = td;
-    s.ys = td + nx;
-    s.cs = td + nx + ny;
-    s.sn = td + nx + ny + nyaw;
+    s.xs = t.xs;
+    s.ys = t.ys;
+    s.cs = t.cs;
+    s.sn = t.sn;
     s.ny = (uint32_t)ny;
     s.nyaw = (uint32_t)nyaw;
     s.n_candidates = (uint32_t)n_candidates;
@@ -387,37 +354,31 @@ ndtgpu_status ndtgpu_locmon_adjust(ndtgpu_locmon *h, const double *ranges, size_
     const char *bad = ndt_locmon_check_counts(n_scans, 0);
     if (!bad) bad = ndt_locmon_check_lattice(nx, ny, nyaw);
     if (!bad) bad = ndt_locmon_check_params(p);
-    if (bad) return locmon_bad(who, bad);
+    if (bad) return fail_in(NDTGPU_ERR_INVALID, who, bad);
     if (!ranges || !result) return fail(NDTGPU_ERR_INVALID, "locmon_adjust: null ranges or result");
-    if (!xs || !ys || !cs || !sn) return fail(NDTGPU_ERR_INVALID, "locmon_adjust: null xs, ys, cs or sn");
-    if ((bad = ndt_locmon_check_tables(xs, nx, ys, ny, cs, sn, nyaw))) return locmon_bad(who, bad);
-    if (scan >= n_scans) return locmon_bad(who, "scan must be < n_scans");
+    ndtgpu_status rc = LatticeTables::check(who, xs, nx, ys, ny, cs, sn, nyaw);
+    if (rc != NDTGPU_OK) return rc;
+    if (scan >= n_scans) return fail_in(NDTGPU_ERR_INVALID, who, "scan must be < n_scans");
     if (!h) return fail(NDTGPU_ERR_INVALID, "locmon_adjust: null handle");
     const size_t n_candidates = nx * ny * nyaw;
-    if (n_candidates > h->max_candidates) return locmon_bad(who, "more candidates than the handle was created for", NDTGPU_ERR_CAPACITY);
-    ndtgpu_status rc = locmon_installed(who, h);
-    if (rc != NDTGPU_OK) return rc;
+    if (n_candidates > h->max_candidates) return fail_in(NDTGPU_ERR_CAPACITY, who, "more candidates than the handle was created for");
+    if ((rc = locmon_installed(who, h)) != NDTGPU_OK) return rc;
     // only the scan that is searched travels
     StageLayout in, outl;
     const size_t o_ranges = in.take(h->n_beams * sizeof(double));
     const size_t o_res = outl.take(sizeof(ndtgpu_locmon_adjust_result)), o_vol = outl.take(volume ? n_candidates * sizeof(uint32_t) : 0);
-    const size_t bytes = in.at + outl.at;
     hipStream_t st = h->hst.get();
-    HIP_TRY(h->used.sync());
-    if (h->stage.reserve(bytes) != hipSuccess || h->pin.reserve(bytes) != hipSuccess) return fail(NDTGPU_ERR_ALLOC, "locmon_adjust: staging buffers");
-    char *pin = h->pin.get(), *dev = h->stage.get();
-    memcpy(pin + o_ranges, ranges + (size_t)scan * h->n_beams, h->n_beams * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(dev, pin, in.at, hipMemcpyHostToDevice, st));
-    char *dev_out = dev + in.at, *pin_out = pin + in.at;
-    rc = ndtgpu_locmon_adjust_device(h, (const double *)(dev + o_ranges), 1, 0, grid, xs, nx, ys, ny, cs, sn, nyaw, &p,
-                                     (ndtgpu_locmon_adjust_result *)(dev_out + o_res), volume ? (uint32_t *)(dev_out + o_vol) : nullptr,
+    HostStage &hs = h->host;
+    if ((rc = hs.open(h, who, in, outl)) != NDTGPU_OK) return rc;
+    memcpy(hs.in_host(o_ranges), ranges + (size_t)scan * h->n_beams, h->n_beams * sizeof(double));
+    if ((rc = hs.upload(st)) != NDTGPU_OK) return rc;
+    rc = ndtgpu_locmon_adjust_device(h, (const double *)hs.in_dev(o_ranges), 1, 0, grid, xs, nx, ys, ny, cs, sn, nyaw, &p,
+                                     (ndtgpu_locmon_adjust_result *)hs.out_dev(o_res), volume ? (uint32_t *)hs.out_dev(o_vol) : nullptr,
                                      (ndtgpu_stream)st);
     if (rc != NDTGPU_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(pin_out, dev_out, outl.at, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h->used.record(st));
-    HIP_TRY(hipStreamSynchronize(st));
-    memcpy(result, pin_out + o_res, sizeof *result);
-    if (volume) memcpy(volume, pin_out + o_vol, n_candidates * sizeof(uint32_t));
+    if ((rc = hs.finish(h, st)) != NDTGPU_OK) return rc;
+    memcpy(result, hs.out_host(o_res), sizeof *result);
+    if (volume) memcpy(volume, hs.out_host(o_vol), n_candidates * sizeof(uint32_t));
     return NDTGPU_OK;
 }
 
@@ -427,8 +388,8 @@ ndtgpu_status ndtgpu_locmon_pick_device(ndtgpu_locmon *h, const ndtgpu_featmatch
 {
     const char *who = "locmon_pick_device";
     const ndtgpu_locmon_params p = locmon_params(prm);
-    if (n_pairs > NDT_LOCMON_MAX_PAIRS) return locmon_bad(who, "n_pairs: more than 2^20");
-    if (const char *bad = ndt_locmon_check_params(p)) return locmon_bad(who, bad);
+    if (n_pairs > NDT_LOCMON_MAX_PAIRS) return fail_in(NDTGPU_ERR_INVALID, who, "n_pairs: more than 2^20");
+    if (const char *bad = ndt_locmon_check_params(p)) return fail_in(NDTGPU_ERR_INVALID, who, bad);
     if ((n_pairs && (!matches_dev || !ref_poses_dev)) || !query_dev || !pick_dev)
         return fail(NDTGPU_ERR_INVALID, "locmon_pick_device: null matches_dev, ref_poses_dev, query_dev or pick_dev");
     if (!h) return fail(NDTGPU_ERR_INVALID, "locmon_pick_device: null handle");

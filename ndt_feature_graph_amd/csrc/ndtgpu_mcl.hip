@@ -88,9 +88,7 @@ ndtgpu_status ndtgpu_mcl_create(ndtgpu_mapset *map_set, const uint32_t *map_idx,
     if (!map_set || !map_idx) return fail(NDTGPU_ERR_INVALID, "mcl_create: map set and map indices are required");
     if (n_filters == 0 || n_particles == 0 || n_particles > 65536 || n_filters > (1u << 24) || n_filters * n_particles > (1u << 24))
         return fail(NDTGPU_ERR_INVALID, "mcl_create: n_particles must be 1..65536 and n_filters * n_particles <= 2^24");
-    ndtgpu_mcl_params p;
-    ndtgpu_default_mcl_params(&p);
-    if (params) p = *params;
+    ndtgpu_mcl_params p = params_or_default(params, ndtgpu_default_mcl_params);
     bool ok = finite_nonneg(p.map_res) && finite_nonneg(p.sensor_res) && std::isfinite(p.range_limit) && !std::isnan(p.zfilt_min) &&
               std::isfinite(p.sir_varp_threshold);
     for (int a = 0; a < 3; a++) ok = ok && std::isfinite(p.scan_size[a]) && p.scan_size[a] > 0.0;
@@ -160,9 +158,9 @@ ndtgpu_status ndtgpu_mcl_create(ndtgpu_mapset *map_set, const uint32_t *map_idx,
 
 static ndtgpu_status mcl_range(const ndtgpu_mcl *h, size_t first, size_t count, const char *what)
 {
-    if (!h) return fail(NDTGPU_ERR_INVALID, (std::string(what) + ": null handle").c_str());
+    if (!h) return fail_in(NDTGPU_ERR_INVALID, what, "null handle");
     if (count == 0 || first >= h->F || count > h->F - first)
-        return fail(NDTGPU_ERR_INVALID, (std::string(what) + ": filters [first, first + count) out of range").c_str());
+        return fail_in(NDTGPU_ERR_INVALID, what, "filters [first, first + count) out of range");
     return NDTGPU_OK;
 }
 

@@ -107,9 +107,7 @@ static ndtgpu_status multires_subbatch(ndtgpu_multires *mr, const char *tg, cons
                                        size_t p, const ndtgpu_match_params &mp, int use_initial_guess,
                                        ndtgpu_match_result *results_dev, bool fused, hipStream_t st)
 {
-    ndtgpu_cell_params cp;
-    ndtgpu_default_cell_params(&cp);
-    if (cell) cp = *cell;
+    const ndtgpu_cell_params cp = params_or_default(cell, ndtgpu_default_cell_params);
     const int L = mr->n_levels;
     NdtMatchResultDev *res_out = reinterpret_cast<NdtMatchResultDev *>(results_dev);
     hipError_t e = ndt_launch_multires_step(p, -1, 0, L, 0, use_initial_guess, T16_dev, mr->temp.get(), mr->xf.get(), mr->state.get(), mr->stopped.get(),
@@ -176,8 +174,7 @@ static ndtgpu_status multires_check(ndtgpu_multires *mr, const void *tg, const v
     if (!mr || (n_pairs && (!tg || !sc || !T16 || !results)) || stride_bytes < 12 || (stride_bytes & 3) || n_points == 0 ||
         n_points > 0xFFFFFFFFull || map_stride_bytes < n_points * stride_bytes)
         return fail(NDTGPU_ERR_INVALID, "register_multires: bad argument");
-    ndtgpu_default_match_params(&mp);
-    if (prm) mp = *prm;
+    mp = params_or_default(prm, ndtgpu_default_match_params);
     mp.use_initial_guess = 0;                              // every level matches from the identity
     NdtMatchParamsDev p;
     return match_params_dev(&mp, 0, p);

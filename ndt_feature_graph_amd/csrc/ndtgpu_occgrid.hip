@@ -28,9 +28,7 @@ ndtgpu_status occgrid_prepare(const char *who, ndtgpu_mapset *s, size_t first, s
         snprintf(msg, sizeof msg, "%s: null map set", who);
         return fail(NDTGPU_ERR_INVALID, msg);
     }
-    ndtgpu_occgrid_params p;
-    ndtgpu_default_occgrid_params(&p);
-    if (prm) p = *prm;
+    const ndtgpu_occgrid_params p = params_or_default(prm, ndtgpu_default_occgrid_params);
     if (std::isnan(p.z) || p.occupied_no_gaussian < -128 || p.occupied_no_gaussian > 127) {
         snprintf(msg, sizeof msg, "%s: params.z must be a number, params.occupied_no_gaussian an int8", who);
         return fail(NDTGPU_ERR_INVALID, msg);

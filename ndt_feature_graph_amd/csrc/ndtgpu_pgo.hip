@@ -7,7 +7,6 @@
 #include "ndt_pgo.h"
 #include "ndt_pgo_wide.h"
 
-#include <new>
 #include <numeric>
 
 struct ndtgpu_pgo {
@@ -38,10 +37,9 @@ static void sym6(const double *W9, double *W6)
 static ndtgpu_status pgo_check_graph(const char *what, size_t n_nodes, const double *pose3, size_t n_edges, const uint32_t *ref_idx,
                                      const uint32_t *mov_idx)
 {
-    const std::string w(what);
     if (n_nodes == 0 || !pose3 || (n_edges && (!ref_idx || !mov_idx)))
-        return fail(NDTGPU_ERR_INVALID, (w + ": poses and link indices are required").c_str());
-    if (n_nodes > (1u << 24) || n_edges > (1u << 27)) return fail(NDTGPU_ERR_INVALID, (w + ": graph too large").c_str());
+        return fail_in(NDTGPU_ERR_INVALID, what, "poses and link indices are required");
+    if (n_nodes > (1u << 24) || n_edges > (1u << 27)) return fail_in(NDTGPU_ERR_INVALID, what, "graph too large");
     std::vector<uint32_t> parent(n_nodes);
     std::iota(parent.begin(), parent.end(), 0u);
     auto find = [&](uint32_t a) {
@@ -52,22 +50,20 @@ static ndtgpu_status pgo_check_graph(const char *what, size_t n_nodes, const dou
         return a;
     };
     for (size_t e = 0; e < n_edges; e++) {
-        if (ref_idx[e] >= n_nodes || mov_idx[e] >= n_nodes) return fail(NDTGPU_ERR_INVALID, (w + ": link index out of range").c_str());
-        if (ref_idx[e] == mov_idx[e]) return fail(NDTGPU_ERR_INVALID, (w + ": a link joins a node to itself").c_str());
+        if (ref_idx[e] >= n_nodes || mov_idx[e] >= n_nodes) return fail_in(NDTGPU_ERR_INVALID, what, "link index out of range");
+        if (ref_idx[e] == mov_idx[e]) return fail_in(NDTGPU_ERR_INVALID, what, "a link joins a node to itself");
         const uint32_t a = find(ref_idx[e]), b = find(mov_idx[e]);
         if (a != b) parent[std::max(a, b)] = std::min(a, b);
     }
     for (size_t i = 1; i < n_nodes; i++)
-        if (find((uint32_t)i) != 0) return fail(NDTGPU_ERR_INVALID, (w + ": a node is not connected to node 0").c_str());
+        if (find((uint32_t)i) != 0) return fail_in(NDTGPU_ERR_INVALID, what, "a node is not connected to node 0");
     return NDTGPU_OK;
 }
 
 // the device form of a call's parameters (NULL: the defaults); false where one is out of range
 static bool pgo_params_dev(const ndtgpu_pgo_params *prm, NdtPgoParamsDev &d)
 {
-    ndtgpu_pgo_params p;
-    ndtgpu_default_pgo_params(&p);
-    if (prm) p = *prm;
+    const ndtgpu_pgo_params p = params_or_default(prm, ndtgpu_default_pgo_params);
     bool ok = p.max_iterations >= 0 && p.max_linear_iterations >= 0 && p.eps_step >= 0.0 && p.eps_linear >= 0.0;   // (NaN fails)
     for (double w : p.prior_information) ok = ok && std::isfinite(w);
     d.max_iterations = p.max_iterations;
@@ -92,13 +88,7 @@ void ndtgpu_default_pgo_params(ndtgpu_pgo_params *p)
     p->prior_information[0] = p->prior_information[4] = p->prior_information[8] = 100.0;   // ndt_offline_mapper.h:45, :61
 }
 
-ndtgpu_status ndtgpu_pgo_destroy(ndtgpu_pgo *h)
-{
-    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo_destroy: null");
-    (void)h->used.sync();                  // (the last call may have run on a stream of the caller's)
-    delete h;
-    return NDTGPU_OK;
-}
+ndtgpu_status ndtgpu_pgo_destroy(ndtgpu_pgo *h) { return handle_destroy(h, "pgo_destroy"); }
 
 ndtgpu_status ndtgpu_pgo_create(size_t n_graphs, size_t max_nodes, size_t max_edges, ndtgpu_pgo **out)
 {
@@ -106,9 +96,9 @@ ndtgpu_status ndtgpu_pgo_create(size_t n_graphs, size_t max_nodes, size_t max_ed
     *out = nullptr;
     if (n_graphs == 0 || n_graphs > (1u << 24) || max_nodes == 0 || max_nodes > (1u << 24) || max_edges > (1u << 27))
         return fail(NDTGPU_ERR_INVALID, "pgo_create: n_graphs and max_nodes must be 1 .. 2^24, max_edges <= 2^27");
-    if (!have_device()) return fail(NDTGPU_ERR_NO_DEVICE, "pgo_create: no HIP device");
-    ndtgpu_pgo *h = new (std::nothrow) ndtgpu_pgo();
-    if (!h) return fail(NDTGPU_ERR_ALLOC, "pgo_create: host alloc");
+    ndtgpu_pgo *h;
+    const ndtgpu_status rc = handle_new("pgo_create", h);
+    if (rc != NDTGPU_OK) return rc;
     h->G = n_graphs;
     h->n_nodes.assign(n_graphs, 0);
     h->n_edges.assign(n_graphs, 0);
@@ -142,10 +132,9 @@ ndtgpu_status ndtgpu_pgo_create(size_t n_graphs, size_t max_nodes, size_t max_ed
 static ndtgpu_status pgo_install(ndtgpu_pgo *h, const char *what, size_t g, size_t n_nodes, const double *pose3, size_t n_edges,
                                  const uint32_t *ref_idx, const uint32_t *mov_idx)
 {
-    const std::string w(what);
-    if (g >= h->G) return fail(NDTGPU_ERR_INVALID, (w + ": graph index out of range").c_str());
+    if (g >= h->G) return fail_in(NDTGPU_ERR_INVALID, what, "graph index out of range");
     if (n_nodes > h->v.max_nodes || n_edges > h->v.max_edges)
-        return fail(NDTGPU_ERR_CAPACITY, (w + ": more nodes or links than the handle was created for").c_str());
+        return fail_in(NDTGPU_ERR_CAPACITY, what, "more nodes or links than the handle was created for");
     // (values that are not finite are not refused here: the kernel reports NDTGPU_PGO_NOT_FINITE for that graph)
     // node -> incident edges, CSR; a node's entries in ascending edge order
     std::vector<uint32_t> off(n_nodes + 1, 0), adj(2 * n_edges);
@@ -286,9 +275,7 @@ ndtgpu_status ndtgpu_pgo_optimize_wide(ndtgpu_pgo *h, size_t g, const ndtgpu_pgo
                                        ndtgpu_stream stream)
 {
     if (!h) return fail(NDTGPU_ERR_INVALID, "pgo_optimize_wide: null handle");
-    ndtgpu_pgo_wide_params wp;
-    ndtgpu_default_pgo_wide_params(&wp);
-    if (wide) wp = *wide;
+    const ndtgpu_pgo_wide_params wp = params_or_default(wide, ndtgpu_default_pgo_wide_params);
     NdtPgoWide W{};
     if (!pgo_params_dev(prm, W.prm))
         return fail(NDTGPU_ERR_INVALID, "pgo_optimize_wide: bad parameter (caps and tolerances >= 0, a finite prior)");

@@ -3,8 +3,10 @@
 // what it holds in its destructor and ignores HIP errors there.
 //
 // ORDER OF MEMBERS.  Members are destroyed in reverse declaration order, and a Stream's destructor waits for its work: a handle
-// declares its streams AFTER the buffers and fences that their work uses, so the streams go first.  A *_destroy waits for the work
-// on streams the handle does not own (the caller's), then deletes the handle.
+// declares its streams AFTER the buffers and fences that their work uses, so the streams go first.  That holds for the members
+// that bundle buffers as well -- HostStage and LatticeTables (ndtgpu_host.h) own blocks that the handle's stream copies to and
+// from, and no stream or fence: they stand in front of the handle's `used` and `hst`.  A *_destroy waits for the work on streams
+// the handle does not own (the caller's), then deletes the handle (handle_destroy, ndtgpu_host.h).
 //
 // Objects with static storage keep raw HIP handles instead (g_coop_order in ndtgpu_matcher.hip): at process exit the runtime may
 // be gone before their destructors would run.

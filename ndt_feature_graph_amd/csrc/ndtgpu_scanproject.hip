@@ -5,24 +5,17 @@
 #include "ndtgpu_host.h"
 #include "ndt_scanproject.h"
 
-#include <new>
-
 struct ndtgpu_scanproj {
     size_t max_scans = 0, max_beams = 0;
     DeviceBuffer<uint32_t> tile;           // one count per tile of every scan: what the two launches of a call hand over
-    // the host form's staging, made by its first call and grown by later ones (ranges | scan ids in, rows | counts out)
-    DeviceBuffer<char> stage;
-    PinnedBuffer<char> pin;
+    HostStage host;                        // the host form's staging (ranges | scan ids in, rows | counts out)
     Fence used;                            // recorded after the last launch of a call
     Stream hst;                            // the host form's stream (last: ndtgpu_resource.h)
 };
 
 static ndtgpu_scanproject_params scanproject_params(const ndtgpu_scanproject_params *prm)
 {
-    ndtgpu_scanproject_params p;
-    ndtgpu_default_scanproject_params(&p);
-    if (prm) p = *prm;
-    return p;
+    return params_or_default(prm, ndtgpu_default_scanproject_params);
 }
 
 // the checks every entry makes before it reads the handle
@@ -31,14 +24,13 @@ static ndtgpu_status scanproj_check(const char *who, size_t n_scans, size_t n_be
 {
     const char *bad = ndt_scanproject_check_args(n_scans, n_beams, angle_min, angle_increment, stride_bytes, map_stride_bytes);
     if (!bad) bad = ndt_scanproject_check_params(p);
-    if (!bad) return NDTGPU_OK;
-    return fail(NDTGPU_ERR_INVALID, (std::string(who) + ": " + bad).c_str());
+    return bad ? fail_in(NDTGPU_ERR_INVALID, who, bad) : NDTGPU_OK;
 }
 
 static ndtgpu_status scanproj_fits(const char *who, const ndtgpu_scanproj *h, size_t n_scans, size_t n_beams)
 {
-    if (n_scans > h->max_scans) return fail(NDTGPU_ERR_CAPACITY, (std::string(who) + ": more scans than the handle was created for").c_str());
-    if (n_beams > h->max_beams) return fail(NDTGPU_ERR_CAPACITY, (std::string(who) + ": more beams than the handle was created for").c_str());
+    if (n_scans > h->max_scans) return fail_in(NDTGPU_ERR_CAPACITY, who, "more scans than the handle was created for");
+    if (n_beams > h->max_beams) return fail_in(NDTGPU_ERR_CAPACITY, who, "more beams than the handle was created for");
     return NDTGPU_OK;
 }
 
@@ -76,11 +68,10 @@ ndtgpu_status ndtgpu_scanproj_create(size_t max_scans, size_t max_beams, ndtgpu_
 {
     if (!out) return fail(NDTGPU_ERR_INVALID, "scanproj_create: out is NULL");
     *out = nullptr;
-    if (const char *bad = ndt_scanproject_check_capacity(max_scans, max_beams))
-        return fail(NDTGPU_ERR_INVALID, (std::string("scanproj_create: ") + bad).c_str());
-    if (!have_device()) return fail(NDTGPU_ERR_NO_DEVICE, "scanproj_create: no HIP device");
-    ndtgpu_scanproj *h = new (std::nothrow) ndtgpu_scanproj();
-    if (!h) return fail(NDTGPU_ERR_ALLOC, "scanproj_create: host alloc");
+    if (const char *bad = ndt_scanproject_check_capacity(max_scans, max_beams)) return fail_in(NDTGPU_ERR_INVALID, "scanproj_create", bad);
+    ndtgpu_scanproj *h;
+    const ndtgpu_status rc = handle_new("scanproj_create", h);
+    if (rc != NDTGPU_OK) return rc;
     h->max_scans = max_scans;
     h->max_beams = max_beams;
 #define TRY(expr) CREATE_TRY(h, NDTGPU_ERR_ALLOC, "scanproj_create: device buffers", expr)
@@ -92,13 +83,7 @@ ndtgpu_status ndtgpu_scanproj_create(size_t max_scans, size_t max_beams, ndtgpu_
     return NDTGPU_OK;
 }
 
-ndtgpu_status ndtgpu_scanproj_destroy(ndtgpu_scanproj *h)
-{
-    if (!h) return fail(NDTGPU_ERR_INVALID, "scanproj_destroy: null");
-    (void)h->used.sync();                  // (the last call may have run on a stream of the caller's)
-    delete h;
-    return NDTGPU_OK;
-}
+ndtgpu_status ndtgpu_scanproj_destroy(ndtgpu_scanproj *h) { return handle_destroy(h, "scanproj_destroy"); }
 
 ndtgpu_status ndtgpu_scanproj_project_device(ndtgpu_scanproj *h, const double *ranges_dev, const uint64_t *scan_id_dev, size_t n_scans,
                                              size_t n_beams, double angle_min, double angle_increment,
@@ -140,29 +125,23 @@ ndtgpu_status ndtgpu_scanproj_project(ndtgpu_scanproj *h, const double *ranges, 
     StageLayout in, outl;
     const size_t o_ranges = in.take(beams * sizeof(double)), o_ids = in.take(scan_id ? n_scans * sizeof(uint64_t) : 0);
     const size_t o_rows = outl.take(beams * row), o_kept = outl.take(n_scans * sizeof(uint32_t));
-    const size_t bytes = in.at + outl.at;
     hipStream_t st = h->hst.get();
-    HIP_TRY(h->used.sync());               // (the staging blocks may be replaced below, and are overwritten)
-    if (h->stage.reserve(bytes) != hipSuccess || h->pin.reserve(bytes) != hipSuccess)
-        return fail(NDTGPU_ERR_ALLOC, "scanproj_project: staging buffers");
-    char *pin = h->pin.get(), *dev = h->stage.get();
-    memcpy(pin + o_ranges, ranges, beams * sizeof(double));
-    if (scan_id) memcpy(pin + o_ids, scan_id, n_scans * sizeof(uint64_t));
-    HIP_TRY(hipMemcpyAsync(dev, pin, in.at, hipMemcpyHostToDevice, st));
-    char *dev_out = dev + in.at, *pin_out = pin + in.at;
-    rc = ndtgpu_scanproj_project_device(h, (const double *)(dev + o_ranges), scan_id ? (const uint64_t *)(dev + o_ids) : nullptr, n_scans,
-                                        n_beams, angle_min, angle_increment, &p, dev_out + o_rows, row, n_beams * row,
-                                        (uint32_t *)(dev_out + o_kept), (ndtgpu_stream)st);
+    HostStage &hs = h->host;
+    if ((rc = hs.open(h, "scanproj_project", in, outl)) != NDTGPU_OK) return rc;
+    memcpy(hs.in_host(o_ranges), ranges, beams * sizeof(double));
+    if (scan_id) memcpy(hs.in_host(o_ids), scan_id, n_scans * sizeof(uint64_t));
+    if ((rc = hs.upload(st)) != NDTGPU_OK) return rc;
+    rc = ndtgpu_scanproj_project_device(h, (const double *)hs.in_dev(o_ranges), scan_id ? (const uint64_t *)hs.in_dev(o_ids) : nullptr,
+                                        n_scans, n_beams, angle_min, angle_increment, &p, hs.out_dev(o_rows), row, n_beams * row,
+                                        (uint32_t *)hs.out_dev(o_kept), (ndtgpu_stream)st);
     if (rc != NDTGPU_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(pin_out, dev_out, outl.at, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h->used.record(st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = hs.finish(h, st)) != NDTGPU_OK) return rc;
     for (size_t b = 0; b < n_scans; b++) {
-        const char *src = pin_out + o_rows + b * n_beams * row;
+        const char *src = hs.out_host(o_rows) + b * n_beams * row;
         char *dst = (char *)xyz + b * map_stride_bytes;
         for (size_t i = 0; i < n_beams; i++) memcpy(dst + i * stride_bytes, src + i * row, row);
     }
-    if (n_kept) memcpy(n_kept, pin_out + o_kept, n_scans * sizeof(uint32_t));
+    if (n_kept) memcpy(n_kept, hs.out_host(o_kept), n_scans * sizeof(uint32_t));
     return NDTGPU_OK;
 }
 

@@ -54,9 +54,7 @@ ndtgpu_status ndtgpu_world_assemble(ndtgpu_mapset *dst, size_t dst_first, size_t
         for (size_t k = n0; k < n0 + n_items; k++)
             if (node_idx[k] >= dst_first && node_idx[k] - dst_first < count)
                 return fail(NDTGPU_ERR_INVALID, "world_assemble: a destination map is among the listed nodes");
-    ndtgpu_world_params p;
-    ndtgpu_default_world_params(&p);
-    if (prm) p = *prm;
+    const ndtgpu_world_params p = params_or_default(prm, ndtgpu_default_world_params);
     if (!(p.eval_factor > 0.0) || !std::isfinite(p.eval_factor) || !(p.occupancy_limit > 0.0) || std::isnan(p.maxnumpoints))
         return fail(NDTGPU_ERR_INVALID, "world_assemble: eval_factor and occupancy_limit must be positive, maxnumpoints a number");
     if (!have_device()) return fail(NDTGPU_ERR_NO_DEVICE, "world_assemble: no HIP device");

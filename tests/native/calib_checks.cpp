@@ -3,6 +3,7 @@
 // arithmetic of the launches.  The outputs go into heap blocks of exactly the size a call may touch, so the address sanitizer sees
 // any step past an end (build it with -fsanitize=address,undefined to check that).  Exit code 0 = every check passed.
 #include "../../ndt_feature_graph_amd/csrc/ndt_calib.h"
+#include "../../ndt_feature_graph_amd/csrc/ndt_lattice.h"
 
 #include <cstdio>
 #include <cstring>
@@ -133,11 +134,11 @@ int main()
     REFUSED(ndt_calib_check_capacity(16, 720, (1u << 24) + 1), "max_candidates");
     {
         const std::vector<double> xs = {0.1, 0.2}, ys = {0.0}, cs = {1.0, std::cos(0.3)}, sn = {0.0, std::sin(0.3)};
-        CHECK(!ndt_calib_check_tables(xs.data(), 2, ys.data(), 1, cs.data(), sn.data(), 2), "tables");
+        CHECK(!ndt_lattice_check_tables(xs.data(), 2, ys.data(), 1, cs.data(), sn.data(), 2), "tables");
         const std::vector<double> bx = {0.1, nan}, by = {inf}, bc = {1.0, 0.5};
-        REFUSED(ndt_calib_check_tables(bx.data(), 2, ys.data(), 1, cs.data(), sn.data(), 2), "xs");
-        REFUSED(ndt_calib_check_tables(xs.data(), 2, by.data(), 1, cs.data(), sn.data(), 2), "ys");
-        REFUSED(ndt_calib_check_tables(xs.data(), 2, ys.data(), 1, bc.data(), sn.data(), 2), "cs / sn");
+        REFUSED(ndt_lattice_check_tables(bx.data(), 2, ys.data(), 1, cs.data(), sn.data(), 2), "xs");
+        REFUSED(ndt_lattice_check_tables(xs.data(), 2, by.data(), 1, cs.data(), sn.data(), 2), "ys");
+        REFUSED(ndt_lattice_check_tables(xs.data(), 2, ys.data(), 1, bc.data(), sn.data(), 2), "cs / sn");
     }
 
     // ---- the chunks: a multiple of the tile, at least one tile, pairs x chunk within the scratch; the walk of a lattice covers

@@ -4,6 +4,7 @@
 // grids, the row pass's bytes and the fields live in heap blocks of exactly width x height elements, so the address sanitizer sees
 // any step past an end (build it with -fsanitize=address,undefined to check that).  Exit code 0 = every check passed.
 #include "../../ndt_feature_graph_amd/csrc/ndt_locmon.h"
+#include "../../ndt_feature_graph_amd/csrc/ndt_lattice.h"
 
 #include <cstdio>
 #include <cstring>
@@ -188,15 +189,15 @@ int main()
     REFUSED(ndt_locmon_check_lattice(1 << 23, 2, 2), "candidates");
     {
         std::vector<double> xs = {0.1, 0.2, 0.3}, ys = {0.0, 0.1}, cs = {1.0, std::cos(0.1)}, sn = {0.0, std::sin(0.1)};
-        CHECK(!ndt_locmon_check_tables(xs.data(), 3, ys.data(), 2, cs.data(), sn.data(), 2), "tables");
+        CHECK(!ndt_lattice_check_tables(xs.data(), 3, ys.data(), 2, cs.data(), sn.data(), 2), "tables");
         xs[2] = nan;
-        REFUSED(ndt_locmon_check_tables(xs.data(), 3, ys.data(), 2, cs.data(), sn.data(), 2), "xs");
+        REFUSED(ndt_lattice_check_tables(xs.data(), 3, ys.data(), 2, cs.data(), sn.data(), 2), "xs");
         xs[2] = 0.3; ys[0] = inf;
-        REFUSED(ndt_locmon_check_tables(xs.data(), 3, ys.data(), 2, cs.data(), sn.data(), 2), "ys");
+        REFUSED(ndt_lattice_check_tables(xs.data(), 3, ys.data(), 2, cs.data(), sn.data(), 2), "ys");
         ys[0] = 0.0; cs[1] = 0.5;
-        REFUSED(ndt_locmon_check_tables(xs.data(), 3, ys.data(), 2, cs.data(), sn.data(), 2), "cs / sn");
+        REFUSED(ndt_lattice_check_tables(xs.data(), 3, ys.data(), 2, cs.data(), sn.data(), 2), "cs / sn");
         cs[1] = std::cos(0.1); sn[0] = nan;
-        REFUSED(ndt_locmon_check_tables(xs.data(), 3, ys.data(), 2, cs.data(), sn.data(), 2), "cs / sn");
+        REFUSED(ndt_lattice_check_tables(xs.data(), 3, ys.data(), 2, cs.data(), sn.data(), 2), "cs / sn");
     }
     REFUSED(ndt_locmon_check_capacity(0, 1, 1, 1), "max_grids");
     REFUSED(ndt_locmon_check_capacity(1025, 1, 1, 1), "max_grids");

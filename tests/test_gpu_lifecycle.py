@@ -6,11 +6,18 @@ baseline, three more cycles.  The "use" step reaches every lazily created member
 once (the same call with the larger cloud or more pairs).  While the handle is alive at least one resource of every kind the
 subsystem uses must be counted: a subsystem that went around the owning types would otherwise pass trivially.
 
-Shapes: 0.5 m cells on a 20 m x 20 m x 1 m grid, 2 to 4 maps, clouds of 256 points and 1024 for the grow step."""
+Shapes: 0.5 m cells on a 20 m x 20 m x 1 m grid, 2 to 4 maps, clouds of 256 points and 1024 for the grow step.  The handles
+without a map set (link gate, feature bank, scan projector, calibrator, localisation monitor) take the smallest shapes that reach
+every lazily created member: a few scans of 64 to 180 beams, lattices of 3 x 3 x 2 and 5 x 5 x 4 nodes."""
 import ctypes as C
 
 import numpy as np
 import pytest
+
+import calib_fixtures
+import flirt_fixtures
+import linkgate_fixtures
+import locmon_fixtures
 
 pytestmark = pytest.mark.gpu
 
@@ -253,3 +260,102 @@ def test_pgo(N, live):
         return before, alive
 
     check_cycles(live, cycle, (DEVICE, EVENTS, STREAMS))
+
+
+def lattice(nx, ny, nyaw, x0=0.2, y0=0.05, yaw0=0.02):
+    """nx x ny x nyaw nodes around (x0, y0, yaw0): the tables Calibrator.search and LocalizationMonitor.adjust take"""
+    yaws = yaw0 + 0.04 * (np.arange(nyaw) - (nyaw - 1) / 2)
+    return dict(xs=x0 + 0.02 * (np.arange(nx) - (nx - 1) / 2), ys=y0 + 0.02 * (np.arange(ny) - (ny - 1) / 2), cs=np.cos(yaws), sn=np.sin(yaws))
+
+
+def test_linkgate(N, live):
+    _, node_T = linkgate_fixtures.walk(8, seed=3)
+
+    def cycle():
+        before = live()
+        gate = N.LinkGate(8, 32)                                                                     # 8 nodes, 32 links
+        gate.set_nodes(node_T)                                                                       # from the host
+        ref, mov, T16 = gate.candidates(32, min_idx_dist=1, max_dist=100.0, max_angle=4.0, clip_cosine=1)
+        count, overflow = gate.count()
+        assert count == 28 and not overflow                                                          # every pair i < j of 8 nodes
+        alive = live()
+        gate.close()
+        return before, alive
+
+    check_cycles(live, cycle, (DEVICE, EVENTS, STREAMS))
+
+
+def test_featbank(N, live):
+    halls = {nb: np.stack([flirt_fixtures.hall(4100 + k, nb)[0] for k in range(4)]) for nb in (90, 180)}
+    geometry = {nb: flirt_fixtures.hall(4100, nb)[1:] for nb in (90, 180)}
+
+    def cycle():
+        before = live()
+        fm = N.FeatureMatcher(4, 64, 48)                                                             # 4 sets x 64 points x 48 values
+        for n, nb in ((2, 90), (4, 180)):                                                            # ... then more, larger scans
+            res, per_scan = fm.extract(np.arange(n), halls[nb][:n], *geometry[nb])
+            assert res.shape == (n,) and len(per_scan) == n and (res["n_valid"] > 0).all()
+            res, T, corr = fm.match(np.arange(n), (np.arange(n) + 1) % n)                            # n pairs
+            assert res.shape == (n,) and T.shape == (n, 4, 4) and len(corr) == n
+        alive = live()
+        fm.close()
+        return before, alive
+
+    check_cycles(live, cycle, (DEVICE, PINNED, EVENTS, STREAMS))
+
+
+def test_scanproj(N, live):
+    rng = np.random.default_rng(11)
+
+    def cycle():
+        before = live()
+        sp = N.ScanProjector(4, 128)
+        for n, nb in ((2, 64), (4, 128)):                                                            # the host form; its staging grows
+            xyz, kept = sp.project(rng.uniform(1.0, 20.0, (n, nb)), -1.0, 2.0 / nb)
+            assert xyz.shape == (n, nb, 3) and (kept == nb).all()
+        alive = live()
+        sp.close()
+        return before, alive
+
+    check_cycles(live, cycle, (DEVICE, PINNED, EVENTS, STREAMS))
+
+
+def test_calib(N, live):
+    f = calib_fixtures.planted(n_beams=64)
+    pairs = f["pairs"][:2]                                                                           # 2 pairs of 64-point scans
+    assert len(pairs) == 2 and f["xyz"].shape[1] == 64
+
+    def cycle():
+        before = live()
+        cal = N.Calibrator(2, 64, 100)
+        r = cal.search(f["xyz"], f["n_kept"], f["poses4"], pairs, lattice(3, 3, 2))                   # the host form
+        assert 0 <= r["index"] < 18 and r["volume"] is None
+        r = cal.search(f["xyz"], f["n_kept"], f["poses4"], pairs, lattice(5, 5, 4), want_volume=True)  # staging and tables grow
+        assert 0 <= r["index"] < 100 and r["volume"].shape == (5, 5, 4)
+        alive = live()
+        cal.close()
+        return before, alive
+
+    check_cycles(live, cycle, (DEVICE, PINNED, EVENTS, STREAMS))
+
+
+def test_locmon(N, live):
+    rng = np.random.default_rng(13)
+    grid = locmon_fixtures.random_grid(rng, 32, 32, 0.05)[None]                                      # one 32 x 32 grid
+    ranges = rng.uniform(0.5, 3.0, (2, 64))                                                          # 64 beams
+    q = locmon_fixtures.queries(rng.integers(0, 2, 16), 0, rng.uniform(0.5, 2.5, 16), rng.uniform(0.5, 2.5, 16), rng.uniform(-3.0, 3.0, 16))
+
+    def cycle():
+        before = live()
+        mon = N.LocalizationMonitor(1, 32 * 32, 64, 18)
+        mon.set_beams(64, -1.5, 3.0 / 64)
+        mon.set_grids(grid, 0.1, [[0.0, 0.0]])                                                       # the host form: the device block
+        for n in (4, 16):                                                                            # ... and the pinned block, grown
+            assert mon.evaluate(ranges, q[:n]).shape == (n,)
+        r = mon.adjust(ranges, 1, 0, lattice(3, 3, 2, x0=1.6, y0=1.6), want_volume=True)             # the lattice tables
+        assert 0 <= r["index"] < 18 and r["volume"].shape == (3, 3, 2)
+        alive = live()
+        mon.close()
+        return before, alive
+
+    check_cycles(live, cycle, (DEVICE, PINNED, EVENTS, STREAMS))
