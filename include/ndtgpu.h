@@ -1940,6 +1940,151 @@ ndtgpu_status ndtgpu_locmon_pick_device(ndtgpu_locmon *h, const ndtgpu_featmatch
                                         size_t n_pairs, uint32_t scan, uint32_t grid, const ndtgpu_locmon_params *prm,
                                         ndtgpu_locmon_query *query_dev, ndtgpu_locmon_pick *pick_dev, ndtgpu_stream stream);
 
+/* ---- scan simulation: the ranges a laser would measure in an occupancy grid, and the lattice of reference poses ---------------------
+ * The localisation monitor's pick (ndtgpu_locmon_pick_device) needs a bank of reference scans with known poses.  The reference makes
+ * one from the map alone: generateRefScans (flirtlib_ros/src/place_rec_test.cpp:203-260) walks a lattice of (x, y, theta) over the free
+ * cells of the grid (:218-237), calls occupancy_grid_utils::simulateRangeScan(*grid, pose, scanner_params, true) at each pose (:242) and
+ * runs the FLIRT detector and descriptor on the simulated scan (:245-254); simulate_scans.cpp:120-142 publishes the scans of virtual
+ * lasers through the same call (simulate_scans.cpp:131).  This section is that call and that lattice on the device.  It closes the
+ * loop: grid -> simulated reference scans -> ndtgpu_featbank_extract_device -> ndtgpu_featbank_match_device ->
+ * ndtgpu_locmon_pick_device -> ndtgpu_locmon_evaluate_device, a robot relocalised in a map this library built, without a scan
+ * database and without a visit to the host.
+ * PROVENANCE: restated from the reference's call sites cited above.  occupancy_grid_utils (simulateRangeScan) is not vendored by the
+ * reference, only its call sites are; its semantics are restated here from those call sites and its public documentation: a ray
+ * per beam from the sensor's cell through the grid, the range of the first occupied cell (or unknown cell, where the last argument is
+ * true), range_max + 1 where there is none within range_max.  No program text of the reference is copied.
+ * Semantics (restated; the order of every fp64 operation -- not contracted -- is written out in csrc/ndt_scansim.h; everything that
+ * decides a result is integer: tests/scansim_model.py restates it and the device's outputs equal the model's bit for bit).
+ *   grid     int8, width x height, row-major, origin[2], resolution, as ndtgpu_mapset_occupancy_grid_device writes it.  A pixel is an
+ *            obstacle iff v >= occupied_min (55), unknown iff v < 0; an unknown pixel counts as an obstacle iff unknown_is_obstacle
+ *            (1: every call site passes true).
+ *   pose     (x, y, c, s).  Beam i has the table entry (cb_i, sb_i) of ndtgpu_locmon_beam_table, installed by
+ *            ndtgpu_scansim_set_beams; its direction is ex = c * cb - s * sb, ey = s * cb + c * sb (the order of ndtgpu_locmon_pixel).
+ *   ray      c0 = (floor((x - ox) / res), floor((y - oy) / res)); c1 the same of (x + ex * range_max, y + ey * range_max); (di, dj) =
+ *            c1 - c0, n = max(|di|, |dj|).  The cell of step k = 1 .. n advances sign * k on the major axis (x where |di| == |dj|)
+ *            and sign * floor((2 * k * dmin + n) / (2 * n)) on the minor one.  The start cell is never tested (upstream's !(c ==
+ *            c0)).  A ray with |di| or |dj| above 2^15 or not a number (a direction that is no unit vector) is a miss.
+ *   stop     per visited cell, in this order: outside the grid: miss; d2 = di_k^2 + dj_k^2 > R * R: miss, R = (int)floor(range_max /
+ *            resolution); an obstacle, or an unknown counted as one: hit, range = resolution * sqrt((double)d2); behind step n: miss.
+ *            A miss writes prm.miss (11.0 = range_max + 1, upstream's out-of-range value; above the extraction's r_max, whose gate
+ *            drops it).  At most R + 2 steps a beam.
+ *   scan     a record {n_hits, flags} per pose.  NDTGPU_SCANSIM_OFFMAP: c0 is outside the grid (compared as doubles; a NaN is off the
+ *            map): no walk, every beam a miss.  NDTGPU_SCANSIM_BAD_INDEX: grid index >= n_grids: the same.  NDTGPU_SCANSIM_NO_POSE:
+ *            the row is at or beyond count_dev[0]: the same.
+ *   lattice  positions ix = 0, skip, ... below width (outer loop), iy likewise (middle loop), headings theta = 0, then += angle_step
+ *            while theta < 6.28 (inner loop; cs / sn made on the host by ndtgpu_scansim_headings, the ndtgpu_calib_lattice
+ *            convention).  A position is kept iff its pixel == 0 and its centre (ox + ((double)ix + 0.5) * res, oy likewise) lies in
+ *            [x0, x1] x [y0, y1].  Kept poses are written compacted, in loop order, as poses_dev[.][4]: the ref_poses_dev layout of
+ *            ndtgpu_locmon_pick_device; index_dev[.] is the linear lattice index ((ix / skip) * npy + iy / skip) * nyaw + iyaw, npy =
+ *            ceil(height / skip).  count_dev[0] is the number of poses written, at most capacity; count_dev[1] the number that
+ *            passed.  skip = (unsigned)(ref_pos_resolution / resolution) (ndtgpu_scansim_skip); 0 is refused.
+ * DEVIATIONS:
+ *   - ranges run between cell centres: upstream measures from the pose's point; the two agree for generateRefScans, whose poses are
+ *     cell centres.
+ *   - the reach test is an integer test (d2 > R * R); upstream compares a distance in metres.
+ *   - the walk ends on leaving the grid, instead of projecting the ray's endpoint onto the grid first.
+ *   - occupied_min replaces upstream's OCCUPIED constant (100): 55 is the smallest value this library's rasteriser gives an occupied
+ *     pixel.
+ *   - headings by repeated addition of angle_step from 0 (the reference's loop), their cosines and sines from the host.
+ *   - flags replace the assertions (a pose off the map aborts upstream).
+ *   - left out: the FLIRT detector and descriptor of :245-254 are ndtgpu_featbank_extract_device, behind this on the same stream.
+ * Limits: n_beams 1 .. 8192; R 1 .. 4094; width, height 1 .. 2^15; 1 .. 1024 grids; up to 2^24 poses a call, a lattice's capacity and
+ * headings; a lattice of at most 2^32 - 1 nodes.
+ * Device form (csrc/ndt_scansim.hip): plain launches on the caller's stream, no atomics, no workgroup waits on another, no environment
+ * switches.  Cast: one workgroup of 256 lanes per pose, a lane per beam, tiles of 256 beams in turn; all lanes of a wave advance k
+ * together, so neighbouring beams load neighbouring bytes in the same iteration and a wave leaves the loop once its last lane has
+ * stopped; plain byte loads through L2 (poses in lattice order: neighbouring workgroups walk the same pixels); n_hits by one block
+ * count (csrc/ndt_block.h).  A (tiles of beams) x (poses) grid would need a second pass to add a pose's n_hits over its tiles without
+ * atomics; the workgroup-per-pose form shipped and that variant was not built, nor was an LDS patch of (2 R + 1)^2 pixels (78 KiB at R =
+ * 140 already; R = 200 of the reference's configuration does not fit).  Lattice: the ordered selection of the link gate, three
+ * launches: flag-and-count per tile of 256 positions, one workgroup's scan of the tile counts, emit by block rank.
+ * Measured on MI355X (tools/scansim_cost.py, library 0.13.0; HIP events around the call, median of 7 after a warm-up, min .. max), in
+ * the replay's world at 0.05 m (13600 x 12000 pixels, 2.4 M obstacle pixels; the assembled world carries no free-space evidence, so its
+ * unknown pixels are taken as free): 1024 poses x 1440 beams over the full circle, range_max 30 (R = 600), 1.27 ms (1.27 .. 1.30; 1.24 us
+ * a pose, 63 % of the beams hit; 218 G cells walked a second, the cells counted by the model on 4 poses and SCALED: an extrapolation).
+ * The configuration of place_rec_test -- 181 beams over +- pi / 2, range_max 10 (R = 200), ref_pos_resolution 1 m (skip 20) and 8
+ * headings: the lattice, 3 264 000 nodes -> 3 215 968 poses, 0.138 ms (0.134 .. 0.140); their scans 175.8 ms (175.6 .. 175.9; 0.055 us a
+ * pose; 12 % of the beams hit, the rest walk the whole reach; 595 G cells a second, SCALED the same way).  The FLIRT extraction of the
+ * 11 680 scans within 20 m of the first room on the same stream: 1.75 ms alone (1.73 .. 1.80), 2.27 ms with their simulation in front
+ * (2.23 .. 2.32; +0.52 ms; the simulation alone 0.56 ms), 2.1 features a scan.  tests/scansim_model.py on one core of the same box:
+ * 44.4 ms a pose at 1440 beams and 4.15 ms at 181 beams (4 poses each, the same bits as the device), SCALED 45.5 s and 13 346 s, 35 700
+ * and 75 900 times the device: extrapolations.
+ * Kernels (tools/kernel_resources.py scansim): cast 42, flag 12, scan 16, emit 14 VGPRs, no spills, no scratch; LDS 32 B each. */
+typedef struct ndtgpu_scansim ndtgpu_scansim;
+typedef struct {
+    double range_max;                /* the scanner's reach, metres (10.0); R = floor(range_max / resolution) must be 1 .. 4094 */
+    double miss;                     /* what a beam without a hit reads (11.0 = range_max + 1) */
+    int32_t occupied_min;            /* a pixel >= this is an obstacle (55) */
+    int32_t unknown_is_obstacle;     /* 1: a pixel < 0 stops a ray as an obstacle does (1); 0: it is free */
+} ndtgpu_scansim_params;
+#define NDTGPU_SCANSIM_OFFMAP 1u
+#define NDTGPU_SCANSIM_BAD_INDEX 2u
+#define NDTGPU_SCANSIM_NO_POSE 4u
+typedef struct {
+    uint32_t n_hits;                 /* beams that hit */
+    uint32_t flags;                  /* NDTGPU_SCANSIM_OFFMAP | _BAD_INDEX | _NO_POSE */
+} ndtgpu_scansim_result;
+void ndtgpu_default_scansim_params(ndtgpu_scansim_params *p);
+/* the lanes of a workgroup: the beams of one pass of a cast, the positions of a lattice tile */
+uint32_t ndtgpu_scansim_tile(void);
+/* Pure host functions (no device), built on what the kernels call (csrc/ndt_scansim.h).
+ * ndtgpu_scansim_check: the checks of set_grids* (n_grids, width, height, resolution), set_beams (n_beams, angle_min,
+ * angle_increment) and simulate* (n_poses, prm) at once; prm NULL: the defaults.  NDTGPU_ERR_INVALID with a message that names the
+ * argument. */
+ndtgpu_status ndtgpu_scansim_check(size_t n_grids, size_t width, size_t height, double resolution, size_t n_beams, double angle_min,
+                                   double angle_increment, size_t n_poses, const ndtgpu_scansim_params *prm);
+/* R = (int)floor(range_max / resolution); NDTGPU_ERR_INVALID (and *R = 0) unless both are finite and > 0 and R is 1 .. 4094 */
+ndtgpu_status ndtgpu_scansim_reach(double range_max, double resolution, int32_t *R);
+/* skip = (unsigned)(ref_pos_resolution / resolution); NDTGPU_ERR_INVALID (and *skip = 0) unless it is 1 .. 2^15 */
+ndtgpu_status ndtgpu_scansim_skip(double ref_pos_resolution, double resolution, uint32_t *skip);
+/* the cell of step k (0 .. max(|di|, |dj|)) of a ray of (di, dj) cells, relative to its start: the closed form above */
+ndtgpu_status ndtgpu_scansim_cell(int32_t di, int32_t dj, int32_t k, int32_t cell2[2]);
+/* one beam with table entry (cb, sb) from pose4 = (x, y, c, s) on a HOST grid of width x height: *range, *hit (1 or 0) and *flags (0 or
+ * NDTGPU_SCANSIM_OFFMAP) */
+ndtgpu_status ndtgpu_scansim_beam(const int8_t *grid, size_t width, size_t height, const double origin2[2], double resolution,
+                                  const double pose4[4], double cb, double sb, const ndtgpu_scansim_params *prm, double *range, int32_t *hit,
+                                  uint32_t *flags);
+/* the headings of generateRefScans: *count, and cs[k] = cos(theta_k), sn[k] = sin(theta_k) where not NULL (NDTGPU_ERR_CAPACITY where
+ * *count > room) */
+ndtgpu_status ndtgpu_scansim_headings(double angle_step, size_t *count, double *cs, double *sn, size_t room);
+/* a simulator for up to max_grids grids (1 .. 1024), scans of up to max_beams beams (1 .. 8192) and calls of up to max_poses poses (1 ..
+ * 2^24): it owns the origins, the beam table and, from their first use, the grids of the host form, the lattice's tile counts and
+ * heading tables and the staging of the host forms */
+ndtgpu_status ndtgpu_scansim_create(size_t max_grids, size_t max_beams, size_t max_poses, ndtgpu_scansim **out);
+ndtgpu_status ndtgpu_scansim_destroy(ndtgpu_scansim *h);
+/* installs the beam table of a scanner geometry (made on the host, uploaded on `stream`).  Waits on the host for the handle's
+ * previous call. */
+ndtgpu_status ndtgpu_scansim_set_beams(ndtgpu_scansim *h, size_t n_beams, double angle_min, double angle_increment, ndtgpu_stream stream);
+/* installs n_grids grids: DEVICE grids_dev, n_grids x height x width int8, BORROWED until the next set_grids* or destroy (as the MCL
+ * borrows map sets): the caller keeps the bytes alive and orders its writes to them before the calls that read them; HOST origins2,
+ * n_grids x 2, copied before the call returns.  The arguments are checked before the handle is read and the device is looked for.
+ * Calls on one handle are ordered on the device whatever stream each names. */
+ndtgpu_status ndtgpu_scansim_set_grids_device(ndtgpu_scansim *h, const int8_t *grids_dev, size_t n_grids, size_t width, size_t height,
+                                              double resolution, const double *origins2, ndtgpu_stream stream);
+/* the same on a HOST array of grids, copied into a buffer the handle owns; synchronous */
+ndtgpu_status ndtgpu_scansim_set_grids(ndtgpu_scansim *h, const int8_t *grids, size_t n_grids, size_t width, size_t height, double resolution,
+                                       const double *origins2);
+/* The lattice of grid `grid`.  HOST cs, sn [nyaw] (copied before the call returns), box4 = (x0, y0, x1, y1) or NULL: no box.  DEVICE:
+ * poses_dev capacity x 4 doubles, index_dev capacity uint32 or NULL, count_dev 2 uint32.  Asynchronous on `stream`. */
+ndtgpu_status ndtgpu_scansim_lattice_device(ndtgpu_scansim *h, uint32_t grid, uint32_t skip, const double *cs, const double *sn, size_t nyaw,
+                                            const double *box4, size_t capacity, double *poses_dev, uint32_t *index_dev, uint32_t *count_dev,
+                                            ndtgpu_stream stream);
+/* the same into HOST arrays, synchronous: counts2 and the first counts2[0] rows of poses and index (may be NULL) are written */
+ndtgpu_status ndtgpu_scansim_lattice(ndtgpu_scansim *h, uint32_t grid, uint32_t skip, const double *cs, const double *sn, size_t nyaw,
+                                     const double *box4, size_t capacity, double *poses, uint32_t *index, uint32_t counts2[2]);
+/* The scans of n_poses poses.  DEVICE: poses_dev n_poses x 4; grid_idx_dev n_poses uint32 or NULL: grid 0; count_dev NULL: all rows,
+ * else rows at or beyond count_dev[0] (what _lattice_device wrote) become all-miss scans flagged NDTGPU_SCANSIM_NO_POSE without a walk:
+ * a launch of fixed capacity behind _lattice_device needs no host visit, and the later stages see empty scans, which are never
+ * picked; ranges_dev n_poses x n_beams doubles (the buffer ndtgpu_featbank_extract_device, ndtgpu_scanproj_project_device and
+ * ndtgpu_locmon_evaluate_device read); results_dev n_poses records or NULL.  prm NULL: the defaults.  Asynchronous on `stream`;
+ * NDTGPU_ERR_CAPACITY beyond max_poses; NDTGPU_ERR_INVALID where no grids or no beams are installed. */
+ndtgpu_status ndtgpu_scansim_simulate_device(ndtgpu_scansim *h, const double *poses_dev, const uint32_t *grid_idx_dev, size_t n_poses,
+                                             const uint32_t *count_dev, const ndtgpu_scansim_params *prm, double *ranges_dev,
+                                             ndtgpu_scansim_result *results_dev, ndtgpu_stream stream);
+/* the same on HOST arrays through the handle's pinned staging, synchronous; grid_idx and results may be NULL */
+ndtgpu_status ndtgpu_scansim_simulate(ndtgpu_scansim *h, const double *poses, const uint32_t *grid_idx, size_t n_poses,
+                                      const ndtgpu_scansim_params *prm, double *ranges, ndtgpu_scansim_result *results);
+
 #ifdef __cplusplus
 }
 #endif

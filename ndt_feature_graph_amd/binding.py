@@ -14,7 +14,7 @@ _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hi
             "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndt_pgo_wide.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
             "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip", "ndt_occgrid.hip", "ndtgpu_occgrid.hip", "ndt_linkgate.hip",
             "ndtgpu_linkgate.hip", "ndt_fuserfeat.hip", "ndt_scanproject.hip", "ndtgpu_scanproject.hip",
-            "ndt_calib.hip", "ndtgpu_calib.hip", "ndt_locmon.hip", "ndtgpu_locmon.hip"]
+            "ndt_calib.hip", "ndtgpu_calib.hip", "ndt_locmon.hip", "ndtgpu_locmon.hip", "ndt_scansim.hip", "ndtgpu_scansim.hip"]
 
 STATUS = {0: "OK", -1: "ERR_INVALID", -2: "ERR_HIP", -3: "ERR_NO_DEVICE", -4: "ERR_CAPACITY", -5: "ERR_ALLOC"}
 
@@ -147,6 +147,17 @@ LOCMON_PICK_DTYPE = np.dtype([("pair", "<i4"), ("n_inliers", "<i4"), ("flags", "
 assert LOCMON_QUERY_DTYPE.itemsize == C.sizeof(LocmonQuery) == 40 and LOCMON_RESULT_DTYPE.itemsize == C.sizeof(LocmonResult) == 24
 assert LOCMON_ADJUST_DTYPE.itemsize == C.sizeof(LocmonAdjustResult) == 24 and LOCMON_PICK_DTYPE.itemsize == C.sizeof(LocmonPick) == 16
 
+class ScansimParams(C.Structure):
+    _fields_ = [("range_max", C.c_double), ("miss", C.c_double), ("occupied_min", C.c_int32), ("unknown_is_obstacle", C.c_int32)]
+
+
+class ScansimResult(C.Structure):
+    _fields_ = [("n_hits", C.c_uint32), ("flags", C.c_uint32)]
+
+
+SCANSIM_RESULT_DTYPE = np.dtype([("n_hits", "<u4"), ("flags", "<u4")])
+assert SCANSIM_RESULT_DTYPE.itemsize == C.sizeof(ScansimResult) == 8 and C.sizeof(ScansimParams) == 24
+
 CALIB_RESULT_DTYPE = np.dtype([("score", "<f8"), ("index", "<u4"), ("flags", "<u4"), ("n_skipped", "<u4"), ("reserved", "<u4")])
 assert CALIB_RESULT_DTYPE.itemsize == C.sizeof(CalibResult) == 24
 
@@ -204,7 +215,11 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_locmon_pixel", "ndtgpu_locmon_metres", "ndtgpu_locmon_compose", "ndtgpu_locmon_create", "ndtgpu_locmon_destroy",
            "ndtgpu_locmon_set_beams", "ndtgpu_locmon_set_grids_device", "ndtgpu_locmon_set_grids", "ndtgpu_locmon_field_get",
            "ndtgpu_locmon_evaluate_device", "ndtgpu_locmon_evaluate", "ndtgpu_locmon_adjust_device", "ndtgpu_locmon_adjust",
-           "ndtgpu_locmon_pick_device"]
+           "ndtgpu_locmon_pick_device",
+           "ndtgpu_default_scansim_params", "ndtgpu_scansim_tile", "ndtgpu_scansim_check", "ndtgpu_scansim_reach", "ndtgpu_scansim_skip",
+           "ndtgpu_scansim_cell", "ndtgpu_scansim_beam", "ndtgpu_scansim_headings", "ndtgpu_scansim_create", "ndtgpu_scansim_destroy",
+           "ndtgpu_scansim_set_beams", "ndtgpu_scansim_set_grids_device", "ndtgpu_scansim_set_grids", "ndtgpu_scansim_lattice_device",
+           "ndtgpu_scansim_lattice", "ndtgpu_scansim_simulate_device", "ndtgpu_scansim_simulate"]
 
 _lib = None
 
@@ -443,6 +458,26 @@ def lib():
     L.ndtgpu_locmon_adjust_device.argtypes = [vp, vp, sz, u32, u32, dp, sz, dp, sz, dp, dp, sz, lp, vp, vp, vp]
     L.ndtgpu_locmon_adjust.argtypes = [vp, dp, sz, u32, u32, dp, sz, dp, sz, dp, dp, sz, lp, C.POINTER(LocmonAdjustResult), u32p]
     L.ndtgpu_locmon_pick_device.argtypes = [vp, vp, vp, sz, u32, u32, lp, vp, vp, vp]
+    ssp = C.POINTER(ScansimParams)
+    L.ndtgpu_default_scansim_params.restype = None
+    L.ndtgpu_default_scansim_params.argtypes = [ssp]
+    L.ndtgpu_scansim_tile.restype = u32
+    L.ndtgpu_scansim_tile.argtypes = []
+    L.ndtgpu_scansim_check.argtypes = [sz, sz, sz, C.c_double, sz, C.c_double, C.c_double, sz, ssp]
+    L.ndtgpu_scansim_reach.argtypes = [C.c_double, C.c_double, i32p]
+    L.ndtgpu_scansim_skip.argtypes = [C.c_double, C.c_double, u32p]
+    L.ndtgpu_scansim_cell.argtypes = [C.c_int32, C.c_int32, C.c_int32, i32p]
+    L.ndtgpu_scansim_beam.argtypes = [vp, sz, sz, dp, C.c_double, dp, C.c_double, C.c_double, ssp, dp, i32p, u32p]
+    L.ndtgpu_scansim_headings.argtypes = [C.c_double, C.POINTER(sz), dp, dp, sz]
+    L.ndtgpu_scansim_create.argtypes = [sz, sz, sz, C.POINTER(vp)]
+    L.ndtgpu_scansim_destroy.argtypes = [vp]
+    L.ndtgpu_scansim_set_beams.argtypes = [vp, sz, C.c_double, C.c_double, vp]
+    L.ndtgpu_scansim_set_grids_device.argtypes = [vp, vp, sz, sz, sz, C.c_double, dp, vp]
+    L.ndtgpu_scansim_set_grids.argtypes = [vp, vp, sz, sz, sz, C.c_double, dp]
+    L.ndtgpu_scansim_lattice_device.argtypes = [vp, u32, u32, dp, dp, sz, dp, sz, vp, vp, vp, vp]
+    L.ndtgpu_scansim_lattice.argtypes = [vp, u32, u32, dp, dp, sz, dp, sz, dp, u32p, u32p]
+    L.ndtgpu_scansim_simulate_device.argtypes = [vp, vp, vp, sz, vp, ssp, vp, vp, vp]
+    L.ndtgpu_scansim_simulate.argtypes = [vp, dp, u32p, sz, ssp, dp, vp]
     if hasattr(L, "ndtgpu_live_resources"):            # (NDTGPU_LIB may name a build from before this entry existed)
         L.ndtgpu_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
@@ -2232,6 +2267,181 @@ class LocalizationMonitor(_Handle):
                                                _dev_ptr(ref_poses_t, torch.float64, 4 * n, "LocalizationMonitor.pick_device ref_poses_t") if n
                                                else None, n, int(scan), int(grid), C.byref(p), C.c_void_p(query_t.data_ptr()),
                                                C.c_void_p(pick_t.data_ptr()), _stream_ptr(stream)))
+
+    @staticmethod
+    def read(t, dtype, n=1):
+        """n records of `dtype` from a device tensor (synchronises through the copy to the host)"""
+        import torch
+        return np.frombuffer(t.view(torch.uint8).cpu().numpy().tobytes()[:dtype.itemsize * n], dtype=dtype).copy()
+
+
+SCANSIM_TILE = 256           # ndtgpu_scansim_tile()
+SCANSIM_OFFMAP, SCANSIM_BAD_INDEX, SCANSIM_NO_POSE = 1, 2, 4
+
+
+def scansim_params(**fields):
+    """ndtgpu_default_scansim_params (range_max 10, miss 11, occupied_min 55, unknown_is_obstacle 1) with fields replaced"""
+    return _params(ScansimParams, "ndtgpu_default_scansim_params", "scan-simulation", fields)
+
+
+def scansim_reach(range_max, resolution):
+    """ndtgpu_scansim_reach: R = (int)floor(range_max / resolution), 1 .. 4094"""
+    R = C.c_int32()
+    _check(lib().ndtgpu_scansim_reach(float(range_max), float(resolution), C.byref(R)))
+    return R.value
+
+
+def scansim_skip(ref_pos_resolution, resolution):
+    """ndtgpu_scansim_skip: (unsigned)(ref_pos_resolution / resolution), 1 .. 2^15"""
+    k = C.c_uint32()
+    _check(lib().ndtgpu_scansim_skip(float(ref_pos_resolution), float(resolution), C.byref(k)))
+    return k.value
+
+
+def scansim_cell(di, dj, k):
+    """ndtgpu_scansim_cell -> the cell (a, b) of step k of a ray of (di, dj) cells, relative to its start"""
+    cell = (C.c_int32 * 2)()
+    _check(lib().ndtgpu_scansim_cell(int(di), int(dj), int(k), cell))
+    return cell[0], cell[1]
+
+
+def scansim_beam(grid, origin2, resolution, pose4, cb, sb, **params):
+    """ndtgpu_scansim_beam: one beam on a HOST grid int8 [height, width] -> (range, hit, flags)"""
+    g = np.ascontiguousarray(grid, dtype=np.int8)
+    if g.ndim != 2:
+        raise ValueError("scansim_beam: grid must be [height, width]")
+    o, p4, r = _f64(origin2).reshape(2), _f64(pose4).reshape(4), np.zeros(1)
+    hit, flags = C.c_int32(), C.c_uint32()
+    p = scansim_params(**params)
+    _check(lib().ndtgpu_scansim_beam(C.c_void_p(g.ctypes.data), g.shape[1], g.shape[0], _dp(o), float(resolution), _dp(p4), float(cb), float(sb),
+                                     C.byref(p), _dp(r), C.byref(hit), C.byref(flags)))
+    return float(r[0]), hit.value, flags.value
+
+
+def scansim_headings(angle_step):
+    """ndtgpu_scansim_headings -> (cs [n], sn [n]) of theta = 0, += angle_step while < 6.28"""
+    n = C.c_size_t()
+    _check(lib().ndtgpu_scansim_headings(float(angle_step), C.byref(n), None, None, 0))
+    cs, sn = np.zeros(n.value), np.zeros(n.value)
+    _check(lib().ndtgpu_scansim_headings(float(angle_step), C.byref(n), _dp(cs), _dp(sn), n.value))
+    return cs, sn
+
+
+class ScanSimulator(_Handle):
+    """ndtgpu_scansim: occupancy_grid_utils::simulateRangeScan over installed occupancy grids and the pose lattice of flirtlib_ros'
+    generateRefScans (include/ndtgpu.h "scan simulation")."""
+    _destroy = "ndtgpu_scansim_destroy"
+
+    def __init__(self, max_grids, max_beams, max_poses):
+        h = C.c_void_p()
+        _check(lib().ndtgpu_scansim_create(int(max_grids), int(max_beams), int(max_poses), C.byref(h)))
+        self.h = h
+        self.shape = None
+        self._grids_t = None
+
+    def set_beams(self, n_beams, angle_min, angle_increment, stream=None):
+        _check(lib().ndtgpu_scansim_set_beams(self.h, int(n_beams), float(angle_min), float(angle_increment), _stream_ptr(stream)))
+        self.n_beams = int(n_beams)
+
+    def set_grids(self, grids, resolution, origins):
+        """HOST grids int8 [n_grids, height, width], origins [n_grids, 2].  Synchronous; the handle keeps its own copy."""
+        g = np.ascontiguousarray(grids, dtype=np.int8)
+        if g.ndim != 3:
+            raise ValueError("ScanSimulator.set_grids: grids must be [n_grids, height, width]")
+        o = _f64(origins).reshape(-1, 2)
+        if o.shape[0] != g.shape[0]:
+            raise ValueError("ScanSimulator.set_grids: one origin per grid")
+        _check(lib().ndtgpu_scansim_set_grids(self.h, C.c_void_p(g.ctypes.data), g.shape[0], g.shape[2], g.shape[1], float(resolution), _dp(o)))
+        self.shape = g.shape
+        self._grids_t = None
+
+    def set_grids_device(self, grids_t, resolution, origins, stream=None):
+        """the same on a contiguous int8 device tensor [n_grids, height, width] (what MapSet.occupancy_grid_device writes),
+        asynchronous on `stream`.  The bytes are BORROWED: this object keeps the tensor alive until the next set or close."""
+        import torch
+        if not (grids_t.is_cuda and grids_t.is_contiguous() and grids_t.dtype == torch.int8 and grids_t.dim() == 3):
+            raise ValueError("ScanSimulator.set_grids_device: grids_t must be a contiguous int8 device tensor [n_grids, height, width]")
+        o = _f64(origins).reshape(-1, 2)
+        if o.shape[0] != grids_t.shape[0]:
+            raise ValueError("ScanSimulator.set_grids_device: one origin per grid")
+        n, hgt, wid = (int(v) for v in grids_t.shape)
+        _check(lib().ndtgpu_scansim_set_grids_device(self.h, C.c_void_p(grids_t.data_ptr()), n, wid, hgt, float(resolution), _dp(o),
+                                                     _stream_ptr(stream)))
+        self.shape = (n, hgt, wid)
+        self._grids_t = grids_t
+
+    def close(self):
+        super().close()
+        self._grids_t = None
+
+    @staticmethod
+    def _headings(headings):
+        cs, sn = (_f64(a).reshape(-1) for a in headings)
+        if cs.shape != sn.shape:
+            raise ValueError("ScanSimulator: headings must be (cs [nyaw], sn [nyaw])")
+        return cs, sn
+
+    @staticmethod
+    def _box(box):
+        return None if box is None else _f64(box).reshape(4)
+
+    def lattice(self, skip, headings, capacity, grid=0, box=None, want_index=True):
+        """generateRefScans' lattice into HOST arrays: headings = (cs, sn) of scansim_headings, box = (x0, y0, x1, y1) or None ->
+        dict(poses [written, 4], index uint32 [written] or None, written, passed).  Synchronous."""
+        cs, sn = self._headings(headings)
+        b = self._box(box)
+        poses = np.zeros((int(capacity), 4))
+        index = np.zeros(int(capacity), dtype=np.uint32) if want_index else None
+        counts = (C.c_uint32 * 2)()
+        _check(lib().ndtgpu_scansim_lattice(self.h, int(grid), int(skip), _dp(cs), _dp(sn), cs.shape[0], None if b is None else _dp(b),
+                                            int(capacity), _dp(poses), None if index is None else index.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            counts))
+        n = int(counts[0])
+        return dict(poses=poses[:n], index=None if index is None else index[:n], written=n, passed=int(counts[1]))
+
+    def lattice_device(self, skip, headings, capacity, poses_t, count_t, index_t=None, grid=0, box=None, stream=None):
+        """the same on torch device tensors, asynchronous on `stream`: poses_t float64 [capacity, 4], count_t int32 [2] (read as
+        uint32: written, passed), index_t int32 [capacity] or None"""
+        import torch
+        cs, sn = self._headings(headings)
+        b = self._box(box)
+        _check(lib().ndtgpu_scansim_lattice_device(self.h, int(grid), int(skip), _dp(cs), _dp(sn), cs.shape[0], None if b is None else _dp(b),
+                                                   int(capacity),
+                                                   _dev_ptr(poses_t, torch.float64, 4 * int(capacity), "ScanSimulator.lattice_device poses_t"),
+                                                   _dev_ptr(index_t, torch.int32, int(capacity), "ScanSimulator.lattice_device index_t"),
+                                                   _dev_ptr(count_t, torch.int32, 2, "ScanSimulator.lattice_device count_t"),
+                                                   _stream_ptr(stream)))
+
+    def simulate(self, poses, grid_idx=None, want_results=True, **params):
+        """HOST poses [n, 4] = (x, y, cos, sin), grid_idx [n] or None: grid 0 -> (ranges [n, n_beams], SCANSIM_RESULT_DTYPE [n] or
+        None); keyword arguments: fields of ndtgpu_scansim_params.  Synchronous."""
+        pp = _f64(poses).reshape(-1, 4)
+        n = pp.shape[0]
+        gi = None if grid_idx is None else np.ascontiguousarray(grid_idx, dtype=np.uint32).reshape(-1)
+        if gi is not None and gi.shape[0] != n:
+            raise ValueError("ScanSimulator.simulate: one grid index per pose")
+        ranges = np.zeros((n, getattr(self, "n_beams", 0)))
+        res = np.zeros(n, dtype=SCANSIM_RESULT_DTYPE) if want_results else None
+        p = scansim_params(**params)
+        _check(lib().ndtgpu_scansim_simulate(self.h, _dp(pp), None if gi is None else gi.ctypes.data_as(C.POINTER(C.c_uint32)), n, C.byref(p),
+                                             _dp(ranges), None if res is None else C.c_void_p(res.ctypes.data)))
+        return ranges, res
+
+    def simulate_device(self, poses_t, ranges_t, n_poses=None, grid_idx_t=None, count_t=None, results_t=None, stream=None, **params):
+        """the same on torch device tensors, asynchronous on `stream`: poses_t float64 [n, 4]; ranges_t float64 [n, n_beams]; grid_idx_t
+        int32 [n] or None; count_t int32 [>= 1] or None (rows at or beyond count_t[0] become NO_POSE scans); results_t a contiguous
+        device tensor of 8 bytes a pose or None"""
+        import torch
+        n = int(poses_t.shape[0]) if n_poses is None else int(n_poses)
+        nb = getattr(self, "n_beams", 0)
+        if results_t is not None and not (results_t.is_cuda and results_t.is_contiguous() and results_t.numel() * results_t.element_size() >= 8 * n):
+            raise ValueError("ScanSimulator.simulate_device: results_t must be a contiguous device tensor of 8 bytes a pose")
+        p = scansim_params(**params)
+        _check(lib().ndtgpu_scansim_simulate_device(self.h, _dev_ptr(poses_t, torch.float64, 4 * n, "ScanSimulator.simulate_device poses_t"),
+                                                    _dev_ptr(grid_idx_t, torch.int32, n, "ScanSimulator.simulate_device grid_idx_t"), n,
+                                                    _dev_ptr(count_t, torch.int32, 1, "ScanSimulator.simulate_device count_t"), C.byref(p),
+                                                    _dev_ptr(ranges_t, torch.float64, n * nb, "ScanSimulator.simulate_device ranges_t"),
+                                                    None if results_t is None else C.c_void_p(results_t.data_ptr()), _stream_ptr(stream)))
 
     @staticmethod
     def read(t, dtype, n=1):

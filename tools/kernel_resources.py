@@ -26,7 +26,8 @@ GROUPS = {"pgo_wide": ["ndt_pgo_wide_linearise_kernel", "ndt_pgo_wide_assess_ker
                        "ndt_pgo_wide_node_kernel", "ndt_pgo_wide_step_kernel", "ndt_pgo_wide_update_kernel"],
           "calib": ["ndt_calib_prepare_kernel", "ndt_calib_score_kernel", "ndt_calib_finish_kernel", "ndt_calib_winner_kernel"],
           "locmon": ["ndt_locmon_row_kernel", "ndt_locmon_col_kernel", "ndt_locmon_badness_kernel", "ndt_locmon_finish_kernel",
-                     "ndt_locmon_winner_kernel", "ndt_locmon_pick_kernel"]}
+                     "ndt_locmon_winner_kernel", "ndt_locmon_pick_kernel"],
+          "scansim": ["ndt_scansim_cast_kernel", "ndt_scansim_flag_kernel", "ndt_scansim_scan_kernel", "ndt_scansim_emit_kernel"]}
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
 names = GROUPS.get(flt, [flt])
 for blk in txt.split("- .agpr_count")[1:]:
