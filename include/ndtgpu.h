@@ -2085,6 +2085,127 @@ ndtgpu_status ndtgpu_scansim_simulate_device(ndtgpu_scansim *h, const double *po
 ndtgpu_status ndtgpu_scansim_simulate(ndtgpu_scansim *h, const double *poses, const uint32_t *grid_idx, size_t n_poses,
                                       const ndtgpu_scansim_params *prm, double *ranges, ndtgpu_scansim_result *results);
 
+/* ---- marker export: NDT cell axes, graph links and particles as the points of a LINE_LIST ----------------------------------------------
+ * The reference's publish timer does two things with a map (ndt_feature2d_fuser.cpp:425-433, 448-454): it rasterises it
+ * (toOccupancyGrid: the occupancy-grid export above) and it publishes it as ndt_visualisation::markerNDTCells(...).  markerNDTCells is
+ * the most-called function of the reference's application layer: the 2D fuser node (:425, :448), the 3D fuser node
+ * (ndt_feature_fuser.cpp:253), the MCL node (ndt_feature_mcl_node.cpp:287), ndt_fusion_test.cpp:31, 232-236 and
+ * ndt_feature_pcl_eval.cpp:808-813; markerParticlesNDTMCL3D (mcl node :274) and markerNDTFeatureLinks stand next to it.  Everything
+ * upstream of them lives on the device (fused node maps, assembled worlds, optimised poses, gated links, particle banks); this section
+ * turns it into marker points there: a 3 x 3 symmetric eigendecomposition per Gaussian cell, a threshold per axis, and 0 .. 3 segments a
+ * cell written compacted in a fixed order over all maps of a call, each map under its own pose.
+ * PROVENANCE: restated from ndt_rviz.h:1032-1153, 1163-1233, 1277-1297 and ndt_feature_rviz.h:282-313 of the reference and the call
+ * sites cited above.  No program text of the reference is copied.
+ * Semantics (restated; the order of every fp64 operation -- not contracted -- is written out in csrc/ndt_marker.h, and
+ * tests/marker_model.py restates it: the device's outputs equal the model's bit for bit).
+ *   marker     a LINE_LIST: a list of points, two per segment, three doubles a point (geometry_msgs/Point is float64); scale.x = 0.02.
+ *              A segment is a row of six doubles here: p1, then p2.
+ *   cells      (ndt_rviz.h:1090-1153, 1163-1233) for every Gaussian cell of a map, in the order of the map's cell array (slot order), for
+ *              j = 0, 1, 2 over the eigenvalues in ascending order: skipped if evals(j) < min_eval (0.0001); else offset = evecs.col(j) *
+ *              sqrt(evals(j)), p1 = mean - offset, p2 = mean + offset, emitted as pose * p1, pose * p2 (p1, p2 unchanged with no pose).
+ *              Cells without a Gaussian emit nothing: the cell arrays hold Gaussian cells only.  The segments of a call are in (map,
+ *              cell, axis) order; src[.] = (map index in the set, cell rank in the map) per segment where asked for.
+ *   particles  (ndt_rviz.h:1289-1295) per particle i, in particle order: T.translation() and T * (particle_length, 0, 0) (0.3).
+ *   links      (ndt_feature_rviz.h:294-309) per link, in link order: the translations of pose(ref_idx) and pose(mov_idx); where
+ *              skip_negative (upstream's skipOdom) is set, links with score < 0 are skipped.
+ *   overflow   the link gate's rule: a result larger than `capacity` writes nothing beyond it, the count is still the true count and
+ *              overflow is 1; not an error status.
+ * DEVIATIONS:
+ *   - the eigen-pairs are RECOMPUTED from the stored covariance (NdtCell::cov, already eigen-floored by the build), not kept from
+ *     rescaleCovariance: the cell record carries no eigen-pairs.
+ *   - the solver is a cyclic Jacobi written out in csrc/ndt_marker.h (upstream: Eigen's SelfAdjointEigenSolver); eigenvalues that tie
+ *     keep the order of the Jacobi's diagonal (a stable sort).
+ *   - the SIGN of an eigenvector is fixed: its component of largest magnitude is positive, ties go to the lowest index.  Eigen leaves it
+ *     unspecified; it decides which endpoint is p1.
+ *   - an eigenvalue that is not finite emits nothing and raises NDTGPU_MARKER_NONFINITE in the call's flags (upstream would publish
+ *     sqrt(NaN)).
+ *   - min_eval (0.0001) and the particle length (0.3) are parameters with those defaults.
+ *   - the pose is the upper three rows of a column-major 4 x 4; a point is R p + t, ((R_i0 p0 + R_i1 p1) + R_i2 p2) + t_i as written.
+ *   - a KEPT link whose node index is not a node is refused by the host form and, in the device form, emits nothing and raises
+ *     NDTGPU_MARKER_BAD_INDEX (upstream indexes out of bounds).  A link that skip_negative skips is never looked at, as upstream: its
+ *     indices may be anything.
+ *   - left out: colours, namespaces and ids (host constants: host/ndt_rviz_gpu.h), the ellipsoid visuals of the RViz plugin, pose-arrow,
+ *     interest-point and correspondence markers, colouring by occupancy.
+ * Limits: up to 2^20 maps a call and 5 * 2^20 tiles of 256 cells over them; up to 2^28 links; capacity below 2^32.
+ * Device form (csrc/ndt_marker.hip): plain launches on the caller's stream, no atomics, no workgroup waits on another, no cooperative
+ * launch, no captured graph, no environment switches.  Cells: count (a lane per cell, tiles of 256 cells x maps, the Jacobi in registers,
+ * ndt_block_count), one workgroup's scan of the tile words in (map, tile) order, emit (the eigen-pairs again by the same function,
+ * ndt_block_scan of the lanes' counts plus the tile's base, the lane's segments contiguous).  Links: flag-and-count, the same scan,
+ * emit by ndt_block_rank.  Particles: one launch that reads the bank's poses in place.  The same bytes in any batch, at any `first`,
+ * with any other maps in the call, on any run.
+ * Measured on MI355X (tools/marker_cost.py, library 0.13.0, builder-run; HIP events around the asynchronous call, median of 7 after a
+ * warm-up, min .. max; `no stores`: the same call with capacity 0, every launch and every Jacobi but nothing written).  The replay's
+ * world as one map (24 173 cells, 46 679 segments, with src): 0.032 ms (0.032 .. 0.045; no stores 0.031).  64 node maps under their
+ * poses in one call (11 070 cells, 20 790 segments): 0.044 ms (0.040 .. 0.049; no stores 0.042).  5000 node maps in one call
+ * (1 231 573 cells, 2 315 505 segments, 130 MB written): 1.81 ms (1.80 .. 1.83; no stores 1.81), 1.1 % of the 6.29 TB/s copy ceiling.
+ * Neither the stores nor the per-cell fp64 Jacobi binds: the two small cases are the latency of three launches, and the large one is
+ * the dispatch of its 2 x 80 000 workgroups, 15 of 16 of them empty, because tiles are sized by the set's max_cells (4096) and a node
+ * map holds about 250 cells; a scan of the tile words that needs two barriers instead of 626 moved it from 1.85 to 1.81 ms only.
+ * Against export_cells per map + numpy.linalg.eigh + the loop of ndt_rviz.h in Python on the same box: 95 ms for the world (the loop
+ * over 20 000 cells, SCALED: an extrapolation), 78 ms for the 64 maps, 8.6 s for the 5000 (SCALED the same way) -- 2950, 1770 and 4770
+ * times the device form, 133, 177 and 337 times the host form (0.72 / 0.44 / 25.6 ms, the copy of the points included); the points
+ * agree to 6e-14 m.  The links of 44 486 edges between 5000 nodes (a synthetic list): 0.023 ms (0.021 .. 0.037), with skip_negative
+ * 0.022 ms (29 657 kept), against 0.84 ms of NumPy indexing on the host.  A bank of 64 x 5000 particles: 0.022 ms (0.015 .. 0.039), 33 %
+ * of the copy ceiling over the bytes read and written, against 100 ms for ndtgpu_mcl_particles + NumPy; the same points.
+ * Kernels (tools/kernel_resources.py marker): count 62, scan 18, emit 86, link flag 8, link emit 12, particle 32 VGPRs; no spills, no
+ * scratch; 32 B of LDS each (particle: none). */
+typedef struct ndtgpu_marker ndtgpu_marker;
+typedef struct {
+    double min_eval;                 /* an axis whose eigenvalue is below this emits nothing (0.0001); finite, >= 0 */
+    double particle_length;          /* the length of a particle's segment along its x axis, metres (0.3) */
+    int32_t skip_negative;           /* 1: links with score < 0 are skipped (upstream's skipOdom) (0) */
+    int32_t reserved;
+} ndtgpu_marker_params;
+#define NDTGPU_MARKER_NONFINITE 1u   /* a cell had an eigenvalue that is not finite: that axis emitted nothing */
+#define NDTGPU_MARKER_BAD_INDEX 2u   /* a kept link named a node that is none: it emitted nothing */
+void ndtgpu_default_marker_params(ndtgpu_marker_params *p);
+/* cells, links or particles of one workgroup (256) */
+uint32_t ndtgpu_marker_tile(void);
+/* Pure host, no device needed: the argument checks of a handle (max_maps_per_call, max_links), a cell call (maps [first, first + count) of
+ * n_maps maps of max_cells cells) and a link call (n_nodes, n_links) into `capacity` segments, and of the parameters (NULL: defaults). */
+ndtgpu_status ndtgpu_marker_check(size_t max_maps_per_call, size_t max_links, size_t n_maps, size_t first, size_t count, size_t max_cells,
+                                  size_t n_nodes, size_t n_links, size_t capacity, const ndtgpu_marker_params *prm);
+/* Pure host: the eigen-pairs of cov6 = (xx xy xz yy yz zz) as the kernels compute them: evals3 ascending, V9[3 k + j] component k of the
+ * unit eigenvector of evals3[j] */
+ndtgpu_status ndtgpu_marker_eig3(const double cov6[6], double evals3[3], double V9[9]);
+/* Pure host: the segments of one cell as the kernels compute them.  T16: the map's pose (column-major 4 x 4) or NULL.  seg18: n_seg rows
+ * of (p1, p2), the rest zero; evals3 (may be NULL): the ordered eigenvalues; flags: NDTGPU_MARKER_NONFINITE or 0. */
+ndtgpu_status ndtgpu_marker_cell(const double mean3[3], const double cov6[6], const double *T16, const ndtgpu_marker_params *prm, double seg18[18],
+                                 double evals3[3], uint32_t *n_seg, uint32_t *flags);
+/* A handle owns the tile words and the count words of a selection.  max_maps_per_call: 1 .. 2^20; max_links: 0 .. 2^28. */
+ndtgpu_status ndtgpu_marker_create(size_t max_maps_per_call, size_t max_links, ndtgpu_marker **out);
+ndtgpu_status ndtgpu_marker_destroy(ndtgpu_marker *h);
+/* The cell markers of maps [first, first + count) of `set`, asynchronous on `stream`.  T16_dev: count x 16 doubles, the maps' poses
+ * (column-major), or NULL; points_dev: capacity x 6 doubles; src_dev: capacity x 2 uint32 or NULL.  The counts stay with the handle
+ * (ndtgpu_marker_count).  NDTGPU_ERR_CAPACITY beyond max_maps_per_call. */
+ndtgpu_status ndtgpu_mapset_markers_device(ndtgpu_marker *h, ndtgpu_mapset *set, size_t first, size_t count, const double *T16_dev,
+                                           const ndtgpu_marker_params *prm, double *points_dev, uint32_t *src_dev, size_t capacity,
+                                           ndtgpu_stream stream);
+/* the same with HOST poses in and HOST points out through the handle's pinned staging, synchronous: min(n_segments, capacity) rows are
+ * written; overflow and flags may be NULL */
+ndtgpu_status ndtgpu_mapset_markers(ndtgpu_marker *h, ndtgpu_mapset *set, size_t first, size_t count, const double *T16,
+                                    const ndtgpu_marker_params *prm, double *points, uint32_t *src, size_t capacity, size_t *n_segments,
+                                    int32_t *overflow, uint32_t *flags);
+/* the TRUE number of segments of the handle's last cell or link call, whether it exceeded the capacity, and its flags; waits for the
+ * handle.  overflow and flags may be NULL */
+ndtgpu_status ndtgpu_marker_count(ndtgpu_marker *h, size_t *n_segments, int32_t *overflow, uint32_t *flags);
+/* The link markers of n_links links between n_nodes nodes, asynchronous on `stream`.  T16_nodes_dev: n_nodes x 16 doubles; ref_dev,
+ * mov_dev: n_links uint32; score_dev: n_links doubles or NULL; points_dev: capacity x 6 doubles.  NDTGPU_ERR_CAPACITY beyond max_links. */
+ndtgpu_status ndtgpu_marker_links_device(ndtgpu_marker *h, const double *T16_nodes_dev, size_t n_nodes, const uint32_t *ref_dev,
+                                         const uint32_t *mov_dev, const double *score_dev, size_t n_links, const ndtgpu_marker_params *prm,
+                                         double *points_dev, size_t capacity, ndtgpu_stream stream);
+/* the same on HOST arrays, synchronous; a node index out of range is NDTGPU_ERR_INVALID */
+ndtgpu_status ndtgpu_marker_links(ndtgpu_marker *h, const double *T16_nodes, size_t n_nodes, const uint32_t *ref, const uint32_t *mov,
+                                  const double *score, size_t n_links, const ndtgpu_marker_params *prm, double *points, size_t capacity,
+                                  size_t *n_segments, int32_t *overflow);
+/* The particle markers of filters [first, first + count) of a bank, read in place: count * n_particles rows of points_dev, filters and
+ * particles in order; asynchronous on `stream`, behind the bank's last call.  The call records the BANK's fence on `stream`: the bank's
+ * next update, readback or destroy waits for the marker kernel, so the particles it reads are not overwritten under it. */
+ndtgpu_status ndtgpu_mcl_markers_device(ndtgpu_mcl *mcl, size_t first, size_t count, const ndtgpu_marker_params *prm, double *points_dev,
+                                        ndtgpu_stream stream);
+/* the same into a HOST array, synchronous */
+ndtgpu_status ndtgpu_mcl_markers(ndtgpu_mcl *mcl, size_t first, size_t count, const ndtgpu_marker_params *prm, double *points);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,8 @@ _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hi
             "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndt_pgo_wide.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
             "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip", "ndt_occgrid.hip", "ndtgpu_occgrid.hip", "ndt_linkgate.hip",
             "ndtgpu_linkgate.hip", "ndt_fuserfeat.hip", "ndt_scanproject.hip", "ndtgpu_scanproject.hip",
-            "ndt_calib.hip", "ndtgpu_calib.hip", "ndt_locmon.hip", "ndtgpu_locmon.hip", "ndt_scansim.hip", "ndtgpu_scansim.hip"]
+            "ndt_calib.hip", "ndtgpu_calib.hip", "ndt_locmon.hip", "ndtgpu_locmon.hip", "ndt_scansim.hip", "ndtgpu_scansim.hip",
+            "ndt_marker.hip", "ndtgpu_marker.hip"]
 
 STATUS = {0: "OK", -1: "ERR_INVALID", -2: "ERR_HIP", -3: "ERR_NO_DEVICE", -4: "ERR_CAPACITY", -5: "ERR_ALLOC"}
 
@@ -155,6 +156,12 @@ class ScansimResult(C.Structure):
     _fields_ = [("n_hits", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class MarkerParams(C.Structure):
+    _fields_ = [("min_eval", C.c_double), ("particle_length", C.c_double), ("skip_negative", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(MarkerParams) == 24
+
 SCANSIM_RESULT_DTYPE = np.dtype([("n_hits", "<u4"), ("flags", "<u4")])
 assert SCANSIM_RESULT_DTYPE.itemsize == C.sizeof(ScansimResult) == 8 and C.sizeof(ScansimParams) == 24
 
@@ -219,7 +226,10 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_default_scansim_params", "ndtgpu_scansim_tile", "ndtgpu_scansim_check", "ndtgpu_scansim_reach", "ndtgpu_scansim_skip",
            "ndtgpu_scansim_cell", "ndtgpu_scansim_beam", "ndtgpu_scansim_headings", "ndtgpu_scansim_create", "ndtgpu_scansim_destroy",
            "ndtgpu_scansim_set_beams", "ndtgpu_scansim_set_grids_device", "ndtgpu_scansim_set_grids", "ndtgpu_scansim_lattice_device",
-           "ndtgpu_scansim_lattice", "ndtgpu_scansim_simulate_device", "ndtgpu_scansim_simulate"]
+           "ndtgpu_scansim_lattice", "ndtgpu_scansim_simulate_device", "ndtgpu_scansim_simulate",
+           "ndtgpu_default_marker_params", "ndtgpu_marker_tile", "ndtgpu_marker_check", "ndtgpu_marker_eig3", "ndtgpu_marker_cell",
+           "ndtgpu_marker_create", "ndtgpu_marker_destroy", "ndtgpu_mapset_markers_device", "ndtgpu_mapset_markers", "ndtgpu_marker_count",
+           "ndtgpu_marker_links_device", "ndtgpu_marker_links", "ndtgpu_mcl_markers_device", "ndtgpu_mcl_markers"]
 
 _lib = None
 
@@ -478,6 +488,23 @@ def lib():
     L.ndtgpu_scansim_lattice.argtypes = [vp, u32, u32, dp, dp, sz, dp, sz, dp, u32p, u32p]
     L.ndtgpu_scansim_simulate_device.argtypes = [vp, vp, vp, sz, vp, ssp, vp, vp, vp]
     L.ndtgpu_scansim_simulate.argtypes = [vp, dp, u32p, sz, ssp, dp, vp]
+    mkp = C.POINTER(MarkerParams)
+    L.ndtgpu_default_marker_params.restype = None
+    L.ndtgpu_default_marker_params.argtypes = [mkp]
+    L.ndtgpu_marker_tile.restype = u32
+    L.ndtgpu_marker_tile.argtypes = []
+    L.ndtgpu_marker_check.argtypes = [sz, sz, sz, sz, sz, sz, sz, sz, sz, mkp]
+    L.ndtgpu_marker_eig3.argtypes = [dp, dp, dp]
+    L.ndtgpu_marker_cell.argtypes = [dp, dp, dp, mkp, dp, dp, u32p, u32p]
+    L.ndtgpu_marker_create.argtypes = [sz, sz, C.POINTER(vp)]
+    L.ndtgpu_marker_destroy.argtypes = [vp]
+    L.ndtgpu_mapset_markers_device.argtypes = [vp, vp, sz, sz, vp, mkp, vp, vp, sz, vp]
+    L.ndtgpu_mapset_markers.argtypes = [vp, vp, sz, sz, dp, mkp, dp, u32p, sz, C.POINTER(sz), i32p, u32p]
+    L.ndtgpu_marker_count.argtypes = [vp, C.POINTER(sz), i32p, u32p]
+    L.ndtgpu_marker_links_device.argtypes = [vp, vp, sz, vp, vp, vp, sz, mkp, vp, sz, vp]
+    L.ndtgpu_marker_links.argtypes = [vp, dp, sz, u32p, u32p, dp, sz, mkp, dp, sz, C.POINTER(sz), i32p]
+    L.ndtgpu_mcl_markers_device.argtypes = [vp, sz, sz, mkp, vp, vp]
+    L.ndtgpu_mcl_markers.argtypes = [vp, sz, sz, mkp, dp]
     if hasattr(L, "ndtgpu_live_resources"):            # (NDTGPU_LIB may name a build from before this entry existed)
         L.ndtgpu_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
@@ -768,6 +795,29 @@ class MapSet(_Handle):
             infos[k] = dict(width=rec[k].width, height=rec[k].height, resolution=rec[k].resolution, origin=list(rec[k].origin),
                             n_unknown=rec[k].n_unknown, n_free=rec[k].n_free, n_occupied=rec[k].n_occupied)
         return grid, infos
+
+    def markers(self, first, count, poses=None, marker=None, capacity=None, want_src=True, **params):
+        """ndt_visualisation::markerNDTCells of maps [first, first + count) (ndtgpu_mapset_markers): the axis segments of every
+        Gaussian cell in (map, cell, axis) order, each map under its pose (poses [count, 4, 4] or None) -> (points [n, 2, 3], src
+        uint32 [n, 2] = (map, cell rank) or None, info dict(n_segments, overflow, flags)).  capacity None: three segments a cell.
+        marker: a Marker to reuse (None: one is made for the call).  Keyword arguments: fields of ndtgpu_marker_params.  Synchronous."""
+        first, count = int(first), int(count)
+        own = marker is None
+        if own:
+            marker = Marker(max(count, 1), 0)
+        try:
+            if capacity is None:
+                capacity = 3 * sum(self.num_cells(i) for i in range(first, first + count))
+            return marker.cells(self, first, count, poses=poses, capacity=capacity, want_src=want_src, **params)
+        finally:
+            if own:
+                marker.close()
+
+    def markers_device(self, marker, first, count, points_t, src_t=None, poses_t=None, capacity=None, stream=None, **params):
+        """the same on torch device tensors, asynchronous on `stream` (ndtgpu_mapset_markers_device): points_t float64 [capacity, 6],
+        src_t int32 [capacity, 2] or None (read as uint32), poses_t float64 [count, 16] column-major or None; the counts stay with
+        `marker` (Marker.count)"""
+        marker.cells_device(self, first, count, points_t, src_t=src_t, poses_t=poses_t, capacity=capacity, stream=stream, **params)
 
 
 def derivatives(target, tmap, src_mean, src_cov, n_neighbours=2, compute_hessian=True, lfd1=1.0, lfd2=0.05):
@@ -1161,6 +1211,22 @@ class MCL(_Handle):
         _check(lib().ndtgpu_mcl_particles(self.h, int(first), count, _dp(T), _dp(w), _dp(lik)))
         T = np.transpose(T.reshape(n, 4, 4), (0, 2, 1)).reshape(count, self.n_particles, 4, 4)
         return T, w.reshape(count, self.n_particles), lik.reshape(count, self.n_particles)
+
+    def particle_markers(self, first=0, count=None, out=None, stream=None, **params):
+        """markerParticlesNDTMCL3D of filters [first, first + count) (ndtgpu_mcl_markers): per particle its position and the point
+        particle_length (0.3) along its x axis -> points [count, N, 2, 3].  out: a float64 torch device tensor of count * N * 6
+        elements takes the device form (asynchronous on `stream`) and is returned reshaped."""
+        count = self.n_filters - first if count is None else int(count)
+        p = marker_params(**params)
+        n = count * self.n_particles
+        if out is not None:
+            import torch
+            _check(lib().ndtgpu_mcl_markers_device(self.h, int(first), count, C.byref(p),
+                                                   _dev_ptr(out, torch.float64, 6 * n, "MCL.particle_markers out"), _stream_ptr(stream)))
+            return out.view(-1)[:6 * n].view(count, self.n_particles, 2, 3)
+        pts = np.zeros((max(n, 1), 6))
+        _check(lib().ndtgpu_mcl_markers(self.h, int(first), count, C.byref(p), _dp(pts)))
+        return pts[:n].reshape(count, self.n_particles, 2, 3)
 
     def mean(self, first=0, count=None):
         """pf.getMean() [count, 4, 4] and the last update's records (MCL_RESULT_DTYPE [count])"""
@@ -2482,3 +2548,140 @@ def covariance(target_set, target_idx, source_set, source_idx, T, mode=0, stream
                                          si.ctypes.data_as(C.POINTER(C.c_uint32)), _dp(Tc), n, C.byref(p), int(mode), _dp(cov),
                                          sing.ctypes.data_as(C.POINTER(C.c_int32)), _stream_ptr(stream)))
     return cov, sing
+
+
+MARKER_TILE = 256            # ndtgpu_marker_tile()
+MARKER_NONFINITE, MARKER_BAD_INDEX = 1, 2
+MARKER_SCALE_X = 0.02        # scale.x of the LINE_LIST markers (ndt_rviz.h)
+
+
+def marker_params(**fields):
+    """ndtgpu_default_marker_params (min_eval 0.0001, particle_length 0.3, skip_negative 0) with fields replaced"""
+    return _params(MarkerParams, "ndtgpu_default_marker_params", "marker", fields, hidden=("reserved",))
+
+
+def _cm16(T):
+    """[n, 4, 4] math convention -> [n, 16] column-major"""
+    T = _f64(T).reshape(-1, 4, 4)
+    return np.ascontiguousarray(np.transpose(T, (0, 2, 1))).reshape(-1, 16)
+
+
+def marker_eig3(cov):
+    """ndtgpu_marker_eig3 (host): cov [3, 3] symmetric or [6] = (xx xy xz yy yz zz) -> (evals [3] ascending, V [3, 3], column j the
+    unit eigenvector of evals[j], its largest component positive)"""
+    c = _f64(cov).reshape(-1)
+    if c.shape[0] == 9:
+        c = c[[0, 1, 2, 4, 5, 8]].copy()
+    if c.shape[0] != 6:
+        raise ValueError("marker_eig3: cov must be [3, 3] or [6]")
+    ev, V = np.zeros(3), np.zeros(9)
+    _check(lib().ndtgpu_marker_eig3(_dp(c), _dp(ev), _dp(V)))
+    return ev, V.reshape(3, 3)
+
+
+def marker_cell(mean, cov, pose=None, **params):
+    """ndtgpu_marker_cell (host): the segments of one cell -> (seg [n_seg, 2, 3], evals [3], flags); pose: [4, 4] or None"""
+    m, c = _f64(mean).reshape(3), _f64(cov).reshape(-1)
+    if c.shape[0] == 9:
+        c = c[[0, 1, 2, 4, 5, 8]].copy()
+    if c.shape[0] != 6:
+        raise ValueError("marker_cell: cov must be [3, 3] or [6]")
+    T = None if pose is None else _cm16(pose)
+    seg, ev = np.zeros(18), np.zeros(3)
+    n, flags = C.c_uint32(), C.c_uint32()
+    p = marker_params(**params)
+    _check(lib().ndtgpu_marker_cell(_dp(m), _dp(c), None if T is None else _dp(T), C.byref(p), _dp(seg), _dp(ev), C.byref(n), C.byref(flags)))
+    return seg.reshape(3, 2, 3)[:n.value].copy(), ev, flags.value
+
+
+class Marker(_Handle):
+    """ndtgpu_marker: the tile words and count words of a marker selection (include/ndtgpu.h "marker export")."""
+    _destroy = "ndtgpu_marker_destroy"
+
+    def __init__(self, max_maps_per_call, max_links=0):
+        h = C.c_void_p()
+        _check(lib().ndtgpu_marker_create(int(max_maps_per_call), int(max_links), C.byref(h)))
+        self.h = h
+
+    def count(self):
+        """(n_segments, overflow, flags) of the last cell or link call; waits for the handle"""
+        n, o, f = C.c_size_t(), C.c_int32(), C.c_uint32()
+        _check(lib().ndtgpu_marker_count(self.h, C.byref(n), C.byref(o), C.byref(f)))
+        return int(n.value), bool(o.value), int(f.value)
+
+    def cells(self, map_set, first, count, poses=None, capacity=0, want_src=True, **params):
+        """MapSet.markers with this handle"""
+        first, count, cap = int(first), int(count), int(capacity)
+        T = None
+        if poses is not None:
+            T = _cm16(poses)
+            if T.shape[0] != count:
+                raise ValueError("markers: one pose per map")
+        pts = np.zeros((max(cap, 1), 6))
+        src = np.zeros((max(cap, 1), 2), dtype=np.uint32) if want_src else None
+        n, o, f = C.c_size_t(), C.c_int32(), C.c_uint32()
+        p = marker_params(**params)
+        _check(lib().ndtgpu_mapset_markers(self.h, map_set.h, first, count, None if T is None or count == 0 else _dp(T), C.byref(p),
+                                           _dp(pts) if cap else None,
+                                           src.ctypes.data_as(C.POINTER(C.c_uint32)) if want_src and cap else None, cap, C.byref(n),
+                                           C.byref(o), C.byref(f)))
+        m = min(int(n.value), cap)
+        return (pts[:m].reshape(m, 2, 3), None if src is None else src[:m],
+                dict(n_segments=int(n.value), overflow=bool(o.value), flags=int(f.value)))
+
+    def cells_device(self, map_set, first, count, points_t, src_t=None, poses_t=None, capacity=None, stream=None, **params):
+        """MapSet.markers_device with this handle"""
+        import torch
+        count = int(count)
+        cap = points_t.numel() // 6 if capacity is None else int(capacity)
+        p = marker_params(**params)
+        _check(lib().ndtgpu_mapset_markers_device(self.h, map_set.h, int(first), count,
+                                                  _dev_ptr(poses_t, torch.float64, 16 * count, "markers_device poses_t"), C.byref(p),
+                                                  _dev_ptr(points_t, torch.float64, 6 * cap, "markers_device points_t"),
+                                                  _dev_ptr(src_t, torch.int32, 2 * cap, "markers_device src_t"), cap, _stream_ptr(stream)))
+
+    def links(self, poses, ref, mov, score=None, capacity=None, **params):
+        """markerNDTFeatureLinks on HOST arrays: poses [n_nodes, 4, 4], ref / mov [n_links], score [n_links] or None -> (points [n, 2,
+        3], info dict(n_segments, overflow)); skip_negative=1 skips links with score < 0.  Synchronous."""
+        T = _cm16(poses)
+        r = np.ascontiguousarray(ref, dtype=np.uint32).reshape(-1)
+        m = np.ascontiguousarray(mov, dtype=np.uint32).reshape(-1)
+        if r.shape != m.shape:
+            raise ValueError("link_markers: one ref and one mov index per link")
+        sc = None if score is None else _f64(score).reshape(-1)
+        if sc is not None and sc.shape != r.shape:
+            raise ValueError("link_markers: one score per link")
+        cap = r.shape[0] if capacity is None else int(capacity)
+        pts = np.zeros((max(cap, 1), 6))
+        n, o = C.c_size_t(), C.c_int32()
+        p = marker_params(**params)
+        u32p = C.POINTER(C.c_uint32)
+        _check(lib().ndtgpu_marker_links(self.h, _dp(T) if T.shape[0] else None, T.shape[0], r.ctypes.data_as(u32p), m.ctypes.data_as(u32p),
+                                         None if sc is None else _dp(sc), r.shape[0], C.byref(p), _dp(pts) if cap else None, cap, C.byref(n),
+                                         C.byref(o)))
+        k = min(int(n.value), cap)
+        return pts[:k].reshape(k, 2, 3), dict(n_segments=int(n.value), overflow=bool(o.value))
+
+    def links_device(self, poses_t, ref_t, mov_t, points_t, score_t=None, n_links=None, capacity=None, stream=None, **params):
+        """the same on torch device tensors, asynchronous on `stream`: poses_t float64 [n_nodes, 16] column-major, ref_t / mov_t int32
+        (read as uint32), score_t float64 or None, points_t float64 [capacity, 6]; the counts stay with the handle (count())"""
+        import torch
+        n_nodes = poses_t.numel() // 16
+        m = ref_t.numel() if n_links is None else int(n_links)
+        cap = points_t.numel() // 6 if capacity is None else int(capacity)
+        p = marker_params(**params)
+        _check(lib().ndtgpu_marker_links_device(self.h, _dev_ptr(poses_t, torch.float64, 16 * n_nodes, "links_device poses_t"), n_nodes,
+                                                _dev_ptr(ref_t, torch.int32, m, "links_device ref_t"),
+                                                _dev_ptr(mov_t, torch.int32, m, "links_device mov_t"),
+                                                _dev_ptr(score_t, torch.float64, m, "links_device score_t"), m, C.byref(p),
+                                                _dev_ptr(points_t, torch.float64, 6 * cap, "links_device points_t"), cap, _stream_ptr(stream)))
+
+
+def link_markers(poses, ref, mov, score=None, capacity=None, **params):
+    """Marker.links with a handle made for the call"""
+    n = int(np.asarray(ref).size)
+    mk = Marker(1, max(n, 1))
+    try:
+        return mk.links(poses, ref, mov, score=score, capacity=capacity, **params)
+    finally:
+        mk.close()

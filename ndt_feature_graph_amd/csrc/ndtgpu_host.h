@@ -389,4 +389,15 @@ bool invert6(const double *A, double *inv);
 // the device form of a call's match parameters, checked (every matcher entry, the registrar)
 ndtgpu_status match_params_dev(const ndtgpu_match_params *prm, int fusion_flags, NdtMatchParamsDev &p);
 
+// ndtgpu_mcl.hip
+// the particle poses (twelve doubles each: rotation row-major, translation) of filters [first, first + count) of a bank, in place,
+// with the fence its calls record and the stream of its synchronous entries: what ndtgpu_marker.hip reads of a bank
+struct MclParticles {
+    const rigid *T;
+    size_t n;
+    Fence *used;
+    hipStream_t hst;
+};
+ndtgpu_status mcl_particles_view(ndtgpu_mcl *h, size_t first, size_t count, const char *who, MclParticles &out);
+
 #pragma GCC visibility pop

@@ -325,3 +325,15 @@ ndtgpu_status ndtgpu_mcl_mean(ndtgpu_mcl *h, size_t first, size_t count, double 
 }
 
 }   // extern "C"
+
+// the particle poses of filters [first, first + count) in place, for the marker export (ndtgpu_marker.hip)
+ndtgpu_status mcl_particles_view(ndtgpu_mcl *h, size_t first, size_t count, const char *who, MclParticles &out)
+{
+    const ndtgpu_status rc = mcl_range(h, first, count, who);
+    if (rc != NDTGPU_OK) return rc;
+    out.T = h->T + first * h->N;
+    out.n = count * h->N;
+    out.used = &h->used;
+    out.hst = h->hst.get();
+    return NDTGPU_OK;
+}

@@ -84,8 +84,31 @@ public:
     int getN() const { return n_; }
     void setN(int n) { n_ = n; }
     int idx[3] = {0, 0, 0};   // LazyGrid cell index (cells read from a map)
+    // NDTCell::getEvals / getEvecs: the eigen-pairs of the covariance as the marker export computes them (ndtgpu_marker_eig3, pure
+    // host: ascending, column j of getEvecs() the unit eigenvector of getEvals()(j), its largest component positive).  RECOMPUTED
+    // from getCov() at every call: upstream keeps them from rescaleCovariance.
+    Eigen::Vector3d getEvals() const
+    {
+        double ev[3], V[9];
+        eig(ev, V);
+        return Eigen::Vector3d(ev[0], ev[1], ev[2]);
+    }
+    Eigen::Matrix3d getEvecs() const
+    {
+        double ev[3], V[9];
+        eig(ev, V);
+        Eigen::Matrix3d E;
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 3; c++) E(r, c) = V[3 * r + c];
+        return E;
+    }
 
 private:
+    void eig(double ev[3], double V[9]) const
+    {
+        const double c6[6] = {cov_(0, 0), cov_(0, 1), cov_(0, 2), cov_(1, 1), cov_(1, 2), cov_(2, 2)};
+        ndtgpu_host::check(ndtgpu_marker_eig3(c6, ev, V), "ndtgpu_marker_eig3");
+    }
     Eigen::Vector3d mean_;
     Eigen::Matrix3d cov_;
     int n_ = 0;

@@ -27,7 +27,9 @@ GROUPS = {"pgo_wide": ["ndt_pgo_wide_linearise_kernel", "ndt_pgo_wide_assess_ker
           "calib": ["ndt_calib_prepare_kernel", "ndt_calib_score_kernel", "ndt_calib_finish_kernel", "ndt_calib_winner_kernel"],
           "locmon": ["ndt_locmon_row_kernel", "ndt_locmon_col_kernel", "ndt_locmon_badness_kernel", "ndt_locmon_finish_kernel",
                      "ndt_locmon_winner_kernel", "ndt_locmon_pick_kernel"],
-          "scansim": ["ndt_scansim_cast_kernel", "ndt_scansim_flag_kernel", "ndt_scansim_scan_kernel", "ndt_scansim_emit_kernel"]}
+          "scansim": ["ndt_scansim_cast_kernel", "ndt_scansim_flag_kernel", "ndt_scansim_scan_kernel", "ndt_scansim_emit_kernel"],
+          "marker": ["ndt_marker_count_kernel", "ndt_marker_scan_kernel", "ndt_marker_emit_kernel", "ndt_marker_link_flag_kernel",
+                     "ndt_marker_link_emit_kernel", "ndt_marker_particle_kernel"]}
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
 names = GROUPS.get(flt, [flt])
 for blk in txt.split("- .agpr_count")[1:]:
