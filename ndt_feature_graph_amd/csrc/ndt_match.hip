@@ -45,7 +45,8 @@ __device__ long long g_solver_prof[16];
 
 namespace {
 
-// How many of the NDT_VW shares of an evaluation hold cells (the others deliver rows of zeros): a property of the source map alone.
+// How many of the NDT_VW shares of an evaluation hold cells: a property of the source map alone.  Only these are handed out as
+// tickets; the rows of the others stay the zeros the slot was loaded with (MatchSlot::first).
 // Maps of 257..448 cells -- the bench's halls hold 372 -- are dealt to 5..7 shares of 52..64 cells instead of eight at 32..56 of
 // the 64 lanes: TRANSFORM, PROBE, the hit list and the wave sum are paid per share, and the pair terms of a share come in batches
 // of 64 (eight shares of 238 terms: 32 batches, six of 318: 30).  Round 6, measured (bench, 100 steps): 642 k -> 664-671 k
@@ -982,8 +983,13 @@ struct MatchSlot {
     double part[NDT_VW * 32];       // the shares' partial sums
     double sums[32];                // the evaluation's result
     unsigned state;                 // SLOT_*
-    unsigned next;                  // next share to hand out (>= NDT_VW: none)
-    unsigned done;                  // shares delivered
+    // An evaluation hands out the tickets [first, NDT_VW), first = NDT_VW - ndt_shares_of(source cells): ticket t is share
+    // t - first.  `next` and `done` both start an evaluation at `first`, so "no ticket left" and "last delivery" are the same
+    // comparisons with NDT_VW for every map size.  Rows [NDT_VW - first, NDT_VW) of `part` belong to no share: they are zeroed
+    // when the slot is loaded (slot_set_shares) and nothing writes them while the registration runs.
+    unsigned next;                  // next ticket to hand out (>= NDT_VW: none)
+    unsigned done;                  // first + shares delivered
+    unsigned first;
     unsigned session;               // names the registration (key of the hit lists)
     unsigned pair;
     unsigned retry;                 // shader clock (low word) before which a FREE slot is not looked at again
@@ -1019,11 +1025,7 @@ NDT_D void run_share(MatchSlot<QL> &S, unsigned v, double *wsrc, uint2 *wwin, do
 #pragma unroll
     for (int k = 0; k < NACC; k++) w.acc[k] = 0.0;
     const int msrc = S.sv.n_cells;
-    const unsigned nsh = ndt_shares_of(msrc);
-    if (v >= nsh) {                                              // (a share without cells: a row of zeros, no butterfly)
-        if (lane < 29u) S.part[v * 32 + lane] = 0.0;
-        return;
-    }
+    const unsigned nsh = ndt_shares_of(msrc);                    // (v < nsh: shares without cells get no ticket)
     const unsigned key = msrc <= 64 * (int)nsh ? S.session : 0u;   // a share remembers the hit list of ONE group
     for (int base = (int)v; base < msrc; base += 64 * (int)nsh)
         eval_group<NN, WITH_H, QL, false, false, PLANAR>(w, S.tg, S.sv.cells, base, (int)nsh, msrc, S.st.Teval, lfd1, lfd2, key);
@@ -1036,11 +1038,11 @@ NDT_D void run_share(MatchSlot<QL> &S, unsigned v, double *wsrc, uint2 *wwin, do
 #endif
 }
 
+// pose and result record of slot S's registration to `pose16` and `o` (global memory, or the stream-fed form's staging area)
 template <int QL>
-NDT_D void slot_result(const MatchSlot<QL> &S, double *T16, NdtMatchResultDev *res)
+NDT_D void slot_result_to(const MatchSlot<QL> &S, double *pose16, NdtMatchResultDev &o)
 {
-    NdtMatchResultDev &o = res[S.pair];
-    match_state_result(S.st, T16 + (size_t)S.pair * 16, o);
+    match_state_result(S.st, pose16, o);
     o.n_source = S.sv.n_cells;
     o.n_target = S.tg.n_cells;
     o.cycles_eval = (long long)(S.cnt[0] / NDT_MATCH_WAVES);    // CU-time: wave cycles / waves of a CU
@@ -1050,6 +1052,19 @@ NDT_D void slot_result(const MatchSlot<QL> &S, double *T16, NdtMatchResultDev *r
 #ifdef NDT_MATCH_TL
     o.pair_terms_g = (long long)S.wall;      // timeline builds: wall clocks of the evaluations instead
 #endif
+}
+template <int QL>
+NDT_D void slot_result(const MatchSlot<QL> &S, double *T16, NdtMatchResultDev *res)
+{
+    slot_result_to(S, T16 + (size_t)S.pair * 16, res[S.pair]);
+}
+// the record of a registration that never ran (exit_code -2: map index out of range, -3: a map needed more cells than max_cells;
+// converged = 0, the pose is left untouched)
+NDT_D void result_not_run(NdtMatchResultDev &o, int exit_code)
+{
+    o.converged = 0; o.iterations = 0; o.fevals = 0; o.exit_code = exit_code;
+    o.score = 0.0; o.n_source = 0; o.n_target = 0;
+    o.cycles_eval = 0; o.cycles_solver = 0; o.pair_terms_g = 0; o.pair_terms_h = 0;
 }
 
 // NDTMatcherFeatureD2D::derivativesNDT: the pair terms of the n <= 64 correspondences, source cells moved by T
@@ -1253,19 +1268,19 @@ __attribute__((noinline)) NDT_D void slot_cov_jtj(MatchSlot<QL> &S, double lfd1,
 
 // The covariance tail of a registration (phase PH_COV), run by the wave that delivered the last share of the evaluation with
 // the Hessian at the final pose (S.sums): the J^T J pass, then on lane 0 the Gauss-Jordan of cov_from_sums, the flags --
-// POSE_UNCHANGED compares with the initial guess still at T16 -- and the registration is done again (the caller writes pose and
-// result and releases the slot).  All lanes.
+// POSE_UNCHANGED compares with the initial guess still at pose16 -- and the registration is done again (the caller writes pose and
+// result and releases the slot).  out36 / out_flags: this registration's entries (global memory, or the stream-fed form's staging
+// area).  All lanes.
 template <int QL>
-NDT_D void slot_covariance(MatchSlot<QL> &S, double lfd1, double lfd2, const CovOut &co, const double *T16)
+NDT_D void slot_covariance(MatchSlot<QL> &S, double lfd1, double lfd2, int mode, double *out36, int *out_flags, const double *pose16)
 {
     const unsigned lane = threadIdx.x & 63u;
-    slot_cov_jtj(S, lfd1, lfd2, co.mode);
+    slot_cov_jtj(S, lfd1, lfd2, mode);
     ndt_wave_sync();
     if (lane == 0) {
-        const unsigned pair = S.pair;
-        const int singular = cov_from_sums(S.sums + 7, S.part, S.part + 32, S.part + 104, co.cov36 + (size_t)pair * 36);
-        const int unchanged = match_state_pose_unchanged(S.st, T16 + (size_t)pair * 16);
-        co.flags[pair] = (singular ? COV_SINGULAR : 0) | (unchanged ? COV_POSE_UNCHANGED : 0);
+        const int singular = cov_from_sums(S.sums + 7, S.part, S.part + 32, S.part + 104, out36);
+        const int unchanged = match_state_pose_unchanged(S.st, pose16);
+        *out_flags = (singular ? COV_SINGULAR : 0) | (unchanged ? COV_POSE_UNCHANGED : 0);
         S.st.done = 1;
     }
     ndt_wave_sync();
@@ -1274,6 +1289,19 @@ NDT_D void slot_covariance(MatchSlot<QL> &S, double lfd1, double lfd2, const Cov
 NDT_D unsigned lds_load(const unsigned *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 NDT_D void lds_store(unsigned *p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 NDT_D unsigned clock_lo() { return (unsigned)__builtin_readcyclecounter(); }
+
+// A slot was loaded (S.sv is set): its ticket range, and zeros in the rows of S.part that no share of this registration writes
+// -- the sum over all NDT_VW rows in share order adds them as the +0.0 rows the empty shares used to deliver, bit for bit.  (The
+// slot's last registration may have written them: an eight-share map, or the scratch of its covariance tail.)  All lanes,
+// before the slot is published as SLOT_RUN.
+template <int QL>
+NDT_D void slot_set_shares(MatchSlot<QL> &S)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned nsh = ndt_shares_of(S.sv.n_cells);
+    for (unsigned k = nsh * 32u + lane; k < (unsigned)NDT_VW * 32u; k += 64u) S.part[k] = 0.0;
+    if (lane == 0) { S.first = (unsigned)NDT_VW - nsh; S.done = S.first; }
+}
 }  // namespace
 
 // COV = 1: the registrar's covariance entries -- every registration ends with its covariance tail (PH_COV, slot_covariance)
@@ -1368,10 +1396,10 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
 
         if (task >= TASK_LOAD) {
             // ---- fill a slot: the ticket drawn while parking, else a fresh pair, else a parked registration ----
+            const unsigned s = (unsigned)(task - TASK_LOAD);
+            Slot &S = slots[s];
+            unsigned new_state = SLOT_BUSY;
             if (lane == 0) {
-                const unsigned s = (unsigned)(task - TASK_LOAD);
-                Slot &S = slots[s];
-                unsigned new_state = SLOT_BUSY;
                 while (new_state == SLOT_BUSY) {
                     int job = S.preset;         // >= 0: fresh pair, <= -2: resume parked pair (-2 - pair), -1: none
                     S.preset = -1;
@@ -1412,11 +1440,7 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
                     const bool bad_index = ti >= tset.n_maps || si >= sset.n_maps;
                     const bool truncated = !bad_index && (tset.counters[ti].overflow != 0u || sset.counters[si].overflow != 0u);
                     if (bad_index || truncated) {
-                        NdtMatchResultDev *o = res + pair;      // (converged = 0; the pose is left untouched)
-                        o->converged = 0; o->iterations = 0; o->fevals = 0;
-                        o->exit_code = bad_index ? -2 : -3;     // -2 map index out of range, -3 a map needed more cells than max_cells
-                        o->score = 0.0; o->n_source = 0; o->n_target = 0;
-                        o->cycles_eval = 0; o->cycles_solver = 0; o->pair_terms_g = 0; o->pair_terms_h = 0;
+                        result_not_run(res[pair], bad_index ? -2 : -3);
                         continue;
                     }
                     S.tg = map_view(tset, ti);
@@ -1443,17 +1467,23 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
                     S.resumed = resumed ? 1 : 0;
                     S.session = atomicAdd(&s_session, 1u) + 1u;      // (a workgroup never sees 2^32 registrations)
                     S.with_h = S.st.with_h;
-                    S.done = 0u;
                     if (resumed) atomicAdd(&s_resumed, 1u);
                     new_state = SLOT_RUN;
                 }
+            }
+            new_state = (unsigned)__builtin_amdgcn_readfirstlane((int)new_state);
+            if (new_state == SLOT_RUN) {
+                ndt_wave_sync();
+                slot_set_shares(S);
+            }
+            if (lane == 0) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 if (new_state == SLOT_RUN) {
 #ifdef NDT_MATCH_TL
                     S.t_pub = __builtin_readcyclecounter(); if (!S.resumed) S.wall = 0ull;
 #endif
                     lds_store(&S.state, SLOT_RUN);
-                    lds_store(&S.next, 0u);
+                    lds_store(&S.next, S.first);
                 } else {
                     if (new_state == SLOT_FREE) lds_store(&S.retry, clock_lo() + 2048u);
                     else atomicAdd(&s_closed, 1u);
@@ -1466,8 +1496,8 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
         // ---- one share of an evaluation ---------------------------------------------------------------------------
         Slot &S = slots[task >> 4];
         {
-            const unsigned v = (unsigned)task & 15u;
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");     // the request was published before `next`
+            const unsigned v = ((unsigned)task & 15u) - S.first;
             const long long c0 = __builtin_readcyclecounter();
             const int with_h = S.with_h;
             // (NDTMatcherD2D_2D without the Tikhonov term: the planar pair term, see pair_term)
@@ -1500,7 +1530,8 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
         const long long c1 = __builtin_readcyclecounter();
         bool cov_eval = false;
         if constexpr (COV != 0) cov_eval = S.st.phase == PH_COV;
-        if (cov_eval) slot_covariance(S, s_prm.lfd1, s_prm.lfd2, co, T16);
+        if (cov_eval)
+            slot_covariance(S, s_prm.lfd1, s_prm.lfd2, co.mode, co.cov36 + (size_t)S.pair * 36, co.flags + S.pair, T16 + (size_t)S.pair * 16);
         else slot_step(S, s_prm);
         ndt_wave_sync();
         if (lane == 0) {
@@ -1535,7 +1566,7 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
                     __hip_atomic_store(&ids[slot], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
-            lds_store(&S.done, 0u);
+            lds_store(&S.done, S.first);
             if (release) {
                 if (S.resumed) atomicSub(&s_resumed, 1u);
                 lds_store(&S.retry, clock_lo());
@@ -1547,7 +1578,7 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
                 S.t_pub = __builtin_readcyclecounter();
 #endif
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                lds_store(&S.next, 0u);
+                lds_store(&S.next, S.first);
             }
         }
     }
@@ -1566,8 +1597,9 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
 //     instance launch on the matcher stream (it starts when the running one has ended, or finds its batch taken and leaves).
 //   * Memory: the maps of a batch are written by build kernels that have ENDED (stream order) before the batch is published;
 //     a slot that moves to a new batch does a system-scope acquire (L1 / L2 invalidate: the map set of a ring entry is reused
-//     every `depth` batches, stale lines may be cached).  Poses and results are written back with a system-scope release before
-//     a registration is counted as done; queue words are system-scope atomics.
+//     every `depth` batches, stale lines may be cached).  Poses and results are written THROUGH by the wave that finished the
+//     registration, and have arrived before it is counted as done (stream_write_out); the finisher that completes a batch does
+//     the batch's one system-scope release; queue words are system-scope atomics.
 //   * A registration's arithmetic is that of ndt_match_kernel -- same shares, same order of sums: the same bits.
 //   * Two registrations per workgroup, as above.  Measured with three (half the hit list each): best 562 k registrations/s at 128
 //     workgroups against 578 k with two at 144 (100 steps of the bench).
@@ -1644,6 +1676,68 @@ struct StreamSlotExt {               // what a slot of the stream-fed matcher kn
     unsigned worked;                 // this slot has run a registration
     unsigned dry_since;              // 100 MHz clock (low word) when the slot first found everything complete (0: not dry)
 };
+
+// ---- how a finished registration's outputs reach memory ---------------------------------------------------------------------
+// Earlier, lane 0 wrote pose and result with plain stores and made them visible with a system-scope release fence per
+// registration: on gfx950 a write-back of the XCD's WHOLE L2 (also the dirty lines of the build workgroups resident there), waited
+// for by the wave that holds the slot -- 1024 of them per batch for 192 bytes each (measured: DESIGN 4.2, "The stream-fed
+// matcher's cache maintenance").  Now the outputs are put together in LDS -- in the slot's hit list, which nobody reads once
+// the registration is done (the next registration of the slot has another session key) -- and the wave copies them out one
+// 8-byte word per lane with system-scope atomic stores: these write THROUGH the L2, 24 (with a covariance 61) independent
+// stores in flight at once and not a chain of round trips from one lane (round 5).  Layout of the staging area in 8-byte words:
+enum { ST_POSE = 0, ST_RES = 16, ST_COV = 24, ST_FLAGS = 60, ST_WORDS = 61 };
+static_assert(sizeof(NdtMatchResultDev) == 8 * (ST_COV - ST_RES), "the result record is copied out as eight 8-byte words");
+template <int QL>
+NDT_D unsigned long long *slot_stage(MatchSlot<QL> &S)
+{
+    static_assert(offsetof(MatchSlot<QL>, queue) % 8 == 0 && sizeof(S.queue) >= 8 * ST_WORDS, "staging area in the hit list");
+    return reinterpret_cast<unsigned long long *>(S.queue);
+}
+// All lanes of the wave that staged the outputs of slot S (lane 0 did; the caller has put a wave sync in between).  with_pose: the
+// registration ran (one that was refused in the loader leaves its pose untouched); with_cov: its covariance entries were staged.
+// ORDERING.  On return every store of this wave has COMPLETED (s_waitcnt vmcnt(0)): the caller's done_ctr increment comes after
+// them.  That "completed" means "in memory, visible to every XCD and to the host" rests on the hardware, not on the language
+// memory model: a system-scope atomic store is a write-through store (sc0 sc1) whose acknowledgement the wait counts, while to
+// the memory model a relaxed store followed by a workgroup-scope release orders nothing for an observer outside the workgroup.
+// The model's guarantee comes once per batch: the finisher that completes a batch does a system-scope release before it
+// publishes done_seq / completed, and whoever waits for those starts a new kernel (or copy) behind the wait kernel.
+template <int QL>
+NDT_D void stream_write_out(MatchSlot<QL> &S, const StreamSlotExt &E, const CovOut *co, bool with_pose, bool with_cov)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned long long *w = slot_stage(S);
+    const unsigned pair = S.pair;
+    if (lane < (unsigned)ST_COV && (with_pose || lane >= (unsigned)ST_RES)) {
+        unsigned long long *dst = lane < (unsigned)ST_RES ? reinterpret_cast<unsigned long long *>(E.T16 + (size_t)pair * 16) + lane
+                                                          : reinterpret_cast<unsigned long long *>(E.res + pair) + (lane - (unsigned)ST_RES);
+        __hip_atomic_store(dst, w[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (with_cov) {
+        if (lane < 36u)
+            __hip_atomic_store(reinterpret_cast<unsigned long long *>(co->cov36 + (size_t)pair * 36) + lane, w[ST_COV + lane],
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        else if (lane == 36u)
+            __hip_atomic_store(co->flags + pair, (int)w[ST_FLAGS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    // (the wait as an asm statement: the compiler cannot drop or move it; the fence keeps ITS memory operations in order)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+}
+// Lane 0, after stream_write_out: the registration counts as done; the one that completes its batch publishes the batch.
+NDT_D void stream_count_done(NdtStreamQueue *q, const StreamSlotExt &E, unsigned ring)
+{
+    const unsigned d = __hip_atomic_fetch_add(E.done_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (d + 1u != E.n_pairs) return;
+    // (a complete batch has no tickets left: nobody looks at its ring entry again, it may be re-published)
+    __hip_atomic_fetch_max(&q->first_open, E.seq + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    q->stamp[E.seq % NDT_STREAM_STAMPS][1] = wall_clock64();
+    // the one system-scope release of a batch (the stamp; and the model's release for the outputs, see above).  The outputs
+    // other workgroups wrote through were complete before their increments, which this one has observed.
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    sys_store(&q->done_seq[E.seq % ring], E.seq + 1u);
+    __hip_atomic_fetch_add(&q->completed, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 }  // namespace
 
 // 256 threads.  Every result of the batch starts as "not run" (exit_code -4, converged 0): a batch that an abort cuts short
@@ -1806,11 +1900,16 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
 
         if (task >= TASK_LOAD) {
             // ---- fill a slot: the next ticket of the slot's batch, else of the next published batch ------------------------
-            if (lane == 0) {
-                const unsigned s = (unsigned)(task - TASK_LOAD);
-                Slot &S = slots[s];
-                StreamSlotExt &E = ext[s];
-                unsigned new_state = SLOT_BUSY;
+            // (lane 0 draws; a registration that ends in the loader -- SLOT_ENDED, below -- is written out by the whole wave like
+            //  any other, then lane 0 draws again)
+            const unsigned s = (unsigned)(task - TASK_LOAD);
+            Slot &S = slots[s];
+            StreamSlotExt &E = ext[s];
+            enum { SLOT_ENDED = 0x10, SLOT_ENDED_POSE = 0x11 };      // new_state only: refused / finished before its first evaluation
+            unsigned new_state = SLOT_BUSY;
+            for (;;) {
+              if (lane == 0) {
+                new_state = SLOT_BUSY;
                 while (new_state == SLOT_BUSY) {
                     unsigned c = E.cur;
                     // (the queue words in ONE round trip: system-scope loads are issued in program order and waited for where
@@ -1870,8 +1969,13 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
                     c = bseq; E.cur = c;
                     // ONE acquire per workgroup and batch (batches are taken in order: whoever of the workgroup's slots reaches
                     // batch c first does it -- the invalidate also drops the maps its XCD's other registrations are reading)
+                    // (Measured away -- -DNDT_STREAM_ABL_NOACQ, stale maps, timing only: 1.353 against 1.360 ms per
+                    //  step over 1000 steps of the bench, nothing in 100; one invalidate per XCD and batch instead of one per
+                    //  workgroup could only gain less than that and was not built.  DESIGN 4.2.)
                     if ((int)(lds_load(&s_seen) - (c + 1u)) < 0) {
+#ifndef NDT_STREAM_ABL_NOACQ
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");      // (system scope: this CU's L1, this XCD's L2)
+#endif
                         lds_store(&s_seen, c + 1u);
                     }
                     E.prm.n_neighbours = d_nn; E.prm.itr_max = d_itr; E.prm.step_control = d_sc;
@@ -1881,43 +1985,46 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
                     E.T16 = d_T16; E.res = d_res; E.done_ctr = &B->done; E.n_pairs = n; E.seq = c;
                     if constexpr (COV != 0) cext[s] = d_co;
                     const unsigned pair = f, ti = f, si = n + f;
-                    bool finished = false;
+                    S.pair = pair;
+                    unsigned long long *const stage = slot_stage(S);
+                    NdtMatchResultDev &stage_res = *reinterpret_cast<NdtMatchResultDev *>(stage + ST_RES);
                     if (B->set.counters[ti].overflow != 0u || B->set.counters[si].overflow != 0u) {
-                        NdtMatchResultDev *o = E.res + pair;            // (converged = 0; the pose is left untouched)
-                        o->converged = 0; o->iterations = 0; o->fevals = 0; o->exit_code = -3;
-                        o->score = 0.0; o->n_source = 0; o->n_target = 0;
-                        o->cycles_eval = 0; o->cycles_solver = 0; o->pair_terms_g = 0; o->pair_terms_h = 0;
-                        finished = true;
-                    } else {
-                        S.tg = map_view(B->set, ti);
-                        S.sv = map_view(B->set, si);
-                        S.pair = pair;
-                        match_state_init(S.st, E.T16 + (size_t)pair * 16, E.prm, nullptr);
-                        S.cnt[0] = S.cnt[1] = S.cnt[2] = S.cnt[3] = 0ull;
-                        if (S.st.done) { slot_result(S, E.T16, E.res); finished = true; }   // parameters the solver rejects
+                        result_not_run(stage_res, -3);                  // (the pose is left untouched)
+                        new_state = SLOT_ENDED;
+                        break;
                     }
-                    if (finished) {
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-                        const unsigned d = __hip_atomic_fetch_add(E.done_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        if (d + 1u == n) {
-                            __hip_atomic_fetch_max(&q->first_open, c + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                            q->stamp[c % NDT_STREAM_STAMPS][1] = wall_clock64();
-                            sys_store(&q->done_seq[c % ring], c + 1u);
-                            __hip_atomic_fetch_add(&q->completed, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        }
-                        continue;
+                    S.tg = map_view(B->set, ti);
+                    S.sv = map_view(B->set, si);
+                    match_state_init(S.st, E.T16 + (size_t)pair * 16, E.prm, nullptr);
+                    S.cnt[0] = S.cnt[1] = S.cnt[2] = S.cnt[3] = 0ull;
+                    if (S.st.done) {                                    // parameters the solver rejects
+                        slot_result_to(S, reinterpret_cast<double *>(stage + ST_POSE), stage_res);
+                        new_state = SLOT_ENDED_POSE;
+                        break;
                     }
                     S.st.use_feat = 0; S.st.ls_joint = 0;
                     E.worked = 1u; E.dry_since = 0u;
                     S.session = atomicAdd(&s_session, 1u) + 1u;
                     S.with_h = S.st.with_h;
-                    S.done = 0u;
                     new_state = SLOT_RUN;
                 }
+              }
+              new_state = (unsigned)__builtin_amdgcn_readfirstlane((int)new_state);
+              if (new_state != (unsigned)SLOT_ENDED && new_state != (unsigned)SLOT_ENDED_POSE) break;
+              // (covariance entries of such a registration stay what the publish kernel wrote: zeros, NOT_COMPUTED)
+              ndt_wave_sync();
+              stream_write_out(S, E, nullptr, new_state == (unsigned)SLOT_ENDED_POSE, false);
+              if (lane == 0) stream_count_done(q, E, ring);
+            }
+            if (new_state == SLOT_RUN) {
+                ndt_wave_sync();
+                slot_set_shares(S);
+            }
+            if (lane == 0) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 if (new_state == SLOT_RUN) {
                     lds_store(&S.state, SLOT_RUN);
-                    lds_store(&S.next, 0u);
+                    lds_store(&S.next, S.first);
                 } else {
                     if (new_state == SLOT_FREE) lds_store(&S.retry, clock_lo() + (unsigned)NDT_STREAM_RETRY);
                     else atomicAdd(&s_closed, 1u);
@@ -1931,8 +2038,8 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
         Slot &S = slots[task >> 4];
         StreamSlotExt &E = ext[task >> 4];
         {
-            const unsigned v = (unsigned)task & 15u;
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            const unsigned v = ((unsigned)task & 15u) - S.first;
             const long long c0 = __builtin_readcyclecounter();
             const int with_h = S.with_h;
             bool planar = (E.prm.dof_mask & 0x3f) == 0x23 && !(E.prm.fusion_flags & 2);
@@ -1963,37 +2070,43 @@ __global__ __launch_bounds__(NDT_MATCH_THREADS) __attribute__((amdgpu_waves_per_
         bool cov_eval = false;
         if constexpr (COV != 0) cov_eval = S.st.phase == PH_COV;
         if constexpr (COV != 0) {
-            if (cov_eval) slot_covariance(S, E.prm.lfd1, E.prm.lfd2, cext[task >> 4], E.T16);
-            else slot_step(S, E.prm);
+            if (cov_eval) {                  // (to the staging area; the initial guess is still at T16)
+                unsigned long long *const stage = slot_stage(S);
+                slot_covariance(S, E.prm.lfd1, E.prm.lfd2, cext[task >> 4].mode, reinterpret_cast<double *>(stage + ST_COV),
+                                reinterpret_cast<int *>(stage + ST_FLAGS), E.T16 + (size_t)S.pair * 16);
+            } else {
+                slot_step(S, E.prm);
+            }
         } else {
             slot_step(S, E.prm);
         }
         ndt_wave_sync();
+        int finished = 0;
         if (lane == 0) {
             if (!cov_eval) S.cnt[S.with_h ? 3 : 2] += (unsigned long long)S.sums[28];   // (the covariance's evaluation is not the matcher's)
             S.cnt[1] += (unsigned long long)((long long)__builtin_readcyclecounter() - c1);
-            lds_store(&S.done, 0u);
+            lds_store(&S.done, S.first);
             if constexpr (COV != 0)
                 if (S.st.done && !cov_eval && cext[task >> 4].mode >= 0) match_state_cov_request(S.st);   // one more evaluation, with the Hessian
             if (S.st.done) {
-                slot_result(S, E.T16, E.res);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");              // (system scope: pose and result reach memory)
-                const unsigned d = __hip_atomic_fetch_add(E.done_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                if (d + 1u == E.n_pairs) {
-                    // (a complete batch has no tickets left: nobody looks at its ring entry again, it may be re-published)
-                    __hip_atomic_fetch_max(&q->first_open, E.seq + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    q->stamp[E.seq % NDT_STREAM_STAMPS][1] = wall_clock64();
-                    sys_store(&q->done_seq[E.seq % ring], E.seq + 1u);
-                    __hip_atomic_fetch_add(&q->completed, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-                lds_store(&S.retry, clock_lo());
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                lds_store(&S.state, SLOT_FREE);
+                unsigned long long *const stage = slot_stage(S);
+                slot_result_to(S, reinterpret_cast<double *>(stage + ST_POSE), *reinterpret_cast<NdtMatchResultDev *>(stage + ST_RES));
+                finished = 1;
             } else {
                 S.with_h = S.st.with_h;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                lds_store(&S.next, 0u);
+                lds_store(&S.next, S.first);
             }
+        }
+        if (__builtin_amdgcn_readfirstlane(finished) == 0) continue;      // (the next request is out: the slot is not this wave's any more)
+        ndt_wave_sync();
+        // ---- the registration is done: the wave writes its outputs through, then lane 0 counts it and frees the slot -----------
+        stream_write_out(S, E, COV != 0 ? &cext[task >> 4] : nullptr, true, cov_eval);
+        if (lane == 0) {
+            stream_count_done(q, E, ring);
+            lds_store(&S.retry, clock_lo());
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            lds_store(&S.state, SLOT_FREE);
         }
     }
 }
