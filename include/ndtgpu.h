@@ -913,6 +913,111 @@ ndtgpu_status ndtgpu_pgo_wide_plan(size_t n_nodes, size_t n_edges, uint32_t *til
 ndtgpu_status ndtgpu_pgo_optimize_wide(ndtgpu_pgo *h, size_t g, const ndtgpu_pgo_params *prm, const ndtgpu_pgo_wide_params *wide,
                                        ndtgpu_stream stream);
 
+/* ---- SE(3) pose-graph optimisation of 6-DoF links: a bank of graphs ------------------------------------------------------------
+ * Every registration of the library leaves a full pose T16 and a 6x6 covariance cov36 (link.cov_3d, ndt_feature_graph.cpp:296-330,
+ * ndt_feature_link.h:27); the reference calls graph.force2D() (ndt_feature_graph_opt.cpp:147) before its only optimiser, and
+ * ndtgpu_pgo_* above follows it.  ndtgpu_pgo3_* is the back end of the 3D half: it turns 6-DoF links into node poses that
+ * ndtgpu_world_assemble takes as they are.  It is the SE(2) bank's algorithm with 6x6 blocks in place of 3x3.
+ * Semantics (restated):
+ *   - a node's unknown is its pose T_i = (R_i, t_i); it enters and leaves as T16, column-major.  The rotation of an input is
+ *     taken as given: nothing here re-orthonormalises.
+ *   - an update is the local retraction T [+] d = (R Exp(phi), t + R rho), d = (rho, phi), phi a rotation vector (Rodrigues).
+ *   - a link (ref, mov, Z) has Z = the registrar's T16 = the pose of mov in ref's frame.  Its error is e = (t_E, Log R_E) with
+ *     E = T_ref^-1 T_mov Z^-1, associated (T_ref^-1 T_mov) Z^-1.  The error is on the LEFT of Z because the matcher's increment
+ *     is T <- TR T with TR = Trans Rx Ry Rz (ndt_matcher_d2d_fusion.h:1035-1042): cov36, ordered (x, y, z, rx, ry, rz), is
+ *     therefore, to first order, the covariance of exactly this e.
+ *   - Log R = v theta / |v| with v = (R32 - R23, R13 - R31, R21 - R12) / 2 and theta = atan2(|v|, (tr R - 1) / 2); Log R = v
+ *     where |v| < 1e-8 and the trace is positive; where |v| < 1e-8 and the trace is negative R is a half turn whose axis is
+ *     lost: that is reported (NDTGPU_PGO3_HALF_TURN), not guessed.
+ *   - the Jacobians are analytic and exact.  With A = T_ref^-1 T_mov, Z^-1 = (R_z', t_z') and Jr^-1 = Jr^-1(e_phi):
+ *       J_ref = [[-I, [t_E]x], [0, -Jr^-1 R_E^T]]      J_mov = [[R_A, -R_A [t_z']x], [0, Jr^-1 R_z'^T]]
+ *       Jr^-1(phi) = I + [phi]x / 2 + (1 / theta^2 - (1 + cos theta) / (2 theta sin theta)) [phi]x^2
+ *     (the series 1 / 12 + theta^2 / 720 below theta = 0.01; the quotient is evaluated at the half angle, as
+ *     cos(theta / 2) / (2 theta sin(theta / 2))).  tests/test_pgo3_model.py holds them against central differences.
+ *   - the prior acts on node 0: the same error with T_ref = node 0's pose when the graph was set, T_mov = node 0 and Z = I;
+ *     its information is prior_information, default 100 * I6 -- the analogue of ndt_offline_mapper.h:45, :61.
+ *   - the cost is sum e^T W e, W a 6x6 information matrix per link (its symmetric part is used); W = NULL is 100 * I6.
+ *   - a registered link's W is the Cholesky inverse of the symmetric part of cov36; the covariance 0.02 * I6 (W = 50 * I6)
+ *     stands in under NDTGPU_COV_SINGULAR, NDTGPU_COV_POSE_UNCHANGED or NDTGPU_COV_NOT_COMPUTED (ndt_feature_graph.cpp:300-310)
+ *     and where the matrix is not positive definite or its inverse is not finite.  A 3-DoF registration's cov36 is singular, so
+ *     it lands there too.  The conversion uses +, -, *, / and sqrt only, without contraction: host, device and
+ *     tests/pgo3_model.py give the same bits.
+ *   - Gauss-Newton with the stop rule, the defaults and the exit codes of ndtgpu_pgo_params / NDTGPU_PGO_*; eps_step is held
+ *     against the largest |component| of d, in m or rad.  Each system is solved by conjugate gradients from zero, preconditioned
+ *     with the 6x6 diagonal blocks (Cholesky; the identity where a block is not positive definite).  A step that leaves the
+ *     finite numbers is rolled back to the last iterate, as in SE(2).  One more exit code, NDTGPU_PGO3_HALF_TURN: the FIRST
+ *     linearisation found a factor whose residual rotation is a half turn; the poses are returned as set, iterations 0,
+ *     cost_initial NaN.  A half turn met later makes that iterate's cost NaN: the roll-back applies (NDTGPU_PGO_NOT_FINITE).
+ * PROVENANCE: the reference has no SE(3) optimiser; the factor is the standard between-factor on SE(3) restated from memory with
+ * the side of the error chosen to match cov36, and the optimiser is this library's SE(2) one.
+ * DEVIATIONS:
+ *   - the matcher's increment is a product of Euler rotations, the error here is a rotation vector: the two agree to FIRST ORDER
+ *     only, so cov36 is the covariance of e up to terms of second order in the registration error.
+ *   - the stop rule, its defaults and the inner solver are OURS (see the SE(2) section).
+ *   - links are taken as given: nothing is added twice (the SE(2) mirror's doubling reproduces ndt_offline_mapper.h:74-93).
+ * Device form (csrc/ndt_pgo3.hip, ndt_pgo3_kernel): one workgroup of 512 threads optimises one graph from start to finish, `count`
+ * graphs are `count` workgroups of one launch.  Nothing but the workgroup barrier orders its passes: no grid barrier, no queue,
+ * no spin on memory, no atomics; every sum has one fixed order, so a graph's poses and result are the same bits whichever
+ * batch it runs in, whatever first / count are and whatever the bank's capacity is.  512 threads, not 1024: the
+ * linearisation's 3x3 matrices and the gather's 6x6 Cholesky factor do not fit 128 VGPRs a thread without spills (204 of them).
+ * Kernels (tools/kernel_resources.py pgo3): ndt_pgo3_kernel 228 VGPRs, no VGPR spill, no scratch, 256 B of LDS (77 scalar
+ * registers are kept in vector lanes, not in memory); ndt_pgo3_links_kernel 116 VGPRs, no spill, no scratch.
+ * Measured on MI355X, ndtgpu 0.13.0 (tools/pgo3_cost.py: the grid-world graphs of tools/pgo_cost.py lifted to 3D -- heights that
+ * undulate by 0.3 m, roll and pitch of +-0.1 rad, start 0.2 m / 0.1 rad off in every component; defaults; device events round
+ * the call, median of 5 repeats after a warm-up, 2 at the replay's size; the SE(2) bank on the same nodes and links in the same
+ * run):
+ *   graphs x nodes / links   updates / inner iterations   SE(3)      per graph   SE(2) same run   SE(3) : SE(2)
+ *   1 x 500 / 1886           6 / 2433                     101.8 ms   101.8 ms    13.5 ms          7.5
+ *   256 x 500 / 1886         6 / at most 2444             303.2 ms   1.18 ms     24.7 ms          12.3
+ *   1 x 5000 / 43 509        6 / 7528                     9.89 s     9.89 s      0.743 s          13.3
+ * every graph converged; no inner solve reached max_linear_iterations.  An inner iteration costs 42 us at 500 nodes against the
+ * SE(2) kernel's 12.5 us, and the 3D graphs need 2.2 to 3 times as many of them (the 6x6 blocks are worse conditioned than the
+ * 3x3 ones).  The NumPy model (dense solve, 16 threads) takes 1.25 s at 500 nodes on the same box.  One workgroup is the wrong
+ * shape for the replay's one large graph: a chip-wide form like ndtgpu_pgo_optimize_wide is the follow-up. */
+typedef struct ndtgpu_pgo3 ndtgpu_pgo3;
+typedef struct {
+    int32_t max_iterations;          /* Gauss-Newton updates at most (50) */
+    int32_t max_linear_iterations;   /* conjugate-gradient iterations per update at most (2000) */
+    double eps_step;                 /* stop when the largest |component| of the update is <= this (1e-8; m and rad) */
+    double eps_linear;               /* the inner solve's relative residual |r| / |b| (1e-8) */
+    double prior_information[36];    /* the prior's W, row-major, (x, y, z, rx, ry, rz) (100 * I6) */
+} ndtgpu_pgo3_params;
+void ndtgpu_default_pgo3_params(ndtgpu_pgo3_params *p);
+enum {
+    NDTGPU_PGO3_HALF_TURN = 4        /* ndtgpu_pgo_result.exit_code, beside NDTGPU_PGO_*: see above */
+};
+/* room for n_graphs graphs of up to max_nodes nodes and max_edges links each (the limits of ndtgpu_pgo_create) */
+ndtgpu_status ndtgpu_pgo3_create(size_t n_graphs, size_t max_nodes, size_t max_edges, ndtgpu_pgo3 **out);
+ndtgpu_status ndtgpu_pgo3_destroy(ndtgpu_pgo3 *h);
+/* installs graph g.  All arrays HOST: T16_nodes n_nodes x 16 column-major, node 0's is the prior's origin; ref_idx / mov_idx
+ * n_edges node indices; Z16 n_edges x 16 column-major; info36 n_edges x 36 row-major or NULL (100 * I6 for every link).
+ * The checks of ndtgpu_pgo_set_graph -- index range, ref == mov, every node connected to node 0 -- made before the handle is
+ * read and the device is looked for.  Synchronous. */
+ndtgpu_status ndtgpu_pgo3_set_graph(ndtgpu_pgo3 *h, size_t g, size_t n_nodes, const double *T16_nodes, size_t n_edges,
+                                    const uint32_t *ref_idx, const uint32_t *mov_idx, const double *Z16, const double *info36);
+/* the same with the links where ndtgpu_register_batch_cov_device left them: T16_nodes, ref_idx, mov_idx HOST; T16_dev (n_edges x
+ * 16), cov36_dev (n_edges x 36) and cov_flags_dev (n_edges) DEVICE and complete when the call is made.  ndt_pgo3_links_kernel
+ * converts a link per lane (ndtgpu_pgo3_link_from_registration); cov36_dev == NULL gives every link 100 * I6 (cov_flags_dev is
+ * then not read).  No link value visits the host.  Returns when the kernel has run. */
+ndtgpu_status ndtgpu_pgo3_set_links_device(ndtgpu_pgo3 *h, size_t g, size_t n_nodes, const double *T16_nodes, size_t n_edges,
+                                           const uint32_t *ref_idx, const uint32_t *mov_idx, const double *T16_dev,
+                                           const double *cov36_dev, const int32_t *cov_flags_dev);
+/* optimises graphs [first, first + count), each of which has been set, in ONE launch, asynchronous on `stream`; prm NULL: the
+ * defaults.  Calls on one handle are ordered.  A graph that ends with NDTGPU_PGO_NOT_FINITE or NDTGPU_PGO3_HALF_TURN does not
+ * fail the call or touch the other graphs. */
+ndtgpu_status ndtgpu_pgo3_optimize(ndtgpu_pgo3 *h, size_t first, size_t count, const ndtgpu_pgo3_params *prm, ndtgpu_stream stream);
+/* graph g's poses: T16_out HOST n_nodes x 16 column-major (what ndtgpu_world_assemble takes) or NULL; result may be NULL.  Waits
+ * for the handle. */
+ndtgpu_status ndtgpu_pgo3_poses(ndtgpu_pgo3 *h, size_t g, double *T16_out, ndtgpu_pgo_result *result);
+/* Pure host, no device needed; the code the kernel runs (csrc/ndt_pgo3.h) compiled for the host.
+ * e6 = the link's error at (Ti16, Tj16) = (ref, mov); Jref36 / Jmov36 (row-major 6x6, either may be NULL) its derivatives with
+ * respect to the retraction of either pose.  NDTGPU_ERR_INVALID at a half turn. */
+ndtgpu_status ndtgpu_pgo3_link_error(const double *Ti16, const double *Tj16, const double *Z16, double *e6, double *Jref36, double *Jmov36);
+/* T16_out = T16 [+] d6 */
+ndtgpu_status ndtgpu_pgo3_retract(const double *T16, const double *d6, double *T16_out);
+/* a registered link as the factor takes it: Z16 = T16, W36 (row-major) from cov36 and flags as stated above; cov36 NULL: 100 * I6 */
+ndtgpu_status ndtgpu_pgo3_link_from_registration(const double *T16, const double *cov36, int32_t flags, double *Z16, double *W36);
+
 /* ---- world-map assembly: the node maps of a graph, under its poses, merged into one map -------------------------------------
  * The chain scans -> feature sets -> seeded links -> registered links -> optimised poses ends in node poses; the product the
  * reference's consumers use is ONE map: ndt_feature_mcl_node.cpp:174 localises in a single saved NDT map,

@@ -11,7 +11,7 @@ _ROOT = os.path.dirname(_HERE)
 _SO = os.path.join(_HERE, "libndtgpu.so")
 _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hip", "ndt_pack.hip", "ndt_fuser.hip", "ndtgpu_api.hip",
             "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip",
-            "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndt_pgo_wide.hip", "ndtgpu_pgo.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
+            "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndt_pgo_wide.hip", "ndtgpu_pgo.hip", "ndt_pgo3.hip", "ndtgpu_pgo3.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
             "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip", "ndt_occgrid.hip", "ndtgpu_occgrid.hip", "ndt_linkgate.hip",
             "ndtgpu_linkgate.hip", "ndt_fuserfeat.hip", "ndt_scanproject.hip", "ndtgpu_scanproject.hip",
             "ndt_calib.hip", "ndtgpu_calib.hip", "ndt_locmon.hip", "ndtgpu_locmon.hip", "ndt_scansim.hip", "ndtgpu_scansim.hip",
@@ -200,6 +200,9 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_default_pgo_params", "ndtgpu_pgo_create", "ndtgpu_pgo_destroy", "ndtgpu_pgo_set_graph", "ndtgpu_pgo_set_links_device",
            "ndtgpu_pgo_optimize", "ndtgpu_pgo_poses", "ndtgpu_live_resources",
            "ndtgpu_default_pgo_wide_params", "ndtgpu_pgo_wide_plan", "ndtgpu_pgo_optimize_wide",
+           "ndtgpu_default_pgo3_params", "ndtgpu_pgo3_create", "ndtgpu_pgo3_destroy", "ndtgpu_pgo3_set_graph",
+           "ndtgpu_pgo3_set_links_device", "ndtgpu_pgo3_optimize", "ndtgpu_pgo3_poses", "ndtgpu_pgo3_link_error", "ndtgpu_pgo3_retract",
+           "ndtgpu_pgo3_link_from_registration",
            "ndtgpu_default_featmatch_params", "ndtgpu_featbank_create", "ndtgpu_featbank_destroy", "ndtgpu_featbank_set",
            "ndtgpu_featbank_match", "ndtgpu_featbank_match_device", "ndtgpu_featbank_results",
            "ndtgpu_default_featextract_params", "ndtgpu_featbank_extract", "ndtgpu_featbank_extract_device",
@@ -363,6 +366,17 @@ def lib():
     L.ndtgpu_pgo_wide_plan.argtypes = [C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                        C.POINTER(C.c_size_t)]
     L.ndtgpu_pgo_optimize_wide.argtypes = [vp, C.c_size_t, C.POINTER(PgoParams), C.POINTER(PgoWideParams), vp]
+    L.ndtgpu_default_pgo3_params.restype = None
+    L.ndtgpu_default_pgo3_params.argtypes = [C.POINTER(Pgo3Params)]
+    L.ndtgpu_pgo3_create.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.ndtgpu_pgo3_destroy.argtypes = [vp]
+    L.ndtgpu_pgo3_set_graph.argtypes = [vp, C.c_size_t, C.c_size_t, dp, C.c_size_t, u32p, u32p, dp, dp]
+    L.ndtgpu_pgo3_set_links_device.argtypes = [vp, C.c_size_t, C.c_size_t, dp, C.c_size_t, u32p, u32p, vp, vp, vp]
+    L.ndtgpu_pgo3_optimize.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(Pgo3Params), vp]
+    L.ndtgpu_pgo3_poses.argtypes = [vp, C.c_size_t, dp, C.POINTER(PgoResult)]
+    L.ndtgpu_pgo3_link_error.argtypes = [dp, dp, dp, dp, dp, dp]
+    L.ndtgpu_pgo3_retract.argtypes = [dp, dp, dp]
+    L.ndtgpu_pgo3_link_from_registration.argtypes = [dp, dp, C.c_int32, dp, dp]
     L.ndtgpu_default_featmatch_params.restype = None
     L.ndtgpu_default_featmatch_params.argtypes = [C.POINTER(FeatMatchParams)]
     L.ndtgpu_featbank_create.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp)]
@@ -1345,6 +1359,111 @@ class PGO(_Handle):
         if with_T:
             return ps, np.transpose(T.reshape(-1, 4, 4), (0, 2, 1)).copy(), res
         return ps, res
+
+
+class Pgo3Params(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("max_linear_iterations", C.c_int32), ("eps_step", C.c_double), ("eps_linear", C.c_double),
+                ("prior_information", C.c_double * 36)]
+
+
+PGO3_HALF_TURN = 4    # ndtgpu_pgo_result.exit_code beside PGO_* (include/ndtgpu.h NDTGPU_PGO3_HALF_TURN)
+
+
+def pgo3_params(**fields):
+    """ndtgpu_default_pgo3_params with fields replaced (prior_information: 36 values row-major)"""
+    return _params(Pgo3Params, "ndtgpu_default_pgo3_params", "PGO3", fields)
+
+
+def _cm16(T):
+    """poses [n, 4, 4] as the ABI's column-major T16 rows [n, 16]"""
+    return np.ascontiguousarray(np.transpose(_f64(T).reshape(-1, 4, 4), (0, 2, 1))).reshape(-1, 16)
+
+
+def _from_cm16(T16):
+    return np.transpose(T16.reshape(-1, 4, 4), (0, 2, 1)).copy()
+
+
+def pgo3_link_error(Ti, Tj, Z):
+    """ndtgpu_pgo3_link_error (pure host) -> (e [6], J_ref [6, 6], J_mov [6, 6]) of a link ref = Ti, mov = Tj, all 4x4"""
+    e, Jr, Jm = np.zeros(6), np.zeros((6, 6)), np.zeros((6, 6))
+    _check(lib().ndtgpu_pgo3_link_error(_dp(_cm16(Ti)), _dp(_cm16(Tj)), _dp(_cm16(Z)), _dp(e), _dp(Jr), _dp(Jm)))
+    return e, Jr, Jm
+
+
+def pgo3_retract(T, d):
+    """ndtgpu_pgo3_retract (pure host): T [+] d, d = (rho, phi) -> 4x4"""
+    out = np.zeros((1, 16))
+    _check(lib().ndtgpu_pgo3_retract(_dp(_cm16(T)), _dp(_f64(d).reshape(6)), _dp(out)))
+    return _from_cm16(out)[0]
+
+
+def pgo3_link_from_registration(T, cov36=None, flags=0):
+    """ndtgpu_pgo3_link_from_registration (pure host) -> (Z [4, 4], W [6, 6]) of one registered link: T 4x4, cov36 row-major 6x6"""
+    Z, W = np.zeros((1, 16)), np.zeros((6, 6))
+    c = None if cov36 is None else _f64(cov36).reshape(36)
+    _check(lib().ndtgpu_pgo3_link_from_registration(_dp(_cm16(T)), None if c is None else _dp(c), int(flags), _dp(Z), _dp(W)))
+    return _from_cm16(Z)[0], W
+
+
+class PGO3(_Handle):
+    """ndtgpu_pgo3: a bank of n_graphs SE(3) pose graphs of up to max_nodes nodes and max_edges links, optimised one workgroup per
+    graph (include/ndtgpu.h: SE(3) pose-graph optimisation).  Poses are 4x4 matrices [n, 4, 4]."""
+    _destroy = "ndtgpu_pgo3_destroy"
+
+    def __init__(self, n_graphs, max_nodes, max_edges):
+        h = C.c_void_p()
+        _check(lib().ndtgpu_pgo3_create(int(n_graphs), int(max_nodes), int(max_edges), C.byref(h)))
+        self.h, self.n_graphs = h, int(n_graphs)
+        self._n_nodes = [0] * int(n_graphs)
+
+    @staticmethod
+    def _graph(poses, ref, mov):
+        ps = _cm16(poses)
+        ri = np.ascontiguousarray(ref, dtype=np.uint32).reshape(-1)
+        mi = np.ascontiguousarray(mov, dtype=np.uint32).reshape(-1)
+        if ri.shape != mi.shape:
+            raise ValueError("PGO3: one ref and one mov index per link")
+        u32p = C.POINTER(C.c_uint32)
+        return ps, ri, mi, ri.ctypes.data_as(u32p), mi.ctypes.data_as(u32p)
+
+    def set_graph(self, g, poses, ref, mov, meas, info=None):
+        """graph g: poses [n, 4, 4] (node 0's is the prior's origin), links ref -> mov with meas [m, 4, 4] and info [m, 6, 6] (None:
+        100 I)"""
+        ps, ri, mi, rp, mp = self._graph(poses, ref, mov)
+        z = _cm16(meas) if ri.shape[0] else np.zeros((0, 16))
+        W = None if info is None else _f64(info).reshape(-1, 36)
+        if z.shape[0] != ri.shape[0] or (W is not None and W.shape[0] != ri.shape[0]):
+            raise ValueError("PGO3.set_graph: one measurement (and information matrix) per link")
+        _check(lib().ndtgpu_pgo3_set_graph(self.h, int(g), ps.shape[0], _dp(ps), ri.shape[0], rp, mp, _dp(z), None if W is None else _dp(W)))
+        self._n_nodes[int(g)] = ps.shape[0]
+
+    def set_links_device(self, g, poses, ref, mov, T16_dev, cov36_dev=None, cov_flags_dev=None):
+        """graph g with its links as ndtgpu_register_batch_cov_device left them: torch CUDA tensors T16_dev float64 [m, 16]
+        (column-major), cov36_dev float64 [m, 36] and cov_flags_dev int32 [m] (both None: 100 I for every link), complete when the
+        call is made"""
+        ps, ri, mi, rp, mp = self._graph(poses, ref, mov)
+        m = ri.shape[0]
+        assert T16_dev.is_cuda and T16_dev.is_contiguous() and T16_dev.numel() >= 16 * m
+        if cov36_dev is not None:
+            assert cov36_dev.is_cuda and cov36_dev.is_contiguous() and cov36_dev.numel() >= 36 * m
+            assert cov_flags_dev is not None and cov_flags_dev.is_cuda and cov_flags_dev.numel() >= m
+        _check(lib().ndtgpu_pgo3_set_links_device(self.h, int(g), ps.shape[0], _dp(ps), m, rp, mp, C.c_void_p(T16_dev.data_ptr()),
+                                                  None if cov36_dev is None else C.c_void_p(cov36_dev.data_ptr()),
+                                                  None if cov36_dev is None else C.c_void_p(cov_flags_dev.data_ptr())))
+        self._n_nodes[int(g)] = ps.shape[0]
+
+    def optimize(self, first=0, count=None, stream=None, **params):
+        """graphs [first, first + count) in one launch, asynchronous on `stream`; keyword arguments: fields of ndtgpu_pgo3_params"""
+        count = self.n_graphs - first if count is None else int(count)
+        p = pgo3_params(**params)
+        _check(lib().ndtgpu_pgo3_optimize(self.h, int(first), count, C.byref(p), _stream_ptr(stream)))
+
+    def poses(self, g):
+        """(poses [n, 4, 4], result dict) of graph g; waits for the handle"""
+        T = np.zeros((max(self._n_nodes[int(g)], 1), 16))
+        r = PgoResult()
+        _check(lib().ndtgpu_pgo3_poses(self.h, int(g), _dp(T), C.byref(r)))
+        return _from_cm16(T), {k: getattr(r, k) for k, _ in PgoResult._fields_ if k != "pad_"}
 
 
 class WorldParams(C.Structure):

@@ -6,8 +6,7 @@
 #include "ndtgpu_host.h"
 #include "ndt_pgo.h"
 #include "ndt_pgo_wide.h"
-
-#include <numeric>
+#include "ndtgpu_pgo_graph.h"
 
 struct ndtgpu_pgo {
     size_t G = 0;
@@ -31,33 +30,6 @@ static void sym6(const double *W9, double *W6)
 {
     W6[0] = W9[0]; W6[1] = 0.5 * (W9[1] + W9[3]); W6[2] = 0.5 * (W9[2] + W9[6]);
     W6[3] = W9[4]; W6[4] = 0.5 * (W9[5] + W9[7]); W6[5] = W9[8];
-}
-
-// what set_graph / set_links_device check before the handle is read: indices, self links, every node connected to node 0
-static ndtgpu_status pgo_check_graph(const char *what, size_t n_nodes, const double *pose3, size_t n_edges, const uint32_t *ref_idx,
-                                     const uint32_t *mov_idx)
-{
-    if (n_nodes == 0 || !pose3 || (n_edges && (!ref_idx || !mov_idx)))
-        return fail_in(NDTGPU_ERR_INVALID, what, "poses and link indices are required");
-    if (n_nodes > (1u << 24) || n_edges > (1u << 27)) return fail_in(NDTGPU_ERR_INVALID, what, "graph too large");
-    std::vector<uint32_t> parent(n_nodes);
-    std::iota(parent.begin(), parent.end(), 0u);
-    auto find = [&](uint32_t a) {
-        while (parent[a] != a) {
-            parent[a] = parent[parent[a]];
-            a = parent[a];
-        }
-        return a;
-    };
-    for (size_t e = 0; e < n_edges; e++) {
-        if (ref_idx[e] >= n_nodes || mov_idx[e] >= n_nodes) return fail_in(NDTGPU_ERR_INVALID, what, "link index out of range");
-        if (ref_idx[e] == mov_idx[e]) return fail_in(NDTGPU_ERR_INVALID, what, "a link joins a node to itself");
-        const uint32_t a = find(ref_idx[e]), b = find(mov_idx[e]);
-        if (a != b) parent[std::max(a, b)] = std::min(a, b);
-    }
-    for (size_t i = 1; i < n_nodes; i++)
-        if (find((uint32_t)i) != 0) return fail_in(NDTGPU_ERR_INVALID, what, "a node is not connected to node 0");
-    return NDTGPU_OK;
 }
 
 // the device form of a call's parameters (NULL: the defaults); false where one is out of range
@@ -136,18 +108,8 @@ static ndtgpu_status pgo_install(ndtgpu_pgo *h, const char *what, size_t g, size
     if (n_nodes > h->v.max_nodes || n_edges > h->v.max_edges)
         return fail_in(NDTGPU_ERR_CAPACITY, what, "more nodes or links than the handle was created for");
     // (values that are not finite are not refused here: the kernel reports NDTGPU_PGO_NOT_FINITE for that graph)
-    // node -> incident edges, CSR; a node's entries in ascending edge order
-    std::vector<uint32_t> off(n_nodes + 1, 0), adj(2 * n_edges);
-    for (size_t e = 0; e < n_edges; e++) {
-        off[ref_idx[e] + 1]++;
-        off[mov_idx[e] + 1]++;
-    }
-    for (size_t i = 0; i < n_nodes; i++) off[i + 1] += off[i];
-    std::vector<uint32_t> at(off.begin(), off.end() - 1);
-    for (size_t e = 0; e < n_edges; e++) {
-        adj[at[ref_idx[e]]++] = (uint32_t)(e << 1);
-        adj[at[mov_idx[e]]++] = (uint32_t)(e << 1) | 1u;
-    }
+    std::vector<uint32_t> off, adj;
+    pgo_adjacency(n_nodes, n_edges, ref_idx, mov_idx, off, adj);
     std::vector<int32_t> ri(ref_idx, ref_idx + n_edges), mi(mov_idx, mov_idx + n_edges);
     ndtgpu_pgo_result st{};
     st.n_nodes = (int32_t)n_nodes;

@@ -1,0 +1,238 @@
+// ndtgpu_pgo3.hip -- C-ABI (include/ndtgpu.h) of the SE(3) pose-graph optimiser: the back end of the 6-DoF links
+// (link.T and link.cov_3d, ndt_feature_graph.cpp:296-330) for a bank of independent graphs.  Host side only: the handle, the
+// checks of a graph (csrc/ndtgpu_pgo_graph.h, shared with the SE(2) bank), the adjacency and the order of the launches; the
+// optimisation runs in csrc/ndt_pgo3.hip.  The three pure host entries call the same inlines of csrc/ndt_pgo3.h as the kernel.
+#include "ndtgpu_host.h"
+#include "ndt_pgo3.h"
+#include "ndtgpu_pgo_graph.h"
+
+struct ndtgpu_pgo3 {
+    size_t G = 0;
+    NdtPgo3View v{};                       // what the kernels receive: filled from the owners below at create
+    DeviceBuffer<ndtgpu_pgo_result> state;
+    DeviceBuffer<double> pose, origin, meas, info, jac, te, node;
+    DeviceBuffer<int32_t> ref, mov;
+    DeviceBuffer<uint32_t> adj_off, adj;
+    std::vector<uint32_t> n_nodes;         // per graph, 0: not set
+    Fence used;                            // recorded after the last launch of a call
+    Stream hst;                            // the synchronous entries' stream (last: ndtgpu_resource.h)
+};
+
+// the device form of a call's parameters (NULL: the defaults); false where one is out of range
+static bool pgo3_params_dev(const ndtgpu_pgo3_params *prm, NdtPgo3ParamsDev &d)
+{
+    const ndtgpu_pgo3_params p = params_or_default(prm, ndtgpu_default_pgo3_params);
+    bool ok = p.max_iterations >= 0 && p.max_linear_iterations >= 0 && p.eps_step >= 0.0 && p.eps_linear >= 0.0;   // (NaN fails)
+    for (double w : p.prior_information) ok = ok && std::isfinite(w);
+    d.max_iterations = p.max_iterations;
+    d.max_linear_iterations = p.max_linear_iterations;
+    d.eps_step = p.eps_step;
+    d.eps_linear = p.eps_linear;
+    pgo3_sym21(p.prior_information, d.prior);
+    return ok;
+}
+
+extern "C" {
+
+void ndtgpu_default_pgo3_params(ndtgpu_pgo3_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    // the stop rule is that of ndtgpu_default_pgo_params
+    p->max_iterations = 50;
+    p->max_linear_iterations = 2000;
+    p->eps_step = 1e-8;
+    p->eps_linear = 1e-8;
+    for (int k = 0; k < 6; k++) p->prior_information[7 * k] = 100.0;      // the analogue of ndt_offline_mapper.h:45, :61
+}
+
+ndtgpu_status ndtgpu_pgo3_link_error(const double *Ti16, const double *Tj16, const double *Z16, double *e6, double *Jref36, double *Jmov36)
+{
+    if (!Ti16 || !Tj16 || !Z16 || !e6) return fail(NDTGPU_ERR_INVALID, "pgo3_link_error: Ti16, Tj16, Z16 and e6 are required");
+    double Pi[12], Pj[12], Z[12], jac[NDT_PGO3_JAC];
+    pgo3_from_T16(Ti16, Pi);
+    pgo3_from_T16(Tj16, Pj);
+    pgo3_from_T16(Z16, Z);
+    if (!pgo3_link_error(Pi, Pj, Z, e6, jac)) return fail(NDTGPU_ERR_INVALID, "pgo3_link_error: the residual rotation is a half turn");
+    for (int side = 0; side < 2; side++) {
+        double *J = side ? Jmov36 : Jref36;
+        if (!J) continue;
+        for (int q = 0; q < 6; q++) {
+            double col[6];
+            pgo3_j_column(side, jac, q, col);
+            for (int r = 0; r < 6; r++) J[6 * r + q] = col[r];
+        }
+    }
+    return NDTGPU_OK;
+}
+
+ndtgpu_status ndtgpu_pgo3_retract(const double *T16, const double *d6, double *T16_out)
+{
+    if (!T16 || !d6 || !T16_out) return fail(NDTGPU_ERR_INVALID, "pgo3_retract: null argument");
+    double P[12], Q[12];
+    pgo3_from_T16(T16, P);
+    pgo3_retract(P, d6, Q);
+    pgo3_to_T16(Q, T16_out);
+    return NDTGPU_OK;
+}
+
+ndtgpu_status ndtgpu_pgo3_link_from_registration(const double *T16, const double *cov36, int32_t flags, double *Z16, double *W36)
+{
+    if (!T16 || !Z16 || !W36) return fail(NDTGPU_ERR_INVALID, "pgo3_link_from_registration: T16, Z16 and W36 are required");
+    ndt_pgo3_link_from_registration(T16, cov36, flags, Z16, W36);
+    return NDTGPU_OK;
+}
+
+ndtgpu_status ndtgpu_pgo3_destroy(ndtgpu_pgo3 *h) { return handle_destroy(h, "pgo3_destroy"); }
+
+ndtgpu_status ndtgpu_pgo3_create(size_t n_graphs, size_t max_nodes, size_t max_edges, ndtgpu_pgo3 **out)
+{
+    if (!out) return fail(NDTGPU_ERR_INVALID, "pgo3_create: out is NULL");
+    *out = nullptr;
+    if (n_graphs == 0 || n_graphs > (1u << 24) || max_nodes == 0 || max_nodes > (1u << 24) || max_edges > (1u << 27))
+        return fail(NDTGPU_ERR_INVALID, "pgo3_create: n_graphs and max_nodes must be 1 .. 2^24, max_edges <= 2^27");
+    ndtgpu_pgo3 *h;
+    const ndtgpu_status rc = handle_new("pgo3_create", h);
+    if (rc != NDTGPU_OK) return rc;
+    h->G = n_graphs;
+    h->n_nodes.assign(n_graphs, 0);
+    NdtPgo3View &v = h->v;
+    v.max_nodes = max_nodes;
+    v.max_edges = max_edges;
+    const size_t G = n_graphs, E = std::max<size_t>(max_edges, 1);     // (no zero-byte allocations)
+#define TRY(expr) CREATE_TRY(h, NDTGPU_ERR_ALLOC, "pgo3_create: device buffers", expr)
+    TRY(h->state.alloc(G, &v.state));
+    TRY(h->pose.alloc(G * 12 * max_nodes, &v.pose));
+    TRY(h->origin.alloc(G * 24, &v.origin));
+    TRY(h->ref.alloc(G * E, &v.ref));
+    TRY(h->mov.alloc(G * E, &v.mov));
+    TRY(h->meas.alloc(G * 12 * E, &v.meas));
+    TRY(h->info.alloc(G * 21 * E, &v.info));
+    TRY(h->adj_off.alloc(G * (max_nodes + 1), &v.adj_off));
+    TRY(h->adj.alloc(G * 2 * E, &v.adj));
+    TRY(h->jac.alloc(G * NDT_PGO3_JAC * (max_edges + 1), &v.jac));
+    TRY(h->te.alloc(G * 6 * (max_edges + 1), &v.te));
+    TRY(h->node.alloc(G * NDT_PGO3_NODE_DOUBLES * max_nodes, &v.node));
+    TRY(hipMemset(v.state, 0, G * sizeof(ndtgpu_pgo_result)));
+    TRY(h->used.create());
+    TRY(h->hst.create(hipStreamNonBlocking));
+#undef TRY
+    *out = h;
+    return NDTGPU_OK;
+}
+
+// poses, indices and the adjacency of graph g onto the device, on the handle's stream behind its previous call; meas / info are
+// the caller's to fill on the same stream before pgo3_installed
+static ndtgpu_status pgo3_install(ndtgpu_pgo3 *h, const char *what, size_t g, size_t n_nodes, const double *T16_nodes, size_t n_edges,
+                                  const uint32_t *ref_idx, const uint32_t *mov_idx)
+{
+    if (g >= h->G) return fail_in(NDTGPU_ERR_INVALID, what, "graph index out of range");
+    if (n_nodes > h->v.max_nodes || n_edges > h->v.max_edges)
+        return fail_in(NDTGPU_ERR_CAPACITY, what, "more nodes or links than the handle was created for");
+    // (values that are not finite are not refused here: the kernel reports NDTGPU_PGO_NOT_FINITE for that graph)
+    std::vector<uint32_t> off, adj;
+    pgo_adjacency(n_nodes, n_edges, ref_idx, mov_idx, off, adj);
+    std::vector<int32_t> ri(ref_idx, ref_idx + n_edges), mi(mov_idx, mov_idx + n_edges);
+    std::vector<double> P(12 * n_nodes);
+    for (size_t i = 0; i < n_nodes; i++) pgo3_from_T16(T16_nodes + 16 * i, &P[12 * i]);
+    double origin[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    memcpy(origin, P.data(), 12 * sizeof(double));
+    ndtgpu_pgo_result st{};
+    st.n_nodes = (int32_t)n_nodes;
+    st.n_edges = (int32_t)n_edges;
+    const NdtPgo3View &v = h->v;
+    h->n_nodes[g] = 0;
+    HIP_TRY(h->used.order(h->hst.get()));
+    HIP_TRY(hipMemcpyAsync(v.pose + g * 12 * v.max_nodes, P.data(), P.size() * sizeof(double), hipMemcpyHostToDevice, h->hst.get()));
+    HIP_TRY(hipMemcpyAsync(v.origin + g * 24, origin, sizeof origin, hipMemcpyHostToDevice, h->hst.get()));
+    HIP_TRY(hipMemcpyAsync(v.adj_off + g * (v.max_nodes + 1), off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->hst.get()));
+    if (n_edges) {
+        HIP_TRY(hipMemcpyAsync(v.ref + g * v.max_edges, ri.data(), n_edges * sizeof(int32_t), hipMemcpyHostToDevice, h->hst.get()));
+        HIP_TRY(hipMemcpyAsync(v.mov + g * v.max_edges, mi.data(), n_edges * sizeof(int32_t), hipMemcpyHostToDevice, h->hst.get()));
+        HIP_TRY(hipMemcpyAsync(v.adj + g * 2 * v.max_edges, adj.data(), adj.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->hst.get()));
+    }
+    HIP_TRY(hipMemcpyAsync(v.state + g, &st, sizeof st, hipMemcpyHostToDevice, h->hst.get()));
+    HIP_TRY(hipStreamSynchronize(h->hst.get()));               // (the staging vectors above end with this function)
+    return NDTGPU_OK;
+}
+
+static ndtgpu_status pgo3_installed(ndtgpu_pgo3 *h, size_t g, size_t n_nodes)
+{
+    HIP_TRY(h->used.record(h->hst.get()));
+    HIP_TRY(hipStreamSynchronize(h->hst.get()));
+    h->n_nodes[g] = (uint32_t)n_nodes;
+    return NDTGPU_OK;
+}
+
+ndtgpu_status ndtgpu_pgo3_set_graph(ndtgpu_pgo3 *h, size_t g, size_t n_nodes, const double *T16_nodes, size_t n_edges,
+                                    const uint32_t *ref_idx, const uint32_t *mov_idx, const double *Z16, const double *info36)
+{
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo3_set_graph: null handle");
+    if (n_edges && !Z16) return fail(NDTGPU_ERR_INVALID, "pgo3_set_graph: Z16 is required");
+    ndtgpu_status rc = pgo_check_graph("pgo3_set_graph", n_nodes, T16_nodes, n_edges, ref_idx, mov_idx);
+    if (rc != NDTGPU_OK) return rc;
+    if ((rc = pgo3_install(h, "pgo3_set_graph", g, n_nodes, T16_nodes, n_edges, ref_idx, mov_idx)) != NDTGPU_OK) return rc;
+    if (n_edges) {
+        std::vector<double> Z(12 * n_edges), W(21 * n_edges);
+        double I100[36] = {};
+        for (int k = 0; k < 6; k++) I100[7 * k] = 100.0;
+        for (size_t e = 0; e < n_edges; e++) {
+            pgo3_from_T16(Z16 + 16 * e, &Z[12 * e]);
+            pgo3_sym21(info36 ? info36 + 36 * e : I100, &W[21 * e]);
+        }
+        const NdtPgo3View &v = h->v;
+        HIP_TRY(hipMemcpyAsync(v.meas + g * 12 * v.max_edges, Z.data(), Z.size() * sizeof(double), hipMemcpyHostToDevice, h->hst.get()));
+        HIP_TRY(hipMemcpyAsync(v.info + g * 21 * v.max_edges, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice, h->hst.get()));
+        HIP_TRY(hipStreamSynchronize(h->hst.get()));
+    }
+    return pgo3_installed(h, g, n_nodes);
+}
+
+ndtgpu_status ndtgpu_pgo3_set_links_device(ndtgpu_pgo3 *h, size_t g, size_t n_nodes, const double *T16_nodes, size_t n_edges,
+                                           const uint32_t *ref_idx, const uint32_t *mov_idx, const double *T16_dev,
+                                           const double *cov36_dev, const int32_t *cov_flags_dev)
+{
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo3_set_links_device: null handle");
+    if (n_edges && (!T16_dev || (cov36_dev && !cov_flags_dev)))
+        return fail(NDTGPU_ERR_INVALID, "pgo3_set_links_device: T16_dev is required, and cov_flags_dev with cov36_dev");
+    ndtgpu_status rc = pgo_check_graph("pgo3_set_links_device", n_nodes, T16_nodes, n_edges, ref_idx, mov_idx);
+    if (rc != NDTGPU_OK) return rc;
+    if ((rc = pgo3_install(h, "pgo3_set_links_device", g, n_nodes, T16_nodes, n_edges, ref_idx, mov_idx)) != NDTGPU_OK) return rc;
+    hipError_t e = ndt_pgo3_launch_links(h->v, g, n_edges, T16_dev, cov36_dev, cov_flags_dev, h->hst.get());
+    if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "pgo3_set_links_device: launch", e);
+    return pgo3_installed(h, g, n_nodes);
+}
+
+ndtgpu_status ndtgpu_pgo3_optimize(ndtgpu_pgo3 *h, size_t first, size_t count, const ndtgpu_pgo3_params *prm, ndtgpu_stream stream)
+{
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo3_optimize: null handle");
+    if (count == 0 || first >= h->G || count > h->G - first)
+        return fail(NDTGPU_ERR_INVALID, "pgo3_optimize: graphs [first, first + count) out of range");
+    NdtPgo3ParamsDev d;
+    if (!pgo3_params_dev(prm, d)) return fail(NDTGPU_ERR_INVALID, "pgo3_optimize: bad parameter (caps and tolerances >= 0, a finite prior)");
+    for (size_t g = first; g < first + count; g++)
+        if (!h->n_nodes[g]) return fail(NDTGPU_ERR_INVALID, "pgo3_optimize: a graph of the range has not been set");
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(h->used.order(st));   // (the previous call may have run on another stream)
+    hipError_t e = ndt_pgo3_launch(h->v, first, count, d, st);
+    if (e != hipSuccess) return fail(NDTGPU_ERR_HIP, "pgo3_optimize: launch", e);
+    HIP_TRY(h->used.record(st));
+    return NDTGPU_OK;
+}
+
+ndtgpu_status ndtgpu_pgo3_poses(ndtgpu_pgo3 *h, size_t g, double *T16_out, ndtgpu_pgo_result *result)
+{
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo3_poses: null handle");
+    if (g >= h->G || !h->n_nodes[g]) return fail(NDTGPU_ERR_INVALID, "pgo3_poses: no such graph, or it has not been set");
+    HIP_TRY(h->used.sync());
+    const size_t n = h->n_nodes[g];
+    if (T16_out) {
+        std::vector<double> P(12 * n);
+        HIP_TRY(hipMemcpy(P.data(), h->v.pose + g * 12 * h->v.max_nodes, P.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; i++) pgo3_to_T16(&P[12 * i], T16_out + 16 * i);
+    }
+    if (result) HIP_TRY(hipMemcpy(result, h->v.state + g, sizeof *result, hipMemcpyDeviceToHost));
+    return NDTGPU_OK;
+}
+
+}   // extern "C"

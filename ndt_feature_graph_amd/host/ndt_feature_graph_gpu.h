@@ -5,6 +5,7 @@
 //   ndt_feature::NDTFeatureLink / NDTFeatureNode / overlapNDTOccupancyScore   ndt_feature_link.h:9-56, ndt_feature_node.h:38-252
 //   ndt_feature::NDTFeatureGraph      ndt_feature_graph.h:20-280 (initialize, update, updateLink[s]UsingNDTRegistration, ...)
 //   ndt_feature::optimizeGraphUsingISAM   ndt_offline_mapper.h:8-26, 40-107 (on the device: ndtgpu_pgo_*)
+//   ndt_feature::optimizeGraph3D          (added) the same for 6-DoF links and their cov_3d, without force2D (ndtgpu_pgo3_*)
 //   ndt_feature::assembleWorldMap         the graph's node maps under their poses as ONE map (ndt_feature_graph.h:149-152 fuse(),
 //                                         ndt_feature2d_fuser.cpp:425-432; on the device: ndtgpu_world_assemble)
 // Class, member and parameter names are the reference's, so that its callers compile against this header.  What is behind them
@@ -1045,6 +1046,55 @@ inline void optimizeGraphUsingISAM(NDTFeatureGraphInterface &graph, const ndtgpu
 
 // optimizeGraphUsingISAM(graph, wide): the defaults, in the form asked for
 inline void optimizeGraphUsingISAM(NDTFeatureGraphInterface &graph, bool wide) { optimizeGraphUsingISAM(graph, nullptr, nullptr, wide); }
+
+// The 6-DoF back end the reference does not have (it calls graph.force2D() before iSAM, ndt_feature_graph_opt.cpp:147): one graph
+// of a ndtgpu_pgo3 bank (include/ndtgpu.h "SE(3) pose-graph optimisation").  Node poses and link.T go in as they are, WITHOUT
+// force2D; a link's information is the inverse of its cov_3d (ndt_feature_graph.cpp:296-330) by
+// ndtgpu_pgo3_link_from_registration -- 50 * I6 where it does not invert, 100 * I6 for a link whose cov_3d is not 6x6; node 0's
+// pose is the prior; every link is taken once; the poses go back with setPose.  `links` are NDTFeatureLink because cov_3d is not
+// part of NDTFeatureLinkInterface.
+inline void optimizeGraph3D(NDTFeatureGraphInterface &graph, const std::vector<NDTFeatureLink> &links,
+                            const ndtgpu_pgo3_params *params = nullptr, ndtgpu_pgo_result *result = nullptr)
+{
+    const size_t n = graph.getNbNodes(), m = links.size();
+    if (n == 0) return;
+    std::vector<double> T16(16 * n), Z16(16 * m), W36(36 * m);
+    std::vector<uint32_t> ref(m), mov(m);
+    for (size_t i = 0; i < n; i++) std::copy_n(graph.getNodeInterface(i).getPose().data(), 16, &T16[16 * i]);
+    for (size_t k = 0; k < m; k++) {
+        const NDTFeatureLink &l = links[k];
+        ref[k] = (uint32_t)l.ref_idx;
+        mov[k] = (uint32_t)l.mov_idx;
+        double cov[36];
+        const bool has_cov = l.cov_3d.rows() == 6 && l.cov_3d.cols() == 6;
+        if (has_cov)
+            for (int a = 0; a < 6; a++)
+                for (int b = 0; b < 6; b++) cov[6 * a + b] = l.cov_3d(a, b);
+        ndtgpu_host::check(ndtgpu_pgo3_link_from_registration(l.T.data(), has_cov ? cov : nullptr, 0, &Z16[16 * k], &W36[36 * k]),
+                           "ndtgpu_pgo3_link_from_registration");
+    }
+    ndtgpu_pgo3 *h = nullptr;
+    ndtgpu_host::check(ndtgpu_pgo3_create(1, n, m, &h), "ndtgpu_pgo3_create");
+    ndtgpu_status rc = ndtgpu_pgo3_set_graph(h, 0, n, T16.data(), m, ref.data(), mov.data(), Z16.data(), W36.data());
+    if (rc == NDTGPU_OK) rc = ndtgpu_pgo3_optimize(h, 0, 1, params, nullptr);
+    ndtgpu_pgo_result r;
+    if (rc == NDTGPU_OK) rc = ndtgpu_pgo3_poses(h, 0, T16.data(), &r);
+    const std::string err = rc == NDTGPU_OK ? "" : ndtgpu_last_error();
+    ndtgpu_pgo3_destroy(h);
+    if (rc != NDTGPU_OK) throw ndtgpu_host::Error(rc, "optimizeGraph3D: " + err);
+    if (result) *result = r;
+    for (size_t i = 0; i < n; i++) {
+        Eigen::Affine3d T;
+        std::copy_n(&T16[16 * i], 16, T.data());
+        graph.getNodeInterface(i).setPose(T);
+    }
+}
+
+// optimizeGraph3D(graph): the graph's own current links
+inline void optimizeGraph3D(NDTFeatureGraph &graph, const ndtgpu_pgo3_params *params = nullptr, ndtgpu_pgo_result *result = nullptr)
+{
+    optimizeGraph3D(graph, graph.getCurrentLinks(), params, result);
+}
 
 // The product of the mapper: ONE map from the graph's node maps under the node poses T -- graph->getMap() moved by getT()
 // (ndt_feature2d_fuser.cpp:425-432), the combination NDTFeatureGraph::fuse() (ndt_feature_graph.h:149-152) declares but leaves
