@@ -973,7 +973,7 @@ ndtgpu_status ndtgpu_pgo_optimize_wide(ndtgpu_pgo *h, size_t g, const ndtgpu_pgo
  * every graph converged; no inner solve reached max_linear_iterations.  An inner iteration costs 42 us at 500 nodes against the
  * SE(2) kernel's 12.5 us, and the 3D graphs need 2.2 to 3 times as many of them (the 6x6 blocks are worse conditioned than the
  * 3x3 ones).  The NumPy model (dense solve, 16 threads) takes 1.25 s at 500 nodes on the same box.  One workgroup is the wrong
- * shape for the replay's one large graph: a chip-wide form like ndtgpu_pgo_optimize_wide is the follow-up. */
+ * shape for the replay's one large graph: that one is for ndtgpu_pgo3_optimize_wide, the chip-wide form below. */
 typedef struct ndtgpu_pgo3 ndtgpu_pgo3;
 typedef struct {
     int32_t max_iterations;          /* Gauss-Newton updates at most (50) */
@@ -1017,6 +1017,73 @@ ndtgpu_status ndtgpu_pgo3_link_error(const double *Ti16, const double *Tj16, con
 ndtgpu_status ndtgpu_pgo3_retract(const double *T16, const double *d6, double *T16_out);
 /* a registered link as the factor takes it: Z16 = T16, W36 (row-major) from cov36 and flags as stated above; cov36 NULL: 100 * I6 */
 ndtgpu_status ndtgpu_pgo3_link_from_registration(const double *T16, const double *cov36, int32_t flags, double *Z16, double *W36);
+
+/* ---- the chip-wide form of the SE(3) optimiser: ONE large graph spread over the device -----------------------------------------
+ * ndtgpu_pgo3_optimize gives a graph to one workgroup of 512 threads: right for a bank of small graphs, wrong for the one large
+ * graph the offline mapper's loop optimises once per round.  ndtgpu_pgo3_optimize_wide optimises graph g of an ndtgpu_pgo3 bank
+ * alone with the same algorithm, operation for operation -- the per-link and per-node bodies are the same inlines of
+ * csrc/ndt_pgo3.h: linearisation per link with the prior as the link behind the last, gather and 6x6 Cholesky factor per node,
+ * preconditioned conjugate gradients from zero with the same break rules, the retraction with the roll-back to the last finite
+ * iterate, the same stop rule and exit codes -- so ndtgpu_pgo3_poses and ndtgpu_pgo_result mean the same, field for field;
+ * linear_iterations counts the inner iterations TAKEN, never the launches enqueued.  It is ndtgpu_pgo_optimize_wide's structure
+ * and shares its control block, tile, combiners and steering loop (csrc/ndt_pgo_wide_core.h), and its parameter struct
+ * (ndtgpu_pgo_wide_params, check_every).
+ * Launch structure (csrc/ndt_pgo3_wide.hip): a lane per link or per node, workgroups of 256 lanes, ONE PLAIN LAUNCH PER PASS on
+ * `stream`; the boundary between two launches is the only synchronisation: no grid barrier, no cooperative launch, no workgroup
+ * that waits for another, no spin on memory, no atomics, no captured graph.  The node passes run over n_nodes items, the link
+ * passes over n_edges + 1 -- item n_edges is the prior -- so link_tiles = ceil((n_edges + 1) / 256) is never 0 and no pass is
+ * skipped for a graph without links; the product pass does nothing for the prior, whose J^T W J p stays in node 0's lane.  Per
+ * Gauss-Newton update: ONE launch that gathers, factors and starts the solve (gather and start fit one kernel without a spill, so
+ * START is not split); THREE launches per inner iteration (a link pass that forms p = z + beta p of its two end nodes on the fly
+ * as one fma, a node pass that stores the same bits of p and gathers A p, a node pass for alpha, x, r and z); then the pose
+ * update, the linearisation and the cost assessment.  The run's scalars travel in the double-buffered control block; every
+ * launch begins by reading it and does nothing where its phase is over.  The host enqueues check_every inner iterations at a
+ * time, then copies the control block to pinned memory and waits for it (also after every cost assessment): the call is
+ * SYNCHRONOUS TOWARDS THE HOST and returns when the graph is done.  Launches enqueued past a stop do nothing.
+ * Summation rule: items are cut into tiles of 256 consecutive items (ndtgpu_pgo3_wide_plan), a tile's sum is taken by its
+ * workgroup in the order of csrc/ndt_block.h and stored per tile -- the cost and, beside it, the tile's count of half turns --;
+ * every workgroup that needs the graph's sum adds the per-tile sums in one fixed order (thread t takes t, t + 256, ... ascending,
+ * then the workgroup sum).  A node's incident links are summed in ascending link order by one lane.  The tiling follows the
+ * graph's n_nodes and n_edges alone: a graph's poses and result are the same bits for every check_every, whatever the bank's
+ * capacity, whatever the other graphs of the bank hold or have just run, and from run to run.  They are NOT the bits of
+ * ndtgpu_pgo3_optimize, which adds in another order (a thread's strided items, 512 threads) and leaves z + beta * p to the
+ * compiler: the two forms agree to rounding (tests/test_gpu_pgo3_wide.py).
+ * Exit codes as in ndtgpu_pgo3_optimize: a half turn at the FIRST linearisation gives NDTGPU_PGO3_HALF_TURN -- tested before the
+ * finiteness of the cost --, poses as set, iterations 0, cost_initial NaN; a half turn or a cost that is not finite later gives
+ * the roll-back and NDTGPU_PGO_NOT_FINITE; NDTGPU_PGO_LINEAR_CAP replaces 0 or 1 where an inner solve was capped.
+ * Two more device buffers (the per-tile sums and the control blocks, with a pinned mirror) are allocated by a handle's first
+ * wide call, for the handle's capacity, and released by ndtgpu_pgo3_destroy.
+ * Kernels (tools/kernel_resources.py pgo3_wide), each of 256 threads with the whole register file to itself: linearise 74 VGPRs,
+ * assess 18, start (gather, factor and the solve's start in one) 116, link 70, node 116, step 72, update 72; no VGPR spill, no
+ * SGPR spill, no scratch in any of them, 128 B of LDS each -- against the one-workgroup kernel's 228 VGPRs at 512 threads.
+ * Measured on MI355X (tools/pgo3_cost.py --wide; the graphs and defaults of the section above; one-workgroup form by device
+ * events, wide form by host wall time round the synchronous call, median of the repeats after a warm-up):
+ *   nodes / links   updates / inner iterations   one workgroup            wide, check_every 8 / 32 / 128       wide per inner iteration
+ *   500 / 1886      6 / 2433                    101.7 ms (41.8 us each)  64.9 / 61.9 / 64.1 ms  (1.6 x)       25.4 us
+ *   1500 / 8575     6 / 3992                    921 ms   (231 us each)   134.1 / 127.1 / 126.4 ms  (7.2 x)    31.8 us
+ *   5000 / 43 509   6 / 7534 (wide 7450)        9.98 s   (1325 us each)  455 / 446 / 443 ms  (22.4 x)         59.8 us
+ * (ratios at the default check_every, 32; every run converged with the same cost_final to the digits printed; the forms took
+ * the same updates, and the same inner iterations except at the replay's size).  THE REPLAY'S GRAPH TAKES 0.446 s IN PLACE OF
+ * 9.98 s.  Below 500 nodes, same graphs, same run, one workgroup against wide at check_every 32: 60 nodes / 195 links 8.5 against
+ * 11.8 ms, 125 / 416 20.3 against 26.5 ms, 200 / 710 31.2 against 35.4 ms, 250 / 906 38.9 against 40.9 ms, 350 / 1298 62.1
+ * against 50.8 ms: the forms cross between 250 and 350 nodes -- BELOW SOME 300 NODES (1.1 k links) ndtgpu_pgo3_optimize IS THE
+ * ONE TO CALL, and always for a bank of graphs, which it fills the chip with; above it the wide form.  At the replay's size the
+ * device, not the host, sets the pace: the three launches of an inner iteration run 8.3 + 42.9 + 6.6 us (link, node, step:
+ * rocprofv3 --kernel-trace, a run of its own); the node pass gathers some 17 links of 39 + 6 doubles per lane from 20
+ * workgroups.  START (gather, factor, start) runs 342 us, six times in the run; the linearisation 16 us. */
+/* pure host: the tile (256), the node and link tiles of a graph of this size -- link_tiles counts the prior, n_edges + 1 items --
+ * and the extra device bytes the wide form needs for it (8 per per-tile sum: four per node tile, two per link tile; and the two
+ * control blocks; a handle allocates them for its capacity).  NDTGPU_ERR_INVALID beyond ndtgpu_pgo3_create's limits (n_nodes
+ * 1 .. 2^24, n_edges <= 2^27).  Any out pointer may be NULL. */
+ndtgpu_status ndtgpu_pgo3_wide_plan(size_t n_nodes, size_t n_edges, uint32_t *tile, size_t *node_tiles, size_t *link_tiles,
+                                    size_t *extra_bytes);
+/* graph g alone, spread over the device; launches on `stream`; RETURNS WHEN THE GRAPH IS DONE (the host steers the phases).
+ * prm / wide NULL: the defaults.  The parameter checks of ndtgpu_pgo3_optimize and check_every >= 1, made before the handle is
+ * read and the device is looked for; NDTGPU_ERR_INVALID for a graph that has not been set or g out of range.  Calls on one
+ * handle stay ordered, whichever form and stream they name.  A graph that ends with NDTGPU_PGO_NOT_FINITE or
+ * NDTGPU_PGO3_HALF_TURN does not fail the call. */
+ndtgpu_status ndtgpu_pgo3_optimize_wide(ndtgpu_pgo3 *h, size_t g, const ndtgpu_pgo3_params *prm, const ndtgpu_pgo_wide_params *wide,
+                                        ndtgpu_stream stream);
 
 /* ---- world-map assembly: the node maps of a graph, under its poses, merged into one map -------------------------------------
  * The chain scans -> feature sets -> seeded links -> registered links -> optimised poses ends in node poses; the product the

@@ -11,7 +11,7 @@ _ROOT = os.path.dirname(_HERE)
 _SO = os.path.join(_HERE, "libndtgpu.so")
 _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hip", "ndt_pack.hip", "ndt_fuser.hip", "ndtgpu_api.hip",
             "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip",
-            "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndt_pgo_wide.hip", "ndtgpu_pgo.hip", "ndt_pgo3.hip", "ndtgpu_pgo3.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
+            "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndt_pgo_wide.hip", "ndtgpu_pgo.hip", "ndt_pgo3.hip", "ndt_pgo3_wide.hip", "ndtgpu_pgo3.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
             "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip", "ndt_occgrid.hip", "ndtgpu_occgrid.hip", "ndt_linkgate.hip",
             "ndtgpu_linkgate.hip", "ndt_fuserfeat.hip", "ndt_scanproject.hip", "ndtgpu_scanproject.hip",
             "ndt_calib.hip", "ndtgpu_calib.hip", "ndt_locmon.hip", "ndtgpu_locmon.hip", "ndt_scansim.hip", "ndtgpu_scansim.hip",
@@ -202,7 +202,7 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_default_pgo_wide_params", "ndtgpu_pgo_wide_plan", "ndtgpu_pgo_optimize_wide",
            "ndtgpu_default_pgo3_params", "ndtgpu_pgo3_create", "ndtgpu_pgo3_destroy", "ndtgpu_pgo3_set_graph",
            "ndtgpu_pgo3_set_links_device", "ndtgpu_pgo3_optimize", "ndtgpu_pgo3_poses", "ndtgpu_pgo3_link_error", "ndtgpu_pgo3_retract",
-           "ndtgpu_pgo3_link_from_registration",
+           "ndtgpu_pgo3_link_from_registration", "ndtgpu_pgo3_wide_plan", "ndtgpu_pgo3_optimize_wide",
            "ndtgpu_default_featmatch_params", "ndtgpu_featbank_create", "ndtgpu_featbank_destroy", "ndtgpu_featbank_set",
            "ndtgpu_featbank_match", "ndtgpu_featbank_match_device", "ndtgpu_featbank_results",
            "ndtgpu_default_featextract_params", "ndtgpu_featbank_extract", "ndtgpu_featbank_extract_device",
@@ -377,6 +377,9 @@ def lib():
     L.ndtgpu_pgo3_link_error.argtypes = [dp, dp, dp, dp, dp, dp]
     L.ndtgpu_pgo3_retract.argtypes = [dp, dp, dp]
     L.ndtgpu_pgo3_link_from_registration.argtypes = [dp, dp, C.c_int32, dp, dp]
+    L.ndtgpu_pgo3_wide_plan.argtypes = [C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_size_t)]
+    L.ndtgpu_pgo3_optimize_wide.argtypes = [vp, C.c_size_t, C.POINTER(Pgo3Params), C.POINTER(PgoWideParams), vp]
     L.ndtgpu_default_featmatch_params.restype = None
     L.ndtgpu_default_featmatch_params.argtypes = [C.POINTER(FeatMatchParams)]
     L.ndtgpu_featbank_create.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp)]
@@ -1405,6 +1408,14 @@ def pgo3_link_from_registration(T, cov36=None, flags=0):
     return _from_cm16(Z)[0], W
 
 
+def pgo3_wide_plan(n_nodes, n_edges):
+    """ndtgpu_pgo3_wide_plan -> (tile, node tiles, link tiles, extra device bytes) of a graph of this size; the link tiles count
+    the prior, the link behind the last"""
+    tile, nt, lt, extra = C.c_uint32(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+    _check(lib().ndtgpu_pgo3_wide_plan(int(n_nodes), int(n_edges), C.byref(tile), C.byref(nt), C.byref(lt), C.byref(extra)))
+    return tile.value, nt.value, lt.value, extra.value
+
+
 class PGO3(_Handle):
     """ndtgpu_pgo3: a bank of n_graphs SE(3) pose graphs of up to max_nodes nodes and max_edges links, optimised one workgroup per
     graph (include/ndtgpu.h: SE(3) pose-graph optimisation).  Poses are 4x4 matrices [n, 4, 4]."""
@@ -1457,6 +1468,12 @@ class PGO3(_Handle):
         count = self.n_graphs - first if count is None else int(count)
         p = pgo3_params(**params)
         _check(lib().ndtgpu_pgo3_optimize(self.h, int(first), count, C.byref(p), _stream_ptr(stream)))
+
+    def optimize_wide(self, g, stream=None, check_every=None, **params):
+        """graph g alone, spread over the device (ndtgpu_pgo3_optimize_wide): returns when the graph is done; check_every: inner
+        iterations enqueued between two looks at the control block (None: the default); keyword arguments: fields of ndtgpu_pgo3_params"""
+        p, w = pgo3_params(**params), pgo_wide_params(check_every)
+        _check(lib().ndtgpu_pgo3_optimize_wide(self.h, int(g), C.byref(p), C.byref(w), _stream_ptr(stream)))
 
     def poses(self, g):
         """(poses [n, 4, 4], result dict) of graph g; waits for the handle"""

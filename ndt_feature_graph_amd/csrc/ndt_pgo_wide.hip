@@ -10,7 +10,7 @@
 // ndt_block_sum.  The tiling follows n_nodes and n_edges alone, so the bits do not depend on the bank's capacity, the other
 // graphs, the CU count or the run.  A node's incident links are summed in ascending link order by one lane.
 //
-// CONTROL.  Every launch begins by reading the control block (ndt_pgo_wide.h: two copies, read one, write the other) and does
+// CONTROL.  Every launch begins by reading the control block (ndt_pgo_wide_core.h: two copies, read one, write the other) and does
 // nothing where its phase is over -- the solve has stopped, or the run has ended -- so the host may enqueue more inner
 // iterations than the solve takes and the result is the same bits.
 //
@@ -20,76 +20,9 @@
 //         the fly -- the fourth launch that would store the new search direction first is saved;
 //   NODE  per node: the same head (it is the one that records it), p = z + beta p stored, (A p)_i gathered, per-tile p.Ap;
 //   STEP  per node: combines p.Ap, alpha, x += alpha p, r -= alpha A p, z = D^-1 r, per-tile r.z and r.r.
+// The combiners of the per-tile sums, the control block's store and the head of an inner iteration are csrc/ndt_pgo_wide_core.h's.
 #include "ndt_pgo_wide.h"
 #include "ndt_block.h"
-
-typedef NdtBlockSums<NDT_PGO_WIDE_WAVES, 2> WideRed;
-
-// the graph's sums of N interleaved-by-stride partial arrays, in every thread
-template <int N>
-__device__ __forceinline__ void wide_combine(const double *part, unsigned tiles, double (&v)[N], WideRed &red, int &par)
-{
-#pragma unroll
-    for (int k = 0; k < N; k++) v[k] = 0.0;
-    for (unsigned t = threadIdx.x; t < tiles; t += NDT_PGO_WIDE_TILE) {
-#pragma unroll
-        for (int k = 0; k < N; k++) v[k] += part[(size_t)k * tiles + t];
-    }
-    ndt_block_sum(v, red, par);
-}
-
-__device__ __forceinline__ double wide_combine_max(const double *part, unsigned tiles, WideRed &red, int &par)
-{
-    double m = 0.0;
-    for (unsigned t = threadIdx.x; t < tiles; t += NDT_PGO_WIDE_TILE) m = fmax(m, part[t]);
-    return ndt_block_max(m, red, par);
-}
-
-// one lane of the launch writes the next control block, every word of it (ordinary stores)
-__device__ __forceinline__ void wide_store(const NdtPgoWide &W, const NdtPgoWideCtl &n)
-{
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    NdtPgoWideCtl *d = W.dst;
-    d->run_done = n.run_done;
-    d->solve_done = n.solve_done;
-    d->exit_code = n.exit_code;
-    d->iterations = n.iterations;
-    d->linear = n.linear;
-    d->any_capped = n.any_capped;
-    d->k = n.k;
-    d->pad_ = 0;
-    d->rz = n.rz;
-    d->tol2 = n.tol2;
-    d->cost = n.cost;
-    d->cost_initial = n.cost_initial;
-    d->max_step = n.max_step;
-    d->prior_cost = n.prior_cost;
-}
-
-// the new search direction of a node: z + beta p, the same bits in the link pass that uses it and the node pass that stores it
-__device__ __forceinline__ double wide_direction(double z, double beta, double p) { return fma(beta, p, z); }
-
-// The head of an inner iteration, from the per-tile r.z / r.r of the solve's start (k == 0) or of the step before: the break
-// rules of pgo_solve -- `rr > tol2`, then the cap -- and beta.
-struct WideHead {
-    bool stop, capped;
-    double beta, rz, tol2;
-};
-__device__ __forceinline__ WideHead wide_head(const NdtPgoWide &W, const NdtPgoWideCtl &c, WideRed &red, int &par)
-{
-    double dot[2];
-    wide_combine(W.part_dot, W.node_tiles, dot, red, par);
-    WideHead h;
-    h.rz = dot[0];
-    h.beta = 0.0;
-    h.tol2 = c.tol2;
-    if (c.k == 0) h.tol2 = W.prm.eps_linear * W.prm.eps_linear * dot[1];
-    else h.beta = dot[0] / c.rz;
-    h.capped = false;
-    h.stop = !(dot[1] > h.tol2);
-    if (!h.stop && c.k >= W.prm.max_linear_iterations) h.stop = h.capped = true;
-    return h;
-}
 
 __global__ __launch_bounds__(NDT_PGO_WIDE_TILE) void ndt_pgo_wide_linearise_kernel(NdtPgoWide W)
 {

@@ -230,9 +230,10 @@ ndtgpu_status ndtgpu_pgo_wide_plan(size_t n_nodes, size_t n_edges, uint32_t *til
     return NDTGPU_OK;
 }
 
-// The host steers the phases: it enqueues the passes of ndt_pgo_wide.hip on `stream` one launch each, and after every chunk of
-// check_every inner iterations -- and after every cost assessment -- copies the control block to pinned memory and waits for it.
-// Launches enqueued past a stop do nothing, so the result does not depend on check_every.
+// The host steers the phases (ndt_pgo_wide_steer, csrc/ndt_pgo_wide_core.h): it enqueues the passes of ndt_pgo_wide.hip on
+// `stream` one launch each, and after every chunk of check_every inner iterations -- and after every cost assessment -- copies
+// the control block to pinned memory and waits for it.  Launches enqueued past a stop do nothing, so the result does not depend
+// on check_every.
 ndtgpu_status ndtgpu_pgo_optimize_wide(ndtgpu_pgo *h, size_t g, const ndtgpu_pgo_params *prm, const ndtgpu_pgo_wide_params *wide,
                                        ndtgpu_stream stream)
 {
@@ -259,42 +260,15 @@ ndtgpu_status ndtgpu_pgo_optimize_wide(ndtgpu_pgo *h, size_t g, const ndtgpu_pgo
     W.part_step = W.part_pap + W.node_tiles;
     W.part_cost = W.part_step + W.node_tiles;
     W.out = v.state + g;
-    NdtPgoWideCtl *ctl = h->wide_ctl.get(), *mirror = h->wide_mirror.get();
-    int cur = 0;                           // which of the two control blocks holds the state
-    // a link pass reads the control block the node pass behind it reads; a node pass writes the other one
-    auto pass = [&](NdtPgoWidePass what) -> hipError_t {
-        const bool link = ndt_pgo_wide_is_link_pass(what);
-        if (link && !E) return hipSuccess;                   // (a launch with a grid of no workgroups is an error)
-        W.src = ctl + cur;
-        W.dst = ctl + (cur ^ 1);
-        const hipError_t e = ndt_pgo_wide_launch(what, W, st);
-        if (!link) cur ^= 1;
-        return e;
-    };
-    auto look = [&]() -> hipError_t {
-        const hipError_t e = hipMemcpyAsync(mirror, ctl + cur, sizeof *mirror, hipMemcpyDeviceToHost, st);
-        return e != hipSuccess ? e : hipStreamSynchronize(st);
+    // (a launch with a grid of no workgroups is an error: a graph without links has no link passes)
+    auto launch = [&](NdtPgoWidePass what, const NdtPgoWideCtl *src, NdtPgoWideCtl *dst) -> hipError_t {
+        if (ndt_pgo_wide_is_link_pass(what) && !E) return hipSuccess;
+        W.src = src;
+        W.dst = dst;
+        return ndt_pgo_wide_launch(what, W, st);
     };
     HIP_TRY(h->used.order(st));            // (the previous call may have run on another stream)
-    HIP_TRY(hipMemsetAsync(ctl, 0, 2 * sizeof *ctl, st));
-    HIP_TRY(pass(NDT_PGO_WIDE_LINEARISE));
-    HIP_TRY(pass(NDT_PGO_WIDE_ASSESS_FIRST));
-    HIP_TRY(look());
-    while (!mirror->run_done) {
-        HIP_TRY(pass(NDT_PGO_WIDE_START));
-        do {
-            for (int k = 0; k < wp.check_every; k++) {
-                HIP_TRY(pass(NDT_PGO_WIDE_LINK));
-                HIP_TRY(pass(NDT_PGO_WIDE_NODE));
-                HIP_TRY(pass(NDT_PGO_WIDE_STEP));
-            }
-            HIP_TRY(look());
-        } while (!mirror->solve_done && !mirror->run_done);
-        HIP_TRY(pass(NDT_PGO_WIDE_UPDATE));
-        HIP_TRY(pass(NDT_PGO_WIDE_LINEARISE));
-        HIP_TRY(pass(NDT_PGO_WIDE_ASSESS));
-        HIP_TRY(look());
-    }
+    HIP_TRY(ndt_pgo_wide_steer(launch, h->wide_ctl.get(), h->wide_mirror.get(), wp.check_every, st));
     HIP_TRY(h->used.record(st));
     return NDTGPU_OK;
 }

@@ -1,9 +1,12 @@
 // ndtgpu_pgo3.hip -- C-ABI (include/ndtgpu.h) of the SE(3) pose-graph optimiser: the back end of the 6-DoF links
 // (link.T and link.cov_3d, ndt_feature_graph.cpp:296-330) for a bank of independent graphs.  Host side only: the handle, the
 // checks of a graph (csrc/ndtgpu_pgo_graph.h, shared with the SE(2) bank), the adjacency and the order of the launches; the
-// optimisation runs in csrc/ndt_pgo3.hip.  The three pure host entries call the same inlines of csrc/ndt_pgo3.h as the kernel.
+// optimisation runs in csrc/ndt_pgo3.hip and, for one large graph spread over the device with the host steering the phases
+// (ndtgpu_pgo3_optimize_wide), in csrc/ndt_pgo3_wide.hip.  The three pure host entries call the same inlines of csrc/ndt_pgo3.h
+// as the kernels.
 #include "ndtgpu_host.h"
 #include "ndt_pgo3.h"
+#include "ndt_pgo3_wide.h"
 #include "ndtgpu_pgo_graph.h"
 
 struct ndtgpu_pgo3 {
@@ -14,6 +17,12 @@ struct ndtgpu_pgo3 {
     DeviceBuffer<int32_t> ref, mov;
     DeviceBuffer<uint32_t> adj_off, adj;
     std::vector<uint32_t> n_nodes;         // per graph, 0: not set
+    std::vector<uint32_t> n_edges;         // per graph
+    // the chip-wide form's own (ndtgpu_pgo3_optimize_wide), allocated by the handle's first wide call for the handle's capacity:
+    // per-tile partial sums, the two control blocks and their pinned mirror
+    DeviceBuffer<double> wide_part;
+    DeviceBuffer<NdtPgoWideCtl> wide_ctl;
+    PinnedBuffer<NdtPgoWideCtl> wide_mirror;
     Fence used;                            // recorded after the last launch of a call
     Stream hst;                            // the synchronous entries' stream (last: ndtgpu_resource.h)
 };
@@ -96,6 +105,7 @@ ndtgpu_status ndtgpu_pgo3_create(size_t n_graphs, size_t max_nodes, size_t max_e
     if (rc != NDTGPU_OK) return rc;
     h->G = n_graphs;
     h->n_nodes.assign(n_graphs, 0);
+    h->n_edges.assign(n_graphs, 0);
     NdtPgo3View &v = h->v;
     v.max_nodes = max_nodes;
     v.max_edges = max_edges;
@@ -142,6 +152,7 @@ static ndtgpu_status pgo3_install(ndtgpu_pgo3 *h, const char *what, size_t g, si
     st.n_edges = (int32_t)n_edges;
     const NdtPgo3View &v = h->v;
     h->n_nodes[g] = 0;
+    h->n_edges[g] = (uint32_t)n_edges;
     HIP_TRY(h->used.order(h->hst.get()));
     HIP_TRY(hipMemcpyAsync(v.pose + g * 12 * v.max_nodes, P.data(), P.size() * sizeof(double), hipMemcpyHostToDevice, h->hst.get()));
     HIP_TRY(hipMemcpyAsync(v.origin + g * 24, origin, sizeof origin, hipMemcpyHostToDevice, h->hst.get()));
@@ -232,6 +243,56 @@ ndtgpu_status ndtgpu_pgo3_poses(ndtgpu_pgo3 *h, size_t g, double *T16_out, ndtgp
         for (size_t i = 0; i < n; i++) pgo3_to_T16(&P[12 * i], T16_out + 16 * i);
     }
     if (result) HIP_TRY(hipMemcpy(result, h->v.state + g, sizeof *result, hipMemcpyDeviceToHost));
+    return NDTGPU_OK;
+}
+
+ndtgpu_status ndtgpu_pgo3_wide_plan(size_t n_nodes, size_t n_edges, uint32_t *tile, size_t *node_tiles, size_t *link_tiles, size_t *extra_bytes)
+{
+    if (n_nodes == 0 || n_nodes > (1u << 24) || n_edges > (1u << 27))
+        return fail(NDTGPU_ERR_INVALID, "pgo3_wide_plan: n_nodes must be 1 .. 2^24, n_edges <= 2^27");
+    if (tile) *tile = NDT_PGO_WIDE_TILE;
+    if (node_tiles) *node_tiles = ndt_pgo_wide_tiles(n_nodes);
+    if (link_tiles) *link_tiles = ndt_pgo3_wide_link_tiles(n_edges);
+    if (extra_bytes) *extra_bytes = ndt_pgo3_wide_partials(n_nodes, n_edges) * sizeof(double) + 2 * sizeof(NdtPgoWideCtl);
+    return NDTGPU_OK;
+}
+
+// The host steers the phases with the SE(2) wide form's loop (ndt_pgo_wide_steer, csrc/ndt_pgo_wide_core.h) over the passes of
+// ndt_pgo3_wide.hip.  Every pass is launched for every graph: the link passes run over E + 1 items, the prior included.
+ndtgpu_status ndtgpu_pgo3_optimize_wide(ndtgpu_pgo3 *h, size_t g, const ndtgpu_pgo3_params *prm, const ndtgpu_pgo_wide_params *wide,
+                                        ndtgpu_stream stream)
+{
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo3_optimize_wide: null handle");
+    const ndtgpu_pgo_wide_params wp = params_or_default(wide, ndtgpu_default_pgo_wide_params);
+    NdtPgo3Wide W{};
+    if (!pgo3_params_dev(prm, W.prm))
+        return fail(NDTGPU_ERR_INVALID, "pgo3_optimize_wide: bad parameter (caps and tolerances >= 0, a finite prior)");
+    if (wp.check_every < 1) return fail(NDTGPU_ERR_INVALID, "pgo3_optimize_wide: check_every must be >= 1");
+    if (g >= h->G || !h->n_nodes[g]) return fail(NDTGPU_ERR_INVALID, "pgo3_optimize_wide: no such graph, or it has not been set");
+    const NdtPgo3View &v = h->v;
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->wide_ctl.get()) {
+        HIP_TRY(h->wide_part.alloc(ndt_pgo3_wide_partials(v.max_nodes, v.max_edges)));
+        HIP_TRY(h->wide_mirror.alloc(1));
+        HIP_TRY(h->wide_ctl.alloc(2));
+    }
+    const size_t N = h->n_nodes[g], E = h->n_edges[g];
+    W.G = ndt_pgo3_graph(v, g, (unsigned)N, (unsigned)E);
+    W.node_tiles = (unsigned)ndt_pgo_wide_tiles(N);
+    W.link_tiles = (unsigned)ndt_pgo3_wide_link_tiles(E);
+    W.part_dot = h->wide_part.get();
+    W.part_pap = W.part_dot + 2 * (size_t)W.node_tiles;
+    W.part_step = W.part_pap + W.node_tiles;
+    W.part_cost = W.part_step + W.node_tiles;
+    W.out = v.state + g;
+    auto launch = [&](NdtPgoWidePass what, const NdtPgoWideCtl *src, NdtPgoWideCtl *dst) -> hipError_t {
+        W.src = src;
+        W.dst = dst;
+        return ndt_pgo3_wide_launch(what, W, st);
+    };
+    HIP_TRY(h->used.order(st));            // (the previous call may have run on another stream)
+    HIP_TRY(ndt_pgo_wide_steer(launch, h->wide_ctl.get(), h->wide_mirror.get(), wp.check_every, st));
+    HIP_TRY(h->used.record(st));
     return NDTGPU_OK;
 }
 

@@ -1052,9 +1052,10 @@ inline void optimizeGraphUsingISAM(NDTFeatureGraphInterface &graph, bool wide) {
 // force2D; a link's information is the inverse of its cov_3d (ndt_feature_graph.cpp:296-330) by
 // ndtgpu_pgo3_link_from_registration -- 50 * I6 where it does not invert, 100 * I6 for a link whose cov_3d is not 6x6; node 0's
 // pose is the prior; every link is taken once; the poses go back with setPose.  `links` are NDTFeatureLink because cov_3d is not
-// part of NDTFeatureLinkInterface.
+// part of NDTFeatureLinkInterface.  `wide`: the chip-wide form (ndtgpu_pgo3_optimize_wide: one launch per pass over the whole
+// device), the one to ask for for the mapper's one large graph; include/ndtgpu.h says where the two forms cross.
 inline void optimizeGraph3D(NDTFeatureGraphInterface &graph, const std::vector<NDTFeatureLink> &links,
-                            const ndtgpu_pgo3_params *params = nullptr, ndtgpu_pgo_result *result = nullptr)
+                            const ndtgpu_pgo3_params *params = nullptr, ndtgpu_pgo_result *result = nullptr, bool wide = false)
 {
     const size_t n = graph.getNbNodes(), m = links.size();
     if (n == 0) return;
@@ -1076,7 +1077,7 @@ inline void optimizeGraph3D(NDTFeatureGraphInterface &graph, const std::vector<N
     ndtgpu_pgo3 *h = nullptr;
     ndtgpu_host::check(ndtgpu_pgo3_create(1, n, m, &h), "ndtgpu_pgo3_create");
     ndtgpu_status rc = ndtgpu_pgo3_set_graph(h, 0, n, T16.data(), m, ref.data(), mov.data(), Z16.data(), W36.data());
-    if (rc == NDTGPU_OK) rc = ndtgpu_pgo3_optimize(h, 0, 1, params, nullptr);
+    if (rc == NDTGPU_OK) rc = wide ? ndtgpu_pgo3_optimize_wide(h, 0, params, nullptr, nullptr) : ndtgpu_pgo3_optimize(h, 0, 1, params, nullptr);
     ndtgpu_pgo_result r;
     if (rc == NDTGPU_OK) rc = ndtgpu_pgo3_poses(h, 0, T16.data(), &r);
     const std::string err = rc == NDTGPU_OK ? "" : ndtgpu_last_error();
@@ -1091,9 +1092,10 @@ inline void optimizeGraph3D(NDTFeatureGraphInterface &graph, const std::vector<N
 }
 
 // optimizeGraph3D(graph): the graph's own current links
-inline void optimizeGraph3D(NDTFeatureGraph &graph, const ndtgpu_pgo3_params *params = nullptr, ndtgpu_pgo_result *result = nullptr)
+inline void optimizeGraph3D(NDTFeatureGraph &graph, const ndtgpu_pgo3_params *params = nullptr, ndtgpu_pgo_result *result = nullptr,
+                            bool wide = false)
 {
-    optimizeGraph3D(graph, graph.getCurrentLinks(), params, result);
+    optimizeGraph3D(graph, graph.getCurrentLinks(), params, result, wide);
 }
 
 // The product of the mapper: ONE map from the graph's node maps under the node poses T -- graph->getMap() moved by getT()

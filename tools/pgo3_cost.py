@@ -9,7 +9,10 @@ NumPy model's time (tests/pgo3_model.py, dense solve) at 500 nodes on the same b
 lawn-mower trajectories over a grid of 0.5 m cells with noisy links to the nodes in the next rows -- lifted to 3D: a height that
 undulates by 0.3 m and roll and pitch of +-0.1 rad, started 0.2 m and 0.1 rad off in every component.  Every line carries the
 library's version.  Figures, not pass / fail.
-usage: python tools/pgo3_cost.py [--repeats R] [--skip-model] [--skip-replay]"""
+--wide: the chip-wide form (ndtgpu_pgo3_optimize_wide; host wall time round the synchronous call, the device idle before it) at
+check_every 8, 32 and 128 against the one-workgroup form (device events) in the same run, on one graph of 500, 1500 and 5000
+nodes: updates, inner iterations and us per inner iteration of both, and the ratio.
+usage: python tools/pgo3_cost.py [--repeats R] [--skip-model] [--skip-replay] [--wide]"""
 import argparse
 import json
 import math
@@ -60,14 +63,62 @@ def timed(graphs, repeats):
                 cost_initial=res[0]["cost_initial"], cost_final=res[0]["cost_final"], worst_position_error_m=err)
 
 
+def timed_wide(G, repeats, check_every):
+    """the chip-wide form of one graph: host wall time round the synchronous call, the device idle before it"""
+    import torch
+    bank = N.PGO3(1, G.n_nodes, G.n_edges)
+    st = torch.cuda.current_stream()
+    times = []
+    for _ in range(repeats + 1):                   # (the first run warms up)
+        bank.set_graph(0, G.poses, G.ref, G.mov, G.meas, G.info)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        bank.optimize_wide(0, stream=st, check_every=check_every)
+        times.append(1e3 * (time.perf_counter() - t))
+    T, r = bank.poses(0)
+    bank.close()
+    return times[1:], r, float(np.max(np.abs((T - G.truth)[:, :3, 3])))
+
+
+def report(case, form, clock, G, ms, repeats, r, err, **more):
+    """ms: (median, min, max)"""
+    print(json.dumps(dict(case=case, form=form, clock=clock, nodes=G.n_nodes, links=G.n_edges, ms_median=ms[0], ms_min=ms[1], ms_max=ms[2],
+                          repeats=repeats, iterations=r["iterations"], linear_iterations=r["linear_iterations"],
+                          us_per_inner_iteration=1e3 * ms[0] / max(r["linear_iterations"], 1), exit_code=r["exit_code"],
+                          cost_final=r["cost_final"], worst_position_error_m=err, **more)), flush=True)
+
+
+def wide_leg(repeats, skip_replay):
+    version = N.lib().ndtgpu_version().decode()
+    cases = [("500 nodes", pgo_cost.grid(20, 25, (1,), 1), repeats), ("1500 nodes", pgo_cost.grid(30, 50, (2,), 3), repeats)]
+    if not skip_replay:
+        cases.append(("replay size", pgo_cost.grid(50, 100, (2, 1), 2), max(1, repeats // 2)))
+    for k, (case, G2, reps) in enumerate(cases):
+        G = lift(G2, 7 + k)
+        one = timed([G], reps)
+        r1 = dict(iterations=one["iterations"][0], linear_iterations=one["linear_iterations_max"], exit_code=one["exit_codes"][0],
+                  cost_final=one["cost_final"])
+        report(case, "one workgroup", "device events", G, (one["ms_median"], one["ms_min"], one["ms_max"]), reps, r1,
+               one["worst_position_error_m"], version=version)
+        for every in (8, 32, 128):
+            t, r, err = timed_wide(G, repeats, every)
+            ms = (float(np.median(t)), float(np.min(t)), float(np.max(t)))
+            report(case, "wide", "host wall time", G, ms, repeats, r, err, check_every=every, ratio_to_one_workgroup=one["ms_median"] / ms[0],
+                   version=version)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--skip-replay", action="store_true")
+    ap.add_argument("--wide", action="store_true", help="both forms on one graph of 500, 1500 and 5000 nodes")
     a = ap.parse_args()
     if N.device_count() < 1:
         raise SystemExit("pgo3_cost: no HIP device (nothing to measure)")
+    if a.wide:
+        wide_leg(a.repeats, a.skip_replay)
+        return
     version = N.lib().ndtgpu_version().decode()
     cases = [("one graph of 500 nodes", [pgo_cost.grid(20, 25, (1,), 1)], a.repeats),
              ("256 graphs of 500 nodes", [pgo_cost.grid(20, 25, (1,), 100 + k) for k in range(256)], a.repeats)]
