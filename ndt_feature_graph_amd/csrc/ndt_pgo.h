@@ -7,6 +7,7 @@
 #pragma once
 #include "../../include/ndtgpu.h"
 #include "ndt_math.h"
+#include <string.h>                               // memcpy (ndt_pgo_acos, on the host side)
 
 #define NDT_PGO_THREADS 1024                      // one workgroup per graph
 #define NDT_PGO_WAVES (NDT_PGO_THREADS / 64)
@@ -36,9 +37,11 @@ struct NdtPgoView {
     double *node;                                 // [G][NDT_PGO_NODE_DOUBLES max_nodes]
 };
 
-// an angle in (-pi, pi]
+// an angle in (-pi, pi].  Without contraction: the device compiler made the last line one fma, the host's is a rounded product and
+// a sum, and the two differed in the last place for angles outside the interval (tests/test_pgo_direct.py holds them to the same bits).
 NDT_HD double ndt_pgo_wrap(double t)
 {
+#pragma clang fp contract(off)
     const double two_pi = 6.283185307179586;
     if (t > -3.141592653589793 && t <= 3.141592653589793) return t;
     return t + two_pi * floor((3.141592653589793 - t) / two_pi);
