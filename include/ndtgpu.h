@@ -1085,6 +1085,115 @@ ndtgpu_status ndtgpu_pgo3_wide_plan(size_t n_nodes, size_t n_edges, uint32_t *ti
 ndtgpu_status ndtgpu_pgo3_optimize_wide(ndtgpu_pgo3 *h, size_t g, const ndtgpu_pgo3_params *prm, const ndtgpu_pgo_wide_params *wide,
                                         ndtgpu_stream stream);
 
+/* ---- Marginal covariances of the pose-graph banks: the uncertainty of what ndtgpu_pgo_* / ndtgpu_pgo3_* estimated -----------
+ * The reference keeps a place for a node's covariance -- NDTFeatureNodeInterface::setCov beside setPose (interfaces.h:16),
+ * NDTFeatureNode::cov carried in NDTNodeMsg.cov (ndtgraph_conversion.h:51), drawn by markerMeanCovariance2d (ndt_rviz.h:1261) --
+ * but optimizeGraphUsingISAM (ndt_offline_mapper.h:101-104) only ever calls setPose: after optimisation a node's cov is whatever
+ * the fuser left there.  ndtgpu_pgo_marginals / ndtgpu_pgo3_marginals fill the place.
+ * Semantics (restated; both banks):
+ *   - at the poses graph g currently HOLDS -- as set, or after ndtgpu_pgo_optimize / _optimize_wide -- let H = sum J^T W J over
+ *     the prior and all links, with exactly the Jacobians, the symmetric part of W and the prior of the optimiser's
+ *     linearisation (the sections above).  The cost is sum e^T W e, so the covariance of the estimate is H^-1.
+ *   - a query names a graph, a node q and optionally a second node o.  cov is the symmetric part (B + B^T) / 2 of the diagonal
+ *     block B = (H^-1)[q, q]; cross, where asked, is the raw block (H^-1)[o, q]: the rows of o, the columns of q.
+ *   - SE(2): cov is 3x3 row-major in (x, y, yaw), the coordinates of the additive update p + d: the covariance of (x, y, yaw) IN
+ *     THE GRAPH'S FRAME.  SE(3): 6x6 row-major in (rho, phi), the coordinates of the local retraction T [+] d = (R Exp(phi),
+ *     t + R rho): the covariance lives IN THE NODE'S OWN TANGENT FRAME, translation part included.
+ *   - column k of block column q is the solution of H x = e_(q,k), found by the optimiser's own solve -- from zero, preconditioned
+ *     with the inverses of the diagonal blocks, to the relative residual eps_linear, at most max_linear_iterations, the pap > 0
+ *     break; the same operations in the same order.  The columns are independent recurrences.
+ *   - prior_information, eps_linear and max_linear_iterations come from the ndtgpu_pgo_params / ndtgpu_pgo3_params passed (NULL:
+ *     the defaults); the other fields are ignored.  prior_information HAS TO BE THE ONE THE GRAPH WAS OPTIMISED WITH: it is part
+ *     of H, and nothing records it with the graph.
+ *   - per query a record (ndtgpu_pgo_marginal_result).  exit_code reuses NDTGPU_PGO_*: CONVERGED; LINEAR_CAP: at least one column
+ *     stopped at the cap, the values are the iterates so far; NOT_FINITE: the linearisation's cost at the held poses is not finite,
+ *     cov and cross are NaN; NDTGPU_PGO3_HALF_TURN: the linearisation met a half turn, the outputs are NaN.  A graph at fault
+ *     does not fail the call or touch other graphs' queries.
+ *   - ndtgpu_pgo_relative_covariance / ndtgpu_pgo3_relative_covariance: the covariance of the error of a link ref -> mov whose
+ *     measurement is the current relative pose, J_ref S_rr J_ref^T + J_ref S_rm J_mov^T + J_mov S_mr J_ref^T + J_mov S_mm J_mov^T
+ *     with the link Jacobians of the sections above -- what a covariance-aware loop-closure gate would test.  On a tree it is the
+ *     link's W^-1; a loop makes it smaller.
+ * PROVENANCE: the reference never asks iSAM for covariances; this is the standard Gauss-Newton covariance of OUR OWN cost.
+ * DEVIATIONS:
+ *   - not iSAM's marginals (a sparse factorisation's back-substitution): each column is an iterative solve to eps_linear, so a
+ *     block is good to about eps_linear times the conditioning the preconditioner leaves, and B is symmetric only to that
+ *     (asymmetry reports it).
+ *   - with the host mirror's link doubling (ndt_offline_mapper.h:74-93; see above) every doubled link counts twice in H: the
+ *     covariances reflect the cost that was optimised, not the links' own covariances.
+ *   NOT BUILT: a chip-wide form (many workgroups per column) for the replay's 5000-node graph; a covariance-aware link gate;
+ *   covariance markers; moving an SE(3) block into the world frame.
+ * Device form (csrc/ndt_pgo.hip, csrc/ndt_pgo3.hip; pgo_solve / pgo3_solve and the inlines of csrc/ndt_pgo.h / ndt_pgo3.h called as
+ * they are): three plain launches on one stream -- no atomics, no grid barrier, no cooperative launch, no captured graph, no
+ * workgroup that waits for another.  PREPARE: one workgroup per distinct graph the call names linearises it and gathers the
+ * preconditioner into the marginals' OWN workspace through a graph view whose written pointers are redirected; the optimiser's
+ * scratch, the poses and the graph's ndtgpu_pgo_result are not touched.  SOLVE: one workgroup (1024 threads SE(2), 512 SE(3)) per
+ * (query, column) with b, x, r, z, p, Ap, t_e in the workgroup's slot of the workspace, b the unit vector; the slot is the
+ * workgroup's position in its launch, nothing is claimed at run time.  FINISH: a lane per query.  A call with more columns than
+ * the workspace has slots is cut into consecutive solve launches of at most `slots` workgroups (ndtgpu_pgo_marginal_plan); stream
+ * order lets a later launch reuse the slots.  A query's numbers are the same bits whatever the slot count, the number of
+ * launches, the other queries of the call, their order and the bank's other graphs are, and from run to run.  The workspace
+ * belongs to the handle: allocated by its first marginals call, regrown when a call needs more, released by ndtgpu_pgo_destroy /
+ * ndtgpu_pgo3_destroy.  Calls on a handle stay ordered with its optimise calls.
+ * Kernels (tools/kernel_resources.py pgo_marginals): SE(2) prepare 110 VGPRs, solve 92, 512 B of LDS; SE(3) prepare 132, solve 133
+ * (against ndt_pgo3_kernel's 228: the solve alone is the lighter pass), 256 B of LDS; none spills a VGPR or has scratch.
+ * Measured on MI355X, ndtgpu 0.13.0 (tools/pgo_marginals_cost.py: device events round the _device call, median of 7 after a
+ * warm-up; the grid-world graphs of tools/pgo_cost.py / pgo3_cost.py, 500 nodes and 1886 links, optimised first; defaults, so every
+ * column of a call in ONE solve launch).  SE(2): ALL 500 marginals of one graph, 1500 columns of at most 222 inner iterations
+ * (329 k together): 19.1 ms; the last node of each of 256 such graphs, 768 columns: 12.8 ms.  SE(3): all 500 marginals, 3000 columns
+ * of at most 412 iterations (1.23 M together): 322 ms; the last node of each of 256 graphs, 1536 columns: 275 ms.  Every query
+ * CONVERGED; the blocks are within 2.7e-10 (SE(3): 2.6e-10) of numpy.linalg.inv of the model's dense H, relative to each block's
+ * largest entry, and asymmetry is 1.0e-11 (2.9e-11) at most.  numpy.linalg.inv itself takes 40 ms for the 1500 x 1500 H and 151 ms
+ * for the 3000 x 3000 one on the same box: for EVERY marginal of ONE graph of this size the dense inverse on the host is as fast
+ * (SE(2)) or faster (SE(3), where a workgroup of 512 threads has a compute unit to itself and the 3000 columns take twelve turns);
+ * the device form is for a few nodes of many graphs -- 256 dense inverses take 10 s and 39 s --, for graphs whose dense H no
+ * longer fits the host's patience, and for results that stay on the device. */
+typedef struct {
+    uint64_t max_workspace_bytes;    /* the slots of a call take at most this much device memory, one slot at least (OURS: 1 GiB) */
+} ndtgpu_pgo_marginal_params;
+/* the default above is OURS */
+void ndtgpu_default_pgo_marginal_params(ndtgpu_pgo_marginal_params *p);
+typedef struct {
+    int32_t exit_code;               /* NDTGPU_PGO_CONVERGED, _LINEAR_CAP, _NOT_FINITE or NDTGPU_PGO3_HALF_TURN */
+    int32_t linear_iterations;       /* the inner iterations of the query's columns, together */
+    int32_t max_column_iterations;   /* ... of the column that took most */
+    int32_t capped_columns;          /* columns that stopped at max_linear_iterations */
+    double asymmetry;                /* max |B - B^T| of the raw diagonal block */
+} ndtgpu_pgo_marginal_result;
+/* pure host: the bytes of one slot for a bank of this capacity (dof 3: ndtgpu_pgo, 6: ndtgpu_pgo3), the slots a budget buys --
+ * slots >= 1 always, slots * slot_bytes <= max_workspace_bytes unless slots == 1, never more than the call has columns (one where
+ * it has none) -- and the solve launches the call takes, ceil(n_queries * dof / slots).  NDTGPU_ERR_INVALID beyond the limits of
+ * ndtgpu_pgo_create, for n_queries > 2^27 or for another dof.  Any out pointer may be NULL. */
+ndtgpu_status ndtgpu_pgo_marginal_plan(size_t max_nodes, size_t max_edges, size_t n_queries, int32_t dof, uint64_t max_workspace_bytes,
+                                       size_t *slot_bytes, size_t *slots, size_t *launches);
+/* n_queries >= 1 queries (graph_idx, node_idx, other_idx: HOST, n_queries each; other_idx NULL: no cross blocks, and cross9_out
+ * may be NULL).  cov9_out, cross9_out (n_queries x 9) and results_out (n_queries): HOST.  Synchronous.  prm / mprm NULL: the
+ * defaults.  NDTGPU_ERR_INVALID -- the outputs' and parameters' checks before the handle is read and the device is looked for --
+ * for NULL outputs or index arrays, eps_linear not finite or not positive, max_linear_iterations < 1, a prior that is not finite,
+ * a graph index out of range or not set, a node index >= n_nodes. */
+ndtgpu_status ndtgpu_pgo_marginals(ndtgpu_pgo *h, size_t n_queries, const uint32_t *graph_idx, const uint32_t *node_idx,
+                                   const uint32_t *other_idx, const ndtgpu_pgo_params *prm, const ndtgpu_pgo_marginal_params *mprm,
+                                   double *cov9_out, double *cross9_out, ndtgpu_pgo_marginal_result *results_out);
+/* ... the queries HOST and copied by the call, the outputs DEVICE, asynchronous on `stream` (the call waits for the handle's
+ * previous call before it overwrites the queries' pinned copy) */
+ndtgpu_status ndtgpu_pgo_marginals_device(ndtgpu_pgo *h, size_t n_queries, const uint32_t *graph_idx, const uint32_t *node_idx,
+                                          const uint32_t *other_idx, const ndtgpu_pgo_params *prm, const ndtgpu_pgo_marginal_params *mprm,
+                                          double *cov9_dev, double *cross9_dev, ndtgpu_pgo_marginal_result *results_dev, ndtgpu_stream stream);
+/* the same for a bank of SE(3) graphs, 36 doubles where the entries above have 9 */
+ndtgpu_status ndtgpu_pgo3_marginals(ndtgpu_pgo3 *h, size_t n_queries, const uint32_t *graph_idx, const uint32_t *node_idx,
+                                    const uint32_t *other_idx, const ndtgpu_pgo3_params *prm, const ndtgpu_pgo_marginal_params *mprm,
+                                    double *cov36_out, double *cross36_out, ndtgpu_pgo_marginal_result *results_out);
+ndtgpu_status ndtgpu_pgo3_marginals_device(ndtgpu_pgo3 *h, size_t n_queries, const uint32_t *graph_idx, const uint32_t *node_idx,
+                                           const uint32_t *other_idx, const ndtgpu_pgo3_params *prm, const ndtgpu_pgo_marginal_params *mprm,
+                                           double *cov36_dev, double *cross36_dev, ndtgpu_pgo_marginal_result *results_dev,
+                                           ndtgpu_stream stream);
+/* Pure host, no device needed; the Jacobians are those of the kernels' headers compiled for the host.  The covariance of the error
+ * of a link ref -> mov at Z = the current relative pose, from the two nodes' cov blocks and cross = the block [mov, ref] (rows of
+ * mov: ndtgpu_pgo_marginals with node = ref, other = mov).  pose_ref3 / pose_mov3: (x, y, yaw); Tref16 / Tmov16: column-major 4x4. */
+ndtgpu_status ndtgpu_pgo_relative_covariance(const double *pose_ref3, const double *pose_mov3, const double *cov_ref9, const double *cov_mov9,
+                                             const double *cross9, double *out9);
+ndtgpu_status ndtgpu_pgo3_relative_covariance(const double *Tref16, const double *Tmov16, const double *cov_ref36, const double *cov_mov36,
+                                              const double *cross36, double *out36);
+
 /* ---- world-map assembly: the node maps of a graph, under its poses, merged into one map -------------------------------------
  * The chain scans -> feature sets -> seeded links -> registered links -> optimised poses ends in node poses; the product the
  * reference's consumers use is ONE map: ndt_feature_mcl_node.cpp:174 localises in a single saved NDT map,

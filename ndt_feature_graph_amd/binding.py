@@ -203,6 +203,8 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_default_pgo3_params", "ndtgpu_pgo3_create", "ndtgpu_pgo3_destroy", "ndtgpu_pgo3_set_graph",
            "ndtgpu_pgo3_set_links_device", "ndtgpu_pgo3_optimize", "ndtgpu_pgo3_poses", "ndtgpu_pgo3_link_error", "ndtgpu_pgo3_retract",
            "ndtgpu_pgo3_link_from_registration", "ndtgpu_pgo3_wide_plan", "ndtgpu_pgo3_optimize_wide",
+           "ndtgpu_default_pgo_marginal_params", "ndtgpu_pgo_marginal_plan", "ndtgpu_pgo_marginals", "ndtgpu_pgo_marginals_device",
+           "ndtgpu_pgo3_marginals", "ndtgpu_pgo3_marginals_device", "ndtgpu_pgo_relative_covariance", "ndtgpu_pgo3_relative_covariance",
            "ndtgpu_default_featmatch_params", "ndtgpu_featbank_create", "ndtgpu_featbank_destroy", "ndtgpu_featbank_set",
            "ndtgpu_featbank_match", "ndtgpu_featbank_match_device", "ndtgpu_featbank_results",
            "ndtgpu_default_featextract_params", "ndtgpu_featbank_extract", "ndtgpu_featbank_extract_device",
@@ -380,6 +382,18 @@ def lib():
     L.ndtgpu_pgo3_wide_plan.argtypes = [C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                         C.POINTER(C.c_size_t)]
     L.ndtgpu_pgo3_optimize_wide.argtypes = [vp, C.c_size_t, C.POINTER(Pgo3Params), C.POINTER(PgoWideParams), vp]
+    L.ndtgpu_default_pgo_marginal_params.restype = None
+    L.ndtgpu_default_pgo_marginal_params.argtypes = [C.POINTER(PgoMarginalParams)]
+    L.ndtgpu_pgo_marginal_plan.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_int32, C.c_uint64, C.POINTER(C.c_size_t),
+                                           C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.ndtgpu_pgo_marginals.argtypes = [vp, C.c_size_t, u32p, u32p, u32p, C.POINTER(PgoParams), C.POINTER(PgoMarginalParams), dp, dp,
+                                       C.POINTER(PgoMarginalResult)]
+    L.ndtgpu_pgo_marginals_device.argtypes = [vp, C.c_size_t, u32p, u32p, u32p, C.POINTER(PgoParams), C.POINTER(PgoMarginalParams), vp, vp, vp, vp]
+    L.ndtgpu_pgo3_marginals.argtypes = [vp, C.c_size_t, u32p, u32p, u32p, C.POINTER(Pgo3Params), C.POINTER(PgoMarginalParams), dp, dp,
+                                        C.POINTER(PgoMarginalResult)]
+    L.ndtgpu_pgo3_marginals_device.argtypes = [vp, C.c_size_t, u32p, u32p, u32p, C.POINTER(Pgo3Params), C.POINTER(PgoMarginalParams), vp, vp, vp, vp]
+    L.ndtgpu_pgo_relative_covariance.argtypes = [dp, dp, dp, dp, dp, dp]
+    L.ndtgpu_pgo3_relative_covariance.argtypes = [dp, dp, dp, dp, dp, dp]
     L.ndtgpu_default_featmatch_params.restype = None
     L.ndtgpu_default_featmatch_params.argtypes = [C.POINTER(FeatMatchParams)]
     L.ndtgpu_featbank_create.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp)]
@@ -1294,10 +1308,104 @@ def pgo_wide_plan(n_nodes, n_edges):
     return tile.value, nt.value, et.value, extra.value
 
 
-class PGO(_Handle):
+class PgoMarginalParams(C.Structure):
+    _fields_ = [("max_workspace_bytes", C.c_uint64)]
+
+
+class PgoMarginalResult(C.Structure):
+    _fields_ = [("exit_code", C.c_int32), ("linear_iterations", C.c_int32), ("max_column_iterations", C.c_int32),
+                ("capped_columns", C.c_int32), ("asymmetry", C.c_double)]
+
+
+# ndtgpu_pgo_marginal_result as a NumPy record: what marginals() returns per query, and how to read a results_dev buffer
+PGO_MARGINAL_RESULT = np.dtype([("exit_code", np.int32), ("linear_iterations", np.int32), ("max_column_iterations", np.int32),
+                                ("capped_columns", np.int32), ("asymmetry", np.float64)])
+
+
+def pgo_marginal_params(max_workspace_bytes=None):
+    """ndtgpu_default_pgo_marginal_params, max_workspace_bytes replaced where given"""
+    p = PgoMarginalParams()
+    lib().ndtgpu_default_pgo_marginal_params(C.byref(p))
+    if max_workspace_bytes is not None:
+        p.max_workspace_bytes = int(max_workspace_bytes)
+    return p
+
+
+def pgo_marginal_plan(max_nodes, max_edges, n_queries, dof, max_workspace_bytes=None):
+    """ndtgpu_pgo_marginal_plan (pure host) -> (slot bytes, slots, solve launches) of a marginals call on a bank of this capacity;
+    dof 3: PGO, 6: PGO3; max_workspace_bytes None: the default budget"""
+    sb, sl, la = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    budget = pgo_marginal_params(max_workspace_bytes).max_workspace_bytes
+    _check(lib().ndtgpu_pgo_marginal_plan(int(max_nodes), int(max_edges), int(n_queries), int(dof), budget, C.byref(sb), C.byref(sl), C.byref(la)))
+    return sb.value, sl.value, la.value
+
+
+def pgo_relative_covariance(pose_ref, pose_mov, cov_ref, cov_mov, cross):
+    """ndtgpu_pgo_relative_covariance (pure host): the 3x3 covariance of the error of a link ref -> mov at the current relative
+    pose; poses (x, y, yaw), cross = the block [mov, ref] (marginals with node = ref, other = mov)"""
+    out = np.zeros((3, 3))
+    _check(lib().ndtgpu_pgo_relative_covariance(_dp(_f64(pose_ref).reshape(3)), _dp(_f64(pose_mov).reshape(3)), _dp(_f64(cov_ref).reshape(9)),
+                                                _dp(_f64(cov_mov).reshape(9)), _dp(_f64(cross).reshape(9)), _dp(out)))
+    return out
+
+
+def pgo3_relative_covariance(T_ref, T_mov, cov_ref, cov_mov, cross):
+    """ndtgpu_pgo3_relative_covariance (pure host): the 6x6 covariance of the error of a link ref -> mov at the current relative
+    pose; poses 4x4, cross = the block [mov, ref]"""
+    out = np.zeros((6, 6))
+    _check(lib().ndtgpu_pgo3_relative_covariance(_dp(_cm16(T_ref)), _dp(_cm16(T_mov)), _dp(_f64(cov_ref).reshape(36)),
+                                                 _dp(_f64(cov_mov).reshape(36)), _dp(_f64(cross).reshape(36)), _dp(out)))
+    return out
+
+
+class _Marginals:
+    """marginals / marginals_device of the two pose-graph banks (include/ndtgpu.h: marginal covariances); _dof, _marginals_fn,
+    _marginals_device_fn and _params_fn are the bank's"""
+
+    def _marginal_queries(self, graph_idx, node_idx, other_idx):
+        u32p = C.POINTER(C.c_uint32)
+        ni = np.ascontiguousarray(node_idx, dtype=np.uint32).reshape(-1)
+        gi = np.ascontiguousarray(np.broadcast_to(np.asarray(graph_idx, dtype=np.uint32), ni.shape))
+        oi = None if other_idx is None else np.ascontiguousarray(other_idx, dtype=np.uint32).reshape(-1)
+        if oi is not None and oi.shape != ni.shape:
+            raise ValueError("marginals: one other node per query")
+        return gi, ni, oi, gi.ctypes.data_as(u32p), ni.ctypes.data_as(u32p), None if oi is None else oi.ctypes.data_as(u32p)
+
+    def marginals(self, graph_idx, node_idx, other_idx=None, max_workspace_bytes=None, **params):
+        """(cov [n, dof, dof], cross [n, dof, dof] or None, results: PGO_MARGINAL_RESULT records [n]) of the queries (graph_idx: one
+        index or one per query; other_idx None: no cross blocks) at the poses the graphs hold; keyword arguments: fields of the
+        bank's params, of which prior_information -- the one the graph was optimised with --, eps_linear and max_linear_iterations
+        are read.  Waits for the result."""
+        gi, ni, oi, gp, np_, op = self._marginal_queries(graph_idx, node_idx, other_idx)
+        n, d = ni.shape[0], self._dof
+        cov = np.zeros((n, d, d))
+        cross = None if oi is None else np.zeros((n, d, d))
+        res = np.zeros(n, dtype=PGO_MARGINAL_RESULT)
+        p, mp = self._params_fn(**params), pgo_marginal_params(max_workspace_bytes)
+        _check(getattr(lib(), self._marginals_fn)(self.h, n, gp, np_, op, C.byref(p), C.byref(mp), _dp(cov), None if cross is None else _dp(cross),
+                                                  res.ctypes.data_as(C.POINTER(PgoMarginalResult))))
+        return cov, cross, res
+
+    def marginals_device(self, graph_idx, node_idx, other_idx, cov_dev, cross_dev, results_dev, stream=None, max_workspace_bytes=None, **params):
+        """the same into torch CUDA tensors, asynchronous on `stream`: cov_dev (and cross_dev unless other_idx is None) float64 with
+        n * dof * dof elements, results_dev uint8 with n * 24 bytes (read back: .cpu().numpy().view(PGO_MARGINAL_RESULT))"""
+        gi, ni, oi, gp, np_, op = self._marginal_queries(graph_idx, node_idx, other_idx)
+        n, d = ni.shape[0], self._dof
+        assert cov_dev.is_cuda and cov_dev.is_contiguous() and cov_dev.numel() * cov_dev.element_size() >= 8 * n * d * d
+        assert results_dev.is_cuda and results_dev.is_contiguous() and results_dev.numel() * results_dev.element_size() >= n * PGO_MARGINAL_RESULT.itemsize
+        if oi is not None:
+            assert cross_dev.is_cuda and cross_dev.is_contiguous() and cross_dev.numel() * cross_dev.element_size() >= 8 * n * d * d
+        p, mp = self._params_fn(**params), pgo_marginal_params(max_workspace_bytes)
+        _check(getattr(lib(), self._marginals_device_fn)(self.h, n, gp, np_, op, C.byref(p), C.byref(mp), C.c_void_p(cov_dev.data_ptr()),
+                                                         None if oi is None else C.c_void_p(cross_dev.data_ptr()),
+                                                         C.c_void_p(results_dev.data_ptr()), _stream_ptr(stream)))
+
+
+class PGO(_Handle, _Marginals):
     """ndtgpu_pgo: a bank of n_graphs SE(2) pose graphs of up to max_nodes nodes and max_edges links, optimised one workgroup per
     graph (include/ndtgpu.h: optimizeGraphUsingISAM).  Poses are (x, y, yaw) rows."""
     _destroy = "ndtgpu_pgo_destroy"
+    _dof, _marginals_fn, _marginals_device_fn, _params_fn = 3, "ndtgpu_pgo_marginals", "ndtgpu_pgo_marginals_device", staticmethod(pgo_params)
 
     def __init__(self, n_graphs, max_nodes, max_edges):
         h = C.c_void_p()
@@ -1416,10 +1524,11 @@ def pgo3_wide_plan(n_nodes, n_edges):
     return tile.value, nt.value, lt.value, extra.value
 
 
-class PGO3(_Handle):
+class PGO3(_Handle, _Marginals):
     """ndtgpu_pgo3: a bank of n_graphs SE(3) pose graphs of up to max_nodes nodes and max_edges links, optimised one workgroup per
     graph (include/ndtgpu.h: SE(3) pose-graph optimisation).  Poses are 4x4 matrices [n, 4, 4]."""
     _destroy = "ndtgpu_pgo3_destroy"
+    _dof, _marginals_fn, _marginals_device_fn, _params_fn = 6, "ndtgpu_pgo3_marginals", "ndtgpu_pgo3_marginals_device", staticmethod(pgo3_params)
 
     def __init__(self, n_graphs, max_nodes, max_edges):
         h = C.c_void_p()

@@ -15,6 +15,7 @@
 // per-graph scratch area in device memory (27 doubles per node, 7 per edge), LDS holds the reductions' partial sums.
 // The per-link and per-node bodies are inlines of ndt_pgo.h, shared with the chip-wide form for one large graph (ndt_pgo_wide.hip).
 #include "ndt_pgo.h"
+#include "ndt_pgo_marginals.h"
 #include "ndt_block.h"
 
 typedef NdtBlockSums<NDT_PGO_WAVES, 2> PgoRed;
@@ -169,6 +170,110 @@ __global__ void ndt_pgo_links_kernel(NdtPgoView v, size_t g, unsigned n_edges, c
     if (e >= n_edges) return;
     ndt_pgo_link_from_registration(T16 + 16 * (size_t)e, cov36 ? cov36 + 36 * (size_t)e : nullptr, (cov36 && flags) ? flags[e] : 0,
                                    v.meas + (g * v.max_edges + e) * 3, v.info + (g * v.max_edges + e) * 6);
+}
+
+// ---- marginal covariances (include/ndtgpu.h, ndtgpu_pgo_marginals): three plain launches that drive the passes above ----
+// Column k of block column q of H^-1 is the solution of H x = e_(q,k), and the columns of a call are independent: prepare
+// linearises each graph named once, into the marginals' own workspace; solve gives every column a workgroup and a slot and calls
+// pgo_solve as it is; finish symmetrises a lane per query.  Nothing is shared between workgroups except what prepare wrote, and
+// a workgroup's slot is its position in the launch: no atomics, no waiting, and a column's bits do not depend on what runs beside it.
+
+__global__ __launch_bounds__(NDT_PGO_THREADS) void ndt_pgo_marginal_prepare_kernel(NdtPgoView v, NdtPgoMarginalWork w, NdtPgoParamsDev prm)
+{
+    __shared__ PgoRed red;
+    int par = 0;
+    const size_t g = (size_t)w.area_graph[blockIdx.x];
+    const ndtgpu_pgo_result *st = v.state + g;
+    PgoGraph G = ndt_pgo_graph(v, g, (unsigned)st->n_nodes, (unsigned)st->n_edges);
+    ndt_pgo_marginal_area(G, w.areas + blockIdx.x * w.area_doubles, v.max_nodes, v.max_edges);
+    const double cost = pgo_linearise(G, prm, red, par);
+    pgo_gather(G, prm);
+    if (threadIdx.x == 0) w.verdict[blockIdx.x] = (cost - cost == 0.0) ? NDTGPU_PGO_CONVERGED : NDTGPU_PGO_NOT_FINITE;
+}
+
+__global__ __launch_bounds__(NDT_PGO_THREADS) void ndt_pgo_marginal_solve_kernel(NdtPgoView v, NdtPgoMarginalWork w, unsigned first,
+                                                                                 NdtPgoParamsDev prm)
+{
+    __shared__ PgoRed red;
+    int par = 0;
+    const unsigned col = first + blockIdx.x, q = col / 3, k = col % 3;
+    const NdtPgoMarginalQuery Q = w.query[q];
+    if (w.verdict[Q.area] != NDTGPU_PGO_CONVERGED) return;       // (the whole workgroup: finish writes NaN)
+    const ndtgpu_pgo_result *st = v.state + Q.graph;
+    PgoGraph G = ndt_pgo_graph(v, (size_t)Q.graph, (unsigned)st->n_nodes, (unsigned)st->n_edges);
+    ndt_pgo_marginal_slot(G, w.areas + Q.area * w.area_doubles, w.slots + blockIdx.x * w.slot_doubles, v.max_nodes, v.max_edges);
+    for (unsigned i = threadIdx.x; i < G.N; i += NDT_PGO_THREADS)
+        for (unsigned d = 0; d < 3; d++) G.b[3 * (size_t)i + d] = (i == (unsigned)Q.node && d == k) ? 1.0 : 0.0;
+    bool capped;
+    const int iterations = pgo_solve(G, prm, red, par, capped);  // (a node's b is read by the thread that wrote it)
+    __syncthreads();
+    double *raw = w.raw + 18 * (size_t)q;
+    if (threadIdx.x < 3) raw[3 * threadIdx.x + k] = G.x[3 * (size_t)Q.node + threadIdx.x];
+    else if (threadIdx.x < 6 && Q.other >= 0) raw[9 + 3 * (threadIdx.x - 3) + k] = G.x[3 * (size_t)Q.other + threadIdx.x - 3];
+    if (threadIdx.x == 0) w.col[col] = NdtPgoMarginalCol{iterations, capped ? 1 : 0};
+}
+
+// a lane per query (both banks: DOF is 3 or 6): the symmetric part of the raw diagonal block, its asymmetry, the raw cross block
+// and the record; NaN for a graph whose linearisation was not finite or met a half turn
+template <int DOF>
+__global__ void ndt_pgo_marginal_finish_kernel(NdtPgoMarginalWork w, double *cov, double *cross, ndtgpu_pgo_marginal_result *results)
+{
+    const unsigned q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= w.n_queries) return;
+    constexpr int NN = DOF * DOF;
+    const NdtPgoMarginalQuery Q = w.query[q];
+    const int verdict = w.verdict[Q.area];
+    const double *B = w.raw + 2 * NN * (size_t)q;
+    double *C = cov + NN * (size_t)q, *X = (cross && Q.other >= 0) ? cross + NN * (size_t)q : nullptr;
+    ndtgpu_pgo_marginal_result r;
+    r.exit_code = verdict;
+    r.linear_iterations = r.max_column_iterations = r.capped_columns = 0;
+    r.asymmetry = 0.0;
+    if (verdict != NDTGPU_PGO_CONVERGED) {
+        for (int k = 0; k < NN; k++) C[k] = NAN;
+        if (X)
+            for (int k = 0; k < NN; k++) X[k] = NAN;
+        r.asymmetry = NAN;
+    } else {
+#pragma unroll 1
+        for (int i = 0; i < DOF; i++)                    // (rolled: unrolled, the 6x6 block's 36 loads set the kernel's registers)
+            for (int j = 0; j < DOF; j++) {
+                C[DOF * i + j] = 0.5 * (B[DOF * i + j] + B[DOF * j + i]);
+                r.asymmetry = fmax(r.asymmetry, fabs(B[DOF * i + j] - B[DOF * j + i]));
+            }
+        if (X)
+            for (int k = 0; k < NN; k++) X[k] = B[NN + k];
+        for (int k = 0; k < DOF; k++) {
+            const NdtPgoMarginalCol c = w.col[DOF * (size_t)q + k];
+            r.linear_iterations += c.iterations;
+            r.max_column_iterations = c.iterations > r.max_column_iterations ? c.iterations : r.max_column_iterations;
+            r.capped_columns += c.capped;
+        }
+        if (r.capped_columns) r.exit_code = NDTGPU_PGO_LINEAR_CAP;
+    }
+    results[q] = r;
+}
+
+hipError_t ndt_pgo_marginal_launch_prepare(const NdtPgoView &v, const NdtPgoMarginalWork &w, size_t n_areas, const NdtPgoParamsDev &prm, hipStream_t st)
+{
+    hipLaunchKernelGGL(ndt_pgo_marginal_prepare_kernel, dim3((unsigned)n_areas), dim3(NDT_PGO_THREADS), 0, st, v, w, prm);
+    return hipGetLastError();
+}
+
+hipError_t ndt_pgo_marginal_launch_solve(const NdtPgoView &v, const NdtPgoMarginalWork &w, size_t first, size_t count, const NdtPgoParamsDev &prm,
+                                         hipStream_t st)
+{
+    hipLaunchKernelGGL(ndt_pgo_marginal_solve_kernel, dim3((unsigned)count), dim3(NDT_PGO_THREADS), 0, st, v, w, (unsigned)first, prm);
+    return hipGetLastError();
+}
+
+hipError_t ndt_pgo_marginal_launch_finish(const NdtPgoMarginalWork &w, int dof, double *cov_dev, double *cross_dev,
+                                          ndtgpu_pgo_marginal_result *results_dev, hipStream_t st)
+{
+    const dim3 grid((w.n_queries + 255) / 256), block(256);
+    if (dof == 3) hipLaunchKernelGGL(ndt_pgo_marginal_finish_kernel<3>, grid, block, 0, st, w, cov_dev, cross_dev, results_dev);
+    else hipLaunchKernelGGL(ndt_pgo_marginal_finish_kernel<6>, grid, block, 0, st, w, cov_dev, cross_dev, results_dev);
+    return hipGetLastError();
 }
 
 hipError_t ndt_pgo_launch(const NdtPgoView &v, size_t first, size_t count, const NdtPgoParamsDev &prm, hipStream_t st)

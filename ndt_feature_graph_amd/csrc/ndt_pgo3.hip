@@ -20,6 +20,7 @@
 // (tools/kernel_resources.py pgo3 prints the figures).  The gather sums its block in the node's scratch, not in registers, and
 // the linearisation stores each Jacobian block as soon as it is known, for the same reason.
 #include "ndt_pgo3.h"
+#include "ndt_pgo_marginals.h"
 #include "ndt_block.h"
 
 typedef NdtBlockSums<NDT_PGO3_WAVES, 2> Pgo3Red;
@@ -176,6 +177,60 @@ __global__ void ndt_pgo3_links_kernel(NdtPgo3View v, size_t g, unsigned n_edges,
     ndt_pgo3_link_from_registration(T16 + 16 * (size_t)e, cov36 ? cov36 + 36 * (size_t)e : nullptr, (cov36 && flags) ? flags[e] : 0, Z16, W36);
     pgo3_from_T16(Z16, v.meas + (g * v.max_edges + e) * 12);
     pgo3_sym21(W36, v.info + (g * v.max_edges + e) * 21);
+}
+
+// ---- marginal covariances (include/ndtgpu.h, ndtgpu_pgo3_marginals): the structure of csrc/ndt_pgo.hip's, with 6x6 blocks ----
+// prepare: one workgroup per graph named linearises it at the held poses into the marginals' own workspace; solve: one workgroup
+// and one slot per column, pgo3_solve as it is on the unit vector; finish: ndt_pgo_marginal_finish_kernel<6> (csrc/ndt_pgo.hip).
+
+__global__ __launch_bounds__(NDT_PGO3_THREADS) void ndt_pgo3_marginal_prepare_kernel(NdtPgo3View v, NdtPgoMarginalWork w, NdtPgo3ParamsDev prm)
+{
+    __shared__ Pgo3Red red;
+    int par = 0;
+    const size_t g = (size_t)w.area_graph[blockIdx.x];
+    const ndtgpu_pgo_result *st = v.state + g;
+    Pgo3Graph G = ndt_pgo3_graph(v, g, (unsigned)st->n_nodes, (unsigned)st->n_edges);
+    ndt_pgo3_marginal_area(G, w.areas + blockIdx.x * w.area_doubles, v.max_nodes, v.max_edges);
+    bool half;
+    const double cost = pgo3_linearise(G, prm, red, par, half);
+    for (unsigned i = threadIdx.x; i < G.N; i += NDT_PGO3_THREADS) pgo3_gather_node(G, prm, i);
+    if (threadIdx.x == 0)
+        w.verdict[blockIdx.x] = half ? NDTGPU_PGO3_HALF_TURN : (cost - cost == 0.0) ? NDTGPU_PGO_CONVERGED : NDTGPU_PGO_NOT_FINITE;
+}
+
+__global__ __launch_bounds__(NDT_PGO3_THREADS) void ndt_pgo3_marginal_solve_kernel(NdtPgo3View v, NdtPgoMarginalWork w, unsigned first,
+                                                                                   NdtPgo3ParamsDev prm)
+{
+    __shared__ Pgo3Red red;
+    int par = 0;
+    const unsigned col = first + blockIdx.x, q = col / 6, k = col % 6;
+    const NdtPgoMarginalQuery Q = w.query[q];
+    if (w.verdict[Q.area] != NDTGPU_PGO_CONVERGED) return;       // (the whole workgroup: finish writes NaN)
+    const ndtgpu_pgo_result *st = v.state + Q.graph;
+    Pgo3Graph G = ndt_pgo3_graph(v, (size_t)Q.graph, (unsigned)st->n_nodes, (unsigned)st->n_edges);
+    ndt_pgo3_marginal_slot(G, w.areas + Q.area * w.area_doubles, w.slots + blockIdx.x * w.slot_doubles, v.max_nodes, v.max_edges);
+    for (unsigned i = threadIdx.x; i < G.N; i += NDT_PGO3_THREADS)
+        for (unsigned d = 0; d < 6; d++) G.b[6 * (size_t)i + d] = (i == (unsigned)Q.node && d == k) ? 1.0 : 0.0;
+    bool capped;
+    const int iterations = pgo3_solve(G, prm, red, par, capped); // (a node's b is read by the thread that wrote it)
+    __syncthreads();
+    double *raw = w.raw + 72 * (size_t)q;
+    if (threadIdx.x < 6) raw[6 * threadIdx.x + k] = G.x[6 * (size_t)Q.node + threadIdx.x];
+    else if (threadIdx.x < 12 && Q.other >= 0) raw[36 + 6 * (threadIdx.x - 6) + k] = G.x[6 * (size_t)Q.other + threadIdx.x - 6];
+    if (threadIdx.x == 0) w.col[col] = NdtPgoMarginalCol{iterations, capped ? 1 : 0};
+}
+
+hipError_t ndt_pgo3_marginal_launch_prepare(const NdtPgo3View &v, const NdtPgoMarginalWork &w, size_t n_areas, const NdtPgo3ParamsDev &prm, hipStream_t st)
+{
+    hipLaunchKernelGGL(ndt_pgo3_marginal_prepare_kernel, dim3((unsigned)n_areas), dim3(NDT_PGO3_THREADS), 0, st, v, w, prm);
+    return hipGetLastError();
+}
+
+hipError_t ndt_pgo3_marginal_launch_solve(const NdtPgo3View &v, const NdtPgoMarginalWork &w, size_t first, size_t count,
+                                          const NdtPgo3ParamsDev &prm, hipStream_t st)
+{
+    hipLaunchKernelGGL(ndt_pgo3_marginal_solve_kernel, dim3((unsigned)count), dim3(NDT_PGO3_THREADS), 0, st, v, w, (unsigned)first, prm);
+    return hipGetLastError();
 }
 
 hipError_t ndt_pgo3_launch(const NdtPgo3View &v, size_t first, size_t count, const NdtPgo3ParamsDev &prm, hipStream_t st)

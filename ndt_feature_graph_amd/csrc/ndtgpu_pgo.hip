@@ -7,6 +7,7 @@
 #include "ndt_pgo.h"
 #include "ndt_pgo_wide.h"
 #include "ndtgpu_pgo_graph.h"
+#include "ndtgpu_pgo_marginals.h"
 
 struct ndtgpu_pgo {
     size_t G = 0;
@@ -22,6 +23,7 @@ struct ndtgpu_pgo {
     DeviceBuffer<double> wide_part;
     DeviceBuffer<NdtPgoWideCtl> wide_ctl;
     PinnedBuffer<NdtPgoWideCtl> wide_mirror;
+    PgoMarginalSpace marginal;             // the marginals' own workspace, allocated by the handle's first marginals call
     Fence used;                            // recorded after the last launch of a call
     Stream hst;                            // the synchronous entries' stream (last: ndtgpu_resource.h)
 };
@@ -271,6 +273,80 @@ ndtgpu_status ndtgpu_pgo_optimize_wide(ndtgpu_pgo *h, size_t g, const ndtgpu_pgo
     HIP_TRY(ndt_pgo_wide_steer(launch, h->wide_ctl.get(), h->wide_mirror.get(), wp.check_every, st));
     HIP_TRY(h->used.record(st));
     return NDTGPU_OK;
+}
+
+// ---- marginal covariances (csrc/ndtgpu_pgo_marginals.h holds what the two banks share) ----
+
+void ndtgpu_default_pgo_marginal_params(ndtgpu_pgo_marginal_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->max_workspace_bytes = (uint64_t)1 << 30;      // ours: every column of a 500-node graph of either bank in one launch
+}
+
+ndtgpu_status ndtgpu_pgo_marginal_plan(size_t max_nodes, size_t max_edges, size_t n_queries, int32_t dof, uint64_t max_workspace_bytes,
+                                       size_t *slot_bytes, size_t *slots, size_t *launches)
+{
+    size_t sb, sl, la;
+    if (!ndt_pgo_marginal_plan(max_nodes, max_edges, n_queries, dof, max_workspace_bytes, sb, sl, la))
+        return fail(NDTGPU_ERR_INVALID, "pgo_marginal_plan: dof must be 3 or 6, max_nodes 1 .. 2^24, max_edges and n_queries <= 2^27");
+    if (slot_bytes) *slot_bytes = sb;
+    if (slots) *slots = sl;
+    if (launches) *launches = la;
+    return NDTGPU_OK;
+}
+
+ndtgpu_status ndtgpu_pgo_relative_covariance(const double *pose_ref3, const double *pose_mov3, const double *cov_ref9, const double *cov_mov9,
+                                             const double *cross9, double *out9)
+{
+    if (!pose_ref3 || !pose_mov3 || !cov_ref9 || !cov_mov9 || !cross9 || !out9)
+        return fail(NDTGPU_ERR_INVALID, "pgo_relative_covariance: null argument");
+    ndt_pgo_relative_covariance(pose_ref3, pose_mov3, cov_ref9, cov_mov9, cross9, out9);
+    return NDTGPU_OK;
+}
+
+// the checks of a marginals call that need no handle, and the device form of its parameters
+static ndtgpu_status pgo_marginal_args(const char *who, size_t n_queries, const uint32_t *graph_idx, const uint32_t *node_idx,
+                                       const uint32_t *other_idx, const ndtgpu_pgo_params *prm, const void *cov, const void *cross,
+                                       const void *results, NdtPgoParamsDev &d)
+{
+    const ndtgpu_pgo_params p = params_or_default(prm, ndtgpu_default_pgo_params);
+    (void)pgo_params_dev(&p, d);           // (its verdict covers fields this call ignores: the three it reads are checked below)
+    bool finite = true;
+    for (double w : p.prior_information) finite = finite && std::isfinite(w);
+    return pgo_marginal_check_args(who, n_queries, graph_idx, node_idx, other_idx, cov, cross, results, p.eps_linear, p.max_linear_iterations, finite);
+}
+
+ndtgpu_status ndtgpu_pgo_marginals_device(ndtgpu_pgo *h, size_t n_queries, const uint32_t *graph_idx, const uint32_t *node_idx,
+                                          const uint32_t *other_idx, const ndtgpu_pgo_params *prm, const ndtgpu_pgo_marginal_params *mprm,
+                                          double *cov9_dev, double *cross9_dev, ndtgpu_pgo_marginal_result *results_dev, ndtgpu_stream stream)
+{
+    NdtPgoParamsDev d;
+    const ndtgpu_status rc = pgo_marginal_args("pgo_marginals_device", n_queries, graph_idx, node_idx, other_idx, prm, cov9_dev, cross9_dev, results_dev, d);
+    if (rc != NDTGPU_OK) return rc;
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo_marginals_device: null handle");
+    hipStream_t st = (hipStream_t)stream;
+    auto launch = [&](int phase, const NdtPgoMarginalWork &w, size_t first, size_t count) -> hipError_t {
+        return phase == 0 ? ndt_pgo_marginal_launch_prepare(h->v, w, count, d, st) : ndt_pgo_marginal_launch_solve(h->v, w, first, count, d, st);
+    };
+    HIP_TRY(h->used.order(st));            // (the previous call may have run on another stream)
+    return pgo_marginals_device_core<3>(h, h->marginal, "pgo_marginals_device", n_queries, graph_idx, node_idx, other_idx, mprm, cov9_dev,
+                                        cross9_dev, results_dev, st, launch);
+}
+
+ndtgpu_status ndtgpu_pgo_marginals(ndtgpu_pgo *h, size_t n_queries, const uint32_t *graph_idx, const uint32_t *node_idx,
+                                   const uint32_t *other_idx, const ndtgpu_pgo_params *prm, const ndtgpu_pgo_marginal_params *mprm,
+                                   double *cov9_out, double *cross9_out, ndtgpu_pgo_marginal_result *results_out)
+{
+    NdtPgoParamsDev d;
+    const ndtgpu_status rc = pgo_marginal_args("pgo_marginals", n_queries, graph_idx, node_idx, other_idx, prm, cov9_out, cross9_out, results_out, d);
+    if (rc != NDTGPU_OK) return rc;
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo_marginals: null handle");
+    return pgo_marginals_host_core<3>(h, h->marginal, "pgo_marginals", n_queries, other_idx != nullptr, cov9_out, cross9_out, results_out,
+                                      [&](double *cov_dev, double *cross_dev, ndtgpu_pgo_marginal_result *res_dev, hipStream_t st) {
+                                          return ndtgpu_pgo_marginals_device(h, n_queries, graph_idx, node_idx, other_idx, prm, mprm, cov_dev,
+                                                                             cross_dev, res_dev, (ndtgpu_stream)st);
+                                      });
 }
 
 }   // extern "C"

@@ -8,6 +8,7 @@
 #include "ndt_pgo3.h"
 #include "ndt_pgo3_wide.h"
 #include "ndtgpu_pgo_graph.h"
+#include "ndtgpu_pgo_marginals.h"
 
 struct ndtgpu_pgo3 {
     size_t G = 0;
@@ -23,6 +24,7 @@ struct ndtgpu_pgo3 {
     DeviceBuffer<double> wide_part;
     DeviceBuffer<NdtPgoWideCtl> wide_ctl;
     PinnedBuffer<NdtPgoWideCtl> wide_mirror;
+    PgoMarginalSpace marginal;             // the marginals' own workspace, allocated by the handle's first marginals call
     Fence used;                            // recorded after the last launch of a call
     Stream hst;                            // the synchronous entries' stream (last: ndtgpu_resource.h)
 };
@@ -294,6 +296,65 @@ ndtgpu_status ndtgpu_pgo3_optimize_wide(ndtgpu_pgo3 *h, size_t g, const ndtgpu_p
     HIP_TRY(ndt_pgo_wide_steer(launch, h->wide_ctl.get(), h->wide_mirror.get(), wp.check_every, st));
     HIP_TRY(h->used.record(st));
     return NDTGPU_OK;
+}
+
+// ---- marginal covariances (csrc/ndtgpu_pgo_marginals.h holds what the two banks share) ----
+
+ndtgpu_status ndtgpu_pgo3_relative_covariance(const double *Tref16, const double *Tmov16, const double *cov_ref36, const double *cov_mov36,
+                                              const double *cross36, double *out36)
+{
+    if (!Tref16 || !Tmov16 || !cov_ref36 || !cov_mov36 || !cross36 || !out36)
+        return fail(NDTGPU_ERR_INVALID, "pgo3_relative_covariance: null argument");
+    double Pr[12], Pm[12];
+    pgo3_from_T16(Tref16, Pr);
+    pgo3_from_T16(Tmov16, Pm);
+    if (!ndt_pgo3_relative_covariance(Pr, Pm, cov_ref36, cov_mov36, cross36, out36))
+        return fail(NDTGPU_ERR_INVALID, "pgo3_relative_covariance: the relative pose's residual is a half turn (poses that are not finite)");
+    return NDTGPU_OK;
+}
+
+// the checks of a marginals call that need no handle, and the device form of its parameters
+static ndtgpu_status pgo3_marginal_args(const char *who, size_t n_queries, const uint32_t *graph_idx, const uint32_t *node_idx,
+                                       const uint32_t *other_idx, const ndtgpu_pgo3_params *prm, const void *cov, const void *cross,
+                                       const void *results, NdtPgo3ParamsDev &d)
+{
+    const ndtgpu_pgo3_params p = params_or_default(prm, ndtgpu_default_pgo3_params);
+    (void)pgo3_params_dev(&p, d);          // (its verdict covers fields this call ignores: the three it reads are checked below)
+    bool finite = true;
+    for (double w : p.prior_information) finite = finite && std::isfinite(w);
+    return pgo_marginal_check_args(who, n_queries, graph_idx, node_idx, other_idx, cov, cross, results, p.eps_linear, p.max_linear_iterations, finite);
+}
+
+ndtgpu_status ndtgpu_pgo3_marginals_device(ndtgpu_pgo3 *h, size_t n_queries, const uint32_t *graph_idx, const uint32_t *node_idx,
+                                          const uint32_t *other_idx, const ndtgpu_pgo3_params *prm, const ndtgpu_pgo_marginal_params *mprm,
+                                          double *cov36_dev, double *cross36_dev, ndtgpu_pgo_marginal_result *results_dev, ndtgpu_stream stream)
+{
+    NdtPgo3ParamsDev d;
+    const ndtgpu_status rc = pgo3_marginal_args("pgo3_marginals_device", n_queries, graph_idx, node_idx, other_idx, prm, cov36_dev, cross36_dev, results_dev, d);
+    if (rc != NDTGPU_OK) return rc;
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo3_marginals_device: null handle");
+    hipStream_t st = (hipStream_t)stream;
+    auto launch = [&](int phase, const NdtPgoMarginalWork &w, size_t first, size_t count) -> hipError_t {
+        return phase == 0 ? ndt_pgo3_marginal_launch_prepare(h->v, w, count, d, st) : ndt_pgo3_marginal_launch_solve(h->v, w, first, count, d, st);
+    };
+    HIP_TRY(h->used.order(st));            // (the previous call may have run on another stream)
+    return pgo_marginals_device_core<6>(h, h->marginal, "pgo3_marginals_device", n_queries, graph_idx, node_idx, other_idx, mprm, cov36_dev,
+                                        cross36_dev, results_dev, st, launch);
+}
+
+ndtgpu_status ndtgpu_pgo3_marginals(ndtgpu_pgo3 *h, size_t n_queries, const uint32_t *graph_idx, const uint32_t *node_idx,
+                                   const uint32_t *other_idx, const ndtgpu_pgo3_params *prm, const ndtgpu_pgo_marginal_params *mprm,
+                                   double *cov36_out, double *cross36_out, ndtgpu_pgo_marginal_result *results_out)
+{
+    NdtPgo3ParamsDev d;
+    const ndtgpu_status rc = pgo3_marginal_args("pgo3_marginals", n_queries, graph_idx, node_idx, other_idx, prm, cov36_out, cross36_out, results_out, d);
+    if (rc != NDTGPU_OK) return rc;
+    if (!h) return fail(NDTGPU_ERR_INVALID, "pgo3_marginals: null handle");
+    return pgo_marginals_host_core<6>(h, h->marginal, "pgo3_marginals", n_queries, other_idx != nullptr, cov36_out, cross36_out, results_out,
+                                      [&](double *cov_dev, double *cross_dev, ndtgpu_pgo_marginal_result *res_dev, hipStream_t st) {
+                                          return ndtgpu_pgo3_marginals_device(h, n_queries, graph_idx, node_idx, other_idx, prm, mprm, cov_dev,
+                                                                             cross_dev, res_dev, (ndtgpu_stream)st);
+                                      });
 }
 
 }   // extern "C"

@@ -1010,8 +1010,11 @@ inline Eigen::Affine3d convertIsamPose2dToEigenAffine3d(const Pose2d &p)
 // additions: the stop rule's parameters (NULL: the defaults), the optimiser's report, and `wide`: the chip-wide form
 // (ndtgpu_pgo_optimize_wide: one launch per pass over the whole device), the one to ask for above some 600 nodes -- the mapper's
 // graph of thousands of nodes -- where the one-workgroup form leaves the chip idle.
-inline void optimizeGraphUsingISAM(NDTFeatureGraphInterface &graph, const ndtgpu_pgo_params *params = nullptr,
-                                   ndtgpu_pgo_result *result = nullptr, bool wide = false)
+namespace pgo_detail {
+// the body of optimizeGraphUsingISAM and of optimizeGraphUsingISAMWithCov: `marginals` (NULL: none) receives the nodes' records and
+// makes the call ask for every node's 3x3 block behind the optimisation, on the same handle, and hand it over with setCov
+inline void optimize_graph_se2(NDTFeatureGraphInterface &graph, const ndtgpu_pgo_params *params, ndtgpu_pgo_result *result, bool wide,
+                               std::vector<ndtgpu_pgo_marginal_result> *marginals)
 {
     const size_t n = graph.getNbNodes();
     if (n == 0) return;
@@ -1036,12 +1039,48 @@ inline void optimizeGraphUsingISAM(NDTFeatureGraphInterface &graph, const ndtgpu
     if (rc == NDTGPU_OK) rc = wide ? ndtgpu_pgo_optimize_wide(h, 0, params, nullptr, nullptr) : ndtgpu_pgo_optimize(h, 0, 1, params, nullptr);
     ndtgpu_pgo_result r;
     if (rc == NDTGPU_OK) rc = ndtgpu_pgo_poses(h, 0, pose.data(), nullptr, &r);
+    std::vector<double> cov9;
+    if (rc == NDTGPU_OK && marginals) {
+        std::vector<uint32_t> g(n, 0), q(n);
+        for (size_t i = 0; i < n; i++) q[i] = (uint32_t)i;
+        cov9.resize(9 * n);
+        marginals->resize(n);
+        rc = ndtgpu_pgo_marginals(h, n, g.data(), q.data(), nullptr, params, nullptr, cov9.data(), nullptr, marginals->data());
+    }
     const std::string err = rc == NDTGPU_OK ? "" : ndtgpu_last_error();
     ndtgpu_pgo_destroy(h);
     if (rc != NDTGPU_OK) throw ndtgpu_host::Error(rc, "optimizeGraphUsingISAM: " + err);
     if (result) *result = r;
-    for (size_t i = 0; i < n; i++)
+    for (size_t i = 0; i < n; i++) {
         graph.getNodeInterface(i).setPose(convertIsamPose2dToEigenAffine3d(Pose2d(pose[3 * i], pose[3 * i + 1], pose[3 * i + 2])));
+        if (marginals) {
+            Eigen::Matrix3d C;
+            for (int a = 0; a < 3; a++)
+                for (int b = 0; b < 3; b++) C(a, b) = cov9[9 * i + 3 * a + b];
+            graph.getNodeInterface(i).setCov(C);
+        }
+    }
+}
+}   // namespace pgo_detail
+
+inline void optimizeGraphUsingISAM(NDTFeatureGraphInterface &graph, const ndtgpu_pgo_params *params = nullptr,
+                                   ndtgpu_pgo_result *result = nullptr, bool wide = false)
+{
+    pgo_detail::optimize_graph_se2(graph, params, result, wide, nullptr);
+}
+
+// optimizeGraphUsingISAM, and what it leaves out upstream (ndt_offline_mapper.h:101-104 only ever calls setPose): the same
+// optimisation -- the same poses, bit for bit -- and then every node's marginal covariance through setCov
+// (NDTFeatureNodeInterface, interfaces.h:16): the 3x3 block of (x, y, yaw) in the graph's frame (include/ndtgpu.h "Marginal
+// covariances").  The link doubling above is part of the cost, so the covariances reflect it: a link with score < 0 counts twice.
+// `params` is used for both steps, as the marginals need the prior the graph was optimised with; `marginals` (NULL: not wanted)
+// receives a record per node.
+inline void optimizeGraphUsingISAMWithCov(NDTFeatureGraphInterface &graph, const ndtgpu_pgo_params *params = nullptr,
+                                          ndtgpu_pgo_result *result = nullptr, std::vector<ndtgpu_pgo_marginal_result> *marginals = nullptr,
+                                          bool wide = false)
+{
+    std::vector<ndtgpu_pgo_marginal_result> own;
+    pgo_detail::optimize_graph_se2(graph, params, result, wide, marginals ? marginals : &own);
 }
 
 // optimizeGraphUsingISAM(graph, wide): the defaults, in the form asked for
@@ -1054,8 +1093,11 @@ inline void optimizeGraphUsingISAM(NDTFeatureGraphInterface &graph, bool wide) {
 // pose is the prior; every link is taken once; the poses go back with setPose.  `links` are NDTFeatureLink because cov_3d is not
 // part of NDTFeatureLinkInterface.  `wide`: the chip-wide form (ndtgpu_pgo3_optimize_wide: one launch per pass over the whole
 // device), the one to ask for for the mapper's one large graph; include/ndtgpu.h says where the two forms cross.
-inline void optimizeGraph3D(NDTFeatureGraphInterface &graph, const std::vector<NDTFeatureLink> &links,
-                            const ndtgpu_pgo3_params *params = nullptr, ndtgpu_pgo_result *result = nullptr, bool wide = false)
+namespace pgo_detail {
+// the body of optimizeGraph3D and of optimizeGraph3DWithCov: `cov36` (NULL: none) receives every node's 6x6 block, row-major, asked
+// for behind the optimisation on the same handle, `marginals` (may be NULL) the nodes' records
+inline void optimize_graph_se3(NDTFeatureGraphInterface &graph, const std::vector<NDTFeatureLink> &links, const ndtgpu_pgo3_params *params,
+                               ndtgpu_pgo_result *result, bool wide, std::vector<double> *cov36, std::vector<ndtgpu_pgo_marginal_result> *marginals)
 {
     const size_t n = graph.getNbNodes(), m = links.size();
     if (n == 0) return;
@@ -1080,6 +1122,15 @@ inline void optimizeGraph3D(NDTFeatureGraphInterface &graph, const std::vector<N
     if (rc == NDTGPU_OK) rc = wide ? ndtgpu_pgo3_optimize_wide(h, 0, params, nullptr, nullptr) : ndtgpu_pgo3_optimize(h, 0, 1, params, nullptr);
     ndtgpu_pgo_result r;
     if (rc == NDTGPU_OK) rc = ndtgpu_pgo3_poses(h, 0, T16.data(), &r);
+    if (rc == NDTGPU_OK && cov36) {
+        std::vector<uint32_t> g(n, 0), q(n);
+        for (size_t i = 0; i < n; i++) q[i] = (uint32_t)i;
+        std::vector<ndtgpu_pgo_marginal_result> own;
+        std::vector<ndtgpu_pgo_marginal_result> &mr = marginals ? *marginals : own;
+        cov36->resize(36 * n);
+        mr.resize(n);
+        rc = ndtgpu_pgo3_marginals(h, n, g.data(), q.data(), nullptr, params, nullptr, cov36->data(), nullptr, mr.data());
+    }
     const std::string err = rc == NDTGPU_OK ? "" : ndtgpu_last_error();
     ndtgpu_pgo3_destroy(h);
     if (rc != NDTGPU_OK) throw ndtgpu_host::Error(rc, "optimizeGraph3D: " + err);
@@ -1089,6 +1140,23 @@ inline void optimizeGraph3D(NDTFeatureGraphInterface &graph, const std::vector<N
         std::copy_n(&T16[16 * i], 16, T.data());
         graph.getNodeInterface(i).setPose(T);
     }
+}
+}   // namespace pgo_detail
+
+inline void optimizeGraph3D(NDTFeatureGraphInterface &graph, const std::vector<NDTFeatureLink> &links,
+                            const ndtgpu_pgo3_params *params = nullptr, ndtgpu_pgo_result *result = nullptr, bool wide = false)
+{
+    pgo_detail::optimize_graph_se3(graph, links, params, result, wide, nullptr, nullptr);
+}
+
+// optimizeGraph3D, and beside it the nodes' 6x6 marginal covariances: cov36 receives n_nodes x 36 doubles, node i's block row-major
+// in (rho, phi) of the node's OWN tangent frame (include/ndtgpu.h "Marginal covariances"; NDTFeatureNodeInterface has no place for
+// a 6x6, so setCov is not called).  The poses are those of optimizeGraph3D, bit for bit; `params` is used for both steps.
+inline void optimizeGraph3DWithCov(NDTFeatureGraphInterface &graph, const std::vector<NDTFeatureLink> &links, std::vector<double> &cov36,
+                                   const ndtgpu_pgo3_params *params = nullptr, ndtgpu_pgo_result *result = nullptr,
+                                   std::vector<ndtgpu_pgo_marginal_result> *marginals = nullptr, bool wide = false)
+{
+    pgo_detail::optimize_graph_se3(graph, links, params, result, wide, &cov36, marginals);
 }
 
 // optimizeGraph3D(graph): the graph's own current links

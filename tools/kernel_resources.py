@@ -25,6 +25,8 @@ with tempfile.TemporaryDirectory() as d:
 GROUPS = {"pgo_wide": ["ndt_pgo_wide_linearise_kernel", "ndt_pgo_wide_assess_kernel", "ndt_pgo_wide_start_kernel", "ndt_pgo_wide_link_kernel",
                        "ndt_pgo_wide_node_kernel", "ndt_pgo_wide_step_kernel", "ndt_pgo_wide_update_kernel"],
           "pgo3": ["ndt_pgo3_kernel", "ndt_pgo3_links_kernel"],
+          "pgo_marginals": ["ndt_pgo_marginal_prepare_kernel", "ndt_pgo_marginal_solve_kernel", "ndt_pgo_marginal_finish_kernel",
+                            "ndt_pgo3_marginal_prepare_kernel", "ndt_pgo3_marginal_solve_kernel"],
           "pgo3_wide": ["ndt_pgo3_wide_linearise_kernel", "ndt_pgo3_wide_assess_kernel", "ndt_pgo3_wide_start_kernel", "ndt_pgo3_wide_link_kernel",
                         "ndt_pgo3_wide_node_kernel", "ndt_pgo3_wide_step_kernel", "ndt_pgo3_wide_update_kernel"],
           "calib": ["ndt_calib_prepare_kernel", "ndt_calib_score_kernel", "ndt_calib_finish_kernel", "ndt_calib_winner_kernel"],
