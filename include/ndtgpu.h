@@ -1194,6 +1194,126 @@ ndtgpu_status ndtgpu_pgo_relative_covariance(const double *pose_ref3, const doub
 ndtgpu_status ndtgpu_pgo3_relative_covariance(const double *Tref16, const double *Tmov16, const double *cov_ref36, const double *cov_mov36,
                                               const double *cross36, double *out36);
 
+/* ---- robust loop-closure weighting of the pose-graph banks: Huber, Cauchy, DCS -------------------------------------------------
+ * Links are seeded by feature RANSAC (ndtgpu_featbank_match*), refined by D2D and gated on score, distance and angle
+ * (ndtgpu_linkgate_valid: getValidLinks); whatever passes enters ndtgpu_pgo_* / ndtgpu_pgo3_* as a plain quadratic factor, and one
+ * perceptual-aliasing link bends the whole map.  ndtgpu_pgo_optimize_robust / ndtgpu_pgo3_optimize_robust optimise with a robust
+ * cost by ITERATIVELY RE-WEIGHTED LEAST SQUARES ROUND THE OPTIMISERS AS THEY ARE, and say which links were weighted down.
+ * Semantics (restated; both banks):
+ *   - W0 is a link's information AS THE GRAPH WAS SET (ndtgpu_pgo_set_graph / _set_links_device); chi2 = e^T W0 e with the link
+ *     error e of the sections above at the poses the graph holds.
+ *   - the weight w of a link from its chi2 and the scale (k, c or Phi):
+ *       Huber(k):    w = 1 where sqrt(chi2) <= k, else k / sqrt(chi2)
+ *       Cauchy(c):   w = 1 / (1 + chi2 / c^2)
+ *       DCS(Phi):    s = min(1, 2 Phi / (Phi + chi2)), w = s^2
+ *     written with +, -, *, / and a correctly rounded square root alone, without contraction: host (ndtgpu_pgo_robust_weight),
+ *     device and tests/pgo_robust_model.py give the same bits from the same chi2.
+ *   - the link's term of the robust cost: Huber chi2, or 2 k sqrt(chi2) - k^2 where sqrt(chi2) > k; Cauchy c^2 log(1 + chi2 / c^2);
+ *     DCS s^2 chi2 + Phi (1 - s)^2.  The robust cost of a graph is the sum of its links' terms: the prior is never re-weighted
+ *     and is not part of it (nor of chi2_final).
+ *   - links with |mov - ref| < min_index_gap keep w = 1, their information bits and the plain term chi2: at the default gap, 2, that
+ *     is the odometry chain.  The prior and the protected chain keep the system non-singular whatever the other weights are.
+ *   - a ROUND: at the poses the graph holds every link is weighed and w * W0 written into the bank's information; then the
+ *     unchanged ndtgpu_pgo_optimize (ndtgpu_pgo_optimize_wide where `wide` is given; the pgo3 pair) takes updates_per_round
+ *     Gauss-Newton updates with the weights frozen.  A graph stops CONVERGED when its optimiser call took at most one update and
+ *     that update's max_step <= eps_step; with MAX_ROUNDS -- the slot of NDTGPU_PGO_MAX_ITERATIONS -- after max_rounds rounds; or
+ *     with the inner call's NDTGPU_PGO_LINEAR_CAP / NDTGPU_PGO_NOT_FINITE / NDTGPU_PGO3_HALF_TURN passed through.  When a graph
+ *     stops its links are weighed once more at the poses it ends with: chi2, weight, inlier, cost_final, chi2_final and outliers
+ *     describe those poses, and THE BANK IS LEFT WEIGHTED with exactly these weights, so that ndtgpu_pgo_marginals /
+ *     ndtgpu_pgo3_marginals and ndtgpu_world_assemble see the robust problem.  ndtgpu_pgo_robust_restore puts W0 back.
+ *   - a chi2 (or weight) that is not finite -- a NaN input, an SE(3) half turn -- ends that graph with NDTGPU_PGO_NOT_FINITE /
+ *     NDTGPU_PGO3_HALF_TURN: that weighing is not applied to it, the graph holds W0 again, and the other graphs are unaffected.
+ *   - max_rounds = 0 only evaluates: chi2, weights, flags and the record at the held poses; the bank's poses, information and
+ *     optimiser records do not change (exit MAX_ROUNDS).  Like every weighing it overwrites the bank's per-link scratch (the
+ *     linearisation jac and te = W0 e, written by the optimiser's own per-link body): no entry reads that scratch before it has
+ *     linearised again, and nothing else may.
+ *   - a robust call always weighs the information as set, never the weighted one a previous robust call left: two robust calls
+ *     from the same poses give the same bits as one.  The copy of W0 is taken by the first robust call after a graph is set;
+ *     ndtgpu_pgo_set_graph / _set_links_device invalidate it.  A plain ndtgpu_pgo_optimize after a robust call runs on the
+ *     weighted information.
+ * PROVENANCE: the reference, and iSAM as it calls it (ndt_offline_mapper.h:40-107), have NO robust cost: every factor is a plain
+ * quadratic.  Huber's and Cauchy's M-estimators and dynamic covariance scaling (DCS; Agarwal et al., "Robust map optimization using
+ * dynamic covariance scaling", ICRA 2013) are restated from memory.
+ * DEVIATIONS:
+ *   - IRLS FREEZES THE WEIGHTS WITHIN A ROUND: the inner Gauss-Newton updates see a quadratic cost, not the robust cost's own
+ *     second derivative; DCS as published scales the error inside the factor at every linearisation, which is the same thing at
+ *     updates_per_round = 1.
+ *   - all defaults (ndtgpu_pgo_robust_params) and the stop rule are OURS.
+ *   NOT BUILT: a device-side stop without the host; optimize_gated (the binding) in 3D; switchable constraints; a covariance-aware
+ *   gate.
+ * Device form (csrc/ndt_pgo_robust.hip): per round and run of graphs two plain launches in front of the optimiser's.
+ * ndt_pgo_robust_weigh_kernel / ndt_pgo3_robust_weigh_kernel: grid (tiles of 256 links) x (graphs), a lane per link, the optimiser's
+ * own per-link inline (csrc/ndt_pgo.h, ndt_pgo3.h) through a graph view whose information is the copy of W0; it writes chi2,
+ * weight, inlier and w * W0 in the bank's layout, and per-tile sums (robust cost, chi2, links flagged out) taken in the order of
+ * csrc/ndt_block.h.  ndt_pgo_robust_finish_kernel / ndt_pgo3_robust_finish_kernel: one workgroup per graph adds the per-tile sums
+ * in the order of the wide form's combiner (thread t takes t, t + 256, ..., then the workgroup sum).  No atomics, no grid barrier,
+ * no workgroup that waits for another, no spin.  THE HOST STEERS THE ROUNDS, as the wide form's phases: after every round it reads
+ * the graphs' records and launches again for the graphs still active, in contiguous runs; a stopped graph gets no further launch
+ * that changes it.  Hence the call is SYNCHRONOUS TOWARDS THE HOST, and a graph's poses, weights and record are the same bits in
+ * any batch, at any first / count, for any bank capacity and from run to run; with `wide`, for every check_every.
+ * Seven more device buffers (the copy of W0, chi2, weight, inlier, the per-tile sums and counts, the graphs' sums) are allocated
+ * by a handle's first robust call, for its capacity, and released by ndtgpu_pgo_destroy / ndtgpu_pgo3_destroy.
+ * Measured on MI355X: NOT YET MEASURED (tools/pgo_robust_cost.py). */
+enum {
+    NDTGPU_PGO_ROBUST_HUBER = 1,
+    NDTGPU_PGO_ROBUST_CAUCHY = 2,
+    NDTGPU_PGO_ROBUST_DCS = 3
+};
+typedef struct {
+    int32_t kind;                    /* NDTGPU_PGO_ROBUST_* (OURS: DCS) */
+    int32_t max_rounds;              /* rounds at most; 0: evaluate only (OURS: 50) */
+    int32_t updates_per_round;       /* Gauss-Newton updates of a round's optimiser call, >= 1 (OURS: 1) */
+    int32_t min_index_gap;           /* links with |mov - ref| below this are never re-weighted, >= 1 (OURS: 2) */
+    double scale;                    /* k, c or Phi; finite and > 0 (OURS: 1) */
+    double inlier_weight;            /* a link is flagged an inlier where weight >= this; in [0, 1] (OURS: 0.5) */
+} ndtgpu_pgo_robust_params;
+void ndtgpu_default_pgo_robust_params(ndtgpu_pgo_robust_params *p);
+typedef struct {
+    int32_t exit_code;               /* NDTGPU_PGO_*, NDTGPU_PGO3_HALF_TURN; NDTGPU_PGO_MAX_ITERATIONS stands for MAX_ROUNDS */
+    int32_t rounds;                  /* rounds taken */
+    int32_t updates;                 /* Gauss-Newton updates, all rounds together */
+    int32_t linear_iterations;       /* conjugate-gradient iterations, all rounds together */
+    double cost_initial;             /* the robust cost at the poses as the call found them */
+    double cost_final;               /* ... at the poses returned */
+    double chi2_final;               /* the plain sum of the links' chi2 at the poses returned */
+    int32_t outliers;                /* links with weight < inlier_weight at the poses returned */
+    int32_t pad_;
+} ndtgpu_pgo_robust_result;
+/* pure host: the weight of a link from its chi2, the bits the device gives.  NDTGPU_ERR_INVALID for an unknown kind or a scale
+ * that is not finite and positive. */
+ndtgpu_status ndtgpu_pgo_robust_weight(int32_t kind, double scale, double chi2, double *weight);
+/* graphs [first, first + count), each of which has been set, from the poses they hold; launches on `stream`; RETURNS WHEN EVERY
+ * GRAPH HAS STOPPED (the host steers the rounds).  prm / robust NULL: the defaults; prm's max_iterations is not read
+ * (updates_per_round takes its place).  wide NULL: the one-workgroup form; otherwise ndtgpu_pgo_optimize_wide, which requires
+ * count == 1.  NDTGPU_ERR_INVALID -- checked before the handle is read and the device is looked for -- for an unknown kind, a
+ * scale that is not finite and positive, max_rounds < 0, updates_per_round < 1, min_index_gap < 1, inlier_weight outside [0, 1],
+ * and the parameter checks of ndtgpu_pgo_optimize / _optimize_wide.  A graph that ends with NDTGPU_PGO_NOT_FINITE does not fail
+ * the call. */
+ndtgpu_status ndtgpu_pgo_optimize_robust(ndtgpu_pgo *h, size_t first, size_t count, const ndtgpu_pgo_params *prm,
+                                         const ndtgpu_pgo_robust_params *robust, const ndtgpu_pgo_wide_params *wide, ndtgpu_stream stream);
+ndtgpu_status ndtgpu_pgo3_optimize_robust(ndtgpu_pgo3 *h, size_t first, size_t count, const ndtgpu_pgo3_params *prm,
+                                          const ndtgpu_pgo_robust_params *robust, const ndtgpu_pgo_wide_params *wide, ndtgpu_stream stream);
+/* what the last robust call left for graph g: chi2, weight (n_edges doubles each) and inlier (n_edges int32) HOST, and its
+ * record; any out pointer may be NULL.  NDTGPU_ERR_INVALID where no robust call has weighed the graph since it was set.  Waits
+ * for the handle. */
+ndtgpu_status ndtgpu_pgo_robust_links(ndtgpu_pgo *h, size_t g, double *chi2, double *weight, int32_t *inlier, ndtgpu_pgo_robust_result *result);
+ndtgpu_status ndtgpu_pgo3_robust_links(ndtgpu_pgo3 *h, size_t g, double *chi2, double *weight, int32_t *inlier, ndtgpu_pgo_robust_result *result);
+/* ... the DEVICE pointers of the same three arrays (the handle's own: valid until it is destroyed, overwritten by the next robust
+ * call on the graph); any out pointer may be NULL */
+ndtgpu_status ndtgpu_pgo_robust_links_device(ndtgpu_pgo *h, size_t g, const double **chi2_dev, const double **weight_dev, const int32_t **inlier_dev);
+ndtgpu_status ndtgpu_pgo3_robust_links_device(ndtgpu_pgo3 *h, size_t g, const double **chi2_dev, const double **weight_dev,
+                                              const int32_t **inlier_dev);
+/* A TEST AND INSPECTION AID, not part of the optimisation: it exists so that the bank's information can be compared bit for bit
+ * (tests/test_gpu_pgo_robust.py).  Graph g's information as the bank holds it -- as set, or weighted by a robust call -- in the
+ * bank's layout, HOST: SE(2) n_edges x 6,
+ * the symmetric 3x3 as (0,0) (0,1) (0,2) (1,1) (1,2) (2,2); SE(3) n_edges x 21, the lower triangle of the symmetric 6x6 row by row.
+ * Waits for the handle. */
+ndtgpu_status ndtgpu_pgo_link_information(ndtgpu_pgo *h, size_t g, double *W6_out);
+ndtgpu_status ndtgpu_pgo3_link_information(ndtgpu_pgo3 *h, size_t g, double *W21_out);
+/* the information as graph g was set back into the bank, bit for bit; nothing to do where no robust call has touched it.  Synchronous. */
+ndtgpu_status ndtgpu_pgo_robust_restore(ndtgpu_pgo *h, size_t g);
+ndtgpu_status ndtgpu_pgo3_robust_restore(ndtgpu_pgo3 *h, size_t g);
+
 /* ---- world-map assembly: the node maps of a graph, under its poses, merged into one map -------------------------------------
  * The chain scans -> feature sets -> seeded links -> registered links -> optimised poses ends in node poses; the product the
  * reference's consumers use is ONE map: ndt_feature_mcl_node.cpp:174 localises in a single saved NDT map,

@@ -11,7 +11,8 @@ _ROOT = os.path.dirname(_HERE)
 _SO = os.path.join(_HERE, "libndtgpu.so")
 _SOURCES = ["ndt_build.hip", "ndt_build_flat.hip", "ndt_match.hip", "ndt_fuse.hip", "ndt_pack.hip", "ndt_fuser.hip", "ndtgpu_api.hip",
             "ndtgpu_matcher.hip", "ndtgpu_registrar.hip", "ndtgpu_fuser_bank.hip", "ndt_multires.hip", "ndtgpu_multires.hip",
-            "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndt_pgo_wide.hip", "ndtgpu_pgo.hip", "ndt_pgo3.hip", "ndt_pgo3_wide.hip", "ndtgpu_pgo3.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
+            "ndt_mcl.hip", "ndtgpu_mcl.hip", "ndt_pgo.hip", "ndt_pgo_wide.hip", "ndtgpu_pgo.hip", "ndt_pgo3.hip", "ndt_pgo3_wide.hip", "ndtgpu_pgo3.hip",
+            "ndt_pgo_robust.hip", "ndtgpu_pgo_robust.hip", "ndt_featmatch.hip", "ndtgpu_featmatch.hip",
             "ndt_featextract.hip", "ndt_world.hip", "ndtgpu_world.hip", "ndt_occgrid.hip", "ndtgpu_occgrid.hip", "ndt_linkgate.hip",
             "ndtgpu_linkgate.hip", "ndt_fuserfeat.hip", "ndt_scanproject.hip", "ndtgpu_scanproject.hip",
             "ndt_calib.hip", "ndtgpu_calib.hip", "ndt_locmon.hip", "ndtgpu_locmon.hip", "ndt_scansim.hip", "ndtgpu_scansim.hip",
@@ -205,6 +206,9 @@ EXPORTS = ["ndtgpu_version", "ndtgpu_last_error", "ndtgpu_device_count", "ndtgpu
            "ndtgpu_pgo3_link_from_registration", "ndtgpu_pgo3_wide_plan", "ndtgpu_pgo3_optimize_wide",
            "ndtgpu_default_pgo_marginal_params", "ndtgpu_pgo_marginal_plan", "ndtgpu_pgo_marginals", "ndtgpu_pgo_marginals_device",
            "ndtgpu_pgo3_marginals", "ndtgpu_pgo3_marginals_device", "ndtgpu_pgo_relative_covariance", "ndtgpu_pgo3_relative_covariance",
+           "ndtgpu_default_pgo_robust_params", "ndtgpu_pgo_robust_weight", "ndtgpu_pgo_optimize_robust", "ndtgpu_pgo3_optimize_robust",
+           "ndtgpu_pgo_robust_links", "ndtgpu_pgo3_robust_links", "ndtgpu_pgo_robust_links_device", "ndtgpu_pgo3_robust_links_device",
+           "ndtgpu_pgo_robust_restore", "ndtgpu_pgo3_robust_restore", "ndtgpu_pgo_link_information", "ndtgpu_pgo3_link_information",
            "ndtgpu_default_featmatch_params", "ndtgpu_featbank_create", "ndtgpu_featbank_destroy", "ndtgpu_featbank_set",
            "ndtgpu_featbank_match", "ndtgpu_featbank_match_device", "ndtgpu_featbank_results",
            "ndtgpu_default_featextract_params", "ndtgpu_featbank_extract", "ndtgpu_featbank_extract_device",
@@ -394,6 +398,21 @@ def lib():
     L.ndtgpu_pgo3_marginals_device.argtypes = [vp, C.c_size_t, u32p, u32p, u32p, C.POINTER(Pgo3Params), C.POINTER(PgoMarginalParams), vp, vp, vp, vp]
     L.ndtgpu_pgo_relative_covariance.argtypes = [dp, dp, dp, dp, dp, dp]
     L.ndtgpu_pgo3_relative_covariance.argtypes = [dp, dp, dp, dp, dp, dp]
+    L.ndtgpu_default_pgo_robust_params.restype = None
+    L.ndtgpu_default_pgo_robust_params.argtypes = [C.POINTER(PgoRobustParams)]
+    L.ndtgpu_pgo_robust_weight.argtypes = [C.c_int32, C.c_double, C.c_double, dp]
+    L.ndtgpu_pgo_optimize_robust.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(PgoParams), C.POINTER(PgoRobustParams),
+                                             C.POINTER(PgoWideParams), vp]
+    L.ndtgpu_pgo3_optimize_robust.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(Pgo3Params), C.POINTER(PgoRobustParams),
+                                              C.POINTER(PgoWideParams), vp]
+    for fn in (L.ndtgpu_pgo_robust_links, L.ndtgpu_pgo3_robust_links):
+        fn.argtypes = [vp, C.c_size_t, dp, dp, i32p, C.POINTER(PgoRobustResult)]
+    for fn in (L.ndtgpu_pgo_robust_links_device, L.ndtgpu_pgo3_robust_links_device):
+        fn.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.ndtgpu_pgo_robust_restore.argtypes = [vp, C.c_size_t]
+    L.ndtgpu_pgo_link_information.argtypes = [vp, C.c_size_t, dp]
+    L.ndtgpu_pgo3_link_information.argtypes = [vp, C.c_size_t, dp]
+    L.ndtgpu_pgo3_robust_restore.argtypes = [vp, C.c_size_t]
     L.ndtgpu_default_featmatch_params.restype = None
     L.ndtgpu_default_featmatch_params.argtypes = [C.POINTER(FeatMatchParams)]
     L.ndtgpu_featbank_create.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp)]
@@ -1358,6 +1377,84 @@ def pgo3_relative_covariance(T_ref, T_mov, cov_ref, cov_mov, cross):
     return out
 
 
+class PgoRobustParams(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("max_rounds", C.c_int32), ("updates_per_round", C.c_int32), ("min_index_gap", C.c_int32),
+                ("scale", C.c_double), ("inlier_weight", C.c_double)]
+
+
+class PgoRobustResult(C.Structure):
+    _fields_ = [("exit_code", C.c_int32), ("rounds", C.c_int32), ("updates", C.c_int32), ("linear_iterations", C.c_int32),
+                ("cost_initial", C.c_double), ("cost_final", C.c_double), ("chi2_final", C.c_double), ("outliers", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+assert C.sizeof(PgoRobustParams) == 32 and C.sizeof(PgoRobustResult) == 48
+
+# ndtgpu_pgo_robust_params.kind (include/ndtgpu.h NDTGPU_PGO_ROBUST_*); PGO_MAX_ROUNDS: ndtgpu_pgo_robust_result.exit_code, the
+# slot of PGO_MAX_ITERATIONS
+PGO_ROBUST_HUBER, PGO_ROBUST_CAUCHY, PGO_ROBUST_DCS = 1, 2, 3
+PGO_MAX_ROUNDS = PGO_MAX_ITERATIONS
+_PGO_ROBUST_KINDS = {"huber": PGO_ROBUST_HUBER, "cauchy": PGO_ROBUST_CAUCHY, "dcs": PGO_ROBUST_DCS}
+
+
+def _pgo_robust_kind(kind):
+    return _PGO_ROBUST_KINDS[kind.lower()] if isinstance(kind, str) else int(kind)
+
+
+def pgo_robust_params(**fields):
+    """ndtgpu_default_pgo_robust_params with fields replaced; kind: PGO_ROBUST_* or "huber" / "cauchy" / "dcs" """
+    if "kind" in fields:
+        fields = dict(fields, kind=_pgo_robust_kind(fields["kind"]))
+    return _params(PgoRobustParams, "ndtgpu_default_pgo_robust_params", "PGO robust", fields)
+
+
+def pgo_robust_weight(kind, scale, chi2):
+    """ndtgpu_pgo_robust_weight (pure host): the weights of links from their chi2 (a number or an array), the device's bits"""
+    x = np.asarray(chi2, dtype=np.float64)
+    out = np.empty(x.size)
+    w = C.c_double()
+    for k, v in enumerate(x.ravel()):
+        _check(lib().ndtgpu_pgo_robust_weight(_pgo_robust_kind(kind), float(scale), float(v), C.byref(w)))
+        out[k] = w.value
+    return out.reshape(x.shape) if x.ndim else float(out[0])
+
+
+class _Robust:
+    """optimize_robust / robust_links / robust_restore of the two pose-graph banks (include/ndtgpu.h: robust loop-closure weighting);
+    _robust_fn, _robust_links_fn, _robust_restore_fn and _params_fn are the bank's"""
+
+    def optimize_robust(self, first=0, count=None, robust=None, wide=False, check_every=None, stream=None, **params):
+        """graphs [first, first + count) by iteratively re-weighted least squares round optimize (wide: optimize_wide, one graph);
+        returns when every graph has stopped.  robust: a dict of ndtgpu_pgo_robust_params fields or a PgoRobustParams (None: the
+        defaults); keyword arguments: fields of the bank's params.  The bank is left weighted: robust_restore(g) puts the
+        information as set back."""
+        count = self.n_graphs - first if count is None else int(count)
+        p = self._params_fn(**params)
+        rp = robust if isinstance(robust, PgoRobustParams) else pgo_robust_params(**(robust or {}))
+        w = pgo_wide_params(check_every) if wide else None
+        _check(getattr(lib(), self._robust_fn)(self.h, int(first), count, C.byref(p), C.byref(rp), None if w is None else C.byref(w),
+                                               _stream_ptr(stream)))
+
+    def robust_links(self, g):
+        """(chi2 [m], weight [m], inlier [m] bool, result dict) of graph g's m links as the last robust call left them"""
+        m = self._n_edges[int(g)]
+        chi2, weight, inlier = np.zeros(max(m, 1)), np.zeros(max(m, 1)), np.zeros(max(m, 1), dtype=np.int32)
+        r = PgoRobustResult()
+        _check(getattr(lib(), self._robust_links_fn)(self.h, int(g), _dp(chi2), _dp(weight), inlier.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(r)))
+        return chi2[:m], weight[:m], inlier[:m] != 0, {k: getattr(r, k) for k, _ in PgoRobustResult._fields_ if k != "pad_"}
+
+    def information(self, g):
+        """[m, 6] (PGO) or [m, 21] (PGO3): graph g's information as the bank holds it, in the bank's layout (include/ndtgpu.h)"""
+        m, k = self._n_edges[int(g)], 6 if self._dof == 3 else 21
+        out = np.zeros((max(m, 1), k))
+        _check(getattr(lib(), self._information_fn)(self.h, int(g), _dp(out)))
+        return out[:m]
+
+    def robust_restore(self, g):
+        """the information as graph g was set back into the bank"""
+        _check(getattr(lib(), self._robust_restore_fn)(self.h, int(g)))
+
+
 class _Marginals:
     """marginals / marginals_device of the two pose-graph banks (include/ndtgpu.h: marginal covariances); _dof, _marginals_fn,
     _marginals_device_fn and _params_fn are the bank's"""
@@ -1401,17 +1498,19 @@ class _Marginals:
                                                          C.c_void_p(results_dev.data_ptr()), _stream_ptr(stream)))
 
 
-class PGO(_Handle, _Marginals):
+class PGO(_Handle, _Marginals, _Robust):
     """ndtgpu_pgo: a bank of n_graphs SE(2) pose graphs of up to max_nodes nodes and max_edges links, optimised one workgroup per
     graph (include/ndtgpu.h: optimizeGraphUsingISAM).  Poses are (x, y, yaw) rows."""
     _destroy = "ndtgpu_pgo_destroy"
     _dof, _marginals_fn, _marginals_device_fn, _params_fn = 3, "ndtgpu_pgo_marginals", "ndtgpu_pgo_marginals_device", staticmethod(pgo_params)
+    _robust_fn, _robust_links_fn, _robust_restore_fn = "ndtgpu_pgo_optimize_robust", "ndtgpu_pgo_robust_links", "ndtgpu_pgo_robust_restore"
+    _information_fn = "ndtgpu_pgo_link_information"
 
     def __init__(self, n_graphs, max_nodes, max_edges):
         h = C.c_void_p()
         _check(lib().ndtgpu_pgo_create(int(n_graphs), int(max_nodes), int(max_edges), C.byref(h)))
         self.h, self.n_graphs = h, int(n_graphs)
-        self._n_nodes = [0] * int(n_graphs)
+        self._n_nodes, self._n_edges = [0] * int(n_graphs), [0] * int(n_graphs)
 
     @staticmethod
     def _graph(poses, ref, mov):
@@ -1431,7 +1530,7 @@ class PGO(_Handle, _Marginals):
         if z.shape[0] != ri.shape[0] or (W is not None and W.shape[0] != ri.shape[0]):
             raise ValueError("PGO.set_graph: one measurement (and information matrix) per link")
         _check(lib().ndtgpu_pgo_set_graph(self.h, int(g), ps.shape[0], _dp(ps), ri.shape[0], rp, mp, _dp(z), None if W is None else _dp(W)))
-        self._n_nodes[int(g)] = ps.shape[0]
+        self._n_nodes[int(g)], self._n_edges[int(g)] = ps.shape[0], ri.shape[0]
 
     def set_links_device(self, g, poses, ref, mov, T16_dev, cov36_dev=None, cov_flags_dev=None):
         """graph g with its links as ndtgpu_register_batch_cov_device left them: torch CUDA tensors T16_dev float64 [m, 16],
@@ -1445,7 +1544,7 @@ class PGO(_Handle, _Marginals):
         _check(lib().ndtgpu_pgo_set_links_device(self.h, int(g), ps.shape[0], _dp(ps), m, rp, mp, C.c_void_p(T16_dev.data_ptr()),
                                                  None if cov36_dev is None else C.c_void_p(cov36_dev.data_ptr()),
                                                  None if cov36_dev is None else C.c_void_p(cov_flags_dev.data_ptr())))
-        self._n_nodes[int(g)] = ps.shape[0]
+        self._n_nodes[int(g)], self._n_edges[int(g)] = ps.shape[0], ri.shape[0]
 
     def optimize(self, first=0, count=None, stream=None, **params):
         """graphs [first, first + count) in one launch, asynchronous on `stream`; keyword arguments: fields of ndtgpu_pgo_params"""
@@ -1524,17 +1623,19 @@ def pgo3_wide_plan(n_nodes, n_edges):
     return tile.value, nt.value, lt.value, extra.value
 
 
-class PGO3(_Handle, _Marginals):
+class PGO3(_Handle, _Marginals, _Robust):
     """ndtgpu_pgo3: a bank of n_graphs SE(3) pose graphs of up to max_nodes nodes and max_edges links, optimised one workgroup per
     graph (include/ndtgpu.h: SE(3) pose-graph optimisation).  Poses are 4x4 matrices [n, 4, 4]."""
     _destroy = "ndtgpu_pgo3_destroy"
     _dof, _marginals_fn, _marginals_device_fn, _params_fn = 6, "ndtgpu_pgo3_marginals", "ndtgpu_pgo3_marginals_device", staticmethod(pgo3_params)
+    _robust_fn, _robust_links_fn, _robust_restore_fn = "ndtgpu_pgo3_optimize_robust", "ndtgpu_pgo3_robust_links", "ndtgpu_pgo3_robust_restore"
+    _information_fn = "ndtgpu_pgo3_link_information"
 
     def __init__(self, n_graphs, max_nodes, max_edges):
         h = C.c_void_p()
         _check(lib().ndtgpu_pgo3_create(int(n_graphs), int(max_nodes), int(max_edges), C.byref(h)))
         self.h, self.n_graphs = h, int(n_graphs)
-        self._n_nodes = [0] * int(n_graphs)
+        self._n_nodes, self._n_edges = [0] * int(n_graphs), [0] * int(n_graphs)
 
     @staticmethod
     def _graph(poses, ref, mov):
@@ -1555,7 +1656,7 @@ class PGO3(_Handle, _Marginals):
         if z.shape[0] != ri.shape[0] or (W is not None and W.shape[0] != ri.shape[0]):
             raise ValueError("PGO3.set_graph: one measurement (and information matrix) per link")
         _check(lib().ndtgpu_pgo3_set_graph(self.h, int(g), ps.shape[0], _dp(ps), ri.shape[0], rp, mp, _dp(z), None if W is None else _dp(W)))
-        self._n_nodes[int(g)] = ps.shape[0]
+        self._n_nodes[int(g)], self._n_edges[int(g)] = ps.shape[0], ri.shape[0]
 
     def set_links_device(self, g, poses, ref, mov, T16_dev, cov36_dev=None, cov_flags_dev=None):
         """graph g with its links as ndtgpu_register_batch_cov_device left them: torch CUDA tensors T16_dev float64 [m, 16]
@@ -1570,7 +1671,7 @@ class PGO3(_Handle, _Marginals):
         _check(lib().ndtgpu_pgo3_set_links_device(self.h, int(g), ps.shape[0], _dp(ps), m, rp, mp, C.c_void_p(T16_dev.data_ptr()),
                                                   None if cov36_dev is None else C.c_void_p(cov36_dev.data_ptr()),
                                                   None if cov36_dev is None else C.c_void_p(cov_flags_dev.data_ptr())))
-        self._n_nodes[int(g)] = ps.shape[0]
+        self._n_nodes[int(g)], self._n_edges[int(g)] = ps.shape[0], ri.shape[0]
 
     def optimize(self, first=0, count=None, stream=None, **params):
         """graphs [first, first + count) in one launch, asynchronous on `stream`; keyword arguments: fields of ndtgpu_pgo3_params"""
@@ -1786,7 +1887,7 @@ class LinkGate(_Handle):
 
 
 def optimize_gated(pgo, g, gate, start_poses, incr_ref, incr_mov, incr_T16_dev, ref, mov, T16_dev, score_dev=None, cov36_dev=None,
-                   cov_flags_dev=None, max_rounds=10, pgo_fields=None, wide=False, **params):
+                   cov_flags_dev=None, max_rounds=10, pgo_fields=None, wide=False, robust=None, **params):
     """The offline mapper's loop (ndt_feature_graph_opt.cpp:152-173) on the device: every round sets the gate's nodes to the current
     poses, runs getValidLinks (gate.valid) over the matched links (ref, mov host arrays; T16_dev [m, 16], score_dev [m], cov36_dev
     [m, 36], cov_flags_dev [m] device tensors), gathers T16 / cov36 / flags of the links that stay behind the incremental links
@@ -1795,8 +1896,10 @@ def optimize_gated(pgo, g, gate, start_poses, incr_ref, incr_mov, incr_T16_dev, 
     It stops when the kept count repeats, when nothing is kept, or after max_rounds rounds -- max_rounds is OURS: upstream's loop
     has no cap and can oscillate between two link sets.  start_poses: [n, 3] (x, y, yaw).  **params: fields of
     ndtgpu_linkgate_params; pgo_fields: a dict of ndtgpu_pgo_params fields; wide: optimise with the chip-wide form
-    (PGO.optimize_wide), the one for a large graph.  Returns (kept index arrays per round, final poses
-    [n, 3])."""
+    (PGO.optimize_wide), the one for a large graph; robust: None -- the plain optimiser, call for call as before -- or a dict of
+    ndtgpu_pgo_robust_params fields ({} for the defaults): every round optimises with PGO.optimize_robust instead, so a false
+    closure the gate lets through is weighted down (PGO.robust_links(g) tells which, in the order incremental + kept of the last
+    round).  Returns (kept index arrays per round, final poses [n, 3])."""
     import torch
     poses = _f64(start_poses).reshape(-1, 3).copy()
     n = poses.shape[0]
@@ -1832,7 +1935,9 @@ def optimize_gated(pgo, g, gate, start_poses, incr_ref, incr_mov, incr_T16_dev, 
             break
         torch.cuda.synchronize()                         # (the gathers ran on torch's stream; set_links_device takes complete arrays)
         pgo.set_links_device(g, poses, np.concatenate([iref, ref[kept]]), np.concatenate([imov, mov[kept]]), T_all, cov_all, flags_all)
-        if wide:
+        if robust is not None:
+            pgo.optimize_robust(g, 1, robust=robust, wide=wide, **(pgo_fields or {}))
+        elif wide:
             pgo.optimize_wide(g, **(pgo_fields or {}))
         else:
             pgo.optimize(g, 1, **(pgo_fields or {}))

@@ -8,45 +8,7 @@
 #include "ndt_pgo_wide.h"
 #include "ndtgpu_pgo_graph.h"
 #include "ndtgpu_pgo_marginals.h"
-
-struct ndtgpu_pgo {
-    size_t G = 0;
-    NdtPgoView v{};                        // what the kernels receive: filled from the owners below at create
-    DeviceBuffer<ndtgpu_pgo_result> state;
-    DeviceBuffer<double> pose, origin, meas, info, jac, te, node;
-    DeviceBuffer<int32_t> ref, mov;
-    DeviceBuffer<uint32_t> adj_off, adj;
-    std::vector<uint32_t> n_nodes;         // per graph, 0: not set
-    std::vector<uint32_t> n_edges;         // per graph
-    // the chip-wide form's own (ndtgpu_pgo_optimize_wide), allocated by the handle's first wide call for the handle's capacity:
-    // per-tile partial sums, the two control blocks and their pinned mirror
-    DeviceBuffer<double> wide_part;
-    DeviceBuffer<NdtPgoWideCtl> wide_ctl;
-    PinnedBuffer<NdtPgoWideCtl> wide_mirror;
-    PgoMarginalSpace marginal;             // the marginals' own workspace, allocated by the handle's first marginals call
-    Fence used;                            // recorded after the last launch of a call
-    Stream hst;                            // the synchronous entries' stream (last: ndtgpu_resource.h)
-};
-
-static void sym6(const double *W9, double *W6)
-{
-    W6[0] = W9[0]; W6[1] = 0.5 * (W9[1] + W9[3]); W6[2] = 0.5 * (W9[2] + W9[6]);
-    W6[3] = W9[4]; W6[4] = 0.5 * (W9[5] + W9[7]); W6[5] = W9[8];
-}
-
-// the device form of a call's parameters (NULL: the defaults); false where one is out of range
-static bool pgo_params_dev(const ndtgpu_pgo_params *prm, NdtPgoParamsDev &d)
-{
-    const ndtgpu_pgo_params p = params_or_default(prm, ndtgpu_default_pgo_params);
-    bool ok = p.max_iterations >= 0 && p.max_linear_iterations >= 0 && p.eps_step >= 0.0 && p.eps_linear >= 0.0;   // (NaN fails)
-    for (double w : p.prior_information) ok = ok && std::isfinite(w);
-    d.max_iterations = p.max_iterations;
-    d.max_linear_iterations = p.max_linear_iterations;
-    d.eps_step = p.eps_step;
-    d.eps_linear = p.eps_linear;
-    sym6(p.prior_information, d.prior);
-    return ok;
-}
+#include "ndtgpu_pgo_bank.h"           // the handle, the device form of the parameters
 
 extern "C" {
 
@@ -119,6 +81,7 @@ static ndtgpu_status pgo_install(ndtgpu_pgo *h, const char *what, size_t g, size
     const NdtPgoView &v = h->v;
     h->n_nodes[g] = 0;
     h->n_edges[g] = (uint32_t)n_edges;
+    h->robust.invalidate(g);               // (the robust calls' copy of the information as set)
     HIP_TRY(h->used.order(h->hst.get()));
     HIP_TRY(hipMemcpyAsync(v.pose + g * 3 * v.max_nodes, pose3, 3 * n_nodes * sizeof(double), hipMemcpyHostToDevice, h->hst.get()));
     HIP_TRY(hipMemcpyAsync(v.origin + g * 3, pose3, 3 * sizeof(double), hipMemcpyHostToDevice, h->hst.get()));

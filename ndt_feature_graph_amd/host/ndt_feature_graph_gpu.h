@@ -1166,6 +1166,90 @@ inline void optimizeGraph3D(NDTFeatureGraph &graph, const ndtgpu_pgo3_params *pa
     optimizeGraph3D(graph, graph.getCurrentLinks(), params, result, wide);
 }
 
+// optimizeGraphUsingISAM with a robust cost (include/ndtgpu.h "robust loop-closure weighting": Huber, Cauchy or DCS by iteratively
+// re-weighted least squares round the same optimiser), for the wrong loop closure that getValidLinks lets through.  The factors
+// are those of optimizeGraphUsingISAM, the doubling included; links between nodes closer than robust->min_index_gap -- the
+// incremental links -- are never re-weighted.  link_weights_out (NULL: not wanted) receives one weight per link of the graph, in
+// the graph's order: 1 for a link the optimisation trusted, towards 0 for one it weighted down.  `robust` NULL: the defaults (DCS,
+// Phi = 1); `result` the robust call's report.
+inline void optimizeGraphUsingISAMRobust(NDTFeatureGraphInterface &graph, const ndtgpu_pgo_robust_params *robust = nullptr,
+                                         std::vector<double> *link_weights_out = nullptr, const ndtgpu_pgo_params *params = nullptr,
+                                         ndtgpu_pgo_robust_result *result = nullptr, bool wide = false)
+{
+    const size_t n = graph.getNbNodes(), m = graph.getNbLinks();
+    if (n == 0) return;
+    std::vector<double> pose(3 * n), meas;
+    std::vector<uint32_t> ref, mov;
+    for (size_t i = 0; i < n; i++) {
+        const Pose2d p = convertEigenAffine3dToIsamPose2d(graph.getNodeInterface(i).getPose());
+        for (int a = 0; a < 3; a++) pose[3 * i + a] = p(a);
+    }
+    for (int pass = 0; pass < 2; pass++)
+        for (size_t i = 0; i < m; i++) {
+            const NDTFeatureLinkInterface &link = graph.getLinkInterface(i);
+            if (pass == 0 && !(link.getScore() < 0.)) continue;
+            const Pose2d z = convertEigenAffine3dToIsamPose2d(link.getRelPose());
+            ref.push_back((uint32_t)link.getRefIdx());
+            mov.push_back((uint32_t)link.getMovIdx());
+            for (int a = 0; a < 3; a++) meas.push_back(z(a));
+        }
+    const ndtgpu_pgo_wide_params wide_defaults = {32, 0};
+    std::vector<double> weight(ref.size());
+    ndtgpu_pgo *h = nullptr;
+    ndtgpu_host::check(ndtgpu_pgo_create(1, n, ref.size(), &h), "ndtgpu_pgo_create");
+    ndtgpu_status rc = ndtgpu_pgo_set_graph(h, 0, n, pose.data(), ref.size(), ref.data(), mov.data(), meas.data(), nullptr);
+    if (rc == NDTGPU_OK) rc = ndtgpu_pgo_optimize_robust(h, 0, 1, params, robust, wide ? &wide_defaults : nullptr, nullptr);
+    if (rc == NDTGPU_OK) rc = ndtgpu_pgo_poses(h, 0, pose.data(), nullptr, nullptr);
+    if (rc == NDTGPU_OK) rc = ndtgpu_pgo_robust_links(h, 0, nullptr, weight.data(), nullptr, result);
+    const std::string err = rc == NDTGPU_OK ? "" : ndtgpu_last_error();
+    ndtgpu_pgo_destroy(h);
+    if (rc != NDTGPU_OK) throw ndtgpu_host::Error(rc, "optimizeGraphUsingISAMRobust: " + err);
+    for (size_t i = 0; i < n; i++)
+        graph.getNodeInterface(i).setPose(convertIsamPose2dToEigenAffine3d(Pose2d(pose[3 * i], pose[3 * i + 1], pose[3 * i + 2])));
+    if (link_weights_out) link_weights_out->assign(weight.end() - (std::ptrdiff_t)m, weight.end());      // (the second pass: every link, in order)
+}
+
+// optimizeGraph3D with a robust cost: the factors of optimizeGraph3D, the weighting of optimizeGraphUsingISAMRobust; one weight
+// per link of `links`
+inline void optimizeGraph3DRobust(NDTFeatureGraphInterface &graph, const std::vector<NDTFeatureLink> &links,
+                                  const ndtgpu_pgo_robust_params *robust = nullptr, std::vector<double> *link_weights_out = nullptr,
+                                  const ndtgpu_pgo3_params *params = nullptr, ndtgpu_pgo_robust_result *result = nullptr, bool wide = false)
+{
+    const size_t n = graph.getNbNodes(), m = links.size();
+    if (n == 0) return;
+    std::vector<double> T16(16 * n), Z16(16 * m), W36(36 * m), weight(m);
+    std::vector<uint32_t> ref(m), mov(m);
+    for (size_t i = 0; i < n; i++) std::copy_n(graph.getNodeInterface(i).getPose().data(), 16, &T16[16 * i]);
+    for (size_t k = 0; k < m; k++) {
+        const NDTFeatureLink &l = links[k];
+        ref[k] = (uint32_t)l.ref_idx;
+        mov[k] = (uint32_t)l.mov_idx;
+        double cov[36];
+        const bool has_cov = l.cov_3d.rows() == 6 && l.cov_3d.cols() == 6;
+        if (has_cov)
+            for (int a = 0; a < 6; a++)
+                for (int b = 0; b < 6; b++) cov[6 * a + b] = l.cov_3d(a, b);
+        ndtgpu_host::check(ndtgpu_pgo3_link_from_registration(l.T.data(), has_cov ? cov : nullptr, 0, &Z16[16 * k], &W36[36 * k]),
+                           "ndtgpu_pgo3_link_from_registration");
+    }
+    const ndtgpu_pgo_wide_params wide_defaults = {32, 0};
+    ndtgpu_pgo3 *h = nullptr;
+    ndtgpu_host::check(ndtgpu_pgo3_create(1, n, m, &h), "ndtgpu_pgo3_create");
+    ndtgpu_status rc = ndtgpu_pgo3_set_graph(h, 0, n, T16.data(), m, ref.data(), mov.data(), Z16.data(), W36.data());
+    if (rc == NDTGPU_OK) rc = ndtgpu_pgo3_optimize_robust(h, 0, 1, params, robust, wide ? &wide_defaults : nullptr, nullptr);
+    if (rc == NDTGPU_OK) rc = ndtgpu_pgo3_poses(h, 0, T16.data(), nullptr);
+    if (rc == NDTGPU_OK) rc = ndtgpu_pgo3_robust_links(h, 0, nullptr, weight.data(), nullptr, result);
+    const std::string err = rc == NDTGPU_OK ? "" : ndtgpu_last_error();
+    ndtgpu_pgo3_destroy(h);
+    if (rc != NDTGPU_OK) throw ndtgpu_host::Error(rc, "optimizeGraph3DRobust: " + err);
+    for (size_t i = 0; i < n; i++) {
+        Eigen::Affine3d T;
+        std::copy_n(&T16[16 * i], 16, T.data());
+        graph.getNodeInterface(i).setPose(T);
+    }
+    if (link_weights_out) *link_weights_out = weight;
+}
+
 // The product of the mapper: ONE map from the graph's node maps under the node poses T -- graph->getMap() moved by getT()
 // (ndt_feature2d_fuser.cpp:425-432), the combination NDTFeatureGraph::fuse() (ndt_feature_graph.h:149-152) declares but leaves
 // empty, the single map ndt_feature_mcl_node.cpp:174 localises in.  On the device in one call: ndtgpu_world_assemble

@@ -29,6 +29,8 @@ GROUPS = {"pgo_wide": ["ndt_pgo_wide_linearise_kernel", "ndt_pgo_wide_assess_ker
                             "ndt_pgo3_marginal_prepare_kernel", "ndt_pgo3_marginal_solve_kernel"],
           "pgo3_wide": ["ndt_pgo3_wide_linearise_kernel", "ndt_pgo3_wide_assess_kernel", "ndt_pgo3_wide_start_kernel", "ndt_pgo3_wide_link_kernel",
                         "ndt_pgo3_wide_node_kernel", "ndt_pgo3_wide_step_kernel", "ndt_pgo3_wide_update_kernel"],
+          "pgo_robust": ["ndt_pgo_robust_weigh_kernel", "ndt_pgo_robust_finish_kernel", "ndt_pgo3_robust_weigh_kernel",
+                         "ndt_pgo3_robust_finish_kernel"],
           "calib": ["ndt_calib_prepare_kernel", "ndt_calib_score_kernel", "ndt_calib_finish_kernel", "ndt_calib_winner_kernel"],
           "locmon": ["ndt_locmon_row_kernel", "ndt_locmon_col_kernel", "ndt_locmon_badness_kernel", "ndt_locmon_finish_kernel",
                      "ndt_locmon_winner_kernel", "ndt_locmon_pick_kernel"],
